@@ -18,6 +18,17 @@ created, through torch.distributed otherwise (stated in the line).  A bare `pyth
 starts the N ranks itself as fresh child processes; under torchrun (WORLD_SIZE set) it is one of the ranks.
 Every line states `rccl_ranks` = the number of ranks a real all-reduce saw, and the run fails if that is not --gpus.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: it sets up, runs the
+settle and warm-up steps, times the K steps, writes the outputs of the last step if --dump-outputs is given, and prints
+the line.  --full adds everything else this script measures or checks, after (and for the traffic children, before) the
+timed region: the rocprofv3 counter traffic, the same-run stream-read ceiling, the sustained run, the optional extra
+histogram of configs 1-3, the parity spot-check against the CPU oracle and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (float64): every u64
+field of the summary as [high 32 bits, low 32 bits] (exact), or the bucket counts of --config 4 (a fixed, seeded sample of
+them above 2^22 buckets).  With N > 1 ranks each rank writes its own summary as rank<r>_<name>.npy.  The synthetic reads
+are a fixed function of the arguments, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -308,6 +319,39 @@ def traffic_from_counters(res, algo_read_bytes, n_step_launch_sets):
     }
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_MAX_ELEMS = 1 << 22        # float64 elements written per array at most (32 MiB); larger arrays are sampled
+DUMP_SAMPLE_SEED = 0
+
+
+def summary_arrays(words, fields, prefix=""):
+    """u64 summary words -> {name: float64 [high 32 bits, low 32 bits]}: exact in float64, whatever the value"""
+    import numpy as np
+
+    w = np.asarray(words, dtype=np.uint64)
+    return {prefix + f: np.array([float(int(v) >> 32), float(int(v) & 0xFFFFFFFF)], dtype=np.float64) for f, v in zip(fields, w)}
+
+
+def counts_arrays(counts):
+    """bucket counts (u64, far below 2^53) -> float64; above DUMP_MAX_ELEMS buckets a fixed, seeded sample and its indices"""
+    import numpy as np
+
+    c = np.asarray(counts, dtype=np.uint64)
+    if c.size <= DUMP_MAX_ELEMS:
+        return {"counts": c.astype(np.float64)}
+    idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, c.size, size=DUMP_MAX_ELEMS // 2))
+    return {"counts_sample": c[idx].astype(np.float64), "counts_sample_index": idx.astype(np.float64)}
+
+
+def write_outputs(dirpath, arrays):
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 # ------------------------------------------------------------------------------------------------ the bench itself
 
 def parse_args(argv=None):
@@ -322,6 +366,11 @@ def parse_args(argv=None):
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("-k", type=int, default=None)
     ap.add_argument("--hash", action="store_true", help="also fold the LexHasher(k) word hash (BASELINE configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (traffic, stream ceiling, sustained run, "
+                         "extra histogram, parity against the CPU oracle, CPU baseline); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=24.0, help="CPU work the cpu_baseline leg is sized for (rank 0, after the timed region)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure roofline.traffic")
@@ -348,6 +397,8 @@ def parse_args(argv=None):
     args.reads_per_gpu = args.reads_per_gpu or 100_000_000
     if args.config == "4" and not args.histogram:
         args.histogram = 20
+    if args.histogram and args.config != "4" and not args.full:
+        ap.error("--histogram with --config 1-3 is an extra measurement: it needs --full")
     return args
 
 
@@ -503,26 +554,27 @@ def worker(args, traffic_raw=None, traffic_err=None):
         torch.cuda.synchronize()
         return 0
 
-    # Same-run ceiling of the HBM read stream (kmx_calib_stream_read: the scan's load shape, no compute), measured BEFORE the
-    # timed region: it is part of every line, and ~70 ms of streaming also brings the device out of its idle power state --
-    # from cold the first ten launches of any kernel run up to 40 % slow (tools/step_times.py), which W = 5 warm-up steps
-    # alone do not cover.
-    cal = ctx.empty(1, torch.int64)
-    for _ in range(5):
-        ctx.calib_stream_read(bases, out=cal)
-    cevs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(25)]
-    with torch.cuda.stream(ctx.stream):
-        for a, b in cevs:
-            a.record(ctx.stream)
+    # --full: same-run ceiling of the HBM read stream (kmx_calib_stream_read: the scan's load shape, no compute), measured
+    # BEFORE the timed region; ~70 ms of streaming also brings the device out of its idle power state.
+    stream_gbps = None
+    if args.full:
+        cal = ctx.empty(1, torch.int64)
+        for _ in range(5):
             ctx.calib_stream_read(bases, out=cal)
-            b.record(ctx.stream)
-    torch.cuda.synchronize()
-    stream_ms = sorted(a.elapsed_time(b) for a, b in cevs)[len(cevs) // 2]
-    stream_gbps = float(nbytes) / (stream_ms * 1e-3) / 1e9
+        cevs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(25)]
+        with torch.cuda.stream(ctx.stream):
+            for a, b in cevs:
+                a.record(ctx.stream)
+                ctx.calib_stream_read(bases, out=cal)
+                b.record(ctx.stream)
+        torch.cuda.synchronize()
+        stream_ms = sorted(a.elapsed_time(b) for a, b in cevs)[len(cevs) // 2]
+        stream_gbps = float(nbytes) / (stream_ms * 1e-3) / 1e9
 
-    # The read-only calibration kernel draws less power than the scan; the first ~15 scan launches after it run ~1 % slower
-    # than the ones that follow (profiles/r03_step_times.txt), W = 5 alone ends in the middle of that.  These settle steps
-    # are the same workload, untimed and reported ("settle_steps") -- the 1000-step "sustained" figure is the cross-check.
+    # From cold the first ten launches of any kernel run up to 40 % slow (tools/step_times.py), and after the read-only
+    # calibration kernel (--full) the first ~15 scan launches run ~1 % slower than the ones that follow
+    # (profiles/r03_step_times.txt): W = 5 alone ends in the middle of either.  These settle steps are the same workload,
+    # untimed and reported ("settle_steps") -- the 1000-step "sustained" figure of --full is the cross-check.
     with torch.cuda.stream(ctx.stream):
         for _ in range(args.settle_steps):
             step()
@@ -546,6 +598,15 @@ def worker(args, traffic_raw=None, traffic_err=None):
             b.record(ctx.stream)
     barrier()
     elapsed = time.perf_counter() - t0
+
+    # what the timed path returned in its last step, copied out before anything else runs on the device
+    if args.dump_outputs:
+        if hist_mode:
+            dump = counts_arrays(counts.cpu().numpy().view(np.uint64)) if rank == 0 else {}   # all-reduced: the same on every rank
+        else:
+            fields = [f for f, _ in (_lib.Summary2 if two_word else _lib.Summary)._fields_]
+            dump = summary_arrays(out.cpu().numpy().view(np.uint64), fields, prefix=f"rank{rank}_" if world > 1 else "")
+        write_outputs(args.dump_outputs, dump)
 
     kernel_ms = [a.elapsed_time(b) for a, b in evs]
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
@@ -585,7 +646,7 @@ def worker(args, traffic_raw=None, traffic_err=None):
 
     # ---- outside the timed region: sustained run, same-run read ceiling, optional histogram, parity, CPU baseline
     sustained = None
-    if args.sustain_steps > 0:
+    if args.full and args.sustain_steps > 0:
         ev_mid.clear()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         barrier()
@@ -600,7 +661,7 @@ def worker(args, traffic_raw=None, traffic_err=None):
         sustained = {"steps": args.sustain_steps, "ms_per_step": sus_ms}
 
     hist_info = None
-    if args.histogram and not hist_mode:
+    if args.full and args.histogram and not hist_mode:
         b_ = args.histogram
         hist_scan()   # warm-up (grows the work buffer)
         counts.zero_()
@@ -619,29 +680,33 @@ def worker(args, traffic_raw=None, traffic_err=None):
     parity = True
     res = None
     if rank == 0:
-        from oracle import oracle
-
         value = total_kmers_per_step * args.steps / elapsed_max
         # algorithmic bytes per launch: L bytes read per read (L/4 when the reads are 2-bit packed), writes negligible
         algo_bytes = float(nbytes) / (4.0 if args.packed else 1.0)
         achieved = algo_bytes / (avg_scan_ms * 1e-3) / 1e9
-        # parity spot-check against the CPU oracle on the head of this rank's shard (outside the timed region)
-        n_chk = min(n, 200_000)
-        host = bases[: n_chk * L].cpu().numpy()
-        if hist_mode:
-            n_h = min(n, 20_000)
-            o = oracle.histogram(host[: n_h * L], n_h, L, k, k, args.histogram)
-            g = ctx.histogram(bases[: n_h * L], n_h, L, k, _lib.HASH_LEX, k, args.histogram).cpu().numpy().view(np.uint64)
-            parity = bool((g == o).all()) and total_count == world * n * max(L - k + 1, 0)
-        elif two_word:
-            o = oracle.canonical_reduce2(host, n_chk, L, k, with_hash=args.hash)
-            g = ctx.canonical_reduce2(bases[: n_chk * L], n_chk, L, k, with_hash=args.hash)
-            parity = tuple(getattr(g, f) for f, _ in g._fields_) == tuple(getattr(o, f) for f, _ in o._fields_)
-        else:
-            o = oracle.canonical_reduce(host, n_chk, L, k, hasher_k=hk)
-            g = ctx.canonical_reduce(bases[: n_chk * L], n_chk, L, k, hasher, hk, 0)
-            parity = (g.n_valid, g.sum_canon, g.xor_hash) == (o.n_valid, o.sum_canon, o.xor_hash if args.hash else 0)
-        parity = parity and n_valid_local == n * max(L - k + 1, 0)
+        # every run: the k-mer count of the step is exactly the number of windows of the clean synthetic reads
+        parity = (total_count == world * n * max(L - k + 1, 0)) if hist_mode else (n_valid_local == n * max(L - k + 1, 0))
+        if not parity:
+            sys.stderr.write("bench.py: the step's k-mer count is not the number of windows of the reads\n")
+        if args.full:
+            from oracle import oracle
+
+            # parity spot-check against the CPU oracle on the head of this rank's shard (outside the timed region)
+            n_chk = min(n, 200_000)
+            host = bases[: n_chk * L].cpu().numpy()
+            if hist_mode:
+                n_h = min(n, 20_000)
+                o = oracle.histogram(host[: n_h * L], n_h, L, k, k, args.histogram)
+                g = ctx.histogram(bases[: n_h * L], n_h, L, k, _lib.HASH_LEX, k, args.histogram).cpu().numpy().view(np.uint64)
+                parity = parity and bool((g == o).all())
+            elif two_word:
+                o = oracle.canonical_reduce2(host, n_chk, L, k, with_hash=args.hash)
+                g = ctx.canonical_reduce2(bases[: n_chk * L], n_chk, L, k, with_hash=args.hash)
+                parity = parity and tuple(getattr(g, f) for f, _ in g._fields_) == tuple(getattr(o, f) for f, _ in o._fields_)
+            else:
+                o = oracle.canonical_reduce(host, n_chk, L, k, hasher_k=hk)
+                g = ctx.canonical_reduce(bases[: n_chk * L], n_chk, L, k, hasher, hk, 0)
+                parity = parity and (g.n_valid, g.sum_canon, g.xor_hash) == (o.n_valid, o.sum_canon, o.xor_hash if args.hash else 0)
         traffic, traffic_detail = None, traffic_err
         if traffic_raw is not None:
             td = traffic_from_counters(traffic_raw, float(nbytes), 3)
@@ -682,6 +747,7 @@ def worker(args, traffic_raw=None, traffic_err=None):
                          "kernel_ms_min": min(per_rank_kernel_ms), "kernel_ms_max": max(per_rank_kernel_ms),
                          "summary_combine_ms": summary_combine_ms},
             "higher_is_better": True,
+            "full": args.full,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "u64",
@@ -698,12 +764,14 @@ def worker(args, traffic_raw=None, traffic_err=None):
                 "avg_kernel_ms": avg_scan_ms, "min_kernel_ms": min(scan_ms),
                 "median_kernel_ms": sorted(scan_ms)[len(scan_ms) // 2], "algorithmic_bytes_per_launch": algo_bytes,
                 "frac_of_measured_copy_ceiling_6290": achieved / 6290.0,
-                "same_run_stream_read_GBps": stream_gbps, "frac_of_same_run_stream_read": achieved / stream_gbps,
                 "traffic_detail": traffic_detail,
             },
-            "parity_vs_oracle": "ok" if parity else "MISMATCH",
             "checksum": f"{tot['sum_canon']:#018x}",
         }
+        if args.full:
+            res["roofline"]["same_run_stream_read_GBps"] = stream_gbps
+            res["roofline"]["frac_of_same_run_stream_read"] = achieved / stream_gbps
+            res["parity_vs_oracle"] = "ok" if parity else "MISMATCH"
         if sustained is not None:
             sustained["achieved_GBps"] = algo_bytes / (sustained["ms_per_step"] * 1e-3) / 1e9 if not hist_mode else None
             sustained["frac"] = sustained["achieved_GBps"] / HBM_PEAK_GBPS if not hist_mode else None
@@ -714,7 +782,7 @@ def worker(args, traffic_raw=None, traffic_err=None):
                                 "total_count": total_count, "expect": world * n * max(L - k + 1, 0), "collective": collective}
         elif hist_info is not None:
             res["histogram"] = hist_info
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after the timed region, at every N (the other ranks wait at the verdict broadcast below)
             n_s = min(n, 4_000_000)
             sample = bases[: n_s * L].cpu().numpy()
@@ -741,8 +809,8 @@ def main():
         sys.exit(spawn_ranks(args, argv))       # before anything touches the GPU; children are fresh processes
     if args.spawn_selftest:
         sys.exit(selftest_worker(args))
-    traffic_raw, traffic_err = None, "not measured (--no-traffic, N > 1, or a child of another run)"
-    if not have_world and args.gpus == 1 and not args.no_traffic and not args.pmc_child and not args.dist_single:
+    traffic_raw, traffic_err = None, "not measured (a plain run, --no-traffic, N > 1, or a child of another run)"
+    if args.full and not have_world and args.gpus == 1 and not args.no_traffic and not args.pmc_child and not args.dist_single:
         # two short child runs under rocprofv3 --pmc, BEFORE this process initialises the GPU
         traffic_raw, traffic_err = measure_traffic([a for a in argv if a not in ("--no-cpu-baseline",)] + ["--no-cpu-baseline", "--no-traffic"])
     sys.exit(worker(args, traffic_raw, traffic_err))

@@ -536,7 +536,7 @@ def test_bench_two_ranks_share_the_gpu(cfg):
     env["KMX_BENCH_TEST_SHARED_GPU"] = "1"
     n = 2_000_000
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", cfg, "--reads-per-gpu", str(n),
-                        "--steps", "3", "--warmup", "1", "--sustain-steps", "5", "--no-traffic", "--cpu-baseline-seconds", "2"],
+                        "--steps", "3", "--warmup", "1", "--sustain-steps", "5", "--no-traffic", "--cpu-baseline-seconds", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

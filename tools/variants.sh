@@ -8,6 +8,6 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do args+=("$1"); shift; done
 if [ "$1" == "--" ]; then shift; else set -- "${args[@]}"; args=(); fi
 for rep in 1 2; do
   for v in "$@"; do
-    timeout 600 python3 tools/bench_variant.py $v --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --sustain-steps 400 "${args[@]}" 2>/dev/null | python3 tools/bench_line.py "[$v]"
+    timeout 600 python3 tools/bench_variant.py $v --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --sustain-steps 400 --full "${args[@]}" 2>/dev/null | python3 tools/bench_line.py "[$v]"
   done
 done
