@@ -344,6 +344,58 @@ pub fn minimizers_of_reads(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u
     Ok(a.into_iter().zip(b).collect())
 }
 
+/// The canonical k-mer scan of a uniform batch already on the device with std's `DefaultHasher` (`keys = (0, 0)`) or a
+/// `RandomState` (its two keys) folded in: `xor_hash` = xor of SipHash-1-3(keys; canonical word) (`kmx_canonical_reduce_sip13`).
+pub fn canonical_reduce_sip13(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, keys: (u64, u64), flags: u32)
+                              -> Result<kmx_summary, KmxError> {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    let d_out = ctx.alloc(std::mem::size_of::<kmx_summary>())?;
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_canonical_reduce_sip13(ctx.0, &r, k as u32, keys.0, keys.1, flags, d_out.as_mut_ptr()) })?;
+    Ok(d_out.download::<kmx_summary>(1)?[0])
+}
+
+/// Bucket counts of SipHash-1-3(keys; canonical word) over a uniform batch already on the device (`kmx_histogram_sip13`,
+/// 2^log2_buckets counters, the BUILD-DEFINED bucket function of `kmx_histogram`)
+pub fn histogram_sip13(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, keys: (u64, u64), log2_buckets: u32)
+                       -> Result<Vec<u64>, KmxError> {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    let nb = 1usize << log2_buckets.min(30);
+    let d_counts = ctx.alloc(8 * nb)?;
+    ctx.ck(unsafe { kmx_memset(ctx.0, d_counts.as_mut_ptr(), 0, d_counts.len()) })?;
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_histogram_sip13(ctx.0, &r, k as u32, keys.0, keys.1, log2_buckets, d_counts.as_mut_ptr::<u64>()) })?;
+    d_counts.download::<u64>(nb)
+}
+
+/// `Kmer::minimizer_word(word, k, width, &state)` (kmer.rs:170-192) with a std hasher state: `(minimizer, offset)` per word
+pub fn minimizer_words_sip13(ctx: &HipContext, words: &[u64], k: u8, width: u8, keys: (u64, u64)) -> Result<Vec<(u64, u32)>, KmxError> {
+    let bytes = unsafe { std::slice::from_raw_parts(words.as_ptr() as *const u8, words.len() * 8) };
+    let d_in = ctx.upload(bytes)?;
+    let d_mm = ctx.alloc(8 * words.len().max(1))?;
+    let d_off = ctx.alloc(4 * words.len().max(1))?;
+    ctx.ck(unsafe { kmx_minimizer_words_sip13(ctx.0, d_in.as_ptr::<u64>(), words.len() as u64, k as u32, width as u32, keys.0, keys.1,
+                                              d_mm.as_mut_ptr::<u64>(), d_off.as_mut_ptr::<u32>()) })?;
+    let (a, b) = (d_mm.download::<u64>(words.len())?, d_off.download::<u32>(words.len())?);
+    Ok(a.into_iter().zip(b).collect())
+}
+
+/// `minimizers_of_reads` with std's `DefaultHasher` / a `RandomState` (SipHash-1-3 of each l-mer, minimizers.rs:88,113)
+pub fn minimizers_of_reads_sip13(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, w: u8, keys: (u64, u64))
+                                 -> Result<Vec<(u64, u32)>, KmxError> {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(read_len >= k as u32, "SeqVecMinimizerIter::new: assertion failed: sv.len() >= k");
+    let n = (n_reads * (read_len - k as u32 + 1) as u64) as usize;
+    let d_word = ctx.alloc(8 * n.max(1))?;
+    let d_pos = ctx.alloc(4 * n.max(1))?;
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    let mut first_bad = u64::MAX;
+    ctx.ck(unsafe { kmx_minimizers_sip13(ctx.0, &r, ptr::null(), k as u32, w as u32, keys.0, keys.1, d_word.as_mut_ptr::<u64>(),
+                                         d_pos.as_mut_ptr::<u32>(), &mut first_bad) })?;
+    let (a, b) = (d_word.download::<u64>(n)?, d_pos.download::<u32>(n)?);
+    Ok(a.into_iter().zip(b).collect())
+}
+
 // ------------------------------------------------------------------------------------------------ SeqVector
 
 /// `SeqVector` (src/naive_impl/seq_vector.rs) with its words on the device: same bit layout as the crate's `RawVector`
@@ -386,6 +438,17 @@ impl<'c> HipSeqVector<'c> {
         let d_out = self.ctx.alloc(8 * cnt.max(1))?;
         self.ctx.ck(unsafe { kmx_seqvec_iter_kmers(self.ctx.0, self.d_words.as_ptr(), self.len as u64, 0, self.len as u64, k as u32, d_out.as_mut_ptr()) })?;
         d_out.download(cnt)
+    }
+    /// `iter_minimizers(k, w, state)` with std's `DefaultHasher` / a `RandomState` (SipHash-1-3; minimizers.rs:39-141): `(word, pos)`
+    pub fn iter_minimizers_sip13(&self, k: u8, w: u8, keys: (u64, u64)) -> Result<Vec<(u64, u32)>, KmxError> {
+        assert!(self.len >= k as usize, "SeqVecMinimizerIter::new: assertion failed: sv.len() >= k");
+        let cnt = self.len - k as usize + 1;
+        let d_word = self.ctx.alloc(8 * cnt)?;
+        let d_pos = self.ctx.alloc(4 * cnt)?;
+        self.ctx.ck(unsafe { kmx_seqvec_minimizers_sip13(self.ctx.0, self.d_words.as_ptr(), 1, self.len as u32, k as u32, w as u32, keys.0, keys.1,
+                                                         d_word.as_mut_ptr::<u64>(), d_pos.as_mut_ptr::<u32>()) })?;
+        let (a, b) = (d_word.download::<u64>(cnt)?, d_pos.download::<u32>(cnt)?);
+        Ok(a.into_iter().zip(b).collect())
     }
     /// `String::from(&SeqVector)` (seq_vector.rs:171-182)
     pub fn to_string(&self) -> Result<String, KmxError> {

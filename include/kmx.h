@@ -147,6 +147,16 @@ int kmx_memset(kmx_ctx *ctx, void *d_dst, int value, size_t nbytes);
  * d_out is OVERWRITTEN with this batch's summary. */
 int kmx_canonical_reduce(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint32_t hasher, uint32_t hasher_k,
                          uint32_t flags, kmx_summary *d_out);
+/* The same pass with xor_hash = the xor of SipHash-1-3(key0, key1; the 8 little-endian bytes of the canonical word) -- std's
+ * DefaultHasher (key0 = key1 = 0) or a RandomState (its two keys) fed hash_one(state, kmer) (hash.rs:4-20): the hash of
+ * kmx_hash_words_sip13.  n_valid, sum_canon and sum_fw are those of kmx_canonical_reduce on the same input; domain, layouts,
+ * KMX_REDUCE_SUM_FW and codes as there.  Uniform and ragged reads of up to 256 bases (2 <= k <= 31, 16-byte aligned d_bases for
+ * ragged reads) take the tiled word-domain scan; k = 1, longer reads and a misaligned ragged d_bases a lane per read -- correct,
+ * but a batch of long reads then runs at the rate of its longest lanes (no segment cut here).  Bound by VALU work (five SipRounds,
+ * ~110 instructions per window), not by HBM: 0.31e12 k-mers/s on 150 bp reads at k = 31, 2 % dirty 0.28e12 (Lex: ~5e12;
+ * profiles/r07_sip13_bench.txt).  Asynchronous; d_out OVERWRITTEN. */
+int kmx_canonical_reduce_sip13(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint64_t key0, uint64_t key1,
+                               uint32_t flags, kmx_summary *d_out);
 
 /* The same call with its answer in HOST memory when it returns (round 6): what a caller that reduces one small
  * batch at a time -- the reference's iterator over one read set, canonical_kmer_iterator.rs:42-116 -- pays is
@@ -183,6 +193,13 @@ int kmx_canonical_windows2(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t 
  * what is free; kmx_ctx_set_work_buffer_limit overrides): growing it synchronises the stream once. */
 int kmx_histogram(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint32_t hasher, uint32_t hasher_k,
                   uint32_t log2_buckets, uint64_t *d_counts);
+/* The same histogram of the SipHash-1-3(key0, key1) hash of the canonical word (as kmx_canonical_reduce_sip13), same bucket function,
+ * ACCUMULATED into d_counts, through the routes of kmx_histogram: block-private LDS tables up to 2^14 buckets, the partitioned
+ * passes through the context's work buffer for 2^15..2^28 (one level up to 2^22, two above), device atomics where there is no
+ * scratch or above 2^28, a lane per read outside the scan's domain.  Bound by VALU work (the hash), not by HBM: 0.31e12 k-mers/s at
+ * 2^10 buckets, 0.115e12 at 2^20 on 150 bp reads at k = 31 (profiles/r07_sip13_bench.txt). */
+int kmx_histogram_sip13(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint64_t key0, uint64_t key1,
+                        uint32_t log2_buckets, uint64_t *d_counts);
 
 /* Deterministic synthetic reads (BUILD-DEFINED; the reference bench input is unseeded,
  * benches/simple_benchmark.rs:59-65): byte g of the stream = "ACGT"[(splitmix64(seed + g/32) >> 2*(g%32)) & 3].
@@ -305,16 +322,28 @@ int kmx_seqvec_canonical_reduce(kmx_ctx *ctx, const uint64_t *d_words, uint64_t 
 
 /* ---------------------------------------------------------------- minimizers ----
  * hasher: KMX_HASH_LEX with hasher_k (LexHasherState::new(hasher_k): the k of the hasher is independent of the l-mer
- * length, minimizers.rs:240 uses 6 for 3-mers) or KMX_HASH_IDENTITY.  std's RandomState has no pinned outputs. */
+ * length, minimizers.rs:240 uses 6 for 3-mers) or KMX_HASH_IDENTITY.  std's DefaultHasher / RandomState: the *_sip13 calls
+ * below each counterpart. */
 /* Kmer::minimizer_word(word, k, width, state) (kmer.rs:170-192) for n k-mer words: the leftmost minimum-hash
  * sub-word of `width` bases and its offset.  1 <= width <= k <= 32. */
 int kmx_minimizer_words(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n, uint32_t k, uint32_t width, uint32_t hasher,
                         uint32_t hasher_k, uint64_t *d_mmer, uint32_t *d_offset);
+/* The same with hash_one(SipHash-1-3 state (key0, key1), l-mer) (kmer.rs:182): a lane per word, a strict `<` against a running
+ * minimum that starts at u64::MAX (kmer.rs:176-189).  VALU-bound: k - width + 1 hashes per word. */
+int kmx_minimizer_words_sip13(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n, uint32_t k, uint32_t width,
+                              uint64_t key0, uint64_t key1, uint64_t *d_mmer, uint32_t *d_offset);
 /* SeqVectorSlice::iter_minimizers(k, w, hasher) (seq_vector.rs:73-80; SeqVecMinimizerIter, minimizers.rs:39-141) for
  * every read slice [r*read_len, (r+1)*read_len) of a SeqVector: MappedMinimizer{word, pos} per k-mer, slot
  * r*(read_len-k+1) + i, pos relative to the slice.  read_len >= k (the iterator asserts it), 1 <= w <= k, w <= 32. */
 int kmx_seqvec_minimizers(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n_reads, uint32_t read_len, uint32_t k,
                           uint32_t w, uint32_t hasher, uint32_t hasher_k, uint64_t *d_word, uint32_t *d_pos);
+/* The same iterator with SipHash-1-3(key0, key1) of each l-mer (minimizers.rs:88,113): std's DefaultHasher / RandomState.  The
+ * 64-bit hash does not fit the (hash << 8) | position key of the Lex kernel: a wave per slice and per piece of 256 bases, every
+ * l-mer hashed once into LDS, each k-mer the leftmost minimum of its k - w + 1 hashes (the deque's tie rule, minimizers.rs:71).
+ * k above 256: a lane per k-mer (each l-mer hashed once per window that holds it).  Slots, positions and codes as
+ * kmx_seqvec_minimizers.  VALU-bound: 0.12e12 k-mers/s at k = 31 / w = 15 on 150-base slices (profiles/r07_sip13_bench.txt). */
+int kmx_seqvec_minimizers_sip13(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n_reads, uint32_t read_len, uint32_t k,
+                                uint32_t w, uint64_t key0, uint64_t key1, uint64_t *d_word, uint32_t *d_pos);
 
 /* The same iterator over READS (round 6): what SeqVector::from(read).slice(..).iter_minimizers(k, w, hasher) yields
  * (seq_vector.rs:73-80, 230-242; minimizers.rs:39-141) for every read of a batch -- ASCII, one length or behind offsets, as
@@ -329,6 +358,13 @@ int kmx_seqvec_minimizers(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n_read
  * hash fits 56 bits (w <= 28; LexHasher: hasher_k <= 28); anything else a lane-per-k-mer kernel. */
 int kmx_minimizers(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_win_offsets, uint32_t k, uint32_t w, uint32_t hasher,
                    uint32_t hasher_k, uint64_t *d_word, uint32_t *d_pos, uint64_t *h_first_bad);
+/* The same over reads with SipHash-1-3(key0, key1) of each l-mer, through the kernel of kmx_seqvec_minimizers_sip13 (a wave per read,
+ * read by read in pieces of 256 bases: reads of any length, uniform or ragged).  Slots, positions, h_first_bad, KMX_E_INVALID_BASE
+ * and synchronisation as kmx_minimizers (ragged reads: one host round trip for the longest read; a batch with no read of k bases
+ * returns KMX_OK before any kernel runs).  k above 256: a lane per k-mer.  VALU-bound: 0.11e12 k-mers/s at k = 31 / w = 15 on
+ * 150 bp reads (profiles/r07_sip13_bench.txt). */
+int kmx_minimizers_sip13(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_win_offsets, uint32_t k, uint32_t w,
+                         uint64_t key0, uint64_t key1, uint64_t *d_word, uint32_t *d_pos, uint64_t *h_first_bad);
 
 /* ---------------------------------------------------------------- FASTA / FASTQ ingestion ----
  * BUILD-DEFINED: the reference has no parser (its iterators take `&[u8]` reads, canonical_kmer_iterator.rs:72-83);

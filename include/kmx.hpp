@@ -77,6 +77,9 @@ class DeviceBuffer {  // RAII device array
 
 // ---------------------------------------------------------------------------------------------------
 namespace naive_impl {
+namespace hash {
+struct SipHasher13State;
+}
 
 using Base = uint64_t;                       // src/naive_impl/mod.rs:20
 constexpr Base A = 0, C = 1, G = 2, T = 3;   // :21-24
@@ -191,6 +194,8 @@ struct Kmer {  // src/naive_impl/kmer.rs:6-10
         ctx.check(st, "Kmer::minimizer");
         return {from_u64(mm.download()[0], static_cast<uint8_t>(width)), off.download()[0]};
     }
+    // ... with one of std's hashers (DefaultHasher / RandomState: SipHash-1-3, kmer.rs:182): defined below hash::SipHasher13State
+    std::pair<Kmer, size_t> minimizer(size_t width, const hash::SipHasher13State& st, Context& ctx = Context::instance()) const;
 
   private:
     Base shift(bool append, Base c, Context& ctx) {
@@ -346,6 +351,15 @@ inline uint64_t hash_one(const SipHasher13State& st, const Kmer& km, Context& ct
 }
 }  // namespace hash
 
+inline std::pair<Kmer, size_t> Kmer::minimizer(size_t width, const hash::SipHasher13State& st, Context& ctx) const {
+    DeviceBuffer<uint64_t> in(ctx, &data, 1), mm(ctx, 1);
+    DeviceBuffer<uint32_t> off(ctx, 1);
+    int st2 = kmx_minimizer_words_sip13(ctx.get(), in.data(), 1, k, static_cast<uint32_t>(width), st.key0, st.key1, mm.data(), off.data());
+    if (st2 == KMX_E_K_RANGE) throw Panic(st2, "Kmer::minimizer: assertion failed: pos + width <= k");
+    ctx.check(st2, "Kmer::minimizer");
+    return {from_u64(mm.download()[0], static_cast<uint8_t>(width)), off.download()[0]};
+}
+
 // Batch form of the streaming loop (what the GPU is for): summary over many reads resident on the device.
 inline kmx_summary canonical_reduce(Context& ctx, const kmx_reads& reads, uint32_t k, uint32_t hasher = KMX_HASH_NONE,
                                     uint32_t hasher_k = 0, uint32_t flags = 0) {
@@ -353,6 +367,13 @@ inline kmx_summary canonical_reduce(Context& ctx, const kmx_reads& reads, uint32
     kmx_summary out{};
     ctx.check(kmx_canonical_reduce_host(ctx.get(), &reads, k, hasher, hasher_k, flags, &out), "canonical_reduce");
     return out;
+}
+
+// ... with std's DefaultHasher / RandomState folded in: xor_hash = xor of SipHash-1-3(key0, key1; canonical word) (kmx_canonical_reduce_sip13)
+inline kmx_summary canonical_reduce(Context& ctx, const kmx_reads& reads, uint32_t k, const hash::SipHasher13State& st, uint32_t flags = 0) {
+    DeviceBuffer<kmx_summary> out(ctx, 1);
+    ctx.check(kmx_canonical_reduce_sip13(ctx.get(), &reads, k, st.key0, st.key1, flags, out.data()), "canonical_reduce");
+    return out.download()[0];
 }
 
 // FASTA / FASTQ ingestion (build-defined, the reference has no parser): a file image -> the reads
@@ -476,6 +497,21 @@ class SeqVector {
         DeviceBuffer<uint32_t> mp(*ctx_, cnt);
         ctx_->check(kmx_seqvec_minimizers(ctx_->get(), words_->data(), 1, static_cast<uint32_t>(n_), static_cast<uint32_t>(k),
                                           static_cast<uint32_t>(w), KMX_HASH_LEX, static_cast<uint32_t>(lex_hasher_k), mw.data(), mp.data()),
+                    "SeqVector::iter_minimizers");
+        auto a = mw.download();
+        auto b = mp.download();
+        std::vector<MappedMinimizer> out(cnt);
+        for (size_t i = 0; i < cnt; ++i) out[i] = MappedMinimizer{a[i], b[i]};
+        return out;
+    }
+    // iter_minimizers(k, w, state) with one of std's hashers (SipHash-1-3; minimizers.rs:88,113)
+    std::vector<MappedMinimizer> iter_minimizers(size_t k, size_t w, const hash::SipHasher13State& st) const {
+        if (n_ < k) throw Panic(KMX_E_ARG, "SeqVecMinimizerIter::new: assertion failed: sv.len() >= k");
+        const size_t cnt = n_ - k + 1;
+        DeviceBuffer<uint64_t> mw(*ctx_, cnt);
+        DeviceBuffer<uint32_t> mp(*ctx_, cnt);
+        ctx_->check(kmx_seqvec_minimizers_sip13(ctx_->get(), words_->data(), 1, static_cast<uint32_t>(n_), static_cast<uint32_t>(k),
+                                                static_cast<uint32_t>(w), st.key0, st.key1, mw.data(), mp.data()),
                     "SeqVector::iter_minimizers");
         auto a = mw.download();
         auto b = mp.download();

@@ -199,6 +199,26 @@ class Context:
         self._ck(self.lib.kmx_histogram(self._h, C.byref(r), k, hasher, hasher_k, log2_buckets, _ptr(counts)))
         return counts
 
+    # ---- the same two passes under std's DefaultHasher (keys 0, 0) / RandomState (its keys): SipHash-1-3 of the canonical word
+    @_on_ctx_stream
+    def canonical_reduce_sip13(self, bases, n_reads, read_len, k, key0=0, key1=0, flags=0, offsets=None) -> Summary:
+        """kmx_canonical_reduce_sip13: xor_hash = xor of SipHash-1-3(key0, key1; canonical word); the rest as canonical_reduce"""
+        out = self.empty(4, torch.int64)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_canonical_reduce_sip13(self._h, C.byref(r), k, key0 & (2**64 - 1), key1 & (2**64 - 1), flags, _ptr(out)))
+        v = u64_numpy(out)
+        return Summary(int(v[0]), int(v[1]), int(v[2]), int(v[3]))
+
+    @_on_ctx_stream
+    def histogram_sip13(self, bases, n_reads, read_len, k, log2_buckets, key0=0, key1=0, offsets=None,
+                        counts: torch.Tensor | None = None) -> torch.Tensor:
+        """kmx_histogram_sip13: counts (accumulated into) of the bucket of SipHash-1-3(key0, key1; canonical word)"""
+        if counts is None:
+            counts = torch.zeros(1 << log2_buckets, dtype=torch.int64, device=self.device)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_histogram_sip13(self._h, C.byref(r), k, key0 & (2**64 - 1), key1 & (2**64 - 1), log2_buckets, _ptr(counts)))
+        return counts
+
     # --------------------------------------------------------- element-wise
     @_on_ctx_stream
     def kmers_from_bytes(self, seqs: torch.Tensor, n: int, k: int) -> torch.Tensor:
@@ -359,6 +379,46 @@ class Context:
         bad = C.c_uint64(0)
         self._ck(self.lib.kmx_minimizers(self._h, C.byref(r), _ptr(win_offsets) if win_offsets is not None else None, k, w, hasher, hasher_k,
                                          _ptr(mw) if tot else None, _ptr(mp) if tot else None, C.byref(bad) if check else None))
+        return mw, mp
+
+    # ---- minimizers under std's DefaultHasher (keys 0, 0) / RandomState (its keys): SipHash-1-3 of each l-mer
+    @_on_ctx_stream
+    def minimizer_words_sip13(self, words: torch.Tensor, k: int, width: int, key0: int = 0, key1: int = 0):
+        """kmx_minimizer_words_sip13 -> (mmer words int64, offsets int32)"""
+        n = words.numel()
+        mm, off = self.empty(n, torch.int64), self.empty(n, torch.int32)
+        self._ck(self.lib.kmx_minimizer_words_sip13(self._h, _ptr(words) if n else None, n, k, width, key0 & (2**64 - 1), key1 & (2**64 - 1),
+                                                    _ptr(mm) if n else None, _ptr(off) if n else None))
+        return mm, off
+
+    @_on_ctx_stream
+    def seqvec_minimizers_sip13(self, words: torch.Tensor, n_reads: int, read_len: int, k: int, w: int, key0: int = 0, key1: int = 0):
+        """kmx_seqvec_minimizers_sip13 -> (word int64, pos int32), slot r*(L-k+1)+i"""
+        tot = n_reads * max(read_len - k + 1, 0)
+        mw, mp = self.empty(tot, torch.int64), self.empty(tot, torch.int32)
+        self._ck(self.lib.kmx_seqvec_minimizers_sip13(self._h, _ptr(words) if n_reads else None, n_reads, read_len, k, w, key0 & (2**64 - 1),
+                                                      key1 & (2**64 - 1), _ptr(mw) if tot else None, _ptr(mp) if tot else None))
+        return mw, mp
+
+    @_on_ctx_stream
+    def minimizers_sip13(self, bases, n_reads: int, read_len: int, k: int, w: int, key0: int = 0, key1: int = 0, offsets=None,
+                         win_offsets=None, check: bool = True):
+        """kmx_minimizers_sip13 -> (word int64, pos int32); check: KmxError (KMX_E_INVALID_BASE, .first_bad = the read) on an invalid byte"""
+        if offsets is None:
+            tot = n_reads * max(read_len - k + 1, 0)
+        else:
+            tot = int(win_offsets[-1].item()) if n_reads else 0
+        mw, mp = self.empty(tot, torch.int64), self.empty(tot, torch.int32)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        bad = C.c_uint64(0)
+        st = self.lib.kmx_minimizers_sip13(self._h, C.byref(r), _ptr(win_offsets) if win_offsets is not None else None, k, w,
+                                           key0 & (2**64 - 1), key1 & (2**64 - 1), _ptr(mw) if tot else None, _ptr(mp) if tot else None,
+                                           C.byref(bad) if check else None)
+        if st == _lib.E_INVALID_BASE:
+            e = KmxError(st, f"invalid base in read {bad.value}")
+            e.first_bad = bad.value
+            raise e
+        self._ck(st)
         return mw, mp
 
     @_on_ctx_stream

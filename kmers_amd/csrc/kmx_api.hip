@@ -19,7 +19,8 @@ hipError_t launch_scan_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
                                const u64* offsets);
 hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets,
                                u64* counts, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
-                               void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets);
+                               void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets, u64 k0 = 0,
+                               u64 k1 = 0);
 hipError_t launch_windows_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon,
                                   uint8_t* flags, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
 hipError_t launch_windows_ragged(const uint8_t* bases, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L, u32 k,
@@ -112,6 +113,20 @@ hipError_t launch_calib_stream_read(const uint8_t* buf, u64 nbytes, unsigned lon
 hipError_t launch_length_range(const u64* offsets, u64 n_reads, u32* out, int n_cu, hipStream_t st);
 hipError_t launch_offsets_uniform_gate(const u64* offsets, u64 n_reads, u32 bound, u32 k, u32* gate, int n_cu, hipStream_t st);
 hipError_t launch_fix_hash_fold(kmx_summary* out, u32 k, u32 hasher, u32 hk, hipStream_t st);
+// the *_sip13 calls (SipHash-1-3 under std's DefaultHasher / RandomState): kmx_scan.hip, kmx_hist.hip, kmx_generic.hip, kmx_sip13.hip
+constexpr u32 KMX_HASH_SIP13_INTERNAL = 0x5313u;   // the hasher id launch_hist_uniform takes for them (kmx_device.h; not an ABI value)
+hipError_t launch_scan_reduce_sip(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64 k0, u64 k1, bool want_sumfw, kmx_summary* out,
+                                  unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled, const u64* offsets);
+hipError_t launch_reduce_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 want_sumfw, kmx_summary* out, int n_cu, hipStream_t st,
+                                     unsigned long long* too_long);
+hipError_t launch_histogram_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 log2_buckets, u64* counts, int n_cu, hipStream_t st,
+                                        unsigned long long* too_long);
+hipError_t launch_minimizer_words_sip(const u64* in, u64 n, u32 k, u32 w, u64 k0, u64 k1, u64* out_mm, u32* out_off, int n_cu,
+                                      hipStream_t st);
+hipError_t launch_minimizers_reads_sip(const uint8_t* bases, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L, u32 k, u32 w,
+                                       u64 k0, u64 k1, u64* out_word, u32* out_pos, unsigned long long* first_bad, int n_cu, hipStream_t st);
+hipError_t launch_seqvec_minimizers_sip(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u64 k0, u64 k1, u64* out_word, u32* out_pos,
+                                        int n_cu, hipStream_t st);
 }  // namespace kmx
 
 using kmx::u32;
@@ -1240,6 +1255,99 @@ int kmx_minimizers(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_o
     bool tiled = false;
     KMX_HIP(ctx, kmx::launch_minimizers_reads(reads->d_bases, total_bytes, reads->d_offsets, d_win_offsets, reads->n_reads, reads->read_len, bound, k, w,
                                               hasher, hasher_k, d_word, d_pos, ctx->d_scratch, ctx->n_cu, ctx->stream, &tiled));
+    if (!h_first_bad) return KMX_OK;
+    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->h_pinned[0] != ~0ull) {
+        *h_first_bad = ctx->h_pinned[0];
+        return KMX_E_INVALID_BASE;
+    }
+    return KMX_OK;
+}
+
+/* ------------------------------------------------- SipHash-1-3 (std's DefaultHasher / RandomState) ---- */
+// The counterparts of kmx_canonical_reduce, kmx_histogram and the three minimizer calls with the hash SipHash-1-3(key0, key1; the
+// word's 8 little-endian bytes) -- kmx_hash_words_sip13's.  Same domains, layouts, slots, codes and synchronisation as the
+// counterpart; the kernels are their own (the Lex / identity instantiations are untouched).
+
+int kmx_canonical_reduce_sip13(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t key0, uint64_t key1, uint32_t flags,
+                               kmx_summary* d_out) {
+    if (!ctx || !reads_ok(reads) || !d_out) return KMX_E_ARG;
+    if (k < 1 || k > 31) return KMX_E_K_RANGE;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(kmx_summary), ctx->stream));
+    if (reads->n_reads == 0) return KMX_OK;
+    const bool want_sumfw = (flags & KMX_REDUCE_SUM_FW) != 0;
+    // (the ticket heads are cleared unconditionally: this scan does not put them back, and a captured graph must hold the clear)
+    KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
+    bool handled = false;
+    KMX_HIP(ctx, kmx::launch_scan_reduce_sip(reads->d_bases, reads->n_reads, reads->read_len, k, key0, key1, want_sumfw, d_out,
+                                             ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, reads->d_offsets));
+    if (handled) return KMX_OK;
+    // k = 1, reads above 256 bases, a misaligned ragged d_bases: a lane per read
+    KMX_HIP(ctx, kmx::launch_reduce_generic_sip(reads, k, key0, key1, want_sumfw ? 1u : 0u, d_out, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    return KMX_OK;
+}
+
+int kmx_histogram_sip13(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t key0, uint64_t key1, uint32_t log2_buckets,
+                        uint64_t* d_counts) {
+    if (!ctx || !reads_ok(reads) || !d_counts) return KMX_E_ARG;
+    if (k < 1 || k > 31) return KMX_E_K_RANGE;
+    if (log2_buckets > 30) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    ctx->fx_valid = false;   // (the partitioned passes write their id streams over the work buffer)
+    KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
+    bool handled = false;
+    // the routes of kmx_histogram (LDS tables, one- and two-level partitions, device atomics) with the SipHash sinks
+    KMX_HIP(ctx, kmx::launch_hist_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, kmx::KMX_HASH_SIP13_INTERNAL, 0u, log2_buckets,
+                                          d_counts, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, &big_scratch, ctx,
+                                          hist_scratch_budget(ctx->big_bytes, ctx->big_limit), reads->d_offsets, key0, key1));
+    if (handled) return KMX_OK;
+    KMX_HIP(ctx, kmx::launch_histogram_generic_sip(reads, k, key0, key1, log2_buckets, d_counts, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    return KMX_OK;
+}
+
+int kmx_minimizer_words_sip13(kmx_ctx* ctx, const uint64_t* d_words, uint64_t n, uint32_t k, uint32_t width, uint64_t key0,
+                              uint64_t key1, uint64_t* d_mmer, uint32_t* d_offset) {
+    if (!ctx || (n && (!d_words || !d_mmer || !d_offset))) return KMX_E_ARG;
+    if (k < 1 || k > 32 || width < 1 || width > k) return KMX_E_K_RANGE;   // sub_kmer_word asserts pos + width <= k
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_minimizer_words_sip(d_words, n, k, width, key0, key1, d_mmer, d_offset, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_seqvec_minimizers_sip13(kmx_ctx* ctx, const uint64_t* d_words, uint64_t n_reads, uint32_t read_len, uint32_t k, uint32_t w,
+                                uint64_t key0, uint64_t key1, uint64_t* d_word, uint32_t* d_pos) {
+    if (!ctx || (n_reads && (!d_words || !d_word || !d_pos))) return KMX_E_ARG;
+    if (k < 1 || w < 1 || w > k || w > 32) return KMX_E_K_RANGE;
+    if (read_len < k) return KMX_E_ARG;   // SeqVecMinimizerIter::new: assert!(sv.len() >= k)
+    if (n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_seqvec_minimizers_sip(d_words, n_reads, read_len, k, w, key0, key1, d_word, d_pos, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_minimizers_sip13(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, uint32_t w, uint64_t key0,
+                         uint64_t key1, uint64_t* d_word, uint32_t* d_pos, uint64_t* h_first_bad) {
+    if (!ctx || !reads_ok(reads)) return KMX_E_ARG;
+    if (k < 1 || w < 1 || w > k || w > 32) return KMX_E_K_RANGE;
+    if (h_first_bad) *h_first_bad = ~0ull;
+    if (reads->n_reads == 0) return KMX_OK;
+    if (!d_word || !d_pos) return KMX_E_ARG;
+    if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
+    if (!reads->d_offsets && reads->read_len < k) return KMX_E_ARG;   // SeqVecMinimizerIter::new: assert!(sv.len() >= k)
+    DeviceGuard g(ctx->device);
+    if (reads->d_offsets) {
+        // as kmx_minimizers: a batch without a read of k bases returns here (one host round trip for its longest read)
+        uint32_t lo = 0, hi = 0;
+        if (int st = kmx_reads_length_range(ctx, reads->d_offsets, reads->n_reads, &lo, &hi)) return st;
+        if (hi < k) return KMX_OK;
+    }
+    KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch, 0xFF, 8, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_minimizers_reads_sip(reads->d_bases, reads->d_offsets, d_win_offsets, reads->n_reads, reads->read_len, k, w, key0,
+                                                  key1, d_word, d_pos, ctx->d_scratch, ctx->n_cu, ctx->stream));
     if (!h_first_bad) return KMX_OK;
     KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));

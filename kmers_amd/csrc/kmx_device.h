@@ -156,6 +156,38 @@ __device__ __forceinline__ u64 bucket_of(u64 h, u32 log2_buckets) {
     return log2_buckets ? (u64)(bucket_mix((u32)h, (u32)(h >> 32)) >> (32u - log2_buckets)) : 0ull;
 }
 
+// ---- SipHash-1-3 of one u64: hash_one(&DefaultHasher / RandomState, kmer) (kmx.h; hash.rs:4-20).  One full message block
+// m = w (the word's 8 little-endian bytes), then the final block b = 8 << 56 (length in the top byte, no tail bytes).  The one
+// SipHash core of the library: kmx_hash_words_sip13 and every *_sip13 stream call hash through it.  A 64-bit rotate by a
+// constant is two v_alignbit_b32, a rotate by 32 a register swap.
+__device__ __forceinline__ u64 rotl64(u64 x, int b) { return (x << b) | (x >> (64 - b)); }
+__device__ __forceinline__ void sip_round(u64& v0, u64& v1, u64& v2, u64& v3) {
+    v0 += v1; v1 = rotl64(v1, 13); v1 ^= v0; v0 = rotl64(v0, 32);
+    v2 += v3; v3 = rotl64(v3, 16); v3 ^= v2;
+    v0 += v3; v3 = rotl64(v3, 21); v3 ^= v0;
+    v2 += v1; v1 = rotl64(v1, 17); v1 ^= v2; v2 = rotl64(v2, 32);
+}
+// the keyed initial state v0..v3, computed once per launch on the host: a kernel argument, so it sits in SGPRs and only
+// v3 ^= m differs between lanes in the first compression
+struct SipKey {
+    u64 v0, v1, v2, v3;
+};
+__host__ __device__ __forceinline__ SipKey sip_key(u64 k0, u64 k1) {
+    return SipKey{k0 ^ 0x736f6d6570736575ull, k1 ^ 0x646f72616e646f6dull, k0 ^ 0x6c7967656e657261ull, k1 ^ 0x7465646279746573ull};
+}
+__device__ __forceinline__ u64 siphash13(u64 w, const SipKey& key) {
+    u64 v0 = key.v0, v1 = key.v1, v2 = key.v2, v3 = key.v3 ^ w;
+    sip_round(v0, v1, v2, v3); v0 ^= w;
+    const u64 b = 8ull << 56;
+    v3 ^= b; sip_round(v0, v1, v2, v3); v0 ^= b;
+    v2 ^= 0xffull;
+    sip_round(v0, v1, v2, v3); sip_round(v0, v1, v2, v3); sip_round(v0, v1, v2, v3);
+    return v0 ^ v1 ^ v2 ^ v3;
+}
+__device__ __forceinline__ u64 siphash13_u64(u64 w, u64 k0, u64 k1) { return siphash13(w, sip_key(k0, k1)); }
+// the hasher id of the *_sip13 calls inside the library (not an ABI value: kmx.h's hashers stop at KMX_HASH_IDENTITY)
+constexpr u32 KMX_HASH_SIP13_INTERNAL = 0x5313u;
+
 // max over the 64 lanes, returned wave-uniform: DPP inside the 16-lane rows (no LDS round trips), then 4 v_readlane
 __device__ __forceinline__ u32 wave_max_u32(u32 v) {
     auto mx = [](u32 a, u32 b) { return a > b ? a : b; };

@@ -106,24 +106,7 @@ hash_words_kernel(const u64* __restrict__ in, u64 n, u32 hasher, u32 hk, u64* __
     else map_words(in, n, out, [](u64 w) { return w; });
 }
 
-// hash_one(&DefaultHasher / RandomState, kmer): SipHash-1-3 of the word's 8 little-endian bytes (kmx.h; hash.rs:4-20).  One full
-// message block m = w, then the final block b = 8 << 56 (length in the top byte, no tail bytes).
-__device__ __forceinline__ u64 rotl64(u64 x, int b) { return (x << b) | (x >> (64 - b)); }
-__device__ __forceinline__ void sip_round(u64& v0, u64& v1, u64& v2, u64& v3) {
-    v0 += v1; v1 = rotl64(v1, 13); v1 ^= v0; v0 = rotl64(v0, 32);
-    v2 += v3; v3 = rotl64(v3, 16); v3 ^= v2;
-    v0 += v3; v3 = rotl64(v3, 21); v3 ^= v0;
-    v2 += v1; v1 = rotl64(v1, 17); v1 ^= v2; v2 = rotl64(v2, 32);
-}
-__device__ __forceinline__ u64 siphash13_u64(u64 w, u64 k0, u64 k1) {
-    u64 v0 = k0 ^ 0x736f6d6570736575ull, v1 = k1 ^ 0x646f72616e646f6dull, v2 = k0 ^ 0x6c7967656e657261ull, v3 = k1 ^ 0x7465646279746573ull;
-    v3 ^= w; sip_round(v0, v1, v2, v3); v0 ^= w;
-    const u64 b = 8ull << 56;
-    v3 ^= b; sip_round(v0, v1, v2, v3); v0 ^= b;
-    v2 ^= 0xffull;
-    sip_round(v0, v1, v2, v3); sip_round(v0, v1, v2, v3); sip_round(v0, v1, v2, v3);
-    return v0 ^ v1 ^ v2 ^ v3;
-}
+// hash_one(&DefaultHasher / RandomState, kmer): siphash13_u64 (kmx_device.h)
 __global__ void __launch_bounds__(256)
 hash_words_sip13_kernel(const u64* __restrict__ in, u64 n, u64 k0, u64 k1, u64* __restrict__ out) {
     map_words(in, n, out, [k0, k1](u64 w) { return siphash13_u64(w, k0, k1); });

@@ -99,6 +99,42 @@ histogram_generic_kernel(ReadsView rv, u32 k, u32 hasher, u32 hk, u32 log2_bucke
     }
 }
 
+// ---- the SipHash-1-3 forms of the two kernels above (kmx_canonical_reduce_sip13 / kmx_histogram_sip13 outside the scan's domain:
+// k = 1, reads above 256 bases, a misaligned ragged d_bases).  Kernels of their own: the Lex / identity ones keep their code.
+// A lane walks a whole read, so a batch of long reads runs at the rate of its longest lanes (kmx.h).
+__global__ void __launch_bounds__(256)
+reduce_generic_sip_kernel(ReadsView rv, u32 k, SipKey key, u32 want_sumfw, kmx_summary* __restrict__ out) {
+    Acc acc;
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < rv.n_reads; r += stride) {
+        const uint8_t* s;
+        u32 len;
+        rv.span(r, s, len);
+        roll_read(s, len, k, [&](u32, u64 fw, u64 rc) {
+            const u64 canon = fw < rc ? fw : rc;
+            acc.n_valid += 1;
+            acc.sum_canon += canon;
+            acc.xor_hash ^= siphash13(canon, key);
+            if (want_sumfw) acc.sum_fw += fw;
+        });
+    }
+    flush_acc(acc, out, true, want_sumfw != 0);
+}
+
+__global__ void __launch_bounds__(256)
+histogram_generic_sip_kernel(ReadsView rv, u32 k, SipKey key, u32 log2_buckets, u64* __restrict__ counts) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < rv.n_reads; r += stride) {
+        const uint8_t* s;
+        u32 len;
+        rv.span(r, s, len);
+        roll_read(s, len, k, [&](u32, u64 fw, u64 rc) {
+            const u64 h = siphash13(fw < rc ? fw : rc, key);
+            atomicAdd((unsigned long long*)&counts[bucket_of(h, log2_buckets)], 1ull);
+        });
+    }
+}
+
 // ---------------------------------------------------------------- [u64;2] k-mers (U128, roll_read2: kmx_device.h)
 __global__ void __launch_bounds__(256)
 reduce2_generic_kernel(ReadsView rv, u32 k, u32 with_hash, kmx_summary2* __restrict__ out, const u32* __restrict__ gate) {
@@ -550,6 +586,21 @@ hipError_t launch_histogram_generic(const kmx_reads* r, u32 k, u32 hasher, u32 h
     ReadsView rv{r->d_bases, r->n_reads, r->read_len, r->d_offsets, too_long};
     hipLaunchKernelGGL(histogram_generic_kernel, dim3(grid_for(r->n_reads, n_cu)), dim3(256), 0, st, rv, k, hasher, hk,
                        log2_buckets, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_reduce_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 want_sumfw, kmx_summary* out, int n_cu, hipStream_t st,
+                                     unsigned long long* too_long) {
+    ReadsView rv{r->d_bases, r->n_reads, r->read_len, r->d_offsets, too_long};
+    hipLaunchKernelGGL(reduce_generic_sip_kernel, dim3(grid_for(r->n_reads, n_cu)), dim3(256), 0, st, rv, k, sip_key(k0, k1), want_sumfw, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_histogram_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 log2_buckets, u64* counts, int n_cu, hipStream_t st,
+                                        unsigned long long* too_long) {
+    ReadsView rv{r->d_bases, r->n_reads, r->read_len, r->d_offsets, too_long};
+    hipLaunchKernelGGL(histogram_generic_sip_kernel, dim3(grid_for(r->n_reads, n_cu)), dim3(256), 0, st, rv, k, sip_key(k0, k1), log2_buckets,
+                       counts);
     return hipGetLastError();
 }
 

@@ -85,6 +85,57 @@ struct SinkHistLds {
     }
 };
 
+// kmx_histogram_sip13: the bucket of SipHash-1-3(canonical word) (std's DefaultHasher / RandomState, kmx.h).  Sinks of their own, so
+// the sinks above keep their instantiations.  No kMarksDirty: a tile with an invalid byte takes the scan's exact rolling path and no
+// sweep follows (the sweep would have to hash the spoiled windows again).  LDS: a block-private table (<= 2^14 buckets); GLOBAL: one
+// device-scope atomic per window (what the partitioned passes -- SinkHistPartT<3> -- leave over: no scratch, or above 2^28).
+struct HistSipParams {
+    u64* counts;
+    SipKey key;
+    u32 log2_buckets;
+};
+template <bool LDS>
+struct SinkHistSip {
+    u64* counts;
+    u32* tab;
+    SipKey key;
+    u32 b, tid;
+    static constexpr u32 kLdsDwordsPerWave = 0;
+    static constexpr bool kRagged = true;
+    static u32 block_lds_dwords(const HistSipParams& p) { return LDS ? 1u << p.log2_buckets : 0u; }
+    __device__ SinkHistSip(const HistSipParams& p, u32, u32, u32*, u32, u32* block_lds, u32 tid_)
+        : counts(p.counts), tab(block_lds), key(p.key), b(p.log2_buckets), tid(tid_) {
+        if (LDS) {
+            for (u32 j = tid; j < (1u << b); j += 256u) tab[j] = 0;
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ void block_done(u64, u32, u32) {}
+    __device__ __forceinline__ void emit(u64 fw, u64 rc) {
+        const u64 h = siphash13(fw < rc ? fw : rc, key);
+        if (LDS) atomicAdd(&tab[(u32)bucket_of(h, b)], 1u);
+        else atomicAdd((unsigned long long*)&counts[bucket_of(h, b)], 1ull);
+    }
+    __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) { emit(fw, rc); }
+    __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) { emit(fw, rc); }
+    __device__ __forceinline__ void begin_read(u64) {}
+    __device__ __forceinline__ void slow_block(u32) {}
+    __device__ __forceinline__ void tile_slow_begin(u64) {}
+    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
+    __device__ __forceinline__ void tile_slow_end() {}
+    __device__ __forceinline__ void end_read() {}
+    __device__ __forceinline__ void tile_fast_done(u32) {}
+    __device__ __forceinline__ void finish(const HistSipParams&) {
+        if (LDS) {
+            __syncthreads();
+            for (u32 j = tid; j < (1u << b); j += 256u) {
+                const u32 c = tab[j];
+                if (c) atomicAdd((unsigned long long*)&counts[j], (unsigned long long)c);
+            }
+        }
+    }
+};
+
 // Histogram, 2^15..2^22 buckets, pass 1 of 2: scatter the bucket ids into 64 partitions (the top 6 bits of the bucket).
 // Every wave owns a private segment of every partition's stream, so no global cursor and no global atomic is
 // involved.  The low b-6 bits of an id are staged in a ROW-entry ring per partition in the wave's LDS slice: ONE
@@ -221,17 +272,27 @@ hipError_t launch_sweep_hist(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u3
 // the reads of a dirty tile instead of rolling it -- kmx_scan_kernel.h, SinkMarksDirty; a no-op on clean input).
 hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets,
                                u64* counts, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
-                               void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets) {
+                               void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets, u64 k0, u64 k1) {
     *handled = offsets ? scan_domain_ragged(bases, L, k) : scan_domain(bases, n_reads, L, k);
     if (!*handled) return hipSuccess;
+    // hasher KMX_HASH_SIP13_INTERNAL (kmx_histogram_sip13, keys k0 / k1): the SipHash sinks on every route; they do not mark dirty
+    // tiles (they roll them), so no sweep follows their scans
+    const bool sip = hasher == KMX_HASH_SIP13_INTERNAL;
+    const SipKey key = sip_key(k0, k1);
     const HistParams p{counts, hasher, hk, log2_buckets};
-    auto sweep = [&](const uint8_t* b, u64 n, const u64* o) { return launch_sweep_hist(b, n, L, k, hasher, hk, log2_buckets, counts, queue, n_cu, stream, o); };
+    const HistSipParams ps{counts, key, log2_buckets};
+    auto sweep = [&](const uint8_t* b, u64 n, const u64* o) -> hipError_t {
+        if (sip) return hipSuccess;
+        return launch_sweep_hist(b, n, L, k, hasher, hk, log2_buckets, counts, queue, n_cu, stream, o);
+    };
     auto atomic_scan = [&](const uint8_t* b, u64 n, const u64* o) -> hipError_t {
-        hipError_t e = dispatch<SinkHist>(b, n, L, k, p, queue, n_cu, stream, NoPre(), o);
+        hipError_t e = sip ? dispatch<SinkHistSip<false>>(b, n, L, k, ps, queue, n_cu, stream, NoPre(), o)
+                           : dispatch<SinkHist>(b, n, L, k, p, queue, n_cu, stream, NoPre(), o);
         return e != hipSuccess ? e : sweep(b, n, o);
     };
     if (log2_buckets <= 14u) {
-        hipError_t e = dispatch<SinkHistLds>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
+        hipError_t e = sip ? dispatch<SinkHistSip<true>>(bases, n_reads, L, k, ps, queue, n_cu, stream, NoPre(), offsets)
+                           : dispatch<SinkHistLds>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
         return e != hipSuccess ? e : sweep(bases, n_reads, offsets);
     }
     if (log2_buckets >= 23u && log2_buckets <= 28u && get_scratch != nullptr && n_reads >= 4096u) {
@@ -254,7 +315,8 @@ hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
             const u32 low1 = log2_buckets - 6u;
             for (u64 first = 0; first < n_reads; first += chunk) {
                 const u64 n = n_reads - first < chunk ? n_reads - first : chunk;
-                HistPartParams pp{counts, hasher, hk, log2_buckets, nullptr, nullptr, 0};
+                HistPartSipParams pp{};   // (the key is read by the SipHash sink only; the other modes get the base part)
+                pp.counts = counts; pp.hasher = hasher; pp.hk = hk; pp.log2_buckets = log2_buckets; pp.key = key;
                 u32 n_waves = 0, n_waves2 = 0, cap2 = 0;
                 uint16_t* stream2 = nullptr;
                 u32* seg_len2 = nullptr;
@@ -283,7 +345,8 @@ hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
                 }
                 const uint8_t* cb = offsets ? bases : bases + first * (u64)L;
                 const u64* co = offsets ? offsets + first : nullptr;
-                hipError_t e = dispatch_part_u32(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co);
+                hipError_t e = sip ? dispatch_part_u32(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co)
+                                   : dispatch_part_u32(cb, n, L, k, static_cast<HistPartParams&>(pp), queue, n_cu, stream, make_hist_pre(pre), co);
                 if (e == hipErrorOutOfMemory) {   // no scratch: the atomic sink handles the rest
                     (void)hipGetLastError();
                     return atomic_scan(cb, n_reads - first, co);
@@ -332,7 +395,8 @@ hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
         if (chunk >= 4096u) {
             for (u64 first = 0; first < n_reads; first += chunk) {
                 const u64 n = n_reads - first < chunk ? n_reads - first : chunk;
-                HistPartParams pp{counts, hasher, hk, log2_buckets, nullptr, nullptr, 0};
+                HistPartSipParams pp{};   // (the key is read by the SipHash sink only; the other modes get the base part)
+                pp.counts = counts; pp.hasher = hasher; pp.hk = hk; pp.log2_buckets = log2_buckets; pp.key = key;
                 u32 n_waves = 0;
                 auto pre = [&](u64 grid) -> bool {
                     n_waves = (u32)(grid * 4u);
@@ -356,7 +420,8 @@ hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
                 // (ragged reads: the offsets are absolute, the chunk is a window into them)
                 const uint8_t* cb = offsets ? bases : bases + first * (u64)L;
                 const u64* co = offsets ? offsets + first : nullptr;
-                hipError_t e = dispatch_part<HistPartPre>(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co);
+                hipError_t e = sip ? dispatch_part<HistPartPre>(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co)
+                                   : dispatch_part<HistPartPre>(cb, n, L, k, static_cast<HistPartParams&>(pp), queue, n_cu, stream, make_hist_pre(pre), co);
                 if (e == hipErrorOutOfMemory) {   // no scratch: the atomic sink handles the rest
                     (void)hipGetLastError();
                     return atomic_scan(cb, n_reads - first, co);

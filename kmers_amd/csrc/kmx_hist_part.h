@@ -5,6 +5,8 @@
 // compile in parallel (together they took 3.6 minutes, twice the rest of the library).
 #pragma once
 // (the 64-byte rows of pass 1 are plain stores: with the nt hint they measured -0.2 ... +2 %, inside the noise)
+#include <type_traits>
+
 #include "kmx_scan_kernel.h"
 
 namespace kmx {
@@ -28,10 +30,17 @@ struct HistPartParams {
     u32* seg_len;       // [n_waves][64]
     u32 cap;            // entries per (wave, partition) segment, multiple of 64
 };
+// MODE 3 (kmx_histogram_sip13): the same plus the keyed SipHash-1-3 state -- a type of its own, so that the kernels of modes 0..2 keep
+// their parameter block as it was
+struct HistPartSipParams : HistPartParams {
+    SipKey key;
+};
 // MODE (how the hash of a window comes about, fixed at compile time: three uniform branches per window otherwise):
 //   0 LexHasher with hasher_k == k: hash = the 2k-bit complement of the LARGER of fw / rc (kmx_device.h lex_hash: the
 //     reversed groups of the canonical word are the complement of the other strand) -- no hash arithmetic at all;
-//   1 identity: hash = the smaller of the two;   2 LexHasher with another hasher_k.
+//   1 identity: hash = the smaller of the two;   2 LexHasher with another hasher_k;
+//   3 SipHash-1-3 of the smaller of the two (kmx_histogram_sip13): no marks -- a tile with an invalid byte is rolled, exactly, and the
+//     sweep behind the scan finds nothing to take back.
 // E (round 3): the stream's entry type.  uint16_t: up to 16 low bits per id (2^15..2^22 buckets).  u32: the whole bucket --
 // the first level of the TWO-level partition of 2^23..2^28 buckets (hist_repartition_kernel splits every partition's u32 stream
 // once more, by the next six bits, into uint16_t streams).  A ring is 128 bytes either way: 64 or 32 entries.
@@ -48,10 +57,11 @@ struct SinkHistPartT {
     static constexpr u32 kLdsDwordsPerWave = 2u * NP + NP / 4u;
     static constexpr u32 kBlockLdsAlign = 2048u;   // dwords (8 KB)
     static constexpr bool kRagged = true;
-    static constexpr bool kMarksDirty = true;   // (a tile with an invalid byte: fast path + marks, kmx_scan_kernel.h; launch_hist_uniform sweeps behind every scan)   // (ragged reads come window by window through fast(): no batches)
+    static constexpr bool kMarksDirty = MODE != 3;   // (a tile with an invalid byte: fast path + marks, kmx_scan_kernel.h; launch_hist_uniform sweeps behind every scan)   // (ragged reads come window by window through fast(): no batches)
     static constexpr u32 kRingDwords = 4u * NP * 32u;   // 4 waves x 64 rings x 128 bytes
-    static u32 block_lds_dwords(const HistPartParams&) { return kRingDwords; }
-    HistPartParams p;
+    using Params = std::conditional_t<MODE == 3, HistPartSipParams, HistPartParams>;
+    static u32 block_lds_dwords(const Params&) { return kRingDwords; }
+    Params p;
     E* ring;           // [NP][ROW]
     u32* word;         // [NP] appended (mod 2^16) << 16 | written out (mod 2^16)
     u32* cur;          // [NP] ids already in this wave's segment of the partition
@@ -59,7 +69,7 @@ struct SinkHistPartT {
     u64 maskk;
     u32 k, lane, lowbits;
     u32 shift_b, ring_hi, word_rel;   // 32 - log2_buckets; LDS byte address of ring[] >> 13; LDS byte address of word[] minus 4 * (ring_hi << 6)
-    __device__ SinkHistPartT(const HistPartParams& p_, u32 k_, u32, u32* lds, u32 lane_, u32* block_lds, u32 tid)
+    __device__ SinkHistPartT(const Params& p_, u32 k_, u32, u32* lds, u32 lane_, u32* block_lds, u32 tid)
         : p(p_), ring(reinterpret_cast<E*>(block_lds + (tid >> 6) * (NP * 32u))), word(lds), cur(lds + NP),
           maskk(mask2k(k_)), k(k_), lane(lane_), lowbits(p_.log2_buckets - 6u) {
         shift_b = 32u - p.log2_buckets;
@@ -90,7 +100,8 @@ struct SinkHistPartT {
         if constexpr (MODE == 0 && COMPL) h = fw < rc ? fw : rc;
         else if constexpr (MODE == 0) h = (fw < rc ? rc : fw) ^ maskk;
         else if constexpr (MODE == 1) h = fw < rc ? fw : rc;
-        else h = lex_hash(fw < rc ? fw : rc, p.hk);
+        else if constexpr (MODE == 2) h = lex_hash(fw < rc ? fw : rc, p.hk);
+        else h = siphash13(fw < rc ? fw : rc, p.key);
         return bucket_mix((u32)h, (u32)(h >> 32));
     }
     __device__ __forceinline__ u32 bucket_of_window(u64 fw, u64 rc) const { return mix_of_window(fw, rc) >> shift_b; }
@@ -231,7 +242,7 @@ struct SinkHistPartT {
         }
     }
     __device__ __forceinline__ void tile_fast_done(u32) {}
-    __device__ __forceinline__ void finish(const HistPartParams&) {
+    __device__ __forceinline__ void finish(const Params&) {
         flush_rows();
         flush_rows();
         // the tails (< HALF ids per ring), one ring at a time
@@ -256,19 +267,23 @@ struct SinkHistPartT {
 // SUB_BITS = 1 (2^22 buckets: a partition's 2^16-entry table does not fit the LDS): blockIdx.z picks the half of the partition's
 
 template <typename SinkHistPart, typename Pre, bool RAGGED>
-static hipError_t dispatch_part_mode(const uint8_t* bases, u64 n_reads, u32 L, u32 k, HistPartParams& p, unsigned long long* queue,
+static hipError_t dispatch_part_mode(const uint8_t* bases, u64 n_reads, u32 L, u32 k, typename SinkHistPart::Params& p, unsigned long long* queue,
                                      int n_cu, hipStream_t stream, Pre pre, const u64* offsets) {
     const bool big = L > 160 || (RAGGED && L == 0);
-#define KMX_PART(NW, V, DW) launch_one<NW, V, DW, SinkHistPart, HistPartParams, Pre, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets)
+#define KMX_PART(NW, V, DW) launch_one<NW, V, DW, SinkHistPart, typename SinkHistPart::Params, Pre, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets)
     if (k <= 16) return big ? KMX_PART(16, 1, 1) : KMX_PART(10, 1, 1);
     if (k == 17) return big ? KMX_PART(16, 1, 2) : KMX_PART(10, 1, 2);
     return big ? KMX_PART(16, 2, 2) : KMX_PART(10, 2, 2);
 #undef KMX_PART
 }
 
-template <typename Pre, typename E = uint16_t>
-static hipError_t dispatch_part(const uint8_t* bases, u64 n_reads, u32 L, u32 k, HistPartParams& p, unsigned long long* queue,
+template <typename Pre, typename E = uint16_t, typename P = HistPartParams>
+static hipError_t dispatch_part(const uint8_t* bases, u64 n_reads, u32 L, u32 k, P& p, unsigned long long* queue,
                                 int n_cu, hipStream_t stream, Pre pre, const u64* offsets) {
+    if constexpr (std::is_same_v<P, HistPartSipParams>) {   // kmx_histogram_sip13
+        if (offsets) return dispatch_part_mode<SinkHistPartT<3, E>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
+        return dispatch_part_mode<SinkHistPartT<3, E>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
+    } else {
     const int mode = p.hasher != KMX_HASH_LEX ? 1 : p.hk == k ? 0 : 2;
     if constexpr (sizeof(E) == 4) {   // first level of the two-level partition (2^23..2^28 buckets)
         if (offsets) {
@@ -288,6 +303,7 @@ static hipError_t dispatch_part(const uint8_t* bases, u64 n_reads, u32 L, u32 k,
     if (mode == 0) return dispatch_part_mode<SinkHistPartT<0>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
     if (mode == 1) return dispatch_part_mode<SinkHistPartT<1>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
     return dispatch_part_mode<SinkHistPartT<2>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
+    }
 }
 
 // Histogram over uniform or ragged reads.  2^b <= 2^14: block-private LDS tables (SinkHistLds).  2^15..2^22: two passes through
@@ -297,6 +313,8 @@ static hipError_t dispatch_part(const uint8_t* bases, u64 n_reads, u32 L, u32 k,
 
 // first level of the two-level partition (u32 entries): instantiated in kmx_hist32.hip
 hipError_t dispatch_part_u32(const uint8_t* bases, u64 n_reads, u32 L, u32 k, HistPartParams& p, unsigned long long* queue,
+                             int n_cu, hipStream_t stream, HistPartPre pre, const u64* offsets);
+hipError_t dispatch_part_u32(const uint8_t* bases, u64 n_reads, u32 L, u32 k, HistPartSipParams& p, unsigned long long* queue,
                              int n_cu, hipStream_t stream, HistPartPre pre, const u64* offsets);
 
 }  // namespace kmx

@@ -77,6 +77,48 @@ struct SinkReduce {
     __device__ __forceinline__ void finish(const ReduceParams& p) { flush_acc(acc, p.out, FULL && p.want_hash, FULL && p.want_sumfw); }
 };
 
+// kmx_canonical_reduce_sip13: xor of SipHash-1-3(canonical word) over every window (std's DefaultHasher / RandomState, kmx.h).
+// Its own sink, so SinkReduce's instantiations stay as they are.  No kMarksDirty: a tile with an invalid byte takes the scan's
+// exact rolling path, and no sweep follows.  The hash is VALU work (five SipRounds, ~110 instructions per window) far above
+// the scan's own, so this sink is bound by VALU issue, not by HBM.
+struct ReduceSipParams {
+    kmx_summary* out;
+    SipKey key;
+};
+template <bool SUMFW>
+struct SinkReduceSip {
+    Acc acc;
+    SipKey key;
+    static constexpr u32 kLdsDwordsPerWave = 0;
+    static constexpr bool kRagged = true;
+    static u32 block_lds_dwords(const ReduceSipParams&) { return 0; }
+    __device__ SinkReduceSip(const ReduceSipParams& p, u32, u32, u32*, u32, u32*, u32) : key(p.key) {}
+    __device__ __forceinline__ void block_done(u64, u32, u32) {}
+    __device__ __forceinline__ void add(u64 fw, u64 rc) {
+        const u64 canon = fw < rc ? fw : rc;  // canonical_kmer.rs:113-119
+        acc.sum_canon += canon;
+        acc.xor_hash ^= siphash13(canon, key);
+        if (SUMFW) acc.sum_fw += fw;
+    }
+    __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) {
+        add(fw, rc);
+        asm volatile("" : "+v"(acc.sum_canon), "+v"(acc.xor_hash));   // (the accumulation order pinned, as in SinkReduce)
+        if (SUMFW) asm volatile("" : "+v"(acc.sum_fw));
+    }
+    __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) {
+        acc.n_valid += 1;
+        add(fw, rc);
+    }
+    __device__ __forceinline__ void begin_read(u64) {}
+    __device__ __forceinline__ void slow_block(u32) {}
+    __device__ __forceinline__ void tile_slow_begin(u64) {}
+    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
+    __device__ __forceinline__ void tile_slow_end() {}
+    __device__ __forceinline__ void end_read() {}
+    __device__ __forceinline__ void tile_fast_done(u32 nwin) { acc.n_valid += nwin; }
+    __device__ __forceinline__ void finish(const ReduceSipParams& p) { flush_acc(acc, p.out, true, SUMFW); }
+};
+
 struct WindowsParams {
     u64 *fw, *rc, *canon;
     uint8_t* flags;
@@ -511,6 +553,17 @@ hipError_t launch_scan_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
     const ReduceParams p{out, want_hash ? 1u : 0u, want_sumfw ? 1u : 0u};
     if (want_hash || want_sumfw) return dispatch<SinkReduce<true>>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
     return dispatch<SinkReduce<false>>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
+}
+
+// kmx_canonical_reduce_sip13 on the word-domain scan: uniform reads in scan_domain, ragged reads in scan_domain_ragged (the
+// caller zeroes `out` and the queue heads; *handled = false outside the domain)
+hipError_t launch_scan_reduce_sip(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64 k0, u64 k1, bool want_sumfw, kmx_summary* out,
+                                  unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled, const u64* offsets) {
+    *handled = offsets ? scan_domain_ragged(bases, L, k) : scan_domain(bases, n_reads, L, k);
+    if (!*handled) return hipSuccess;
+    const ReduceSipParams p{out, sip_key(k0, k1)};
+    if (want_sumfw) return dispatch<SinkReduceSip<true>>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
+    return dispatch<SinkReduceSip<false>>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
 }
 
 hipError_t launch_sweep_windows(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags,
