@@ -368,6 +368,20 @@ pub fn histogram_sip13(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, 
     d_counts.download::<u64>(nb)
 }
 
+/// Exact count of the canonical k-mers of a uniform batch already on the device (`kmx_count_canonical`): the distinct
+/// canonical words in ascending order with how many windows yield each.  `d_kmers` / `d_counts` hold at least `max_distinct`
+/// u64 each; Err(KMX_E_NOMEM) if the batch has more distinct k-mers (or its working set is above the work buffer's cap).
+pub fn count_canonical(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, d_kmers: &DeviceBuf<'_>,
+                       d_counts: &DeviceBuf<'_>, max_distinct: u64) -> Result<u64, KmxError> {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(max_distinct as u128 * 8 <= d_kmers.len().min(d_counts.len()) as u128, "outputs shorter than max_distinct");
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    let mut n_distinct = 0u64;
+    ctx.ck(unsafe { kmx_count_canonical(ctx.0, &r, k as u32, d_kmers.as_mut_ptr::<u64>(), d_counts.as_mut_ptr::<u64>(), max_distinct,
+                                        &mut n_distinct) })?;
+    Ok(n_distinct)
+}
+
 /// `Kmer::minimizer_word(word, k, width, &state)` (kmer.rs:170-192) with a std hasher state: `(minimizer, offset)` per word
 pub fn minimizer_words_sip13(ctx: &HipContext, words: &[u64], k: u8, width: u8, keys: (u64, u64)) -> Result<Vec<(u64, u32)>, KmxError> {
     let bytes = unsafe { std::slice::from_raw_parts(words.as_ptr() as *const u8, words.len() * 8) };

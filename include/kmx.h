@@ -201,6 +201,34 @@ int kmx_histogram(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint32_t has
 int kmx_histogram_sip13(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint64_t key0, uint64_t key1,
                         uint32_t log2_buckets, uint64_t *d_counts);
 
+/* ---------------------------------------------------------------- exact k-mer counting ----
+ * Exact count of the canonical k-mers of a batch (BUILD-DEFINED: the reference crate has no counter; the result is the multiset
+ * CanonicalKmerIterator yields, canonical_kmer_iterator.rs:42-116, of get_canonical_word(), canonical_kmer.rs:113-119):
+ * d_kmers[i] = the i-th distinct canonical word in ASCENDING order, d_counts[i] = how many windows yield it (u64, as kmx_histogram).
+ * Windows holding a byte outside ACGTacgt are skipped as the iterator skips them (no error).  k in [1,31]; every input
+ * kmx_canonical_windows accepts (uniform reads of any length, ragged reads with any bound, any d_bases alignment).  The table is
+ * deterministic: the same input gives bit-identical output on every run.
+ * *h_n_distinct (host) = the number of distinct k-mers.  If it exceeds max_distinct nothing is written, KMX_E_NOMEM is returned and
+ * *h_n_distinct is set (the convention of kmx_fastx_parse's max_reads); with d_kmers == d_counts == NULL only the count is computed.
+ * Working set: the call's arrays live in the context's work buffer (kmx_ctx_set_work_buffer_limit) -- at most 20 bytes per window
+ * + 1 MiB (uniform reads: windows = n_reads * (read_len - k + 1); ragged reads: the batch's number of BASES stands for the windows,
+ * plus 9 bytes per read), and reads longer than 256 bases add their segment plan (24 bytes per segment of at most 257 - k windows).
+ * A batch above the cap (the automatic one: an eighth of the device memory, at least 8 GiB, at most half of what is free) returns
+ * KMX_E_NOMEM BEFORE any kernel runs and writes nothing.  Split larger inputs into batches and combine their tables with
+ * kmx_count_merge: at k = 31 a 150 bp read has 120 windows (2400 bytes), so 3.5e6 such reads fit the 8 GiB floor of the automatic
+ * cap and 1.5e7 fit it on a device of 288 GB.  The call uses the work buffer: a following kmx_fastx_parse cannot reuse its chunk
+ * prefixes (KMX_FASTX_SAME_TEXT is then ignored).
+ * Synchronous (the count comes back to the host; one host round trip per 8 bits of key that a partition still needs, at most
+ * ceil(2k / 8), plus two or three): not capturable in a HIP graph. */
+int kmx_count_canonical(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint64_t *d_kmers, uint64_t *d_counts,
+                        uint64_t max_distinct, uint64_t *h_n_distinct);
+/* Union of two count tables as kmx_count_canonical writes them (ascending, distinct): equal k-mers are merged and their counts
+ * added.  Same max_out / KMX_E_NOMEM / NULL-output convention; *h_n_out = the number of distinct k-mers of the union.  Outputs must
+ * not alias inputs.  Working set in the work buffer: 16 bytes per input entry + 1 MiB.  Synchronous. */
+int kmx_count_merge(kmx_ctx *ctx, const uint64_t *d_kmers_a, const uint64_t *d_counts_a, uint64_t n_a, const uint64_t *d_kmers_b,
+                    const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers_out, uint64_t *d_counts_out, uint64_t max_out,
+                    uint64_t *h_n_out);
+
 /* Deterministic synthetic reads (BUILD-DEFINED; the reference bench input is unseeded,
  * benches/simple_benchmark.rs:59-65): byte g of the stream = "ACGT"[(splitmix64(seed + g/32) >> 2*(g%32)) & 3].
  * Writes nbytes bytes for stream positions [first_byte, first_byte+nbytes). */

@@ -171,6 +171,38 @@ class Context:
         return outs
 
     @_on_ctx_stream
+    def count_canonical(self, bases, n_reads, read_len, k, offsets=None, max_distinct=None):
+        """kmx_count_canonical -> (kmers, counts): the distinct canonical k-mers of the batch in ascending order and how many
+        windows yield each (int64 device tensors holding u64 words, trimmed to the number of distinct k-mers).  Without
+        `max_distinct` the buffers are sized to the batch's window count; with it, KmxError (KMX_E_NOMEM) if there are more."""
+        if max_distinct is None:
+            if offsets is None:
+                max_distinct = int(n_reads) * max(int(read_len) - int(k) + 1, 0)
+            else:
+                lens = offsets[1:] - offsets[:-1]
+                max_distinct = int((lens - int(k) + 1).clamp_(min=0).sum().item()) if int(n_reads) > 0 else 0
+        kmers = self.empty(max(max_distinct, 1), torch.int64)
+        counts = self.empty(max(max_distinct, 1), torch.int64)
+        nd = C.c_uint64(0)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_count_canonical(self._h, C.byref(r), k, _ptr(kmers), _ptr(counts), int(max_distinct), C.byref(nd)))
+        return kmers[:nd.value], counts[:nd.value]
+
+    @_on_ctx_stream
+    def count_merge(self, kmers_a, counts_a, kmers_b, counts_b, max_out=None):
+        """kmx_count_merge -> (kmers, counts): the union of two tables of count_canonical, counts of equal k-mers added."""
+        na, nb = int(kmers_a.numel()), int(kmers_b.numel())
+        if max_out is None:
+            max_out = na + nb
+        kmers = self.empty(max(max_out, 1), torch.int64)
+        counts = self.empty(max(max_out, 1), torch.int64)
+        n = C.c_uint64(0)
+        self._ck(self.lib.kmx_count_merge(self._h, _ptr(kmers_a) if na else None, _ptr(counts_a) if na else None, na,
+                                          _ptr(kmers_b) if nb else None, _ptr(counts_b) if nb else None, nb, _ptr(kmers), _ptr(counts),
+                                          int(max_out), C.byref(n)))
+        return kmers[:n.value], counts[:n.value]
+
+    @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:
         out = self.empty(5, torch.int64)
         r = self._reads(bases, n_reads, read_len, offsets)

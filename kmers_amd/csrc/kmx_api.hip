@@ -127,6 +127,18 @@ hipError_t launch_minimizers_reads_sip(const uint8_t* bases, const u64* offsets,
                                        u64 k0, u64 k1, u64* out_word, u32* out_pos, unsigned long long* first_bad, int n_cu, hipStream_t st);
 hipError_t launch_seqvec_minimizers_sip(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u64 k0, u64 k1, u64* out_word, u32* out_pos,
                                         int n_cu, hipStream_t st);
+// kmx_count.hip
+size_t count_area_bytes(u64 n_win);
+size_t win_offsets_bytes(u64 n_reads);
+hipError_t launch_count_win_offsets(const u64* offsets, u64 n_reads, u32 k, void* area, u64** wo_out, unsigned long long* h_pinned,
+                                    u64* h_total, hipStream_t st);
+hipError_t launch_count_sort(u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
+                             u64* h_distinct, bool* bad, hipStream_t st);
+hipError_t launch_count_emit(const u64* canon, u64 n_win, u64 n_valid, void* area, u64* out_k, u64* out_c, hipStream_t st);
+size_t count_merge_bytes(u64 n);
+hipError_t launch_count_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
+                              u64* h_out, hipStream_t st);
+hipError_t launch_count_merge_emit(u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
 }  // namespace kmx
 
 using kmx::u32;
@@ -721,6 +733,127 @@ int kmx_canonical_windows(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* 
         if (handled) return KMX_OK;
     }
     KMX_HIP(ctx, kmx::launch_windows_generic(reads, d_win_offsets, k, d_fw, d_rc, d_canon, d_flags, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    return KMX_OK;
+}
+
+// Exact counting (kmx_count_canonical): the windows' canonical words and flags through kmx_canonical_windows -- every route it
+// takes, the segment plan of long reads included -- into the context's work buffer, then the partition / leaf sort of
+// kmx_count.hip.  The work buffer is laid out up front, before any kernel runs: [segment plan of long reads][ragged: window
+// offsets][canon 8 B/window][flags 1 B/window][count area: keys 8 B/window, keep 1 B/window, level arrays].  The plan sits at the
+// buffer's start, where the routes of kmx_canonical_windows ask for it (capped_scratch), so it never overlaps the arrays behind it.
+static size_t count_plan_bytes(const kmx_reads* reads, uint32_t k, uint64_t n_bases) {
+    const bool aligned = (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u;
+    if (k < 2u || reads->read_len <= 256u) return 0;
+    if (!reads->d_offsets) {
+        if (!aligned) return 0;
+        const uint32_t L = reads->read_len, W = L - k + 1u, J = (W + (257u - k) - 1u) / (257u - k);
+        return kmx::uniform_segments_scratch_bytes(reads->n_reads * J);
+    }
+    if (!aligned) return 0;
+    return kmx::segments_scratch_bytes(reads->n_reads, kmx::segments_capacity(reads->n_reads, n_bases, 257u - k), true);
+}
+
+static size_t a256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+int kmx_count_canonical(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t* d_kmers, uint64_t* d_counts, uint64_t max_distinct,
+                        uint64_t* h_n_distinct) {
+    if (!ctx || !reads_ok(reads) || !h_n_distinct || ((d_kmers == nullptr) != (d_counts == nullptr))) return KMX_E_ARG;
+    if (k < 1 || k > 31) return KMX_E_K_RANGE;
+    *h_n_distinct = 0;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    // the windows the arrays are sized for: exact for uniform reads, the number of bases (a bound) for ragged ones
+    uint64_t n_bound = 0, n_bases = 0;
+    if (reads->d_offsets) {
+        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->h_pinned[1] < ctx->h_pinned[0]) return KMX_E_ARG;
+        if (ctx->h_pinned[1] - ctx->h_pinned[0] >= (1ull << 40)) return KMX_E_NOMEM;
+        n_bases = n_bound = ctx->h_pinned[1] - ctx->h_pinned[0];
+    } else {
+        if (reads->read_len < k) return KMX_OK;   // no window
+        const uint64_t w = reads->read_len - k + 1u;
+        if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
+        n_bound = reads->n_reads * w;
+    }
+    if (n_bound == 0) return KMX_OK;
+    const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
+    const size_t wo_bytes = reads->d_offsets ? a256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
+    const size_t canon_at = plan + wo_bytes, flags_at = canon_at + a256(8u * n_bound), area_at = flags_at + a256(n_bound);
+    const size_t bytes = area_at + kmx::count_area_bytes(n_bound);
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (bytes > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_count_canonical: %zu bytes of working set above the work buffer's cap of %zu",
+                      bytes, budget);
+        return KMX_E_NOMEM;
+    }
+    char* base = static_cast<char*>(big_scratch(ctx, bytes));
+    if (!base) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_count_canonical: no memory for %zu bytes of working set", bytes);
+        return KMX_E_NOMEM;
+    }
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    const unsigned long long allocs = ctx->big_allocs;
+    uint64_t n_win = n_bound;
+    uint64_t* wo = nullptr;
+    if (reads->d_offsets) {
+        KMX_HIP(ctx, kmx::launch_count_win_offsets(reads->d_offsets, reads->n_reads, k, base + plan, &wo, ctx->h_pinned, &n_win, ctx->stream));
+        if (n_win > n_bound) return fail_hip(ctx, hipErrorUnknown, "kmx_count_canonical: window count above its bound");
+        if (n_win == 0) return KMX_OK;
+    }
+    uint64_t* canon = reinterpret_cast<uint64_t*>(base + canon_at);
+    uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
+    if (int st = kmx_canonical_windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
+    if (ctx->d_big != base || ctx->big_allocs != allocs) return fail_hip(ctx, hipErrorUnknown, "kmx_count_canonical: work buffer moved");
+    uint64_t n_valid = 0, n_distinct = 0;
+    bool bad = false;
+    // (the count area is laid out for the n_win windows there are, inside the bytes reserved for n_bound >= n_win)
+    void* area = base + area_at;
+    KMX_HIP(ctx, kmx::launch_count_sort(canon, flags, n_win, k, area, ctx->h_pinned, &n_valid, &n_distinct, &bad, ctx->stream));
+    if (bad) return fail_hip(ctx, hipErrorUnknown, "kmx_count_canonical: partition arrays above their bounds");
+    *h_n_distinct = n_distinct;
+    if (!d_kmers || n_distinct == 0) return KMX_OK;
+    if (n_distinct > max_distinct) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_count_canonical: %llu distinct k-mers, room for %llu",
+                      (unsigned long long)n_distinct, (unsigned long long)max_distinct);
+        return KMX_E_NOMEM;
+    }
+    KMX_HIP(ctx, kmx::launch_count_emit(canon, n_win, n_valid, area, d_kmers, d_counts, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_merge(kmx_ctx* ctx, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a, const uint64_t* d_kmers_b,
+                    const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers_out, uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
+    if (!ctx || !h_n_out || ((d_kmers_out == nullptr) != (d_counts_out == nullptr))) return KMX_E_ARG;
+    if ((n_a && (!d_kmers_a || !d_counts_a)) || (n_b && (!d_kmers_b || !d_counts_b))) return KMX_E_ARG;
+    if (n_a > (1ull << 40) || n_b > (1ull << 40)) return KMX_E_ARG;
+    *h_n_out = 0;
+    const uint64_t n = n_a + n_b;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    const size_t bytes = kmx::count_merge_bytes(n);
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (bytes > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_count_merge: %zu bytes of working set above the work buffer's cap of %zu",
+                      bytes, budget);
+        return KMX_E_NOMEM;
+    }
+    void* area = big_scratch(ctx, bytes);
+    if (!area) return KMX_E_NOMEM;
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    uint64_t n_out = 0;
+    KMX_HIP(ctx, kmx::launch_count_merge(d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, ctx->h_pinned, &n_out, ctx->stream));
+    *h_n_out = n_out;
+    if (!d_kmers_out) return KMX_OK;
+    if (n_out > max_out) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_count_merge: %llu distinct k-mers, room for %llu", (unsigned long long)n_out,
+                      (unsigned long long)max_out);
+        return KMX_E_NOMEM;
+    }
+    KMX_HIP(ctx, kmx::launch_count_merge_emit(n, area, d_kmers_out, d_counts_out, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
 }
 
