@@ -26,7 +26,7 @@ SOURCES = ["kmx_sweep.hip", "kmx_hist.hip", "kmx_hist32.hip", "kmx_bitslice.hip"
            "kmx_bitslice_ragged_k9_12.hip", "kmx_bitslice_ragged_k13_16.hip", "kmx_bitslice_ragged_k17_20.hip", "kmx_bitslice_ragged_k21_24.hip", "kmx_bitslice_ragged_k25_28.hip",
            "kmx_bitslice_ragged_k29_31.hip", "kmx_bitslice_ragged2_k33_36.hip", "kmx_bitslice_ragged2_k37_40.hip", "kmx_bitslice_ragged2_k41_44.hip", "kmx_bitslice_ragged2_k45_48.hip", "kmx_bitslice_ragged2_k49_52.hip", "kmx_bitslice_ragged2_k53_56.hip", "kmx_bitslice_ragged2_k57_60.hip", "kmx_bitslice_ragged2_k61_64.hip", "kmx_generic.hip", "kmx_segments.hip", "kmx_elem.hip", "kmx_seqvec.hip", "kmx_minimizers.hip", "kmx_sip13.hip", "kmx_fastx.hip", "kmx_count.hip", "kmx_comm.hip", "kmx_api.hip"]
 HEADERS = [os.path.join(CSRC, "kmx_device.h"), os.path.join(CSRC, "kmx_hist_part.h"), os.path.join(CSRC, "kmx_bitslice_kernel.h"), os.path.join(CSRC, "kmx_internal.h"), os.path.join(CSRC, "kmx_scan_kernel.h"),
-           os.path.join(HERE, "..", "include", "kmx.h")]
+           os.path.join(CSRC, "kmx_layout.h"), os.path.join(CSRC, "kmx_launch.h"), os.path.join(HERE, "..", "include", "kmx.h")]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
             "-fno-gpu-rdc", "-munsafe-fp-atomics"]
@@ -48,7 +48,8 @@ def _stale(target: str, deps: list[str]) -> bool:
 
 
 def _headers_of(src: str) -> list[str]:
-    """the headers a source depends on (the two kernel headers are each included by their own few translation units)"""
+    """the headers a source depends on (the kernel headers are each included by their own few translation units; the rest --
+    kmx_device.h, kmx_internal.h, kmx_layout.h, kmx_launch.h, kmx.h -- count for every source)"""
     out = []
     for h in HEADERS:
         base = os.path.basename(h)

@@ -9,140 +9,7 @@
 #include <new>
 
 #include "kmx_internal.h"
-
-namespace kmx {
-typedef uint32_t u32;
-typedef uint64_t u64;
-// kmx_scan.hip
-hipError_t launch_scan_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
-                               kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
-                               const u64* offsets);
-hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets,
-                               u64* counts, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
-                               void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets, u64 k0 = 0,
-                               u64 k1 = 0);
-hipError_t launch_windows_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon,
-                                  uint8_t* flags, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
-hipError_t launch_windows_ragged(const uint8_t* bases, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L, u32 k,
-                                 u64* fw, u64* rc, u64* canon, uint8_t* flags, unsigned long long* queue, int n_cu,
-                                 hipStream_t stream, bool* handled, const u64* ends = nullptr /* the reads' ends: nullptr = offsets + 1 */);
-size_t uniform_segments_scratch_bytes(u64 n_seg);
-hipError_t launch_uniform_segments_plan(u64 n_reads, u32 L, u32 k, u32 T, void* scratch, const u64** starts, const u64** ends, const u64** wins, u64* n_seg_out,
-                                        hipStream_t stream);
-// kmx_bitslice.hip
-hipError_t launch_scan_bitsliced(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, u32 mode /* KMX_BS_* (kmx_device.h): bit 0 = sum_fw */,
-                                 kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
-hipError_t launch_sweep_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw, kmx_summary* out,
-                                unsigned long long* queue, int n_cu, hipStream_t stream);
-hipError_t launch_scan_bitsliced2(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, kmx_summary2* out,
-                                  unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
-u64 bitsliced_segments_per_read(u32 L, u32 k);
-hipError_t launch_scan_bitsliced2_ragged(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 L_hint, u32 k, bool want_hash,
-                                         kmx_summary2* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
-                                         const u64* ends = nullptr);
-hipError_t launch_scan_bitsliced_ragged(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 L_hint, u32 k, bool want_hash,
-                                        kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
-                                        bool want_sumfw = false, const u64* ends = nullptr /* the reads' ends: nullptr = offsets + 1 */);
-// kmx_segments.hip
-size_t segments_scratch_bytes(u64 n_reads, u64 seg_capacity, bool with_wins = false);
-u64 segments_capacity(u64 n_reads, u64 total_bases, u32 t_max);
-hipError_t launch_segments_build(const u64* offsets, u64 n_reads, u32 k, u32 t_max, u64 seg_capacity, void* scratch,
-                                 const u64** starts_out, const u64** ends_out, const u64** total_out, unsigned long long* too_long,
-                                 hipStream_t stream, const u64* win_offsets = nullptr, const u64** wins_out = nullptr);
-hipError_t launch_scan_bitsliced_packed(const uint64_t* words, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
-                                        kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
-// kmx_fastx.hip
-size_t fastx_scratch_bytes(u64 n_bytes);
-hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st);
-hipError_t launch_fastx_emit(const uint8_t* text, u64 n, bool fasta, const void* scratch, const unsigned long long* totals,
-                             uint8_t* bases, u64* offsets, hipStream_t st);
-// kmx_seqvec.hip
-hipError_t launch_seqvec_push(u64* words, u64 first, const uint8_t* bytes, u64 n, unsigned long long* first_bad, int n_cu,
-                              hipStream_t st);
-hipError_t launch_seqvec_to_bytes(const u64* words, u64 n, uint8_t* out, int n_cu, hipStream_t st);
-hipError_t launch_seqvec_get_kmers(const u64* words, u64 n_bases, const u64* pos, u64 n, u32 k, u64* out,
-                                   unsigned long long* first_bad, int n_cu, hipStream_t st);
-hipError_t launch_seqvec_iter_kmers(const u64* words, u64 n_bases, u64 start, u64 count, u32 k, u64* out, int n_cu,
-                                    hipStream_t st);
-hipError_t launch_minimizer_words(const u64* in, u64 n, u32 k, u32 w, u32 hasher, u32 hk, u64* out_mm, u32* out_off, int n_cu,
-                                  hipStream_t st);
-hipError_t launch_seqvec_minimizers(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u32 hasher, u32 hk, u64* out_word,
-                                    u32* out_pos, int n_cu, hipStream_t st);
-hipError_t launch_reduce_packed_generic(const u64* words, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
-                                        kmx_summary* out, int n_cu, hipStream_t st);
-// kmx_generic.hip
-hipError_t launch_reduce_generic(const kmx_reads* r, u32 k, u32 hasher, u32 hk, u32 want_sumfw, kmx_summary* out,
-                                 int n_cu, hipStream_t st, unsigned long long* too_long);
-hipError_t launch_windows_generic(const kmx_reads* r, const u64* win_off, u32 k, u64* fw, u64* rc, u64* canon,
-                                  uint8_t* flags, int n_cu, hipStream_t st, unsigned long long* too_long);
-hipError_t launch_histogram_generic(const kmx_reads* r, u32 k, u32 hasher, u32 hk, u32 log2_buckets, u64* counts,
-                                    int n_cu, hipStream_t st, unsigned long long* too_long);
-hipError_t launch_reduce2_generic(const kmx_reads* r, u32 k, u32 with_hash, kmx_summary2* out, int n_cu, hipStream_t st, unsigned long long* too_long,
-                                  const u32* gate);
-hipError_t launch_windows2_tiled(const kmx_reads* r, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags, int n_cu, hipStream_t st,
-                                 bool* handled, unsigned long long* queue);
-hipError_t launch_windows2_tiled_ragged(const kmx_reads* r, const u64* win_offsets, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags, int n_cu,
-                                        hipStream_t st, bool* handled, unsigned long long* too_long, const u64* ends, unsigned long long* queue);
-hipError_t launch_windows2_generic(const kmx_reads* r, const u64* win_off, u32 k, u64* fw, u64* rc, u64* canon,
-                                   uint8_t* flags, int n_cu, hipStream_t st, unsigned long long* too_long);
-// kmx_elem.hip
-hipError_t launch_gen_reads(u64 seed, u64 first_byte, uint8_t* out, u64 nbytes, int n_cu, hipStream_t st);
-hipError_t launch_kmers_from_bytes(const uint8_t* seqs, u64 n, u32 k, u64* words, unsigned long long* first_bad, int n_cu,
-                                   hipStream_t st);
-hipError_t launch_revcomp_words(const u64* in, u64 n, u32 k, u64* out, int n_cu, hipStream_t st);
-hipError_t launch_canonical_words(const u64* in, u64 n, u32 k, u64* canon, uint8_t* is_canon, int n_cu, hipStream_t st);
-hipError_t launch_hash_words(const u64* in, u64 n, u32 hasher, u32 hk, u64* out, int n_cu, hipStream_t st);
-hipError_t launch_hash_words_sip13(const u64* in, u64 n, u64 k0, u64 k1, u64* out, int n_cu, hipStream_t st);
-hipError_t launch_match_words(const u64* fw, const u64* rc, const u64* other, u64 n, uint8_t* out, int n_cu, hipStream_t st);
-hipError_t launch_ck_shift(bool append, u64* fw, u64* rc, const uint8_t* bases, u64 n, u32 k, uint8_t* dropped, int n_cu,
-                           hipStream_t st);
-hipError_t launch_encode_kmers(const uint8_t* seqs, u64 n, u32 seq_len, u32 enc, u32 B, u64* words, int n_cu, hipStream_t st);
-hipError_t launch_encode_windows(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 enc, u32 B, u64* words, int n_cu,
-                                 hipStream_t st);
-hipError_t launch_encoding_rev_comp(const u64* in, u64 n, u32 K, u32 comp_lut, u32 B, u64* out, int n_cu, hipStream_t st);
-hipError_t launch_encoding_decode(const u64* in, u64 n, u32 nuc_lut, u32 B, uint8_t* seqs, int n_cu, hipStream_t st);
-hipError_t launch_sub_kmer_words(const u64* in, u64 n, u32 pos, u32 width, u64* out, int n_cu, hipStream_t st);
-hipError_t launch_kmers_to_bytes(const u64* in, u64 n, u32 k, bool upper, uint8_t* out, int n_cu, hipStream_t st);
-hipError_t launch_encode_kmers_bytes(const uint8_t* seqs, u64 n, u32 seq_len, u32 enc, u32 nb, uint8_t* arrays, int n_cu, hipStream_t st);
-hipError_t launch_encoding_rev_comp_bytes(const uint8_t* in, u64 n, u32 K, u32 comp_lut, u32 nb, uint8_t* out, int n_cu, hipStream_t st);
-hipError_t launch_encoding_decode_bytes(const uint8_t* in, u64 total_bytes, u32 nuc_lut, uint8_t* seqs, int n_cu, hipStream_t st);
-hipError_t launch_minimizers_reads(const uint8_t* bases, u64 total_bytes, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L,
-                                   u32 bound, u32 k, u32 w, u32 hasher, u32 hk, u64* out_word, u32* out_pos,
-                                   unsigned long long* first_bad, int n_cu, hipStream_t st, bool* tiled);
-hipError_t launch_calib_stream_read(const uint8_t* buf, u64 nbytes, unsigned long long* out, int n_cu, hipStream_t st);
-hipError_t launch_length_range(const u64* offsets, u64 n_reads, u32* out, int n_cu, hipStream_t st);
-hipError_t launch_offsets_uniform_gate(const u64* offsets, u64 n_reads, u32 bound, u32 k, u32* gate, int n_cu, hipStream_t st);
-hipError_t launch_fix_hash_fold(kmx_summary* out, u32 k, u32 hasher, u32 hk, hipStream_t st);
-// the *_sip13 calls (SipHash-1-3 under std's DefaultHasher / RandomState): kmx_scan.hip, kmx_hist.hip, kmx_generic.hip, kmx_sip13.hip
-constexpr u32 KMX_HASH_SIP13_INTERNAL = 0x5313u;   // the hasher id launch_hist_uniform takes for them (kmx_device.h; not an ABI value)
-hipError_t launch_scan_reduce_sip(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64 k0, u64 k1, bool want_sumfw, kmx_summary* out,
-                                  unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled, const u64* offsets);
-hipError_t launch_reduce_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 want_sumfw, kmx_summary* out, int n_cu, hipStream_t st,
-                                     unsigned long long* too_long);
-hipError_t launch_histogram_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 log2_buckets, u64* counts, int n_cu, hipStream_t st,
-                                        unsigned long long* too_long);
-hipError_t launch_minimizer_words_sip(const u64* in, u64 n, u32 k, u32 w, u64 k0, u64 k1, u64* out_mm, u32* out_off, int n_cu,
-                                      hipStream_t st);
-hipError_t launch_minimizers_reads_sip(const uint8_t* bases, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L, u32 k, u32 w,
-                                       u64 k0, u64 k1, u64* out_word, u32* out_pos, unsigned long long* first_bad, int n_cu, hipStream_t st);
-hipError_t launch_seqvec_minimizers_sip(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u64 k0, u64 k1, u64* out_word, u32* out_pos,
-                                        int n_cu, hipStream_t st);
-// kmx_count.hip
-size_t count_area_bytes(u64 n_win);
-size_t win_offsets_bytes(u64 n_reads);
-hipError_t launch_count_win_offsets(const u64* offsets, u64 n_reads, u32 k, void* area, u64** wo_out, unsigned long long* h_pinned,
-                                    u64* h_total, hipStream_t st);
-hipError_t launch_count_sort(u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
-                             u64* h_distinct, bool* bad, hipStream_t st);
-hipError_t launch_count_emit(const u64* canon, u64 n_win, u64 n_valid, void* area, u64* out_k, u64* out_c, hipStream_t st);
-size_t count_merge_bytes(u64 n);
-hipError_t launch_count_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
-                              u64* h_out, hipStream_t st);
-hipError_t launch_count_merge_emit(u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
-}  // namespace kmx
-
-using kmx::u32;
-using kmx::u64;
+#include "kmx_launch.h"
 
 namespace kmx {
 int fail_hip(kmx_ctx* ctx, hipError_t e, const char* where) {
@@ -150,24 +17,45 @@ int fail_hip(kmx_ctx* ctx, hipError_t e, const char* where) {
     return KMX_E_HIP;
 }
 }  // namespace kmx
-using kmx::DeviceGuard;
-using kmx::fail_hip;
+using namespace kmx;   // (the launchers, kmx_launch.h, are called qualified; the layout's names, kmx_layout.h, are not)
 
 namespace {
 
 void* big_scratch(void* user, size_t bytes);
 
-// Zero the first `bytes` of the context's queue block (ticket heads, then the marked-reads count and the gate) ahead of a launch
-// that takes tickets.  The bit-sliced scans put back what they use (kmx_device.h); every other user leaves its tickets behind.
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
+
+// the words of d_scratch the calls address (kmx_layout.h)
+unsigned long long* queue_of(kmx_ctx* ctx) { return ctx->d_scratch + KMX_S_QUEUE; }
+unsigned long long* too_long_of(kmx_ctx* ctx) { return ctx->d_scratch + KMX_S_TOO_LONG; }
+unsigned long long* first_bad_of(kmx_ctx* ctx) { return ctx->d_scratch + KMX_S_FIRST_BAD; }
+uint32_t* gate_of(kmx_ctx* ctx) { return reinterpret_cast<uint32_t*>(queue_of(ctx) + KMX_Q_GATE); }
+
+// Zero the first `bytes` of the context's queue block (KMX_Q_CLEAR_*) ahead of a launch that takes tickets.  The bit-sliced scans
+// put back what they use (kmx_layout.h); every other user leaves its tickets behind.
 hipError_t queue_clear(kmx_ctx* ctx, size_t bytes) {
     ctx->queue_clean = false;
-    return hipMemsetAsync(ctx->d_scratch + 16, 0, bytes, ctx->stream);
+    return hipMemsetAsync(queue_of(ctx), 0, bytes, ctx->stream);
+}
+
+// The uniform / ragged gate (kmx_canonical_reduce, kmx_canonical_reduce2): armed ahead of offsets_uniform_gate_kernel, which leaves
+// its verdict in it; disarmed (verdict and length) behind the launches that read it, so it is never left armed.
+hipError_t gate_arm(kmx_ctx* ctx) { return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate_of(ctx)), 1, 1, ctx->stream); }
+hipError_t gate_disarm(kmx_ctx* ctx) { return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate_of(ctx)), 0, 2, ctx->stream); }
+
+// The element-wise calls that report their first invalid / out-of-range element: KMX_S_FIRST_BAD is set to "none" (~0) ahead of
+// the launch and read back, with a wait, into `h_bad` (a word of the caller's, or a pinned one) behind it.
+hipError_t first_bad_reset(kmx_ctx* ctx) { return hipMemsetAsync(first_bad_of(ctx), 0xFF, 8, ctx->stream); }
+int first_bad_read(kmx_ctx* ctx, unsigned long long* h_bad) {
+    KMX_HIP(ctx, hipMemcpyAsync(h_bad, first_bad_of(ctx), 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
 }
 
 // The bit-sliced scan blanks the reads that hold an invalid byte out of their tile and leaves their 64-bit mask (8 bytes
 // per tile) for sweep_flagged_kernel (kmx_sweep.hip; kmx_bitslice_kernel.h, "reads with an invalid byte").  The masks are the context's
 // own grow-only array, zeroed when it is allocated; the rolling kernel clears every mask it consumes, so it is all-zero
-// again when a call ends and nothing has to be cleared per call.  Its address sits behind the 32 tile-queue heads (d_scratch[16 + 515]), rewritten only
+// again when a call ends and nothing has to be cleared per call.  Its address sits in the queue block (KMX_Q_MASKS), rewritten only
 // when it changes.  No array: 0, and such tiles take the per-lane path as a whole, as they do for k without a bit-sliced kernel.
 int prepare_dirty_flags(kmx_ctx* ctx, uint64_t n_reads, uint32_t k, bool any_k = false) {
     const uint64_t n_tiles = n_reads >> 6;
@@ -200,10 +88,16 @@ int prepare_dirty_flags(kmx_ctx* ctx, uint64_t n_reads, uint32_t k, bool any_k =
     const unsigned long long want = (unsigned long long)reinterpret_cast<uintptr_t>(buf);
     if (want != ctx->dirty_desc) {
         ctx->dirty_desc = want;
-        hipError_t e = hipMemcpyAsync(ctx->d_scratch + 16 + 515, &ctx->dirty_desc, 8, hipMemcpyHostToDevice, ctx->stream);
+        hipError_t e = hipMemcpyAsync(queue_of(ctx) + KMX_Q_MASKS, &ctx->dirty_desc, 8, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return fail_hip(ctx, e, "dirty-tile flags");
     }
     return KMX_OK;
+}
+
+// The queue block cleared through the gate, then the mask array for `n_reads` reads (prepare_dirty_flags): ahead of a tiled launch.
+int queue_clear_marks(kmx_ctx* ctx, uint64_t n_reads, uint32_t k, bool any_k) {
+    KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
+    return prepare_dirty_flags(ctx, n_reads, k, any_k);
 }
 
 // work buffer of the partitioned histogram: grown on demand (hipFree/hipMalloc synchronise, so only when it must grow),
@@ -323,40 +217,27 @@ static int ctx_create_common(int device, hipStream_t stream, bool owns, kmx_ctx*
     if (device < 0 || device >= count) return KMX_E_ARG;
     kmx_ctx* c = new (std::nothrow) kmx_ctx();
     if (!c) return KMX_E_NOMEM;
-    c->device = device;
+    c->device = device;   // (every other member is zero: the context is value-initialised)
     c->stream = stream;
     c->owns_stream = owns;
-    c->d_scratch = nullptr;
-    c->h_pinned = nullptr;
-    c->h_pub = nullptr;
-    c->pub_token = 0;
-    c->queue_clean = false;
-    c->d_big = nullptr;
-    c->big_bytes = 0;
-    c->big_limit = 0;
-    c->big_allocs = 0;
-    c->dirty_desc = 0;
-    c->d_flags = nullptr;
-    c->flags_bytes = 0;
-    c->last_error[0] = 0;
     DeviceGuard g(device);
     hipDeviceProp_t prop;
     hipError_t e = g.ok ? hipGetDeviceProperties(&prop, device) : hipErrorInvalidDevice;
     if (e == hipSuccess && owns) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_scratch), 8192);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), 64, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_scratch), KMX_SCRATCH_BYTES);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_pinned), KMX_PIN_BYTES, hipHostMallocDefault);
     // (the dirty-list descriptor behind the queue heads starts as "no list"; cleared on the context's own stream so that
     // the clear is ordered before every kernel the context launches)
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_pub), 64, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_scratch, 0, 8192, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_scratch, 0, KMX_SCRATCH_BYTES, c->stream);
     if (e == hipSuccess) {
         // the pinned words as the device addresses them, left in the queue block once (kmx_device.h, KMX_Q_HOST)
         void* dev_view = nullptr;
         e = hipHostGetDevicePointer(&dev_view, c->h_pub, 0);
         if (e == hipSuccess) {
             for (int i = 0; i < 8; ++i) c->h_pub[i] = 0;
-            c->h_pinned[7] = (unsigned long long)reinterpret_cast<uintptr_t>(dev_view);
-            e = hipMemcpyAsync(c->d_scratch + 16 + 517, c->h_pinned + 7, 8, hipMemcpyHostToDevice, c->stream);
+            c->h_pinned[KMX_PIN_HOST_VIEW] = (unsigned long long)reinterpret_cast<uintptr_t>(dev_view);
+            e = hipMemcpyAsync(queue_of(c) + KMX_Q_HOST, c->h_pinned + KMX_PIN_HOST_VIEW, 8, hipMemcpyHostToDevice, c->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
@@ -398,11 +279,11 @@ int kmx_ctx_synchronize(kmx_ctx* ctx) {
     // the sticky flag of the scans: a ragged read of 2^31 bases or more was skipped (kmx.h "Limits").  Read back on the context's
     // own stream into pinned memory, ahead of the one wait: no blocking copy on the null stream (which would also synchronise
     // with every other blocking stream of the process)
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_scratch + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, too_long_of(ctx), 8, hipMemcpyDeviceToHost, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned long long too_long = *ctx->h_pinned;
+    const unsigned long long too_long = ctx->h_pinned[KMX_PIN_READ];
     if (too_long) {
-        KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch + 8, 0, 8, ctx->stream));
+        KMX_HIP(ctx, hipMemsetAsync(too_long_of(ctx), 0, 8, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         std::snprintf(ctx->last_error, sizeof ctx->last_error,
                       "a read of 2^31 bases or more was skipped by a scan since the last kmx_ctx_synchronize (cut such records into overlapping pieces)");
@@ -475,32 +356,94 @@ int kmx_memset(kmx_ctx* ctx, void* d_dst, int value, size_t nbytes) {
 
 /* ------------------------------------------------------------ hot path ---- */
 
+// The first and the last offset of a batch behind an offsets array, read back through the pinned words: one host round trip.
+static int offsets_span(kmx_ctx* ctx, const kmx_reads* reads, uint64_t* first, uint64_t* last) {
+    unsigned long long* const h = ctx->h_pinned + KMX_PIN_READ;
+    KMX_HIP(ctx, hipMemcpyAsync(h, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipMemcpyAsync(h + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *first = h[0];
+    *last = h[1];
+    return KMX_OK;
+}
+
 // Long ragged reads (round 4): the reads of a batch behind an offsets array cut into overlapping segments of at most t_max windows
 // on the device (kmx_segments.hip), in the context's work buffer.  Two host round trips: the first and the last offset (the
 // arrays are sized from the number of bases), then the number of segments.  0: *starts / *ends / *n_seg are set (n_seg may be 0);
 // -1: no scratch (the caller falls back); > 0: a status to return.
 static int long_ragged_segments(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t t_max, const uint64_t** starts, const uint64_t** ends,
                                 uint64_t* n_seg, const uint64_t* win_offsets = nullptr, const uint64_t** wins = nullptr) {
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t o_first = ctx->h_pinned[0], o_last = ctx->h_pinned[1];
+    uint64_t o_first = 0, o_last = 0;
+    if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
     if (!(o_last >= o_first && o_last - o_first < (1ull << 62))) return -1;
     const uint64_t cap = kmx::segments_capacity(reads->n_reads, o_last - o_first, t_max);
     void* scratch = capped_scratch(ctx, kmx::segments_scratch_bytes(reads->n_reads, cap, win_offsets != nullptr));
     if (!scratch) return -1;
     ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
     const uint64_t* d_total = nullptr;
-    KMX_HIP(ctx, kmx::launch_segments_build(reads->d_offsets, reads->n_reads, k, t_max, cap, scratch, starts, ends, &d_total, ctx->d_scratch + 8, ctx->stream,
+    KMX_HIP(ctx, kmx::launch_segments_build(reads->d_offsets, reads->n_reads, k, t_max, cap, scratch, starts, ends, &d_total, too_long_of(ctx), ctx->stream,
                                             win_offsets, wins));
     // (the second and last round trip: how many segments there are -- the bound above is up to one per read too high)
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *n_seg = ctx->h_pinned[0];
+    *n_seg = ctx->h_pinned[KMX_PIN_READ];
     if (*n_seg > cap) return fail_hip(ctx, hipErrorUnknown, "segment count above its bound");
     if (wins != nullptr && *wins != nullptr && *n_seg != 0)     // the slot behind the last segment's windows: the batch's total
         KMX_HIP(ctx, hipMemcpyAsync(const_cast<uint64_t*>(*wins) + *n_seg, win_offsets + reads->n_reads, 8, hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
+}
+
+// Uniform reads longer than a frame (round 4) as segments: as few per read as the 16-word frame allows (at most 257 - k windows),
+// all of *T windows but the last.  Returns how many per read.
+static uint32_t uniform_segments_per_read(uint32_t L, uint32_t k, uint32_t* T = nullptr) {
+    const uint32_t W = L - k + 1u, J = (W + (257u - k) - 1u) / (257u - k);
+    if (T) *T = (W + J - 1u) / J;
+    return J;
+}
+
+// ... planned on the device in the context's work buffer (a start, an end and a first output slot per segment: 24 bytes against the
+// ~1.8 KB a segment writes).  0: *starts / *ends / *wins / *n_seg are set; -1: no scratch (the caller falls back); > 0: a status.
+static int uniform_long_segments(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t** starts, const uint64_t** ends,
+                                 const uint64_t** wins, uint64_t* n_seg) {
+    uint32_t T = 0;
+    const uint32_t J = uniform_segments_per_read(reads->read_len, k, &T);
+    void* scratch = capped_scratch(ctx, kmx::uniform_segments_scratch_bytes(reads->n_reads * J));
+    if (!scratch) return -1;
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    KMX_HIP(ctx, kmx::launch_uniform_segments_plan(reads->n_reads, reads->read_len, k, T, scratch, starts, ends, wins, n_seg, ctx->stream));
+    return 0;
+}
+
+// The windows of reads above the frames (a length or a length bound of more than 256 bases; 16-byte aligned base) as segments of at
+// most 257 - k windows: uniform reads planned, ragged ones cut (above).  0: the segments are set (n_seg may be 0); -1: not such
+// reads, or no scratch (the caller falls back); > 0: a status to return.
+static int long_segments(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* win_offsets, uint32_t k, const uint64_t** starts,
+                         const uint64_t** ends, const uint64_t** wins, uint64_t* n_seg) {
+    if (reads->read_len <= 256u || !aligned16(reads->d_bases)) return -1;
+    if (reads->d_offsets) return win_offsets ? long_ragged_segments(ctx, reads, k, 257u - k, starts, ends, n_seg, win_offsets, wins) : -1;
+    if (win_offsets || reads->n_reads >= (1ull << 40) || (uint64_t)reads->read_len * reads->n_reads >= (1ull << 62)) return -1;
+    return uniform_long_segments(ctx, reads, k, starts, ends, wins, n_seg);
+}
+
+// Segments of long reads (long_segments) materialised by the tiled kernels as reads of their own (a bound of 256).
+static int windows_segments(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* starts, const uint64_t* ends, const uint64_t* wins, uint64_t n_seg,
+                            uint32_t k, uint64_t* d_fw, uint64_t* d_rc, uint64_t* d_canon, uint8_t* d_flags, bool* handled) {
+    if (int st = queue_clear_marks(ctx, n_seg, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st;
+    KMX_HIP(ctx, kmx::launch_windows_ragged(reads->d_bases, starts, wins, n_seg, 256u, k, d_fw, d_rc, d_canon, d_flags, queue_of(ctx), ctx->n_cu,
+                                            ctx->stream, handled, ends));
+    return KMX_OK;
+}
+
+static int windows2_segments(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* starts, const uint64_t* ends, const uint64_t* wins, uint64_t n_seg,
+                             uint32_t k, uint64_t* d_fw2, uint64_t* d_rc2, uint64_t* d_canon2, uint8_t* d_flags, bool* handled) {
+    kmx_reads segs = *reads;
+    segs.d_offsets = starts;
+    segs.n_reads = n_seg;
+    segs.read_len = 256u;
+    if (int st = queue_clear_marks(ctx, n_seg, k, true)) return st;
+    KMX_HIP(ctx, kmx::launch_windows2_tiled_ragged(&segs, wins, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, handled, too_long_of(ctx), ends,
+                                                   queue_of(ctx)));
+    return KMX_OK;
 }
 
 // The body of kmx_canonical_reduce.  `host_mode` (kmx_canonical_reduce_host): KMX_BS_PUBLISH | KMX_BS_NO_SWEEP | token << 8 for
@@ -524,17 +467,17 @@ static int reduce_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_
     const bool want_fold = hasher != KMX_HASH_NONE;
     const bool fix_fold = want_fold && !(hasher == KMX_HASH_LEX && hasher_k == k);
     // Uniform reads on the bit-sliced scan (round 6): its last block STORES the summary and puts the queue block back as it found
-    // it (kmx_device.h), so neither `d_out` nor -- after a launch of that kind -- the queue block is cleared here: two fill kernels
+    // it (kmx_layout.h), so neither `d_out` nor -- after a launch of that kind -- the queue block is cleared here: two fill kernels
     // and the gaps around them were 11 us of the 70 a batch of 1e5 reads took (profiles/r06_small_batches.txt).
     if (!reads->d_offsets) {
         bool handled = false;
-        if (!ctx->queue_clean) KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
+        if (!ctx->queue_clean) KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
         // (reads longer than a frame are scanned as segments: a mask word per 64 of THOSE)
         if (int st = prepare_dirty_flags(ctx, reads->n_reads * kmx::bitsliced_segments_per_read(reads->read_len, k), k)) return st;
         const bool alone = host_mode != 0u && !fix_fold && reads->read_len <= 256u;   // (segments: the sweep's geometry is the launcher's)
         const uint32_t mode = (want_sumfw ? 1u : 0u) | 2u /* KMX_BS_STORE */ | (alone ? host_mode : 0u);
         KMX_HIP(ctx, kmx::launch_scan_bitsliced(reads->d_bases, reads->n_reads, reads->read_len, k, want_fold, mode, d_out,
-                                                ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled));
+                                                queue_of(ctx), ctx->n_cu, ctx->stream, &handled));
         if (handled) {
             ctx->queue_clean = true;
             if (published) *published = alone;
@@ -545,7 +488,7 @@ static int reduce_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_
     KMX_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(kmx_summary), ctx->stream));
     {
         bool handled = false;
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));  // 32 tile-queue heads, 128 B apart, + the "a tile was flagged" word + the uniform/ragged gate
+        KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
         // Reads behind an offsets array with a length bound L that the uniform bit-sliced kernels take: most FASTQ is
         // untrimmed -- every read exactly L bases -- and the uniform kernel is ~1.4x the ragged one.  Decided on the device:
         // a small kernel checks offsets[i] == i*L, both scans are launched behind its verdict, the one it names runs.
@@ -554,36 +497,31 @@ static int reduce_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_
         const uint32_t Lh = reads->read_len ? reads->read_len : 160u;
         // (only where BOTH bit-sliced launchers take the call: the ragged one needs a 16-byte aligned base -- with a misaligned
         // base the uniform scan used to be enqueued behind the gate and the generic kernel then counted the batch a second time)
-        if (reads->d_offsets && !want_sumfw && k >= 9 && k <= 31 && Lh >= k && Lh <= 256 && reads->read_len <= 256 &&
-            (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u) {
-            uint32_t* gate = reinterpret_cast<uint32_t*>(ctx->d_scratch + 16 + 513);
-            KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 1, 1, ctx->stream));
-            KMX_HIP(ctx, kmx::launch_offsets_uniform_gate(reads->d_offsets, reads->n_reads, Lh, k, gate, ctx->n_cu, ctx->stream));
+        if (reads->d_offsets && !want_sumfw && k >= 9 && k <= 31 && Lh >= k && Lh <= 256 && reads->read_len <= 256 && aligned16(reads->d_bases)) {
+            KMX_HIP(ctx, gate_arm(ctx));
+            KMX_HIP(ctx, kmx::launch_offsets_uniform_gate(reads->d_offsets, reads->n_reads, Lh, k, gate_of(ctx), ctx->n_cu, ctx->stream));
             if (int st = prepare_dirty_flags(ctx, reads->n_reads, k)) return st;
             bool h_u = false, h_r = false;
-            KMX_HIP(ctx, kmx::launch_scan_bitsliced(reads->d_bases, reads->n_reads, Lh, k, want_fold, 0u, d_out, ctx->d_scratch + 16,
+            KMX_HIP(ctx, kmx::launch_scan_bitsliced(reads->d_bases, reads->n_reads, Lh, k, want_fold, 0u, d_out, queue_of(ctx),
                                                     ctx->n_cu, ctx->stream, &h_u));
-            if (h_u) {
-                // (the uniform scan took tickets from the queue heads only if it ran; if it did not they are still zero)
+            // (the uniform scan took tickets from the queue heads only if it ran; if it did not they are still zero)
+            if (h_u)
                 KMX_HIP(ctx, kmx::launch_scan_bitsliced_ragged(reads->d_bases, reads->d_offsets, reads->n_reads, Lh, k, want_fold, d_out,
-                                                               ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &h_r));
-                if (h_r) {
-                    KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 0, 2, ctx->stream));   // never left armed
-                    if (fix_fold) KMX_HIP(ctx, kmx::launch_fix_hash_fold(d_out, k, hasher, hasher_k, ctx->stream));
-                    return KMX_OK;
-                }
+                                                               queue_of(ctx), ctx->n_cu, ctx->stream, &h_r));
+            KMX_HIP(ctx, gate_disarm(ctx));   // never left armed
+            if (h_u && h_r) {
+                if (fix_fold) KMX_HIP(ctx, kmx::launch_fix_hash_fold(d_out, k, hasher, hasher_k, ctx->stream));
+                return KMX_OK;
+            }
+            if (h_u) {
                 // The ragged launcher takes every aligned (k, L) the uniform one takes.  Should that ever stop being true, the uniform
                 // scan is already enqueued behind the gate and nothing may run after it: fail loudly, never count twice.
-                KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 0, 2, ctx->stream));
                 KMX_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(kmx_summary), ctx->stream));
                 std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx: internal -- the ragged scan refused k=%u, L<=%u that the uniform scan accepted", k, Lh);
                 return KMX_E_HIP;
-            } else {
-                KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 0, 2, ctx->stream));
             }
         }
-        if (!handled && reads->d_offsets && reads->read_len > 256 && k >= 9 && k <= 31 &&
-            (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u) {
+        if (!handled && reads->d_offsets && reads->read_len > 256 && k >= 9 && k <= 31 && aligned16(reads->d_bases)) {
             // Long ragged reads (a length bound above the frames: PacBio / ONT reads, contigs), round 4: cut into overlapping
             // segments on the device (kmx_segments.hip) and scanned by the ragged bit-sliced kernel as reads of their own.  Two
             // host round trips: the first and the last offset (the segment arrays are sized from the number of bases), then the
@@ -597,24 +535,24 @@ static int reduce_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_
                 if (n_seg == 0) return KMX_OK;   // no read holds a window
                 if (int st2 = prepare_dirty_flags(ctx, n_seg, k)) return st2;
                 KMX_HIP(ctx, kmx::launch_scan_bitsliced_ragged(reads->d_bases, starts, n_seg, t_max + k - 1u, k, want_fold, d_out,
-                                                               ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, want_sumfw, ends));
+                                                               queue_of(ctx), ctx->n_cu, ctx->stream, &handled, want_sumfw, ends));
             }
         }
         if (!handled && reads->d_offsets) {   // ragged reads on the bit-sliced kernel (read_len = optional length bound)
             if (int st = prepare_dirty_flags(ctx, reads->n_reads, k)) return st;
             KMX_HIP(ctx, kmx::launch_scan_bitsliced_ragged(reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, k,
-                                                           want_fold, d_out, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, want_sumfw));
+                                                           want_fold, d_out, queue_of(ctx), ctx->n_cu, ctx->stream, &handled, want_sumfw));
         }
         // word-domain kernel: uniform reads of any (k, L) in its domain, and ragged reads (read_len = optional length bound)
         if (!handled)
             KMX_HIP(ctx, kmx::launch_scan_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, want_fold, want_sumfw,
-                                                  d_out, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, reads->d_offsets));
+                                                  d_out, queue_of(ctx), ctx->n_cu, ctx->stream, &handled, reads->d_offsets));
         if (handled) {
             if (fix_fold) KMX_HIP(ctx, kmx::launch_fix_hash_fold(d_out, k, hasher, hasher_k, ctx->stream));
             return KMX_OK;
         }
     }
-    KMX_HIP(ctx, kmx::launch_reduce_generic(reads, k, hasher, hasher_k, want_sumfw ? 1u : 0u, d_out, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    KMX_HIP(ctx, kmx::launch_reduce_generic(reads, k, hasher, hasher_k, want_sumfw ? 1u : 0u, d_out, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
 }
 
@@ -630,7 +568,7 @@ int kmx_canonical_reduce(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint3
 int kmx_canonical_reduce_host(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t hasher, uint32_t hasher_k,
                               uint32_t flags, kmx_summary* h_out) {
     if (!ctx || !h_out) return KMX_E_ARG;
-    kmx_summary* const d_res = reinterpret_cast<kmx_summary*>(ctx->d_scratch + 16 + 528);   // (eight free words of the queue block)
+    kmx_summary* const d_res = reinterpret_cast<kmx_summary*>(queue_of(ctx) + KMX_Q_RESULT);   // (eight free words of the queue block)
     uint32_t token = (ctx->pub_token + 1u) & 0xFFFFFFu;
     if (token == 0u) token = 1u;                       // (the pinned word starts at 0)
     bool published = false;
@@ -662,11 +600,12 @@ int kmx_canonical_reduce_host(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, 
             return KMX_OK;
         }
         KMX_HIP(ctx, kmx::launch_sweep_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, hasher != KMX_HASH_NONE,
-                                               (flags & KMX_REDUCE_SUM_FW) != 0, d_res, ctx->d_scratch + 16, ctx->n_cu, ctx->stream));
+                                               (flags & KMX_REDUCE_SUM_FW) != 0, d_res, queue_of(ctx), ctx->n_cu, ctx->stream));
     }
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + 2, d_res, sizeof(kmx_summary), hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_SUMMARY, d_res, sizeof(kmx_summary), hipMemcpyDeviceToHost, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    h_out->n_valid = ctx->h_pinned[2]; h_out->sum_canon = ctx->h_pinned[3]; h_out->xor_hash = ctx->h_pinned[4]; h_out->sum_fw = ctx->h_pinned[5];
+    const unsigned long long* const hs = ctx->h_pinned + KMX_PIN_SUMMARY;
+    h_out->n_valid = hs[0]; h_out->sum_canon = hs[1]; h_out->xor_hash = hs[2]; h_out->sum_fw = hs[3];
     return KMX_OK;
 }
 
@@ -680,59 +619,33 @@ int kmx_canonical_windows(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* 
     if (!reads->d_offsets && !d_win_offsets) {   // uniform layout: fast word-domain kernel
         bool handled = false;
         // (the window sinks mark the reads of a tile with an invalid byte and the sweep behind the passes zeroes their spoiled slots: round 6)
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-        if (int st = prepare_dirty_flags(ctx, reads->n_reads, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st;
+        if (int st = queue_clear_marks(ctx, reads->n_reads, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st;
         KMX_HIP(ctx, kmx::launch_windows_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, d_fw, d_rc, d_canon,
-                                                 d_flags, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled));
+                                                 d_flags, queue_of(ctx), ctx->n_cu, ctx->stream, &handled));
         if (handled) return KMX_OK;
-        // Uniform reads longer than a frame (round 4): every read as segments of at most 257 - k windows, each a read of its own for the ragged
-        // materialise kernels (its start, its end, its first output slot: three arrays in the work buffer, 24 bytes per segment against
-        // the ~1.8 KB a segment writes).  16-byte aligned base; no scratch -> the lane-per-read kernel below.
-        const uint32_t L = reads->read_len;
-        if (L > 256 && k >= 2 && k <= 31 /* the tiled materialise kernel's domain: nothing is planned for a k it refuses */ && (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u && reads->n_reads < (1ull << 40) && (uint64_t)L * reads->n_reads < (1ull << 62)) {
-            // (as few segments as the 16-word frame allows, all of the same size but the last)
-            const uint32_t W = L - k + 1u, J = (W + (257u - k) - 1u) / (257u - k), T = (W + J - 1u) / J;
-            const uint64_t n_seg_host = reads->n_reads * J;
-            void* scratch = capped_scratch(ctx, kmx::uniform_segments_scratch_bytes(n_seg_host));
-            if (scratch) {
-                ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
-                const uint64_t *starts = nullptr, *ends = nullptr, *wins = nullptr;
-                uint64_t n_seg = 0;
-                KMX_HIP(ctx, kmx::launch_uniform_segments_plan(reads->n_reads, L, k, T, scratch, &starts, &ends, &wins, &n_seg, ctx->stream));
-                KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-                if (int st = prepare_dirty_flags(ctx, n_seg, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st;
-                KMX_HIP(ctx, kmx::launch_windows_ragged(reads->d_bases, starts, wins, n_seg, 256u, k, d_fw, d_rc, d_canon, d_flags, ctx->d_scratch + 16, ctx->n_cu,
-                                                        ctx->stream, &handled, ends));
-                if (handled) return KMX_OK;
-            }
-        }
     }
-    if (reads->d_offsets && d_win_offsets && reads->read_len > 256 && k >= 2 && (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u) {
-        // long ragged reads (a length bound above the frames), round 4: cut into segments of at most 257 - k windows on the device
-        // (kmx_segments.hip: a start, an end and a first output slot each; two host round trips), materialised as reads of their own
+    // Reads longer than a frame (round 4): segments of at most 257 - k windows, each a read of its own for the ragged materialise
+    // kernels (kmx_segments.hip).  No scratch -> the kernels below.  (k = 1 is outside the tiled kernel's domain: nothing is planned)
+    if (k >= 2) {
         const uint64_t *starts = nullptr, *ends = nullptr, *wins = nullptr;
         uint64_t n_seg = 0;
-        const int st = long_ragged_segments(ctx, reads, k, 257u - k, &starts, &ends, &n_seg, d_win_offsets, &wins);
+        const int st = long_segments(ctx, reads, d_win_offsets, k, &starts, &ends, &wins, &n_seg);
         if (st > 0) return st;
         if (st == 0) {
             if (n_seg == 0) return KMX_OK;      // no read holds a window
             bool handled = false;
-            KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-            if (int st2 = prepare_dirty_flags(ctx, n_seg, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st2;
-            KMX_HIP(ctx, kmx::launch_windows_ragged(reads->d_bases, starts, wins, n_seg, 256u, k, d_fw, d_rc, d_canon, d_flags, ctx->d_scratch + 16, ctx->n_cu,
-                                                    ctx->stream, &handled, ends));
+            if (int st2 = windows_segments(ctx, reads, starts, ends, wins, n_seg, k, d_fw, d_rc, d_canon, d_flags, &handled)) return st2;
             if (handled) return KMX_OK;
         }
     }
     if (reads->d_offsets && d_win_offsets) {     // ragged reads: the tiled word-domain kernel (read_len = optional length bound)
         bool handled = false;
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-        if (int st = prepare_dirty_flags(ctx, reads->n_reads, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st;
+        if (int st = queue_clear_marks(ctx, reads->n_reads, k, k >= 2u /* (k = 1: no sweep behind the passes, so no marks) */)) return st;
         KMX_HIP(ctx, kmx::launch_windows_ragged(reads->d_bases, reads->d_offsets, d_win_offsets, reads->n_reads, reads->read_len, k,
-                                                d_fw, d_rc, d_canon, d_flags, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled));
+                                                d_fw, d_rc, d_canon, d_flags, queue_of(ctx), ctx->n_cu, ctx->stream, &handled));
         if (handled) return KMX_OK;
     }
-    KMX_HIP(ctx, kmx::launch_windows_generic(reads, d_win_offsets, k, d_fw, d_rc, d_canon, d_flags, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    KMX_HIP(ctx, kmx::launch_windows_generic(reads, d_win_offsets, k, d_fw, d_rc, d_canon, d_flags, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
 }
 
@@ -742,14 +655,8 @@ int kmx_canonical_windows(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* 
 // offsets][canon 8 B/window][flags 1 B/window][count area: keys 8 B/window, keep 1 B/window, level arrays].  The plan sits at the
 // buffer's start, where the routes of kmx_canonical_windows ask for it (capped_scratch), so it never overlaps the arrays behind it.
 static size_t count_plan_bytes(const kmx_reads* reads, uint32_t k, uint64_t n_bases) {
-    const bool aligned = (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u;
-    if (k < 2u || reads->read_len <= 256u) return 0;
-    if (!reads->d_offsets) {
-        if (!aligned) return 0;
-        const uint32_t L = reads->read_len, W = L - k + 1u, J = (W + (257u - k) - 1u) / (257u - k);
-        return kmx::uniform_segments_scratch_bytes(reads->n_reads * J);
-    }
-    if (!aligned) return 0;
+    if (k < 2u || reads->read_len <= 256u || !aligned16(reads->d_bases)) return 0;
+    if (!reads->d_offsets) return kmx::uniform_segments_scratch_bytes(reads->n_reads * uniform_segments_per_read(reads->read_len, k));
     return kmx::segments_scratch_bytes(reads->n_reads, kmx::segments_capacity(reads->n_reads, n_bases, 257u - k), true);
 }
 
@@ -765,12 +672,11 @@ int kmx_count_canonical(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64
     // the windows the arrays are sized for: exact for uniform reads, the number of bases (a bound) for ragged ones
     uint64_t n_bound = 0, n_bases = 0;
     if (reads->d_offsets) {
-        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_pinned[1] < ctx->h_pinned[0]) return KMX_E_ARG;
-        if (ctx->h_pinned[1] - ctx->h_pinned[0] >= (1ull << 40)) return KMX_E_NOMEM;
-        n_bases = n_bound = ctx->h_pinned[1] - ctx->h_pinned[0];
+        uint64_t o_first = 0, o_last = 0;
+        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
+        if (o_last < o_first) return KMX_E_ARG;
+        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
+        n_bases = n_bound = o_last - o_first;
     } else {
         if (reads->read_len < k) return KMX_OK;   // no window
         const uint64_t w = reads->read_len - k + 1u;
@@ -865,10 +771,9 @@ int kmx_canonical_reduce2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint
     if (reads->n_reads == 0) return KMX_OK;
     if (!reads->d_offsets) {
         bool handled = false;
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));   // queue heads + the "a tile was flagged" word + the uniform / ragged gate
-        if (int st = prepare_dirty_flags(ctx, reads->n_reads * kmx::bitsliced_segments_per_read(reads->read_len, k), k)) return st;
+        if (int st = queue_clear_marks(ctx, reads->n_reads * kmx::bitsliced_segments_per_read(reads->read_len, k), k, false)) return st;
         KMX_HIP(ctx, kmx::launch_scan_bitsliced2(reads->d_bases, reads->n_reads, reads->read_len, k, with_hash != 0, d_out,
-                                                 ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled));
+                                                 queue_of(ctx), ctx->n_cu, ctx->stream, &handled));
         if (handled) return KMX_OK;
     }
     // Reads behind an offsets array (what kmx_fastx_parse hands over), 16-byte aligned base: the tiled kernels.  With a length bound
@@ -876,9 +781,8 @@ int kmx_canonical_reduce2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint
     // kmx_canonical_reduce does it: a small kernel checks offsets[i] == i*L, the uniform scan and the ragged one (the 10-word frame:
     // the reads themselves with a bound of at most 160 or none, segments of them above) are both launched behind its verdict, exactly one counts.
     const uint32_t Lh = reads->read_len;
-    if (reads->d_offsets && (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u) {
-        uint32_t* gate = reinterpret_cast<uint32_t*>(ctx->d_scratch + 16 + 513);
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
+    if (reads->d_offsets && aligned16(reads->d_bases)) {
+        KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
         // A bound above the 10-word frame (161...: 250-base reads, long reads): the ragged kernel scans SEGMENTS of at most 161 - k
         // windows, cut on the device as kmx_canonical_reduce does for long reads (two host round trips) -- first of all, so that the
         // masks of the dirty reads are sized once for whichever kernel will run.
@@ -890,12 +794,10 @@ int kmx_canonical_reduce2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint
             // (a bound the uniform kernel takes: if the batch holds exactly n_reads * bound bases it is, almost certainly, untrimmed --
             // the gate below will say so for sure -- and the segments would be built for nothing: 16 bytes of offsets tell.  Should
             // the gate disagree, the lane-per-read kernel counts.)
-            KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
             // (round 6: at ANY one length up to the bound -- 150-base reads handed over with a bound of 250 paid the segment cut, three host
             // round trips and a second set of marks, for the uniform kernel to run in the end: the gate passes every uniform length)
-            const uint64_t o_first = ctx->h_pinned[0], o_last = ctx->h_pinned[1];
+            uint64_t o_first = 0, o_last = 0;
+            if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
             if (o_first == 0 && o_last % reads->n_reads == 0 && o_last / reads->n_reads >= k && o_last / reads->n_reads <= Lh) cut = false;
         }
         if (cut) {
@@ -908,24 +810,24 @@ int kmx_canonical_reduce2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint
         bool h_u = false, h_r = false;
         const uint32_t Lg = Lh ? Lh : 160u;   // (round 5: the gate passes reads that are uniform at ANY length up to the bound; no bound = the 160-base frame)
         if (Lg >= k && Lg <= 256) {
-            KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 1, 1, ctx->stream));
-            KMX_HIP(ctx, kmx::launch_offsets_uniform_gate(reads->d_offsets, reads->n_reads, Lg, k, gate, ctx->n_cu, ctx->stream));
-            KMX_HIP(ctx, kmx::launch_scan_bitsliced2(reads->d_bases, reads->n_reads, Lg, k, with_hash != 0, d_out, ctx->d_scratch + 16,
+            KMX_HIP(ctx, gate_arm(ctx));
+            KMX_HIP(ctx, kmx::launch_offsets_uniform_gate(reads->d_offsets, reads->n_reads, Lg, k, gate_of(ctx), ctx->n_cu, ctx->stream));
+            KMX_HIP(ctx, kmx::launch_scan_bitsliced2(reads->d_bases, reads->n_reads, Lg, k, with_hash != 0, d_out, queue_of(ctx),
                                                      ctx->n_cu, ctx->stream, &h_u));
             // (not launched: the verdict must not keep the other kernel from running)
-            if (!h_u) KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 0, 2, ctx->stream));
+            if (!h_u) KMX_HIP(ctx, gate_disarm(ctx));
         }
         if (segmented)
-            KMX_HIP(ctx, kmx::launch_scan_bitsliced2_ragged(reads->d_bases, starts, n_seg, 160u, k, with_hash != 0, d_out, ctx->d_scratch + 16, ctx->n_cu,
+            KMX_HIP(ctx, kmx::launch_scan_bitsliced2_ragged(reads->d_bases, starts, n_seg, 160u, k, with_hash != 0, d_out, queue_of(ctx), ctx->n_cu,
                                                             ctx->stream, &h_r, ends));
         else if (Lh <= 160)
             KMX_HIP(ctx, kmx::launch_scan_bitsliced2_ragged(reads->d_bases, reads->d_offsets, reads->n_reads, Lh, k, with_hash != 0, d_out,
-                                                            ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &h_r));
-        if (!h_r) KMX_HIP(ctx, kmx::launch_reduce2_generic(reads, k, with_hash, d_out, ctx->n_cu, ctx->stream, ctx->d_scratch + 8, h_u ? gate : nullptr));
-        if (h_u) KMX_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gate), 0, 2, ctx->stream));   // never left armed
+                                                            queue_of(ctx), ctx->n_cu, ctx->stream, &h_r));
+        if (!h_r) KMX_HIP(ctx, kmx::launch_reduce2_generic(reads, k, with_hash, d_out, ctx->n_cu, ctx->stream, too_long_of(ctx), h_u ? gate_of(ctx) : nullptr));
+        if (h_u) KMX_HIP(ctx, gate_disarm(ctx));   // never left armed
         return KMX_OK;
     }
-    KMX_HIP(ctx, kmx::launch_reduce2_generic(reads, k, with_hash, d_out, ctx->n_cu, ctx->stream, ctx->d_scratch + 8, nullptr));
+    KMX_HIP(ctx, kmx::launch_reduce2_generic(reads, k, with_hash, d_out, ctx->n_cu, ctx->stream, too_long_of(ctx), nullptr));
     return KMX_OK;
 }
 
@@ -939,54 +841,26 @@ int kmx_canonical_windows2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t*
     bool handled = false;   // uniform reads of up to 256 bases in the dense layout (slot r*W + p): the tiled kernel (kmx_generic.hip)
     if (!reads->d_offsets && !d_win_offsets) {   // (a caller's win_offsets for uniform reads are honoured by the lane-per-read kernel, as kmx_canonical_windows does)
         // (a tile with an invalid byte stays on the tiled path: its reads are marked, the sweep behind the passes zeroes the spoiled slots -- round 6)
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-        if (int st = prepare_dirty_flags(ctx, reads->n_reads, k, true)) return st;
-        KMX_HIP(ctx, kmx::launch_windows2_tiled(reads, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, &handled, ctx->d_scratch + 16));
+        if (int st = queue_clear_marks(ctx, reads->n_reads, k, true)) return st;
+        KMX_HIP(ctx, kmx::launch_windows2_tiled(reads, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, &handled, queue_of(ctx)));
     }
-    if (!handled && !reads->d_offsets && !d_win_offsets && reads->read_len > 256 && (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u &&
-        reads->n_reads < (1ull << 40) && (uint64_t)reads->read_len * reads->n_reads < (1ull << 62)) {
-        // uniform reads longer than a frame (round 4): planned as segments on the device, as kmx_canonical_windows does
-        const uint32_t L = reads->read_len, W = L - k + 1u, J = (W + (257u - k) - 1u) / (257u - k), T = (W + J - 1u) / J;
-        void* scratch = capped_scratch(ctx, kmx::uniform_segments_scratch_bytes(reads->n_reads * J));
-        if (scratch) {
-            ctx->fx_valid = false;
-            const uint64_t *starts = nullptr, *ends = nullptr, *wins = nullptr;
-            uint64_t n_seg = 0;
-            KMX_HIP(ctx, kmx::launch_uniform_segments_plan(reads->n_reads, L, k, T, scratch, &starts, &ends, &wins, &n_seg, ctx->stream));
-            kmx_reads segs = *reads;
-            segs.d_offsets = starts;
-            segs.n_reads = n_seg;
-            segs.read_len = 256u;
-            KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-            if (int stf = prepare_dirty_flags(ctx, segs.n_reads, k, true)) return stf;
-            KMX_HIP(ctx, kmx::launch_windows2_tiled_ragged(&segs, wins, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, &handled, ctx->d_scratch + 8, ends, ctx->d_scratch + 16));
-        }
-    }
-    if (!handled && reads->d_offsets && d_win_offsets && reads->read_len > 256 && (reinterpret_cast<uintptr_t>(reads->d_bases) & 15u) == 0u) {
-        // long ragged reads (a length bound above the frames): segments cut on the device, as kmx_canonical_windows does
+    if (!handled) {   // reads longer than a frame (round 4): segments, as kmx_canonical_windows takes them
         const uint64_t *starts = nullptr, *ends = nullptr, *wins = nullptr;
         uint64_t n_seg = 0;
-        const int st = long_ragged_segments(ctx, reads, k, 257u - k, &starts, &ends, &n_seg, d_win_offsets, &wins);
+        const int st = long_segments(ctx, reads, d_win_offsets, k, &starts, &ends, &wins, &n_seg);
         if (st > 0) return st;
         if (st == 0) {
             if (n_seg == 0) return KMX_OK;
-            kmx_reads segs = *reads;
-            segs.d_offsets = starts;
-            segs.n_reads = n_seg;
-            segs.read_len = 256u;
-            KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-            if (int stf = prepare_dirty_flags(ctx, segs.n_reads, k, true)) return stf;
-            KMX_HIP(ctx, kmx::launch_windows2_tiled_ragged(&segs, wins, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, &handled, ctx->d_scratch + 8, ends, ctx->d_scratch + 16));
+            if (int st2 = windows2_segments(ctx, reads, starts, ends, wins, n_seg, k, d_fw2, d_rc2, d_canon2, d_flags, &handled)) return st2;
         }
     }
     if (!handled && reads->d_offsets && d_win_offsets) {   // ragged reads (round 4): tiled too; read_len = optional length bound
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
-        if (int stf = prepare_dirty_flags(ctx, reads->n_reads, k, true)) return stf;
+        if (int st = queue_clear_marks(ctx, reads->n_reads, k, true)) return st;
         KMX_HIP(ctx, kmx::launch_windows2_tiled_ragged(reads, d_win_offsets, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, &handled,
-                                                       ctx->d_scratch + 8, nullptr, ctx->d_scratch + 16));
+                                                       too_long_of(ctx), nullptr, queue_of(ctx)));
     }
     if (handled) return KMX_OK;
-    KMX_HIP(ctx, kmx::launch_windows2_generic(reads, d_win_offsets, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    KMX_HIP(ctx, kmx::launch_windows2_generic(reads, d_win_offsets, k, d_fw2, d_rc2, d_canon2, d_flags, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
 }
 
@@ -1001,17 +875,17 @@ int kmx_histogram(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t has
     ctx->fx_valid = false;   // (the partitioned histogram writes its id streams over the work buffer)
     {
         bool handled = false;
-        KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));   // queue heads + the count of marked reads + the gate
+        KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
         // (the histogram sinks mark the reads of a dirty tile like the bit-sliced scan does; without the array they roll such tiles, exactly)
         if (k >= 2 && k <= 31) {
             if (int st = prepare_dirty_flags(ctx, reads->n_reads, k, true)) return st;
         }
         KMX_HIP(ctx, kmx::launch_hist_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, hasher, hasher_k,
-                                              log2_buckets, d_counts, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled,
+                                              log2_buckets, d_counts, queue_of(ctx), ctx->n_cu, ctx->stream, &handled,
                                               &big_scratch, ctx, hist_scratch_budget(ctx->big_bytes, ctx->big_limit), reads->d_offsets));
         if (handled) return KMX_OK;
     }
-    KMX_HIP(ctx, kmx::launch_histogram_generic(reads, k, hasher, hasher_k, log2_buckets, d_counts, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    KMX_HIP(ctx, kmx::launch_histogram_generic(reads, k, hasher, hasher_k, log2_buckets, d_counts, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
 }
 
@@ -1032,11 +906,10 @@ int kmx_kmers_from_bytes(kmx_ctx* ctx, const uint8_t* d_seqs, uint64_t n, uint32
     if (h_first_bad) *h_first_bad = ~0ull;
     if (n == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch, 0xFF, 8, ctx->stream));
-    KMX_HIP(ctx, kmx::launch_kmers_from_bytes(d_seqs, n, k, d_words, ctx->d_scratch, ctx->n_cu, ctx->stream));
+    KMX_HIP(ctx, first_bad_reset(ctx));
+    KMX_HIP(ctx, kmx::launch_kmers_from_bytes(d_seqs, n, k, d_words, first_bad_of(ctx), ctx->n_cu, ctx->stream));
     unsigned long long bad = 0;
-    KMX_HIP(ctx, hipMemcpyAsync(&bad, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int st = first_bad_read(ctx, &bad)) return st;
     if (bad != ~0ull) {
         if (h_first_bad) *h_first_bad = bad;
         return KMX_E_INVALID_BASE;
@@ -1243,7 +1116,7 @@ int kmx_encoding_decode_p(kmx_ctx* ctx, const void* d_in, uint64_t n, uint8_t en
 
 int kmx_calib_stream_read(kmx_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, uint64_t* d_out) {
     if (!ctx || !d_out || (nbytes && !d_buf)) return KMX_E_ARG;
-    if (reinterpret_cast<uintptr_t>(d_buf) & 15u) return KMX_E_ARG;
+    if (!aligned16(d_buf)) return KMX_E_ARG;
     DeviceGuard g(ctx->device);
     KMX_HIP(ctx, hipMemsetAsync(d_out, 0, 8, ctx->stream));
     if (nbytes < 16) return KMX_OK;
@@ -1259,11 +1132,10 @@ int kmx_seqvec_push_chars(kmx_ctx* ctx, uint64_t* d_words, uint64_t n_bases_befo
     if (h_first_bad) *h_first_bad = ~0ull;
     if (n == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch, 0xFF, 8, ctx->stream));
-    KMX_HIP(ctx, kmx::launch_seqvec_push(d_words, n_bases_before, d_bytes, n, ctx->d_scratch, ctx->n_cu, ctx->stream));
+    KMX_HIP(ctx, first_bad_reset(ctx));
+    KMX_HIP(ctx, kmx::launch_seqvec_push(d_words, n_bases_before, d_bytes, n, first_bad_of(ctx), ctx->n_cu, ctx->stream));
     unsigned long long bad = 0;
-    KMX_HIP(ctx, hipMemcpyAsync(&bad, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int st = first_bad_read(ctx, &bad)) return st;
     if (bad != ~0ull) {
         if (h_first_bad) *h_first_bad = bad;
         return KMX_E_INVALID_BASE;
@@ -1285,11 +1157,10 @@ int kmx_seqvec_get_kmers(kmx_ctx* ctx, const uint64_t* d_words, uint64_t n_bases
     if (k < 1 || k > 32) return KMX_E_K_RANGE;
     if (n == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch, 0xFF, 8, ctx->stream));
-    KMX_HIP(ctx, kmx::launch_seqvec_get_kmers(d_words, n_bases, d_pos, n, k, d_out, ctx->d_scratch, ctx->n_cu, ctx->stream));
+    KMX_HIP(ctx, first_bad_reset(ctx));
+    KMX_HIP(ctx, kmx::launch_seqvec_get_kmers(d_words, n_bases, d_pos, n, k, d_out, first_bad_of(ctx), ctx->n_cu, ctx->stream));
     unsigned long long bad = 0;
-    KMX_HIP(ctx, hipMemcpyAsync(&bad, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int st = first_bad_read(ctx, &bad)) return st;
     if (bad != ~0ull) {
         std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_seqvec_get_kmers: element %llu lies outside the vector", bad);
         return KMX_E_ARG;
@@ -1320,9 +1191,9 @@ int kmx_seqvec_canonical_reduce(kmx_ctx* ctx, const uint64_t* d_words, uint64_t 
     const bool want_hash = hasher != KMX_HASH_NONE, want_sumfw = (flags & KMX_REDUCE_SUM_FW) != 0;
     const bool fix_fold = want_hash && !(hasher == KMX_HASH_LEX && hasher_k == k);   // (as in kmx_canonical_reduce)
     bool handled = false;
-    KMX_HIP(ctx, queue_clear(ctx, 32 * 128));
+    KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_HEADS));
     KMX_HIP(ctx, kmx::launch_scan_bitsliced_packed(d_words, n_reads, read_len, k, want_hash, want_sumfw, d_out,
-                                                   ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled));
+                                                   queue_of(ctx), ctx->n_cu, ctx->stream, &handled));
     if (!handled)
         KMX_HIP(ctx, kmx::launch_reduce_packed_generic(d_words, n_reads, read_len, k, want_hash, want_sumfw, d_out, ctx->n_cu, ctx->stream));
     if (fix_fold) KMX_HIP(ctx, kmx::launch_fix_hash_fold(d_out, k, hasher, hasher_k, ctx->stream));
@@ -1360,16 +1231,25 @@ int kmx_seqvec_minimizers(kmx_ctx* ctx, const uint64_t* d_words, uint64_t n_read
     return KMX_OK;
 }
 
-int kmx_minimizers(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, uint32_t w, uint32_t hasher,
-                   uint32_t hasher_k, uint64_t* d_word, uint32_t* d_pos, uint64_t* h_first_bad) {
+// The argument checks of kmx_minimizers and kmx_minimizers_sip13, in their order (`hasher_st`: what the hasher's own check said,
+// which counts after the k range).  -1: go on; anything else is the status to return.
+static int minimizers_args(const kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, uint32_t w, int hasher_st,
+                           const uint64_t* d_word, const uint32_t* d_pos, uint64_t* h_first_bad) {
     if (!ctx || !reads_ok(reads)) return KMX_E_ARG;
     if (k < 1 || w < 1 || w > k || w > 32) return KMX_E_K_RANGE;
-    if (int st = mm_hasher_ok(hasher, hasher_k)) return st;
+    if (hasher_st != KMX_OK) return hasher_st;
     if (h_first_bad) *h_first_bad = ~0ull;
     if (reads->n_reads == 0) return KMX_OK;
     if (!d_word || !d_pos) return KMX_E_ARG;
     if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
     if (!reads->d_offsets && reads->read_len < k) return KMX_E_ARG;   // SeqVecMinimizerIter::new: assert!(sv.len() >= k) (a ragged read shorter than k owns no slot)
+    return -1;
+}
+
+int kmx_minimizers(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, uint32_t w, uint32_t hasher,
+                   uint32_t hasher_k, uint64_t* d_word, uint32_t* d_pos, uint64_t* h_first_bad) {
+    const int args = minimizers_args(ctx, reads, d_win_offsets, k, w, mm_hasher_ok(hasher, hasher_k), d_word, d_pos, h_first_bad);
+    if (args >= 0) return args;
     DeviceGuard g(ctx->device);
     uint64_t total_bytes = reads->n_reads * (uint64_t)reads->read_len;
     uint32_t bound = reads->read_len;
@@ -1378,21 +1258,20 @@ int kmx_minimizers(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_o
         // of position): one host round trip
         uint32_t lo = 0, hi = 0;
         if (int st = kmx_reads_length_range(ctx, reads->d_offsets, reads->n_reads, &lo, &hi)) return st;
-        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        total_bytes = ctx->h_pinned[0];
+        total_bytes = ctx->h_pinned[KMX_PIN_READ];
         bound = hi;
         if (hi < k) return KMX_OK;      // no read holds a k-mer
     }
-    KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch, 0xFF, 8, ctx->stream));
+    KMX_HIP(ctx, first_bad_reset(ctx));
     bool tiled = false;
     KMX_HIP(ctx, kmx::launch_minimizers_reads(reads->d_bases, total_bytes, reads->d_offsets, d_win_offsets, reads->n_reads, reads->read_len, bound, k, w,
-                                              hasher, hasher_k, d_word, d_pos, ctx->d_scratch, ctx->n_cu, ctx->stream, &tiled));
+                                              hasher, hasher_k, d_word, d_pos, first_bad_of(ctx), ctx->n_cu, ctx->stream, &tiled));
     if (!h_first_bad) return KMX_OK;
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_pinned[0] != ~0ull) {
-        *h_first_bad = ctx->h_pinned[0];
+    if (int st = first_bad_read(ctx, ctx->h_pinned + KMX_PIN_READ)) return st;
+    if (ctx->h_pinned[KMX_PIN_READ] != ~0ull) {
+        *h_first_bad = ctx->h_pinned[KMX_PIN_READ];
         return KMX_E_INVALID_BASE;
     }
     return KMX_OK;
@@ -1412,13 +1291,13 @@ int kmx_canonical_reduce_sip13(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k,
     if (reads->n_reads == 0) return KMX_OK;
     const bool want_sumfw = (flags & KMX_REDUCE_SUM_FW) != 0;
     // (the ticket heads are cleared unconditionally: this scan does not put them back, and a captured graph must hold the clear)
-    KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
+    KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
     bool handled = false;
     KMX_HIP(ctx, kmx::launch_scan_reduce_sip(reads->d_bases, reads->n_reads, reads->read_len, k, key0, key1, want_sumfw, d_out,
-                                             ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, reads->d_offsets));
+                                             queue_of(ctx), ctx->n_cu, ctx->stream, &handled, reads->d_offsets));
     if (handled) return KMX_OK;
     // k = 1, reads above 256 bases, a misaligned ragged d_bases: a lane per read
-    KMX_HIP(ctx, kmx::launch_reduce_generic_sip(reads, k, key0, key1, want_sumfw ? 1u : 0u, d_out, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    KMX_HIP(ctx, kmx::launch_reduce_generic_sip(reads, k, key0, key1, want_sumfw ? 1u : 0u, d_out, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
 }
 
@@ -1430,14 +1309,14 @@ int kmx_histogram_sip13(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64
     if (reads->n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
     ctx->fx_valid = false;   // (the partitioned passes write their id streams over the work buffer)
-    KMX_HIP(ctx, queue_clear(ctx, 32 * 128 + 16));
+    KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
     bool handled = false;
     // the routes of kmx_histogram (LDS tables, one- and two-level partitions, device atomics) with the SipHash sinks
     KMX_HIP(ctx, kmx::launch_hist_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, kmx::KMX_HASH_SIP13_INTERNAL, 0u, log2_buckets,
-                                          d_counts, ctx->d_scratch + 16, ctx->n_cu, ctx->stream, &handled, &big_scratch, ctx,
+                                          d_counts, queue_of(ctx), ctx->n_cu, ctx->stream, &handled, &big_scratch, ctx,
                                           hist_scratch_budget(ctx->big_bytes, ctx->big_limit), reads->d_offsets, key0, key1));
     if (handled) return KMX_OK;
-    KMX_HIP(ctx, kmx::launch_histogram_generic_sip(reads, k, key0, key1, log2_buckets, d_counts, ctx->n_cu, ctx->stream, ctx->d_scratch + 8));
+    KMX_HIP(ctx, kmx::launch_histogram_generic_sip(reads, k, key0, key1, log2_buckets, d_counts, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
 }
 
@@ -1464,13 +1343,8 @@ int kmx_seqvec_minimizers_sip13(kmx_ctx* ctx, const uint64_t* d_words, uint64_t 
 
 int kmx_minimizers_sip13(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, uint32_t w, uint64_t key0,
                          uint64_t key1, uint64_t* d_word, uint32_t* d_pos, uint64_t* h_first_bad) {
-    if (!ctx || !reads_ok(reads)) return KMX_E_ARG;
-    if (k < 1 || w < 1 || w > k || w > 32) return KMX_E_K_RANGE;
-    if (h_first_bad) *h_first_bad = ~0ull;
-    if (reads->n_reads == 0) return KMX_OK;
-    if (!d_word || !d_pos) return KMX_E_ARG;
-    if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
-    if (!reads->d_offsets && reads->read_len < k) return KMX_E_ARG;   // SeqVecMinimizerIter::new: assert!(sv.len() >= k)
+    const int args = minimizers_args(ctx, reads, d_win_offsets, k, w, KMX_OK, d_word, d_pos, h_first_bad);
+    if (args >= 0) return args;
     DeviceGuard g(ctx->device);
     if (reads->d_offsets) {
         // as kmx_minimizers: a batch without a read of k bases returns here (one host round trip for its longest read)
@@ -1478,14 +1352,13 @@ int kmx_minimizers_sip13(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d
         if (int st = kmx_reads_length_range(ctx, reads->d_offsets, reads->n_reads, &lo, &hi)) return st;
         if (hi < k) return KMX_OK;
     }
-    KMX_HIP(ctx, hipMemsetAsync(ctx->d_scratch, 0xFF, 8, ctx->stream));
+    KMX_HIP(ctx, first_bad_reset(ctx));
     KMX_HIP(ctx, kmx::launch_minimizers_reads_sip(reads->d_bases, reads->d_offsets, d_win_offsets, reads->n_reads, reads->read_len, k, w, key0,
-                                                  key1, d_word, d_pos, ctx->d_scratch, ctx->n_cu, ctx->stream));
+                                                  key1, d_word, d_pos, first_bad_of(ctx), ctx->n_cu, ctx->stream));
     if (!h_first_bad) return KMX_OK;
-    KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_pinned[0] != ~0ull) {
-        *h_first_bad = ctx->h_pinned[0];
+    if (int st = first_bad_read(ctx, ctx->h_pinned + KMX_PIN_READ)) return st;
+    if (ctx->h_pinned[KMX_PIN_READ] != ~0ull) {
+        *h_first_bad = ctx->h_pinned[KMX_PIN_READ];
         return KMX_E_INVALID_BASE;
     }
     return KMX_OK;
@@ -1496,7 +1369,7 @@ int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint3
     const bool same_text = (format & KMX_FASTX_SAME_TEXT) != 0u;
     format &= ~KMX_FASTX_SAME_TEXT;
     if (!ctx || format > KMX_FASTX_FASTA || (n_bytes && !d_text) || (!d_bases != !d_offsets)) return KMX_E_ARG;
-    if (reinterpret_cast<uintptr_t>(d_text) & 15u) return KMX_E_ARG;
+    if (!aligned16(d_text)) return KMX_E_ARG;
     if (h_n_reads) *h_n_reads = 0;
     if (h_n_bases) *h_n_bases = 0;
     DeviceGuard g(ctx->device);
@@ -1525,10 +1398,10 @@ int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint3
     const bool fasta = format == KMX_FASTX_FASTA;
     void* scratch = big_scratch(ctx, kmx::fastx_scratch_bytes(n_bytes));
     if (!scratch) return KMX_E_NOMEM;
-    unsigned long long* d_totals = ctx->d_scratch + 2;
+    unsigned long long* d_totals = ctx->d_scratch + KMX_S_FASTX_TOTALS;
     unsigned long long totals[2] = {0, 0};
     if (reuse && scratch == ctx->d_big) {
-        // the chunk prefixes of the counting call are still in the work buffer, its totals in d_scratch[2..3]
+        // the chunk prefixes of the counting call are still in the work buffer, its totals in d_scratch[KMX_S_FASTX_TOTALS]
         totals[0] = ctx->fx_totals[0];
         totals[1] = ctx->fx_totals[1];
     } else {
@@ -1562,7 +1435,7 @@ int kmx_reads_length_range(kmx_ctx* ctx, const uint64_t* d_offsets, uint64_t n_r
     if (h_max_len) *h_max_len = 0;
     if (n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    uint32_t* d_out = reinterpret_cast<uint32_t*>(ctx->d_scratch + 4);   // (d_scratch[4]: free between calls)
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(ctx->d_scratch + KMX_S_LEN_RANGE);
     const uint32_t init[2] = {0xFFFFFFFFu, 0u};
     uint32_t got[2] = {0, 0};
     KMX_HIP(ctx, hipMemcpyAsync(d_out, init, 8, hipMemcpyHostToDevice, ctx->stream));

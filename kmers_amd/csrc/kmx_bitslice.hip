@@ -1,6 +1,7 @@
 // kmx_bitslice.hip -- launchers of the bit-sliced canonical k-mer scan (kernel: kmx_bitslice_kernel.h); this
 // translation unit holds the k = 31 and k = 63 instantiations, kmx_bitslice_k*.hip hold the other k.
 #include "kmx_bitslice_kernel.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 

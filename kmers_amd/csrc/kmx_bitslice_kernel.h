@@ -200,16 +200,16 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
     constexpr u32 VS = RAGGED ? 32u * NV + 8u : 0u;             // validity planes of one set + 8 always-zero words (a lane's windows past the frame, idle lanes)
     constexpr int NXT = NW + NE;                                 // 32x32 transposes per half-wave and tile
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
-    // Gate (queue[513], zero unless kmx_canonical_reduce / kmx_canonical_reduce2 is deciding on the device whether reads behind
+    // Gate (queue[KMX_Q_GATE], zero unless kmx_canonical_reduce / kmx_canonical_reduce2 is deciding on the device whether reads behind
     // an offsets array are in fact uniform -- offsets_uniform_gate_kernel): 1 = only the uniform kernels run, 2 = only the ragged
     // ones (two-word k: the lane-per-read kernel).
     if constexpr (!PACKED) {
-        const u32 gate = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * 513]);
+        const u32 gate = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * KMX_Q_GATE]);
         if (gate == (RAGGED ? 1u : 2u)) return;
         if constexpr (!RAGGED && !SEG) {
             // (round 5) the gate found the reads uniform at a length BELOW the bound this launch was laid out for (frame, windows per
             // lane, LDS): that length is what is scanned -- every quantity below derives from L
-            const u32 gate_len = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * 513 + 1]);
+            const u32 gate_len = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * KMX_Q_GATE + 1]);
             if (gate == 1u && gate_len != 0u) L = gate_len;
         }
     }
@@ -404,14 +404,14 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
     // w[] alive past phase A, the prefetch behind it -- cost 2.7 % on CLEAN input (profiles/r06_dirty_variants.txt).  Round 6:
     //   * phase A parks every chunk's validation word in LDS at no instruction's cost (XOFF above); a dirty tile looks its reads'
     //     chunks up there -- LDS only, the next tile's rows already requested -- and leaves the 64-bit mask of the reads that touch a
-    //     bad chunk in the array behind queue[515] (8 bytes per tile, all zero between calls; queue[512] = how many reads were marked);
+    //     bad chunk in the array behind queue[KMX_Q_MASKS] (8 bytes per tile, all zero between calls; queue[KMX_Q_MARKED] = how many reads were marked);
     //   * nothing is blanked: the tile is scanned as it is, an invalid byte counting as the base its bits (b >> 1) & 3 spell, and
     //     sweep_flagged_kernel (kmx_sweep.hip) takes the windows that hold such a byte -- exactly those the reference's iterator does
     //     not yield (canonical_kmer_iterator.rs:50-66) -- back OUT of the sums, from the same codes.
-    // queue[515] == 0: no array; a ragged tile then rolls as a whole here (uniform input: the host side always provides the array).
+    // queue[KMX_Q_MASKS] == 0: no array; a ragged tile then rolls as a whole here (uniform input: the host side always provides the array).
     constexpr bool INLINE = !PACKED;              // (packed input has no invalid codes)
-    u64* const masks = INLINE ? reinterpret_cast<u64*>(uniform_u64(queue[515])) : nullptr;   // (read once: two scalar registers)
-    u32 n_marked = 0;                             // reads this wave marked (wave-uniform); their total, in queue[512], tells the sweep how many waves to field
+    u64* const masks = INLINE ? reinterpret_cast<u64*>(uniform_u64(queue[KMX_Q_MASKS])) : nullptr;   // (read once: two scalar registers)
+    u32 n_marked = 0;                             // reads this wave marked (wave-uniform); their total, in queue[KMX_Q_MARKED], tells the sweep how many waves to field
     // word-domain accumulators of the fallback path (tiles with invalid bytes, the final partial tile)
     struct FbAcc { u64 n = 0, s0 = 0, s1 = 0, x0 = 0, x1 = 0, fw = 0; };
     // (into one of sixteen partial summaries, each on a line of its own in the queue block -- the launch's last block adds them
@@ -419,7 +419,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
     // line of the summary were served one after the other)
     auto emit_sums = [&](u64 n, u64 r0, u64 r1, u64 h0, u64 h1, u64 f) {   // wave-uniform values, one set of atomics
         if (lane == 0) {
-            unsigned long long* const S = queue + KMX_Q_SLOTS + (blockIdx.x & 15u) * 16u;
+            unsigned long long* const S = queue + KMX_Q_SLOTS + (blockIdx.x & 15u) * KMX_Q_SLOT_STRIDE;
             atomicAdd(S + 0, (unsigned long long)n);
             atomicAdd(S + 1, (unsigned long long)r0);
             if constexpr (K > 32) atomicAdd(S + 2, (unsigned long long)r1);
@@ -512,7 +512,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
         // branch make hipcc wait with vmcnt(0) where phase A would count them down
         // (the stand-in source: a quiet line of the queue block, NOT the ticket heads -- reads of a line that thousands of atomics
         // hit at the same time took ~2.6 us apiece, 26 us per tile that does not fit)
-        const uint8_t* __restrict__ tb = m.fits ? bases + m.base : reinterpret_cast<const uint8_t*>(queue + 544);
+        const uint8_t* __restrict__ tb = m.fits ? bases + m.base : reinterpret_cast<const uint8_t*>(queue + KMX_Q_QUIET);
         const u32 lo = m.fits ? (m.n_ch - 1u) * 16u : 0u;
         u32 l16 = lane16;                       // (opaque copy: see issue_loads)
         asm volatile("" : "+v"(l16));
@@ -585,7 +585,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
     // heads, each on its own cache line, head q owning the tiles == q (mod NQ).  A head is shared by the
     // three co-resident blocks of 8 CUs (old and young waves alike), so heads drain at equal rates.
     // (Handing each head a contiguous region instead changed nothing: 2.50 vs 2.55 ms compute-free, equal in the full kernel.)
-    constexpr u32 NQ = 32;
+    constexpr u32 NQ = KMX_Q_HEADS;
     const u64 n_static = (u64)gridDim.x * 4u;           // the tiles the waves own without a ticket: wave w starts with tile w (below); head q owns the tiles == q (mod NQ) past them
     // (a grid of fewer than 256 blocks -- a small batch -- spreads over all 32 heads too: crowded on gridDim / 8 of them, most waves found their
     // head drained at once and walked the others in step, one round trip per head: 1e4 reads took longer than 1e5)
@@ -614,7 +614,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
             const u32 from = (live >> at) | (at ? live << (NQ - at) : 0u);             // bit i: head at + i
             qid = (at + (u32)__builtin_ctz(from)) & (NQ - 1u);
             unsigned long long v = 0;
-            if (lane_now() == 0u) v = atomicAdd(queue + qid * 16u, 1ull);               // heads are 128 bytes apart
+            if (lane_now() == 0u) v = atomicAdd(queue + qid * KMX_Q_HEAD_STRIDE, 1ull);               // heads are 128 bytes apart
             const u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
             const u64 t = (((u64)hi << 32) | lo) * NQ + qid + n_static;
             if (t < n_full) return t;
@@ -645,7 +645,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
             // rows of the next tile, every tile (~17 % of a wave's cycles sat there since round 3: profiles/r04_phase_timing*.txt).
             u32 zero = 0;
             asm volatile("" : "+v"(zero));
-            pend = atomicAdd(queue + qid * 16u + zero, one);
+            pend = atomicAdd(queue + qid * KMX_Q_HEAD_STRIDE + zero, one);
         }
         if (rot) qid = (qid + 1u) & (NQ - 1u);
     };
@@ -1163,7 +1163,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
         if constexpr (SEG) seg_lane(cur_g);
         // A tile with an invalid byte: which reads touch a bad chunk?  Every lane ORs the validation words of its read's chunks (phase A
         // left them in the plane area, free until phase C) -- a chunk shared by two reads marks both, the sweep looks at the bytes -- and
-        // the reads' mask goes to the array behind queue[515].  LDS reads and ONE global store.
+        // the reads' mask goes to the array behind queue[KMX_Q_MASKS].  LDS reads and ONE global store.
         auto mark_dirty_reads = [&]([[maybe_unused]] const u32 n_chunks) -> bool {
             if (masks == nullptr) {
                 if constexpr (!RAGGED) __builtin_trap();   // (the host side always provides the array)
@@ -1437,7 +1437,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
         }
         if (v[0] != 0ull) emit_sums(v[0], v[1], v[2], v[3], v[4], v[5]);   // (no k-mer: nothing to add -- every word is zero then)
         if (v[6] != 0ull && lane == 0) atomicAdd(queue + KMX_Q_MARKED, (unsigned long long)v[6]);
-        // ---- the last block to hand in closes the launch (kmx_device.h, "the context's queue block")
+        // ---- the last block to hand in closes the launch (kmx_layout.h, the queue block)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         u32 before = 0;
         if (lane == 0) before = (u32)atomicAdd(queue + KMX_Q_DONE, 1ull);
@@ -1449,14 +1449,14 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
 #pragma unroll
             for (u32 i = 0; i < 6u; ++i) {      // lane s < 16 takes partial summary s -- and leaves zeros
                 part[i] = 0;
-                if (ln < 16u) part[i] = atomicExch(queue + KMX_Q_SLOTS + ln * 16u + i, 0ull);
+                if (ln < KMX_Q_N_SLOTS) part[i] = atomicExch(queue + KMX_Q_SLOTS + ln * KMX_Q_SLOT_STRIDE + i, 0ull);
             }
             u64 marked = 0;
             if (ln == 0u) marked = atomicExch(queue + KMX_Q_MARKED, 0ull);
             marked = wave_sum(marked);
             const u64 f_n = wave_sum(part[0]), f_s0 = wave_sum(part[1]), f_s1 = wave_sum(part[2]);
             const u64 f_x0 = wave_xor(part[3]), f_x1 = wave_xor(part[4]), f_fw = wave_sum(part[5]);
-            if (ln < 32u) queue[ln * 16u] = 0ull;          // the ticket heads
+            if (ln < KMX_Q_HEADS) queue[ln * KMX_Q_HEAD_STRIDE] = 0ull;         // the ticket heads
             if (ln == 0u) {
                 queue[KMX_Q_DONE] = 0ull;
                 queue[KMX_Q_MARKED_OUT] = marked;
@@ -1490,7 +1490,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
 }
 
 // ------------------------------------------------------------------ the reads the main pass marked
-// masks[t] (behind queue[515]) = the reads of tile t that touch a chunk with an invalid byte, left by the main pass, which
+// masks[t] (behind queue[KMX_Q_MASKS]) = the reads of tile t that touch a chunk with an invalid byte, left by the main pass, which
 // scanned the tile as it is.  sweep_flagged_kernel (kmx_sweep.hip, round 6) gathers them 64 at a time, finds the windows that
 // hold an invalid byte -- exactly those the reference's iterator does not yield (canonical_kmer_iterator.rs:50-66) -- and
 // subtracts them.  Every mask goes back to zero: the caller never clears the array.

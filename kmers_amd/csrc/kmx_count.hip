@@ -24,6 +24,7 @@
 // is compacted by a block count, a scan, and a write (one more host round trip for the number of distinct keys).
 // No block waits for another: cross-block results travel through kernel boundaries only.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 
@@ -61,6 +62,7 @@ struct Counters {
     u64 n_distinct;
 };
 constexpr size_t LEVEL_COUNTERS = 7u * 8u;   // (n_valid .. n_next_big: cleared before and read back after every level)
+static_assert(LEVEL_COUNTERS <= KMX_PIN_BYTES, "the level counters are read back into the context's pinned words");
 
 __host__ __device__ __forceinline__ u64 ceil_div(u64 a, u64 b) { return (a + b - 1u) / b; }
 __device__ __forceinline__ u32 digit_width(u32 hi_bit) { return hi_bit < RBITS ? hi_bit : RBITS; }

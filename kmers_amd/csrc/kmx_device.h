@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/kmx.h"
+#include "kmx_layout.h"
 
 namespace kmx {
 
@@ -185,8 +186,6 @@ __device__ __forceinline__ u64 siphash13(u64 w, const SipKey& key) {
     return v0 ^ v1 ^ v2 ^ v3;
 }
 __device__ __forceinline__ u64 siphash13_u64(u64 w, u64 k0, u64 k1) { return siphash13(w, sip_key(k0, k1)); }
-// the hasher id of the *_sip13 calls inside the library (not an ABI value: kmx.h's hashers stop at KMX_HASH_IDENTITY)
-constexpr u32 KMX_HASH_SIP13_INTERNAL = 0x5313u;
 
 // max over the 64 lanes, returned wave-uniform: DPP inside the 16-lane rows (no LDS round trips), then 4 v_readlane
 __device__ __forceinline__ u32 wave_max_u32(u32 v) {
@@ -255,26 +254,14 @@ __device__ __forceinline__ u64 half_sum(u64 v) {
 
 // A read of 2^31 bases or more (the iterator's positions are i32, canonical_kmer_iterator.rs:15; kmx.h "Limits") is not
 // scanned: the kernels skip it and raise the context's sticky flag, which kmx_ctx_synchronize reports as KMX_E_ARG.
-// `queue` = the tile-queue block of the context (d_scratch + 16); the flag lives 8 words below it (kmx_internal.h).
-constexpr int KMX_TOOLONG_FROM_QUEUE = -8;
+// `queue` = the tile-queue block of the context; the flag is queue + KMX_TOOLONG_FROM_QUEUE (kmx_layout.h).
 __device__ __forceinline__ bool read_too_long(u64 len, unsigned long long* flag) {
     if (len < (1ull << 31)) return false;
     if (flag) *flag = 1ull;   // (a plain store of one constant: every writer agrees)
     return true;
 }
 
-// ---- the context's queue block (`queue` = d_scratch + 16, u64 words; kmx_internal.h), as the bit-sliced scan uses it (round 6):
-//   [q * 16], q < 32   the ticket heads, 128 bytes apart
-//   [512]              reads marked so far (running count of the launch);  [513] the uniform / ragged gate;  [515] the mask array
-//   [516]              the marked reads of the LAST bit-sliced launch, for its sweep (overwritten, never cleared)
-//   [517]              the context's pinned host words as the device sees them (written once, kmx_ctx_create)
-//   [544..559]         a quiet line (stand-in source of loads that must not fault)
-//   [560]              blocks of the launch that have handed in their sums
-//   [576 + 16 s + i]   partial summary s (s < 16: block b adds into s = b & 15), word i < 6
-// The scan CLOSES its own launch: the last block to hand in adds the sixteen partial summaries up, writes the result, and puts
-// the heads, [512], [560] and the partials back to zero -- so a caller that knows only such launches ran since its last clear
-// need not clear again (two fill kernels and their gaps: 11 us of a small batch's 70, profiles/r06_small_batches.txt).
-constexpr u32 KMX_Q_MARKED = 512, KMX_Q_MARKED_OUT = 516, KMX_Q_HOST = 517, KMX_Q_DONE = 560, KMX_Q_SLOTS = 576;
+// (the context's queue block, which the tiled scans take tickets from and close: kmx_layout.h)
 // `want_sumfw` of scan_bitsliced_kernel / launch_bs carries the launch's mode: bit 0 = the sum of the forward words is wanted;
 // STORE = the last block stores the summary (the caller did not zero `out`; default: adds to it); PUBLISH = ... and leaves
 // {token, marked reads, the summary's words} in the pinned host words, the token (bits 8..31) last; NO_SWEEP = launch_bs does

@@ -1,6 +1,7 @@
 // kmx_elem.hip -- K0 synthetic read generator + K5 element-wise batch operations
 // (one element per lane).  Each kernel cites the reference function it restates.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 

@@ -25,6 +25,7 @@
 // measured twice: 16 KiB tiles, two look-backs (round 3, profiles/r03_fastx_one_pass.txt): 6x slower; 64 KiB tiles held in registers, one
 // look-back of 1024 descriptors per round trip (round 5, profiles/r05_fastq_one_pass.txt, tools/patches/fastq_one_pass.patch): 1.5x slower.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 

@@ -4,6 +4,7 @@
 // exactly like CanonicalKmerIterator::find_next (src/naive_impl/canonical_kmer_iterator.rs:42-70);
 // correctness-first, these are not the roofline kernels.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 // (the line-aligned stores of the tiled [u64;2] write-back carry the nt hint (k = 33 / 64: 5.5 -> 4.7 / 4.7 -> 4.0 ms per 2e7 reads, k = 47 / 63 +2 %: profiles/r03_nt_stores.txt)
 namespace kmx {
@@ -320,12 +321,12 @@ windows2_tiled_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
         const u64 read = t * 64u + lane;
         bool per_read = !fits;
         if (!per_read && __any(chunk_has_invalid(bad))) {
-            const unsigned long long dq = queue ? queue[515] : 0ull;
+            const unsigned long long dq = queue ? queue[KMX_Q_MASKS] : 0ull;
             u64* const dmk = reinterpret_cast<u64*>(((u64)(u32)__builtin_amdgcn_readfirstlane((u32)(dq >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((u32)dq));
             if (dmk != nullptr) {
                 if (lane == 0) {
                     dmk[t] = ~0ull;
-                    queue[512] = 1ull << 40;      // ("many": a plain store every marking wave agrees on)
+                    queue[KMX_Q_MARKED] = 1ull << 40;      // ("many": a plain store every marking wave agrees on)
                 }
             } else {
                 per_read = true;
@@ -472,9 +473,6 @@ windows2_tiled_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
     }
 }
 
-hipError_t launch_sweep_windows(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags,
-                                const u64* win_offsets, unsigned long long* queue, int n_cu, hipStream_t stream, const u64* offsets,
-                                const u64* ends, bool two_words);
 template <int NW, bool RAGGED = false>
 static hipError_t launch_windows2_tiled_nw(const uint8_t* bases, u64 n_reads, u32 L, u32 k, const Win2Out& out, int n_cu, hipStream_t st,
                                            const u64* offsets = nullptr, const u64* win_offsets = nullptr, unsigned long long* too_long = nullptr,

@@ -2,6 +2,7 @@
 // (device-scope atomics, block-private LDS tables, the two-pass partitioned histogram), pass 2 of the latter, and
 // launch_hist_uniform.  BUILD-DEFINED (the reference has no histogram): include/kmx.h kmx_histogram, oracle kmo_histogram.
 #include "kmx_hist_part.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 
@@ -264,9 +265,6 @@ hist_repartition_kernel(const u32* __restrict__ stream1, const u32* __restrict__
     sink.finish(p2);
 }
 
-hipError_t launch_sweep_hist(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets, u64* counts,
-                             unsigned long long* queue, int n_cu, hipStream_t stream, const u64* offsets);
-
 // Larger tables, or no scratch: device-scope u64 atomics (SinkHist).
 // Every scan is followed by the sweep that takes the windows with an invalid byte back out of the counters (round 6: the sinks mark
 // the reads of a dirty tile instead of rolling it -- kmx_scan_kernel.h, SinkMarksDirty; a no-op on clean input).
@@ -340,7 +338,7 @@ hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
                     return true;
                 };
                 if (first != 0) {
-                    hipError_t e = hipMemsetAsync(queue, 0, 32 * 128 + 8, stream);   // (the heads, and the count of marked reads behind them)
+                    hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_THROUGH_MARKED, stream);   // (the heads, and the count of marked reads behind them)
                     if (e != hipSuccess) return e;
                 }
                 const uint8_t* cb = offsets ? bases : bases + first * (u64)L;
@@ -412,7 +410,7 @@ hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, 
                     return true;
                 };
                 if (first != 0) {
-                    hipError_t e = hipMemsetAsync(queue, 0, 32 * 128 + 8, stream);   // (the heads, and the count of marked reads behind them)
+                    hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_THROUGH_MARKED, stream);   // (the heads, and the count of marked reads behind them)
                     if (e != hipSuccess) return e;
                 }
                 // the hook fills pp through the reference captured above; dispatch takes its params by value, so hand it

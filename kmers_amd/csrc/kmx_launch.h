@@ -1,0 +1,140 @@
+// kmx_launch.h -- the one declaration of the host-side launchers kmx_api.hip calls, included by kmx_api.hip and by every
+// translation unit that defines one of them (so each definition is compiled against its declaration).  Default arguments are
+// written here only.  Not part of the ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/kmx.h"
+
+namespace kmx {
+typedef uint32_t u32;
+typedef uint64_t u64;
+// kmx_scan.hip
+hipError_t launch_scan_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
+                               kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled, const u64* offsets);
+hipError_t launch_windows_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon,
+                                  uint8_t* flags, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
+hipError_t launch_windows_ragged(const uint8_t* bases, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L, u32 k,
+                                 u64* fw, u64* rc, u64* canon, uint8_t* flags, unsigned long long* queue, int n_cu,
+                                 hipStream_t stream, bool* handled, const u64* ends = nullptr /* the reads' ends: nullptr = offsets + 1 */);
+// kmx_hist.hip
+hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets,
+                               u64* counts, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
+                               void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets, u64 k0 = 0, u64 k1 = 0);
+// kmx_bitslice.hip
+hipError_t launch_scan_bitsliced(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, u32 mode /* KMX_BS_* (kmx_device.h): bit 0 = sum_fw */,
+                                 kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
+hipError_t launch_scan_bitsliced2(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, kmx_summary2* out,
+                                  unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
+u64 bitsliced_segments_per_read(u32 L, u32 k);
+hipError_t launch_scan_bitsliced2_ragged(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 L_hint, u32 k, bool want_hash,
+                                         kmx_summary2* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
+                                         const u64* ends = nullptr);
+hipError_t launch_scan_bitsliced_ragged(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 L_hint, u32 k, bool want_hash,
+                                        kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
+                                        bool want_sumfw = false, const u64* ends = nullptr /* the reads' ends: nullptr = offsets + 1 */);
+hipError_t launch_scan_bitsliced_packed(const uint64_t* words, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
+                                        kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled);
+// kmx_sweep.hip
+hipError_t launch_sweep_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw, kmx_summary* out,
+                                unsigned long long* queue, int n_cu, hipStream_t stream);
+hipError_t launch_sweep_windows(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags,
+                                const u64* win_offsets, unsigned long long* queue, int n_cu, hipStream_t stream, const u64* offsets,
+                                const u64* ends, bool two_words);
+hipError_t launch_sweep_hist(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets, u64* counts,
+                             unsigned long long* queue, int n_cu, hipStream_t stream, const u64* offsets);
+// kmx_segments.hip
+size_t uniform_segments_scratch_bytes(u64 n_seg);
+hipError_t launch_uniform_segments_plan(u64 n_reads, u32 L, u32 k, u32 T, void* scratch, const u64** starts, const u64** ends, const u64** wins, u64* n_seg_out,
+                                        hipStream_t stream);
+size_t segments_scratch_bytes(u64 n_reads, u64 seg_capacity, bool with_wins = false);
+u64 segments_capacity(u64 n_reads, u64 total_bases, u32 t_max);
+hipError_t launch_segments_build(const u64* offsets, u64 n_reads, u32 k, u32 t_max, u64 seg_capacity, void* scratch,
+                                 const u64** starts_out, const u64** ends_out, const u64** total_out, unsigned long long* too_long,
+                                 hipStream_t stream, const u64* win_offsets = nullptr, const u64** wins_out = nullptr);
+// kmx_fastx.hip
+size_t fastx_scratch_bytes(u64 n_bytes);
+hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st);
+hipError_t launch_fastx_emit(const uint8_t* text, u64 n, bool fasta, const void* scratch, const unsigned long long* totals,
+                             uint8_t* bases, u64* offsets, hipStream_t st);
+// kmx_seqvec.hip
+hipError_t launch_seqvec_push(u64* words, u64 first, const uint8_t* bytes, u64 n, unsigned long long* first_bad, int n_cu, hipStream_t st);
+hipError_t launch_seqvec_to_bytes(const u64* words, u64 n, uint8_t* out, int n_cu, hipStream_t st);
+hipError_t launch_seqvec_get_kmers(const u64* words, u64 n_bases, const u64* pos, u64 n, u32 k, u64* out,
+                                   unsigned long long* first_bad, int n_cu, hipStream_t st);
+hipError_t launch_seqvec_iter_kmers(const u64* words, u64 n_bases, u64 start, u64 count, u32 k, u64* out, int n_cu, hipStream_t st);
+hipError_t launch_minimizer_words(const u64* in, u64 n, u32 k, u32 w, u32 hasher, u32 hk, u64* out_mm, u32* out_off, int n_cu, hipStream_t st);
+hipError_t launch_seqvec_minimizers(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u32 hasher, u32 hk, u64* out_word,
+                                    u32* out_pos, int n_cu, hipStream_t st);
+hipError_t launch_reduce_packed_generic(const u64* words, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
+                                        kmx_summary* out, int n_cu, hipStream_t st);
+// kmx_generic.hip
+hipError_t launch_reduce_generic(const kmx_reads* r, u32 k, u32 hasher, u32 hk, u32 want_sumfw, kmx_summary* out,
+                                 int n_cu, hipStream_t st, unsigned long long* too_long);
+hipError_t launch_windows_generic(const kmx_reads* r, const u64* win_off, u32 k, u64* fw, u64* rc, u64* canon,
+                                  uint8_t* flags, int n_cu, hipStream_t st, unsigned long long* too_long);
+hipError_t launch_histogram_generic(const kmx_reads* r, u32 k, u32 hasher, u32 hk, u32 log2_buckets, u64* counts,
+                                    int n_cu, hipStream_t st, unsigned long long* too_long);
+hipError_t launch_reduce2_generic(const kmx_reads* r, u32 k, u32 with_hash, kmx_summary2* out, int n_cu, hipStream_t st, unsigned long long* too_long,
+                                  const u32* gate);
+hipError_t launch_windows2_tiled(const kmx_reads* r, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags, int n_cu, hipStream_t st,
+                                 bool* handled, unsigned long long* queue);
+hipError_t launch_windows2_tiled_ragged(const kmx_reads* r, const u64* win_offsets, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags, int n_cu,
+                                        hipStream_t st, bool* handled, unsigned long long* too_long, const u64* ends, unsigned long long* queue);
+hipError_t launch_windows2_generic(const kmx_reads* r, const u64* win_off, u32 k, u64* fw, u64* rc, u64* canon,
+                                   uint8_t* flags, int n_cu, hipStream_t st, unsigned long long* too_long);
+// kmx_elem.hip
+hipError_t launch_gen_reads(u64 seed, u64 first_byte, uint8_t* out, u64 nbytes, int n_cu, hipStream_t st);
+hipError_t launch_kmers_from_bytes(const uint8_t* seqs, u64 n, u32 k, u64* words, unsigned long long* first_bad, int n_cu, hipStream_t st);
+hipError_t launch_revcomp_words(const u64* in, u64 n, u32 k, u64* out, int n_cu, hipStream_t st);
+hipError_t launch_canonical_words(const u64* in, u64 n, u32 k, u64* canon, uint8_t* is_canon, int n_cu, hipStream_t st);
+hipError_t launch_hash_words(const u64* in, u64 n, u32 hasher, u32 hk, u64* out, int n_cu, hipStream_t st);
+hipError_t launch_hash_words_sip13(const u64* in, u64 n, u64 k0, u64 k1, u64* out, int n_cu, hipStream_t st);
+hipError_t launch_match_words(const u64* fw, const u64* rc, const u64* other, u64 n, uint8_t* out, int n_cu, hipStream_t st);
+hipError_t launch_ck_shift(bool append, u64* fw, u64* rc, const uint8_t* bases, u64 n, u32 k, uint8_t* dropped, int n_cu, hipStream_t st);
+hipError_t launch_encode_kmers(const uint8_t* seqs, u64 n, u32 seq_len, u32 enc, u32 B, u64* words, int n_cu, hipStream_t st);
+hipError_t launch_encode_windows(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 enc, u32 B, u64* words, int n_cu, hipStream_t st);
+hipError_t launch_encoding_rev_comp(const u64* in, u64 n, u32 K, u32 comp_lut, u32 B, u64* out, int n_cu, hipStream_t st);
+hipError_t launch_encoding_decode(const u64* in, u64 n, u32 nuc_lut, u32 B, uint8_t* seqs, int n_cu, hipStream_t st);
+hipError_t launch_sub_kmer_words(const u64* in, u64 n, u32 pos, u32 width, u64* out, int n_cu, hipStream_t st);
+hipError_t launch_kmers_to_bytes(const u64* in, u64 n, u32 k, bool upper, uint8_t* out, int n_cu, hipStream_t st);
+hipError_t launch_encode_kmers_bytes(const uint8_t* seqs, u64 n, u32 seq_len, u32 enc, u32 nb, uint8_t* arrays, int n_cu, hipStream_t st);
+hipError_t launch_encoding_rev_comp_bytes(const uint8_t* in, u64 n, u32 K, u32 comp_lut, u32 nb, uint8_t* out, int n_cu, hipStream_t st);
+hipError_t launch_encoding_decode_bytes(const uint8_t* in, u64 total_bytes, u32 nuc_lut, uint8_t* seqs, int n_cu, hipStream_t st);
+hipError_t launch_calib_stream_read(const uint8_t* buf, u64 nbytes, unsigned long long* out, int n_cu, hipStream_t st);
+hipError_t launch_length_range(const u64* offsets, u64 n_reads, u32* out, int n_cu, hipStream_t st);
+hipError_t launch_offsets_uniform_gate(const u64* offsets, u64 n_reads, u32 bound, u32 k, u32* gate, int n_cu, hipStream_t st);
+hipError_t launch_fix_hash_fold(kmx_summary* out, u32 k, u32 hasher, u32 hk, hipStream_t st);
+// kmx_minimizers.hip
+hipError_t launch_minimizers_reads(const uint8_t* bases, u64 total_bytes, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L,
+                                   u32 bound, u32 k, u32 w, u32 hasher, u32 hk, u64* out_word, u32* out_pos,
+                                   unsigned long long* first_bad, int n_cu, hipStream_t st, bool* tiled);
+// the *_sip13 calls (SipHash-1-3 under std's DefaultHasher / RandomState): kmx_scan.hip, kmx_hist.hip, kmx_generic.hip, kmx_sip13.hip
+constexpr u32 KMX_HASH_SIP13_INTERNAL = 0x5313u;   // the hasher id launch_hist_uniform takes for them (not an ABI value: kmx.h's hashers stop at KMX_HASH_IDENTITY)
+hipError_t launch_scan_reduce_sip(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64 k0, u64 k1, bool want_sumfw, kmx_summary* out,
+                                  unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled, const u64* offsets);
+hipError_t launch_reduce_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 want_sumfw, kmx_summary* out, int n_cu, hipStream_t st,
+                                     unsigned long long* too_long);
+hipError_t launch_histogram_generic_sip(const kmx_reads* r, u32 k, u64 k0, u64 k1, u32 log2_buckets, u64* counts, int n_cu, hipStream_t st,
+                                        unsigned long long* too_long);
+hipError_t launch_minimizer_words_sip(const u64* in, u64 n, u32 k, u32 w, u64 k0, u64 k1, u64* out_mm, u32* out_off, int n_cu, hipStream_t st);
+hipError_t launch_minimizers_reads_sip(const uint8_t* bases, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L, u32 k, u32 w,
+                                       u64 k0, u64 k1, u64* out_word, u32* out_pos, unsigned long long* first_bad, int n_cu, hipStream_t st);
+hipError_t launch_seqvec_minimizers_sip(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u64 k0, u64 k1, u64* out_word, u32* out_pos,
+                                        int n_cu, hipStream_t st);
+// kmx_count.hip
+size_t count_area_bytes(u64 n_win);
+size_t win_offsets_bytes(u64 n_reads);
+hipError_t launch_count_win_offsets(const u64* offsets, u64 n_reads, u32 k, void* area, u64** wo_out, unsigned long long* h_pinned,
+                                    u64* h_total, hipStream_t st);
+hipError_t launch_count_sort(u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
+                             u64* h_distinct, bool* bad, hipStream_t st);
+hipError_t launch_count_emit(const u64* canon, u64 n_win, u64 n_valid, void* area, u64* out_k, u64* out_c, hipStream_t st);
+size_t count_merge_bytes(u64 n);
+hipError_t launch_count_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
+                              u64* h_out, hipStream_t st);
+hipError_t launch_count_merge_emit(u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
+}  // namespace kmx

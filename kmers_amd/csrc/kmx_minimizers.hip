@@ -14,6 +14,7 @@
 //   * out: the k-mers of a block's reads are consecutive slots -- one run of whole 128-byte lines when the batch is uniform --
 //     written by consecutive threads.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 #include <type_traits>
 

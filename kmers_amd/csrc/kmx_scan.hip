@@ -27,6 +27,7 @@
 //   Tiles come from the same interleaved dynamic queue as the bit-sliced kernel.
 #include <type_traits>
 #include "kmx_scan_kernel.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 
@@ -566,10 +567,6 @@ hipError_t launch_scan_reduce_sip(const uint8_t* bases, u64 n_reads, u32 L, u32 
     return dispatch<SinkReduceSip<false>>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
 }
 
-hipError_t launch_sweep_windows(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon, uint8_t* flags,
-                                const u64* win_offsets, unsigned long long* queue, int n_cu, hipStream_t stream, const u64* offsets,
-                                const u64* ends, bool two_words);
-
 static hipError_t windows_uniform_passes(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u64* fw, u64* rc, u64* canon,
                                          uint8_t* flags, unsigned long long* queue, int n_cu, hipStream_t stream);
 // (the passes, then the sweep over the reads they marked: every pass marks the same reads, the masks are consumed once)
@@ -595,7 +592,7 @@ static hipError_t windows_uniform_passes(const uint8_t* bases, u64 n_reads, u32 
                 first = false;
                 return hipSuccess;
             }
-            return hipMemsetAsync(queue, 0, 32 * 128, stream);
+            return hipMemsetAsync(queue, 0, KMX_Q_CLEAR_HEADS, stream);
         };
         u64* const arr[3] = {fw, rc, canon};
         for (int a = 0; a < 3; ++a) {
@@ -642,14 +639,14 @@ static hipError_t windows_ragged_passes(const uint8_t* bases, const u64* offsets
         for (int a = 0; a < 3; ++a) {
             if (!arr[a]) continue;
             if (!first) {
-                if (hipError_t e = hipMemsetAsync(queue, 0, 32 * 128, stream)) return e;
+                if (hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_HEADS, stream)) return e;
             }
             first = false;
             const WindowsParams one{a == 0 ? fw : nullptr, a == 1 ? rc : nullptr, a == 2 ? canon : nullptr, nullptr, win_offsets};
             if (hipError_t e = dispatch<SinkWindowsT<true, true>, WindowsParams, NoPre, true>(bases, n_reads, L, k, one, queue, n_cu, stream, NoPre(), offsets, ends)) return e;
         }
         if (flags) {
-            if (hipError_t e = hipMemsetAsync(queue, 0, 32 * 128, stream)) return e;
+            if (hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_HEADS, stream)) return e;
             const WindowsParams fo{nullptr, nullptr, nullptr, flags, win_offsets};
             if (hipError_t e = dispatch<SinkWindowsT<false>>(bases, n_reads, L, k, fo, queue, n_cu, stream, NoPre(), offsets, ends)) return e;
         }

@@ -57,7 +57,7 @@ template <typename S, typename = void> struct SinkAliasPacked { static constexpr
 template <typename S> struct SinkAliasPacked<S, decltype((void)S::kAliasPacked)> { static constexpr bool value = S::kAliasPacked; };
 // a sink whose windows a later pass can take back (static constexpr bool kMarksDirty; round 6): a tile that holds an invalid byte is
 // then NOT rolled per lane -- it takes the fast path as it is, an invalid byte counting as the base its bits (b >> 1) & 3 spell, and
-// the reads that touch a bad chunk are marked in the array behind queue[515] exactly as the bit-sliced scan marks them; what the
+// the reads that touch a bad chunk are marked in the array behind queue[KMX_Q_MASKS] exactly as the bit-sliced scan marks them; what the
 // windows with an invalid byte added is subtracted by sweep_flagged_kernel (kmx_sweep.hip).  The bucket histograms: a rolled tile
 // cost 2-3 tiles, and with an N in 2 % of the reads 73 % of the tiles rolled (+62 %: profiles/r05_dirty_bench.txt).
 // The reads of a tile that touch a chunk with an invalid byte (a sink that marks, below): the tile's chunks once more (they are in the L2),
@@ -161,7 +161,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
 
     // dynamic tile queue (see kmx_bitslice.hip): NQ interleaved heads, one tile per ticket, ticket fetched one
     // tile ahead; removes the under-occupied tail that static striding leaves behind
-    constexpr u32 NQ = 32;
+    constexpr u32 NQ = KMX_Q_HEADS;
     // (a grid of fewer than 256 blocks -- a small batch -- spreads over all 32 heads too: crowded on gridDim / 8 of them, most waves found their
     // head drained at once and walked the others in step, one round trip per head: 1e4 reads took longer than 1e5)
     u32 qid = ((blockIdx.x & 255u) * NQ) / (gridDim.x < 256u ? gridDim.x : 256u);
@@ -173,7 +173,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
     auto dequeue = [&]() -> u64 {
         while (heads_left != 0u) {
             unsigned long long v = 0;
-            if (lane == 0) v = atomicAdd(queue + qid * 16u, 1ull);
+            if (lane == 0) v = atomicAdd(queue + qid * KMX_Q_HEAD_STRIDE, 1ull);
             const u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
             const u64 t = (((u64)hi << 32) | lo) * NQ + qid;
             if (t < n_full) {
@@ -183,7 +183,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
             rot = false;
             // (lanes 32..63 look at the heads again -- same answer, no branch)
             const u32 ln = lane & (NQ - 1u);
-            const u64 c = __hip_atomic_load(queue + ln * 16u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const u64 c = __hip_atomic_load(queue + ln * KMX_Q_HEAD_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const u32 live = (u32)__ballot(c < (1ull << 58) && c * NQ + ln < n_full);
             if (live == 0u) {
                 heads_left = 0u;
@@ -212,7 +212,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
             unsigned long long one = 1ull;
             u32 zero = 0;        // (the head's address through a VGPR the compiler cannot see through: a wave-uniform address lets hipcc's atomic optimizer rewrite the add and wait for its result at once)
             asm volatile("" : "+v"(one), "+v"(zero));
-            pend = atomicAdd(queue + qid * 16u + zero, one);
+            pend = atomicAdd(queue + qid * KMX_Q_HEAD_STRIDE + zero, one);
         }
         if (rot) qid = (qid + 1u) & (NQ - 1u);
     };
@@ -226,7 +226,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
         return dequeue();
     };
     constexpr bool MARK = SinkMarksDirty<Sink>::value;
-    [[maybe_unused]] u64* const dirty_masks = (MARK && !SinkMarksCoarse<Sink>::value) ? reinterpret_cast<u64*>(queue[515]) : nullptr;
+    [[maybe_unused]] u64* const dirty_masks = (MARK && !SinkMarksCoarse<Sink>::value) ? reinterpret_cast<u64*>(queue[KMX_Q_MASKS]) : nullptr;
     [[maybe_unused]] u32 n_marked = 0;
     u64 next_tile = dequeue();
     constexpr bool PF = SinkPrefetch<Sink>::value && !RAGGED && NW <= 10;   // (the 16-word frame: 80 more registers do not fit two waves)
@@ -341,12 +341,12 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
             // (nothing of this is carried across the tile loop -- no pointer, no counter: the mask array's address is read here, and
             // what the sweep is told is "many", by a plain store that every marking wave agrees on; it fields all its waves then)
             if (roll_tile && tile_fits) {
-                const unsigned long long dq = queue[515];
+                const unsigned long long dq = queue[KMX_Q_MASKS];
                 u64* const dmk = reinterpret_cast<u64*>(((u64)(u32)__builtin_amdgcn_readfirstlane((u32)(dq >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((u32)dq));
                 if (dmk != nullptr) {
                     if (lane == 0) {      // (all 64: a read without a window costs the sweep nothing)
                         dmk[tile] = ~0ull;
-                        queue[512] = 1ull << 40;
+                        queue[KMX_Q_MARKED] = 1ull << 40;
                     }
                     roll_tile = false;
                 }
@@ -480,7 +480,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
         sink.end_read();
     }
     if constexpr (MARK) {
-        if (n_marked != 0u && lane == 0) atomicAdd(queue + 512, (unsigned long long)n_marked);   // (how many waves the sweep fields)
+        if (n_marked != 0u && lane == 0) atomicAdd(queue + KMX_Q_MARKED, (unsigned long long)n_marked);   // (how many waves the sweep fields)
     }
     sink.finish(params);
 }

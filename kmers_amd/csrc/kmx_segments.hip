@@ -11,6 +11,7 @@
 // the block's base, the block's threads writing its run of the arrays together).  The arrays are sized from an upper bound
 // S_max >= S (the host knows the total number of bases); the host reads S back and scans exactly S segments.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 

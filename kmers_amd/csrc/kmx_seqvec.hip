@@ -13,6 +13,7 @@
 // every slice for (k, L) outside the bit-sliced kernel: reduce_packed_generic_kernel (one lane walks one read with
 // CanonicalKmer::append_base, canonical_kmer.rs:90-94).
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 #include <type_traits>
 

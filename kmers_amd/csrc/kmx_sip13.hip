@@ -15,6 +15,7 @@
 // No block barrier: the waves of a block work on unrelated pieces.  k above 256 bases: minimizers_sip_generic_kernel.  The call is bound by VALU issue (five SipRounds per l-mer,
 // then k - w compares per k-mer), not by HBM.
 #include "kmx_device.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 

@@ -2,7 +2,7 @@
 //
 // scan_bitsliced_kernel (kmx_bitslice_kernel.h, "reads with an invalid byte") scans a tile that holds a non-ACGTacgt byte as it is --
 // such a byte counts as the base its bits (b >> 1) & 3 spell -- and leaves the 64-bit mask of the reads that touch a bad chunk
-// behind queue[515].  What the reference's iterator does NOT yield is exactly the windows that hold an invalid byte (the
+// behind queue[KMX_Q_MASKS].  What the reference's iterator does NOT yield is exactly the windows that hold an invalid byte (the
 // last_invalid rule, canonical_kmer_iterator.rs:50-66): this kernel evaluates those windows, from the same codes, and subtracts them.
 // Until round 5 the scan blanked such reads and they were ROLLED, one lane walking one read base by base: 0.5 TB/s of dirty
 // reads, 2 % of the reads cost 42 % of the time, 10 % cost 2.2x (profiles/r05_dirty_bench.txt).
@@ -15,6 +15,7 @@
 // while any lane has windows left (a read of nothing but N: four rounds).  Every k from 13 to 64: a window is V1 + 1 dwords
 // (V1 = (k - 1) / 16), compared from the top dword down.
 #include "kmx_bitslice_kernel.h"
+#include "kmx_launch.h"
 
 namespace kmx {
 
@@ -41,9 +42,9 @@ __device__ __forceinline__ void sweep_body(const uint8_t* __restrict__ bases, u6
                                            const u64* __restrict__ offsets, u32 lead, const u64* __restrict__ ends,
                                            const BsSeg& seg, const SweepZero& zo) {
     constexpr bool HIST = MODE == 1, ZERO = MODE == 2;
-    u64* const masks = reinterpret_cast<u64*>(queue[515]);
-    // how many reads the scan marked: the bit-sliced scan's last block leaves its count in [516] (and [512] at zero for the next launch,
-    // kmx_device.h); the word-domain scan's histogram sinks count in [512], which their caller clears with the heads
+    u64* const masks = reinterpret_cast<u64*>(queue[KMX_Q_MASKS]);
+    // how many reads the scan marked: the bit-sliced scan's last block leaves its count in KMX_Q_MARKED_OUT (and KMX_Q_MARKED at zero for
+    // the next launch, kmx_layout.h); the word-domain scan's histogram sinks count in KMX_Q_MARKED, which their caller clears with the heads
     const u64 n_marked = queue[(HIST || ZERO) ? KMX_Q_MARKED : KMX_Q_MARKED_OUT];
     if (masks == nullptr || n_marked == 0) return;
     // A sweep costs the same for 5 reads as for 64: as many waves as fill their sweeps (~48 reads each), not as many as were launched
@@ -57,8 +58,8 @@ __device__ __forceinline__ void sweep_body(const uint8_t* __restrict__ bases, u6
     const u64 wave_id = (u64)blockIdx.x * 4u + (threadIdx.x >> 6);
     const bool idle = wave_id >= n_waves;
     if constexpr (!RAGGED && !SEG) {   // (the length the gate found, as in scan_bitsliced_kernel: the reads lie L0 bytes apart)
-        const u32 gate = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * 513]);
-        const u32 gate_len = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * 513 + 1]);
+        const u32 gate = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * KMX_Q_GATE]);
+        const u32 gate_len = __builtin_amdgcn_readfirstlane(reinterpret_cast<const u32*>(queue)[2 * KMX_Q_GATE + 1]);
         if (gate == 1u && gate_len != 0u) L = gate_len;
     }
     constexpr int DWN = V1 + 1;          // dwords of a k-mer
