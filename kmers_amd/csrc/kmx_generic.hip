@@ -230,7 +230,7 @@ windows2_tiled_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
                       const u64* __restrict__ offsets, const u64* __restrict__ win_offsets, unsigned long long* __restrict__ too_long,
                       const u64* __restrict__ ends_arg, unsigned long long* __restrict__ queue) {
     // `queue` (round 6; nullptr: none): the context's queue block.  A tile with an invalid byte then stays on the tiled path -- all its reads
-    // marked, one store, as the single-word window sinks do (kmx_scan_kernel.h, SinkMarksCoarse) -- and the ZERO sweep behind the passes
+    // marked, one store, as the single-word window sinks do (kmx_scan_kernel.h, ScanSink::kMarksCoarse) -- and the ZERO sweep behind the passes
     // (kmx_sweep.hip) writes the spoiled windows' slots as the iterator leaves them; without it such a tile takes the per-read path.
     // `lead`: `bases` is the 16-byte aligned address at or below the first read, which starts `lead` bytes in
     // RAGGED: read r = bases[offsets[r], ends[r]); ends_arg == nullptr: back to back (ends = offsets + 1); a separate array serves

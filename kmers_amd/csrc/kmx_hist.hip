@@ -10,99 +10,89 @@ struct HistParams {
     u64* counts;
     u32 hasher, hk, log2_buckets;
 };
-// d_counts[bucket(hash(canonical k-mer))] += 1 with device-scope u64 atomics.  Measured ~24 G atomics/s on MI355X
-// independent of the bucket count (2^12..2^26) and of the atomic scope (XCD-private copies updated with
-// workgroup-scope atomics ran at the same rate), i.e. bound by the atomic issue rate, not by contention.
-struct SinkHist {
-    u64* counts;
-    u64 maskk;
-    u32 hasher, hk, k, b;
-    static constexpr u32 kLdsDwordsPerWave = 0;
-    __device__ __forceinline__ void block_done(u64, u32, u32) {}
-    static constexpr bool kRagged = true;
-    static constexpr bool kMarksDirty = true;   // (a tile with an invalid byte: fast path + marks, kmx_scan_kernel.h; launch_hist_uniform sweeps behind every scan)
-    static u32 block_lds_dwords(const HistParams&) { return 0; }
-    __device__ SinkHist(const HistParams& p, u32 k_, u32, u32*, u32, u32*, u32)
-        : counts(p.counts), maskk(mask2k(k_)), hasher(p.hasher), hk(p.hk), k(k_), b(p.log2_buckets) {}
-    __device__ __forceinline__ void emit(u64 fw, u64 rc) {
-        const u64 canon = fw < rc ? fw : rc;
-        u64 h;
-        if (hasher == KMX_HASH_LEX) h = (hk == k) ? (maskk ^ fw ^ rc ^ canon) : lex_hash(canon, hk);
-        else h = canon;  // identity: write_u64(data), hash.rs:4-8
-        atomicAdd((unsigned long long*)&counts[bucket_of(h, b)], 1ull);
-    }
-    __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) { emit(fw, rc); }
-    __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) { emit(fw, rc); }
-    __device__ __forceinline__ void begin_read(u64) {}
-    __device__ __forceinline__ void slow_block(u32) {}   // a rolled tile: the wave has completed 16 more windows per read
-    __device__ __forceinline__ void tile_slow_begin(u64 read) { begin_read(read); }
-    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
-    __device__ __forceinline__ void tile_slow_end() { end_read(); }
-    __device__ __forceinline__ void end_read() {}
-    __device__ __forceinline__ void tile_fast_done(u32) {}
-    __device__ __forceinline__ void finish(const HistParams&) {}
-};
-
-// Histogram, 2^b <= 2^14 buckets: block-private u32 table in LDS (ds_add_u32, no return), merged into d_counts
-// with one u64 atomic per non-empty bucket per block when the block retires.  The global-atomic sink above is bound
-// by the atomic rate (24 G/s => 0.5 s per 1e8 reads); LDS atomics are not.
-struct SinkHistLds {
-    u64* counts;
-    u32* tab;
-    u64 maskk;
-    u32 hasher, hk, k, b, tid;
-    static constexpr u32 kLdsDwordsPerWave = 0;
-    static constexpr bool kRagged = true;
-    static constexpr bool kMarksDirty = true;   // (a tile with an invalid byte: fast path + marks, kmx_scan_kernel.h; launch_hist_uniform sweeps behind every scan)
-    static u32 block_lds_dwords(const HistParams& p) { return 1u << p.log2_buckets; }
-    __device__ SinkHistLds(const HistParams& p, u32 k_, u32, u32*, u32, u32* block_lds, u32 tid_)
-        : counts(p.counts), tab(block_lds), maskk(mask2k(k_)), hasher(p.hasher), hk(p.hk), k(k_), b(p.log2_buckets), tid(tid_) {
-        for (u32 j = tid; j < (1u << b); j += 256u) tab[j] = 0;
-        __syncthreads();
-    }
-    __device__ __forceinline__ void block_done(u64, u32, u32) {}
-    __device__ __forceinline__ void emit(u64 fw, u64 rc) {
-        const u64 canon = fw < rc ? fw : rc;
-        u64 h;
-        if (hasher == KMX_HASH_LEX) h = (hk == k) ? (maskk ^ fw ^ rc ^ canon) : lex_hash(canon, hk);
-        else h = canon;
-        atomicAdd(&tab[(u32)bucket_of(h, b)], 1u);
-    }
-    __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) { emit(fw, rc); }
-    __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) { emit(fw, rc); }
-    __device__ __forceinline__ void begin_read(u64) {}
-    __device__ __forceinline__ void slow_block(u32) {}   // a rolled tile: the wave has completed 16 more windows per read
-    __device__ __forceinline__ void tile_slow_begin(u64 read) { begin_read(read); }
-    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
-    __device__ __forceinline__ void tile_slow_end() { end_read(); }
-    __device__ __forceinline__ void end_read() {}
-    __device__ __forceinline__ void tile_fast_done(u32) {}
-    __device__ __forceinline__ void finish(const HistParams&) {
-        __syncthreads();
-        for (u32 j = tid; j < (1u << b); j += 256u) {
-            const u32 c = tab[j];
-            if (c) atomicAdd((unsigned long long*)&counts[j], (unsigned long long)c);
-        }
-    }
-};
-
-// kmx_histogram_sip13: the bucket of SipHash-1-3(canonical word) (std's DefaultHasher / RandomState, kmx.h).  Sinks of their own, so
-// the sinks above keep their instantiations.  No kMarksDirty: a tile with an invalid byte takes the scan's exact rolling path and no
-// sweep follows (the sweep would have to hash the spoiled windows again).  LDS: a block-private table (<= 2^14 buckets); GLOBAL: one
-// device-scope atomic per window (what the partitioned passes -- SinkHistPartT<3> -- leave over: no scratch, or above 2^28).
 struct HistSipParams {
     u64* counts;
     SipKey key;
     u32 log2_buckets;
 };
+template <class Hash, bool LDS> struct SinkHistTable;
+template <bool LDS> struct SinkHistSip;
+// One policy per entry point: its parameter blocks for the table sinks (Params) and for the partitioned passes (PartParams,
+// kmx_hist_part.h), its table sink (Table<LDS>: a block-private LDS table or device atomics), and whether that sink marks dirty tiles.
+// kmx_histogram: LexHasher or identity, the choice made at run time.  kMarksDirty: a tile with an invalid byte takes the fast path
+// and is marked (kmx_scan_kernel.h); launch_hist_uniform sweeps behind every scan.
+struct HashLex {
+    using Params = HistParams;
+    using PartParams = HistPartParams;
+    template <bool LDS> using Table = SinkHistTable<HashLex, LDS>;
+    static constexpr bool kMarksDirty = true;
+    u64 maskk;
+    u32 hasher, hk, k;
+    __device__ HashLex(const HistParams& p, u32 k_) : maskk(mask2k(k_)), hasher(p.hasher), hk(p.hk), k(k_) {}
+    __device__ __forceinline__ u64 operator()(u64 fw, u64 rc) const {
+        const u64 canon = fw < rc ? fw : rc;
+        u64 h;
+        if (hasher == KMX_HASH_LEX) h = (hk == k) ? (maskk ^ fw ^ rc ^ canon) : lex_hash(canon, hk);
+        else h = canon;  // identity: write_u64(data), hash.rs:4-8
+        return h;
+    }
+};
+// kmx_histogram_sip13: SipHash-1-3 of the canonical word (std's DefaultHasher / RandomState, kmx.h).  No kMarksDirty: a tile with an
+// invalid byte takes the scan's exact rolling path and no sweep follows (the sweep would have to hash the spoiled windows again).
+struct HashSip13 {
+    using Params = HistSipParams;
+    using PartParams = HistPartSipParams;
+    template <bool LDS> using Table = SinkHistSip<LDS>;
+    static constexpr bool kMarksDirty = false;
+};
+
+// d_counts[bucket(hash(canonical k-mer))] += 1.
+// LDS = false: device-scope u64 atomics.  Measured ~24 G atomics/s on MI355X independent of the bucket count (2^12..2^26) and of
+// the atomic scope (XCD-private copies updated with workgroup-scope atomics ran at the same rate), i.e. bound by the atomic issue
+// rate, not by contention.  What the partitioned passes leave over: no scratch, or above 2^28 buckets.
+// LDS = true, 2^b <= 2^14 buckets: block-private u32 table in LDS (ds_add_u32, no return), merged into d_counts with one u64
+// atomic per non-empty bucket per block when the block retires.  The global-atomic sink is bound by the atomic rate (24 G/s =>
+// 0.5 s per 1e8 reads); LDS atomics are not.
+template <class Hash, bool LDS>
+struct SinkHistTable : ScanSink<SinkHistTable<Hash, LDS>> {
+    u64* counts;
+    u32* tab;
+    Hash hash;
+    u32 b, tid;
+    static constexpr bool kMarksDirty = Hash::kMarksDirty;
+    static u32 block_lds_dwords(const typename Hash::Params& p) { return LDS ? 1u << p.log2_buckets : 0u; }
+    __device__ SinkHistTable(const typename Hash::Params& p, u32 k_, u32, u32*, u32, u32* block_lds, u32 tid_)
+        : counts(p.counts), tab(block_lds), hash(p, k_), b(p.log2_buckets), tid(tid_) {
+        if (LDS) {
+            for (u32 j = tid; j < (1u << b); j += 256u) tab[j] = 0;
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ void emit(u64 fw, u64 rc) {
+        const u64 h = hash(fw, rc);
+        if (LDS) atomicAdd(&tab[(u32)bucket_of(h, b)], 1u);
+        else atomicAdd((unsigned long long*)&counts[bucket_of(h, b)], 1ull);
+    }
+    __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) { emit(fw, rc); }
+    __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) { emit(fw, rc); }
+    __device__ __forceinline__ void finish(const typename Hash::Params&) {
+        if (LDS) {
+            __syncthreads();
+            for (u32 j = tid; j < (1u << b); j += 256u) {
+                const u32 c = tab[j];
+                if (c) atomicAdd((unsigned long long*)&counts[j], (unsigned long long)c);
+            }
+        }
+    }
+};
+// The same table for SipHash-1-3.  Not SinkHistTable<HashSip13, LDS>: with the key behind a policy member the compiler orders the
+// SipRounds' adds and rotates differently (the same instructions, another schedule), so the kernels would not stay as they were.
 template <bool LDS>
-struct SinkHistSip {
+struct SinkHistSip : ScanSink<SinkHistSip<LDS>> {
     u64* counts;
     u32* tab;
     SipKey key;
     u32 b, tid;
-    static constexpr u32 kLdsDwordsPerWave = 0;
-    static constexpr bool kRagged = true;
     static u32 block_lds_dwords(const HistSipParams& p) { return LDS ? 1u << p.log2_buckets : 0u; }
     __device__ SinkHistSip(const HistSipParams& p, u32, u32, u32*, u32, u32* block_lds, u32 tid_)
         : counts(p.counts), tab(block_lds), key(p.key), b(p.log2_buckets), tid(tid_) {
@@ -111,7 +101,6 @@ struct SinkHistSip {
             __syncthreads();
         }
     }
-    __device__ __forceinline__ void block_done(u64, u32, u32) {}
     __device__ __forceinline__ void emit(u64 fw, u64 rc) {
         const u64 h = siphash13(fw < rc ? fw : rc, key);
         if (LDS) atomicAdd(&tab[(u32)bucket_of(h, b)], 1u);
@@ -119,13 +108,6 @@ struct SinkHistSip {
     }
     __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) { emit(fw, rc); }
     __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) { emit(fw, rc); }
-    __device__ __forceinline__ void begin_read(u64) {}
-    __device__ __forceinline__ void slow_block(u32) {}
-    __device__ __forceinline__ void tile_slow_begin(u64) {}
-    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
-    __device__ __forceinline__ void tile_slow_end() {}
-    __device__ __forceinline__ void end_read() {}
-    __device__ __forceinline__ void tile_fast_done(u32) {}
     __device__ __forceinline__ void finish(const HistSipParams&) {
         if (LDS) {
             __syncthreads();
@@ -146,6 +128,8 @@ struct SinkHistSip {
 // Pass 2 (hist_part_reduce_kernel) builds each partition's 2^(b-6)-bucket table in LDS.  Ids that find their ring or
 // their segment full (adversarial input: everything in one partition) go straight to the global table, so the result
 // is exact for every input.
+// Pass 2: block (partition q, group g) adds the segments of the waves w == g (mod gridDim.y) into an LDS table.
+// SUB_BITS = 1 (2^22 buckets: a partition's 2^16-entry table does not fit the LDS): blockIdx.z picks the half of the partition's
 // buckets this block counts; both halves read the whole id stream of the partition.
 template <int THREADS, int SUB_BITS = 0>
 __global__ void __launch_bounds__(THREADS)
@@ -265,187 +249,153 @@ hist_repartition_kernel(const u32* __restrict__ stream1, const u32* __restrict__
     sink.finish(p2);
 }
 
-// Larger tables, or no scratch: device-scope u64 atomics (SinkHist).
-// Every scan is followed by the sweep that takes the windows with an invalid byte back out of the counters (round 6: the sinks mark
-// the reads of a dirty tile instead of rolling it -- kmx_scan_kernel.h, SinkMarksDirty; a no-op on clean input).
+// Pass 2 of a partitioned route: the 64 partitions' streams of `n_waves` waves each into LDS tables of 2^(log2_buckets - 6)
+// entries, `groups` blocks per partition.  Two levels: `tops` first-level partitions, log2_buckets the bucket bits below the first
+// level, their streams and lengths `top_stream_stride` / `top_len_stride` apart.
+static hipError_t launch_part_reduce(const uint16_t* stream, const u32* seg_len, u32 cap, u32 n_waves, u32 log2_buckets, u64* counts,
+                                     u32 groups, u32 tops, u64 top_stream_stride, u32 top_len_stride, hipStream_t st) {
+    const bool halves = log2_buckets == 22u;   // 2^16 buckets per partition: two blocks of 2^15 each
+    const u32 nb_bytes = 4u << (log2_buckets - 6u - (halves ? 1u : 0u));
+    auto red = halves ? hist_part_reduce_kernel<512, 1> : hist_part_reduce_kernel<512, 0>;
+    if (nb_bytes > 64u * 1024u) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(red), hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(red, dim3(64, groups, tops * (halves ? 2u : 1u)), dim3(512), nb_bytes, st, stream, seg_len, cap, n_waves,
+                       log2_buckets, counts, top_stream_stride, top_len_stride);
+    return hipGetLastError();
+}
+
+// The routes of one hash policy (launch_hist_uniform).  Larger tables, or no scratch: device-scope u64 atomics.
+// Every scan of a sink that marks is followed by the sweep that takes the windows with an invalid byte back out of the counters
+// (round 6: the sinks mark the reads of a dirty tile instead of rolling it -- kmx_scan_kernel.h, ScanSink::kMarksDirty; a no-op on
+// clean input).
+template <class Hash>
+static hipError_t hist_routes(const typename Hash::Params& p, const typename Hash::PartParams& pp0, const uint8_t* bases, u64 n_reads,
+                              u32 L, u32 k, unsigned long long* queue, int n_cu, hipStream_t stream, void* (*get_scratch)(void*, size_t),
+                              void* user, size_t scratch_budget, const u64* offsets) {
+    u64* const counts = p.counts;
+    const u32 log2_buckets = p.log2_buckets;
+    auto sweep = [&](const uint8_t* b, u64 n, const u64* o) -> hipError_t {
+        if constexpr (!Hash::kMarksDirty) return hipSuccess;
+        else return launch_sweep_hist(b, n, L, k, p.hasher, p.hk, log2_buckets, counts, queue, n_cu, stream, o);
+    };
+    auto atomic_scan = [&](const uint8_t* b, u64 n, const u64* o) -> hipError_t {
+        hipError_t e = dispatch<typename Hash::template Table<false>>(b, n, L, k, p, queue, n_cu, stream, NoPre(), o);
+        return e != hipSuccess ? e : sweep(b, n, o);
+    };
+    if (log2_buckets <= 14u) {
+        hipError_t e = dispatch<typename Hash::template Table<true>>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
+        return e != hipSuccess ? e : sweep(bases, n_reads, offsets);
+    }
+    if (log2_buckets > 28u || get_scratch == nullptr || n_reads < 4096u) return atomic_scan(bases, n_reads, offsets);
+    // Partitioned.  2^15..2^22 buckets: one level of 64 partitions.  2^23..2^28 (TWO levels, round 3; these sizes took device
+    // atomics before: 0.5 s per 1e8 reads): pass 1 with the whole bucket per id (u32 entries); hist_repartition_kernel splits each
+    // partition's stream by the next six bits into uint16_t streams; hist_part_reduce_kernel counts the 64 x 64 streams in LDS
+    // tables of 2^(b-12) entries (2^16 at b = 28: two halves).
+    const bool two = log2_buckets >= 23u;
+    // windows per read the segments are sized for.  Ragged reads: from the caller's bound of the lengths (the frame's 256 if
+    // there is none); a read that is longer after all only fills its wave's segments sooner, and what finds a segment full
+    // goes to the global table (exact, slow).
+    const u32 Lb = offsets ? (L ? L : 256u) : L;
+    const u64 W = Lb >= k ? Lb - k + 1u : 1u;
+    const u32 gx2 = (u32)((n_cu * 4 + 63) / 64 > 0 ? (n_cu * 4 + 63) / 64 : 1);   // two levels: blocks per first-level partition in the pass between
+    // Scratch per window: 1.5x slack on 2 bytes per id (two levels: 1.5 x (4 + 2)), plus the fixed per-segment pads.  One level: at
+    // most 319 entries for each of the 64 segments of at most 8 blocks per CU of four waves, and their lengths.  Two levels: <= 319
+    // entries for each of the 64 x waves first-level and 64 x 64 x waves second-level segments, ~0.8 GB on 256 CUs.  The pads are
+    // taken off the budget first and the reads chunked so that a request never EXCEEDS the budget -- a request above it made the
+    // context's buffer larger than the budget, the next call was handed that size as its budget (kmx_api.hip), asked for a little
+    // more again, and every call re-allocated a 36 GB buffer (1.1 s; round 3)
+    const u64 fixed_max = two ? (u64)n_cu * 16u * 64u * 319u * 4u + 64ull * gx2 * 4u * 64u * 319u * 2u + (64u << 20)
+                              : (u64)n_cu * 8u * 4u * 64u * (319u * 2u + 4u);
+    const u64 fixed = fixed_max < scratch_budget / 4u ? fixed_max : scratch_budget / 4u;
+    u64 chunk = (scratch_budget - fixed) / ((two ? 9u : 3u) * W);
+    if (chunk > n_reads) chunk = n_reads;
+    chunk &= ~63ull;
+    if (chunk < 4096u) return atomic_scan(bases, n_reads, offsets);
+    const u32 low1 = log2_buckets - 6u;   // two levels: the bucket bits below the first level
+    for (u64 first = 0; first < n_reads; first += chunk) {
+        const u64 n = n_reads - first < chunk ? n_reads - first : chunk;
+        typename Hash::PartParams pp = pp0;
+        u32 n_waves = 0, n_waves2 = 0, cap2 = 0;
+        uint16_t* stream2 = nullptr;
+        u32* seg_len2 = nullptr;
+        // (launch_one's hook: the grid is known -- size the segments, fetch the scratch; the proxy of make_hist_pre hands the
+        // launcher this pp, filled, at launch time)
+        auto pre = [&](u64 grid) -> bool {
+            n_waves = (u32)(grid * 4u);
+            const u64 per_seg = (n * W * 3u / 2u) / ((u64)n_waves * 64u) + 256u;
+            pp.cap = (u32)((per_seg + 63u) & ~63ull);
+            if (pp.cap > (1u << 24)) return false;   // 64 * cap must stay below 2^31 (SinkHistPart::dest)
+            const size_t s1 = (size_t)n_waves * 64u * pp.cap * (two ? 4u : 2u), l1 = (size_t)n_waves * 64u * 4u;
+            size_t s2 = 0, l2 = 0;
+            if (two) {
+                n_waves2 = gx2 * 4u;
+                const u64 per_seg2 = (n * W * 3u / 2u) / (64ull * n_waves2 * 64u) + 256u;
+                cap2 = (u32)((per_seg2 + 63u) & ~63ull);
+                s2 = (size_t)64u * n_waves2 * 64u * cap2 * 2u;
+                l2 = (size_t)64u * n_waves2 * 64u * 4u;
+            }
+            char* buf = static_cast<char*>(get_scratch(user, s1 + l1 + s2 + l2));
+            if (!buf) return false;
+            pp.stream = buf;
+            pp.seg_len = reinterpret_cast<u32*>(buf + s1);
+            stream2 = reinterpret_cast<uint16_t*>(buf + s1 + l1);
+            seg_len2 = reinterpret_cast<u32*>(buf + s1 + l1 + s2);
+            return true;
+        };
+        if (first != 0) {
+            hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_THROUGH_MARKED, stream);   // (the heads, and the count of marked reads behind them)
+            if (e != hipSuccess) return e;
+        }
+        // (ragged reads: the offsets are absolute, the chunk is a window into them)
+        const uint8_t* cb = offsets ? bases : bases + first * (u64)L;
+        const u64* co = offsets ? offsets + first : nullptr;
+        hipError_t e = two ? dispatch_part_u32(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co)
+                           : dispatch_part<uint16_t>(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co);
+        if (e == hipErrorOutOfMemory) {   // no scratch: the atomic sink handles the rest
+            (void)hipGetLastError();
+            return atomic_scan(cb, n_reads - first, co);
+        }
+        if (e != hipSuccess) return e;
+        e = sweep(cb, n, co);
+        if (e != hipSuccess) return e;
+        if (two) {
+            typedef SinkHistPartT<1, uint16_t> Sink2;
+            const HistPartParams dummy{};
+            const size_t lds2 = ((size_t)Sink2::block_lds_dwords(dummy) + 4u * Sink2::kLdsDwordsPerWave) * 4u;
+            hipLaunchKernelGGL(hist_repartition_kernel, dim3(gx2, 64), dim3(256), lds2, stream, static_cast<const u32*>(pp.stream), pp.seg_len,
+                               pp.cap, n_waves, log2_buckets, counts, stream2, seg_len2, cap2);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            e = launch_part_reduce(stream2, seg_len2, cap2, n_waves2, low1, counts, n_waves2 < 4u ? n_waves2 : 4u, 64u,
+                                   (u64)n_waves2 * 64u * (u64)cap2, n_waves2 * 64u, stream);
+        } else {
+            // (eight blocks per partition: 16 measured the same at 1.25e8 reads and 35 us slower per call up to 4e6 -- every block flushes a whole
+            // table --, one or two slower again: profiles/r05_small_batches.txt)
+            e = launch_part_reduce(static_cast<const uint16_t*>(pp.stream), pp.seg_len, pp.cap, n_waves, log2_buckets, counts,
+                                   n_waves < 8u ? n_waves : 8u, 1u, 0u, 0u, stream);
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Histogram routes: 2^b <= 2^14 block-private LDS tables; 2^15..2^28 the partitioned passes in chunks of the scratch budget (one level
+// up to 2^22, two above); otherwise device atomics.
 hipError_t launch_hist_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, u32 hasher, u32 hk, u32 log2_buckets,
                                u64* counts, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled,
                                void* (*get_scratch)(void*, size_t), void* user, size_t scratch_budget, const u64* offsets, u64 k0, u64 k1) {
     *handled = offsets ? scan_domain_ragged(bases, L, k) : scan_domain(bases, n_reads, L, k);
     if (!*handled) return hipSuccess;
-    // hasher KMX_HASH_SIP13_INTERNAL (kmx_histogram_sip13, keys k0 / k1): the SipHash sinks on every route; they do not mark dirty
-    // tiles (they roll them), so no sweep follows their scans
-    const bool sip = hasher == KMX_HASH_SIP13_INTERNAL;
-    const SipKey key = sip_key(k0, k1);
-    const HistParams p{counts, hasher, hk, log2_buckets};
-    const HistSipParams ps{counts, key, log2_buckets};
-    auto sweep = [&](const uint8_t* b, u64 n, const u64* o) -> hipError_t {
-        if (sip) return hipSuccess;
-        return launch_sweep_hist(b, n, L, k, hasher, hk, log2_buckets, counts, queue, n_cu, stream, o);
-    };
-    auto atomic_scan = [&](const uint8_t* b, u64 n, const u64* o) -> hipError_t {
-        hipError_t e = sip ? dispatch<SinkHistSip<false>>(b, n, L, k, ps, queue, n_cu, stream, NoPre(), o)
-                           : dispatch<SinkHist>(b, n, L, k, p, queue, n_cu, stream, NoPre(), o);
-        return e != hipSuccess ? e : sweep(b, n, o);
-    };
-    if (log2_buckets <= 14u) {
-        hipError_t e = sip ? dispatch<SinkHistSip<true>>(bases, n_reads, L, k, ps, queue, n_cu, stream, NoPre(), offsets)
-                           : dispatch<SinkHistLds>(bases, n_reads, L, k, p, queue, n_cu, stream, NoPre(), offsets);
-        return e != hipSuccess ? e : sweep(bases, n_reads, offsets);
+    // hasher KMX_HASH_SIP13_INTERNAL (kmx_histogram_sip13, keys k0 / k1): the SipHash sinks on every route
+    if (hasher == KMX_HASH_SIP13_INTERNAL) {
+        const SipKey key = sip_key(k0, k1);
+        return hist_routes<HashSip13>(HistSipParams{counts, key, log2_buckets}, HistPartSipParams{{counts, hasher, hk, log2_buckets, nullptr, nullptr, 0u}, key},
+                                      bases, n_reads, L, k, queue, n_cu, stream, get_scratch, user, scratch_budget, offsets);
     }
-    if (log2_buckets >= 23u && log2_buckets <= 28u && get_scratch != nullptr && n_reads >= 4096u) {
-        // Two levels of 64 partitions each (round 3; these sizes took device atomics before: 0.5 s per 1e8 reads).  Pass 1 as
-        // below but with the whole bucket per id (u32 entries); hist_repartition_kernel splits each partition's stream by the
-        // next six bits into uint16_t streams; hist_part_reduce_kernel counts the 64 x 64 streams in LDS tables of 2^(b-12)
-        // entries (2^16 at b = 28: two halves).  Scratch per window: 1.5 x (4 + 2) bytes.
-        const u32 Lb = offsets ? (L ? L : 256u) : L;
-        const u64 W = Lb >= k ? Lb - k + 1u : 1u;
-        // scratch per window: 1.5 x (4 + 2) bytes, plus the fixed pads of the segments (<= 319 entries for each of the 64 x waves
-        // first-level and 64 x 64 x waves second-level segments, ~0.8 GB on 256 CUs) -- taken off the budget first, as the
-        // one-level path does: a request above the budget grows the context's buffer past it, and the next call asks for
-        // slightly more again (a re-allocation per call)
-        const u64 fixed_max = (u64)n_cu * 16u * 64u * 319u * 4u + 64ull * (u64)((n_cu * 4 + 63) / 64 > 0 ? (n_cu * 4 + 63) / 64 : 1) * 4u * 64u * 319u * 2u + (64u << 20);
-        const u64 fixed = fixed_max < scratch_budget / 4u ? fixed_max : scratch_budget / 4u;
-        u64 chunk = (scratch_budget - fixed) / (9u * W);
-        if (chunk > n_reads) chunk = n_reads;
-        chunk &= ~63ull;
-        if (chunk >= 4096u) {
-            const u32 low1 = log2_buckets - 6u;
-            for (u64 first = 0; first < n_reads; first += chunk) {
-                const u64 n = n_reads - first < chunk ? n_reads - first : chunk;
-                HistPartSipParams pp{};   // (the key is read by the SipHash sink only; the other modes get the base part)
-                pp.counts = counts; pp.hasher = hasher; pp.hk = hk; pp.log2_buckets = log2_buckets; pp.key = key;
-                u32 n_waves = 0, n_waves2 = 0, cap2 = 0;
-                uint16_t* stream2 = nullptr;
-                u32* seg_len2 = nullptr;
-                const u32 gx2 = (u32)((n_cu * 4 + 63) / 64 > 0 ? (n_cu * 4 + 63) / 64 : 1);   // blocks per first-level partition in the pass between
-                auto pre = [&](u64 grid) -> bool {
-                    n_waves = (u32)(grid * 4u);
-                    const u64 per_seg = (n * W * 3u / 2u) / ((u64)n_waves * 64u) + 256u;
-                    pp.cap = (u32)((per_seg + 63u) & ~63ull);
-                    if (pp.cap > (1u << 24)) return false;
-                    n_waves2 = gx2 * 4u;
-                    const u64 per_seg2 = (n * W * 3u / 2u) / (64ull * n_waves2 * 64u) + 256u;
-                    cap2 = (u32)((per_seg2 + 63u) & ~63ull);
-                    const size_t s1 = (size_t)n_waves * 64u * pp.cap * 4u, l1 = (size_t)n_waves * 64u * 4u;
-                    const size_t s2 = (size_t)64u * n_waves2 * 64u * cap2 * 2u, l2 = (size_t)64u * n_waves2 * 64u * 4u;
-                    char* buf = static_cast<char*>(get_scratch(user, s1 + l1 + s2 + l2));
-                    if (!buf) return false;
-                    pp.stream = buf;
-                    pp.seg_len = reinterpret_cast<u32*>(buf + s1);
-                    stream2 = reinterpret_cast<uint16_t*>(buf + s1 + l1);
-                    seg_len2 = reinterpret_cast<u32*>(buf + s1 + l1 + s2);
-                    return true;
-                };
-                if (first != 0) {
-                    hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_THROUGH_MARKED, stream);   // (the heads, and the count of marked reads behind them)
-                    if (e != hipSuccess) return e;
-                }
-                const uint8_t* cb = offsets ? bases : bases + first * (u64)L;
-                const u64* co = offsets ? offsets + first : nullptr;
-                hipError_t e = sip ? dispatch_part_u32(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co)
-                                   : dispatch_part_u32(cb, n, L, k, static_cast<HistPartParams&>(pp), queue, n_cu, stream, make_hist_pre(pre), co);
-                if (e == hipErrorOutOfMemory) {   // no scratch: the atomic sink handles the rest
-                    (void)hipGetLastError();
-                    return atomic_scan(cb, n_reads - first, co);
-                }
-                if (e != hipSuccess) return e;
-                e = sweep(cb, n, co);
-                if (e != hipSuccess) return e;
-                typedef SinkHistPartT<1, uint16_t> Sink2;
-                const HistPartParams dummy{};
-                const size_t lds2 = ((size_t)Sink2::block_lds_dwords(dummy) + 4u * Sink2::kLdsDwordsPerWave) * 4u;
-                hipLaunchKernelGGL(hist_repartition_kernel, dim3(gx2, 64), dim3(256), lds2, stream, static_cast<const u32*>(pp.stream), pp.seg_len,
-                                   pp.cap, n_waves, log2_buckets, counts, stream2, seg_len2, cap2);
-                e = hipGetLastError();
-                if (e != hipSuccess) return e;
-                const bool halves = low1 == 22u;   // 2^16 buckets per second-level partition: two blocks of 2^15 each
-                const u32 nb_bytes = 4u << (low1 - 6u - (halves ? 1u : 0u));
-                auto red = halves ? hist_part_reduce_kernel<512, 1> : hist_part_reduce_kernel<512, 0>;
-                if (nb_bytes > 64u * 1024u) {
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(red), hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb_bytes);
-                    if (e != hipSuccess) return e;
-                }
-                const u32 groups = n_waves2 < 4u ? n_waves2 : 4u;
-                hipLaunchKernelGGL(red, dim3(64, groups, 64u * (halves ? 2u : 1u)), dim3(512), nb_bytes, stream, stream2, seg_len2, cap2, n_waves2,
-                                   low1, counts, (u64)n_waves2 * 64u * (u64)cap2, n_waves2 * 64u);
-                e = hipGetLastError();
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
-        }
-    }
-    if (log2_buckets <= 22u && get_scratch != nullptr && n_reads >= 4096u) {
-        // windows per read the segments are sized for.  Ragged reads: from the caller's bound of the lengths (the frame's 256 if
-        // there is none); a read that is longer after all only fills its wave's segments sooner, and what finds a segment full
-        // goes to the global table (exact, slow).
-        const u32 Lb = offsets ? (L ? L : 256u) : L;
-        const u64 W = Lb >= k ? Lb - k + 1u : 1u;
-        // scratch per read: 1.5x slack on 2 bytes per window, plus the fixed per-segment pad (at most 319 entries for each of the 64
-        // segments of at most 8 blocks per CU of four waves, and their lengths); chunk the reads so that a request never EXCEEDS
-        // the budget -- a request above it made the context's buffer larger than the budget, the next call was handed that size as
-        // its budget (kmx_api.hip), asked for a little more again, and every call re-allocated a 36 GB buffer (1.1 s; round 3)
-        const u64 fixed_max = (u64)n_cu * 8u * 4u * 64u * (319u * 2u + 4u);
-        const u64 fixed = fixed_max < scratch_budget / 4u ? fixed_max : scratch_budget / 4u;
-        u64 chunk = (scratch_budget - fixed) / (3u * W);
-        if (chunk > n_reads) chunk = n_reads;
-        chunk &= ~63ull;
-        if (chunk >= 4096u) {
-            for (u64 first = 0; first < n_reads; first += chunk) {
-                const u64 n = n_reads - first < chunk ? n_reads - first : chunk;
-                HistPartSipParams pp{};   // (the key is read by the SipHash sink only; the other modes get the base part)
-                pp.counts = counts; pp.hasher = hasher; pp.hk = hk; pp.log2_buckets = log2_buckets; pp.key = key;
-                u32 n_waves = 0;
-                auto pre = [&](u64 grid) -> bool {
-                    n_waves = (u32)(grid * 4u);
-                    const u64 per_seg = (n * W * 3u / 2u) / ((u64)n_waves * 64u) + 256u;
-                    pp.cap = (u32)((per_seg + 63u) & ~63ull);
-                    if (pp.cap > (1u << 24)) return false;   // 64 * cap must stay below 2^31 (SinkHistPart::dest)
-                    const size_t stream_bytes = (size_t)n_waves * 64u * pp.cap * 2u;
-                    const size_t len_bytes = (size_t)n_waves * 64u * 4u;
-                    char* buf = static_cast<char*>(get_scratch(user, stream_bytes + len_bytes));
-                    if (!buf) return false;
-                    pp.stream = buf;
-                    pp.seg_len = reinterpret_cast<u32*>(buf + stream_bytes);
-                    return true;
-                };
-                if (first != 0) {
-                    hipError_t e = hipMemsetAsync(queue, 0, KMX_Q_CLEAR_THROUGH_MARKED, stream);   // (the heads, and the count of marked reads behind them)
-                    if (e != hipSuccess) return e;
-                }
-                // the hook fills pp through the reference captured above; dispatch takes its params by value, so hand it
-                // a proxy that copies the finished pp at launch time
-                // (ragged reads: the offsets are absolute, the chunk is a window into them)
-                const uint8_t* cb = offsets ? bases : bases + first * (u64)L;
-                const u64* co = offsets ? offsets + first : nullptr;
-                hipError_t e = sip ? dispatch_part<HistPartPre>(cb, n, L, k, pp, queue, n_cu, stream, make_hist_pre(pre), co)
-                                   : dispatch_part<HistPartPre>(cb, n, L, k, static_cast<HistPartParams&>(pp), queue, n_cu, stream, make_hist_pre(pre), co);
-                if (e == hipErrorOutOfMemory) {   // no scratch: the atomic sink handles the rest
-                    (void)hipGetLastError();
-                    return atomic_scan(cb, n_reads - first, co);
-                }
-                if (e != hipSuccess) return e;
-                e = sweep(cb, n, co);
-                if (e != hipSuccess) return e;
-                const bool halves = log2_buckets == 22u;   // 2^16 buckets per partition: two blocks of 2^15 each
-                const u32 nb_bytes = 4u << (log2_buckets - 6u - (halves ? 1u : 0u));
-                auto red = halves ? hist_part_reduce_kernel<512, 1> : hist_part_reduce_kernel<512, 0>;
-                if (nb_bytes > 64u * 1024u) {
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(red), hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb_bytes);
-                    if (e != hipSuccess) return e;
-                }
-                // (eight blocks per partition: 16 measured the same at 1.25e8 reads and 35 us slower per call up to 4e6 -- every block flushes a whole
-                // table --, one or two slower again: profiles/r05_small_batches.txt)
-                const u32 groups = n_waves < 8u ? n_waves : 8u;
-                hipLaunchKernelGGL(red, dim3(64, groups, halves ? 2 : 1), dim3(512), nb_bytes, stream, static_cast<const uint16_t*>(pp.stream), pp.seg_len,
-                                   pp.cap, n_waves, log2_buckets, counts, (u64)0, 0u);
-                e = hipGetLastError();
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
-        }
-    }
-    return atomic_scan(bases, n_reads, offsets);
+    return hist_routes<HashLex>(HistParams{counts, hasher, hk, log2_buckets}, HistPartParams{counts, hasher, hk, log2_buckets, nullptr, nullptr, 0u},
+                                bases, n_reads, L, k, queue, n_cu, stream, get_scratch, user, scratch_budget, offsets);
 }
 
 }  // namespace kmx

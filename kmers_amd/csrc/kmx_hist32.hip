@@ -6,11 +6,11 @@ namespace kmx {
 
 hipError_t dispatch_part_u32(const uint8_t* bases, u64 n_reads, u32 L, u32 k, HistPartParams& p, unsigned long long* queue,
                              int n_cu, hipStream_t stream, HistPartPre pre, const u64* offsets) {
-    return dispatch_part<HistPartPre, u32>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
+    return dispatch_part<u32>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
 }
 hipError_t dispatch_part_u32(const uint8_t* bases, u64 n_reads, u32 L, u32 k, HistPartSipParams& p, unsigned long long* queue,
                              int n_cu, hipStream_t stream, HistPartPre pre, const u64* offsets) {
-    return dispatch_part<HistPartPre, u32>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
+    return dispatch_part<u32>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
 }
 
 }  // namespace kmx

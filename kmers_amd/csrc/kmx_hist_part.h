@@ -45,7 +45,7 @@ struct HistPartSipParams : HistPartParams {
 // the first level of the TWO-level partition of 2^23..2^28 buckets (hist_repartition_kernel splits every partition's u32 stream
 // once more, by the next six bits, into uint16_t streams).  A ring is 128 bytes either way: 64 or 32 entries.
 template <int MODE, typename E = uint16_t>
-struct SinkHistPartT {
+struct SinkHistPartT : ScanSink<SinkHistPartT<MODE, E>> {
     static_assert(sizeof(E) == 2 || sizeof(E) == 4, "stream entries: uint16_t or u32");
     static constexpr u32 NP = 64, ROW = 128u / (u32)sizeof(E);   // partitions; ring entries per partition; rows of ROW/2 ids (64 bytes) leave together
     static constexpr u32 HALF = ROW / 2u;
@@ -56,7 +56,6 @@ struct SinkHistPartT {
     // (mix >> 26 | base >> 13 << 6) << 7 -- one v_alignbit_b32 with the wave's base in the high word -- plus the slot bytes
     static constexpr u32 kLdsDwordsPerWave = 2u * NP + NP / 4u;
     static constexpr u32 kBlockLdsAlign = 2048u;   // dwords (8 KB)
-    static constexpr bool kRagged = true;
     static constexpr bool kMarksDirty = MODE != 3;   // (a tile with an invalid byte: fast path + marks, kmx_scan_kernel.h; launch_hist_uniform sweeps behind every scan)   // (ragged reads come window by window through fast(): no batches)
     static constexpr u32 kRingDwords = 4u * NP * 32u;   // 4 waves x 64 rings x 128 bytes
     using Params = std::conditional_t<MODE == 3, HistPartSipParams, HistPartParams>;
@@ -228,11 +227,7 @@ struct SinkHistPartT {
         place(bucket, take_slot(bucket));
     }
     __device__ __forceinline__ void slow(u32, u64 fw, u64 rc) { emit(fw, rc); }
-    __device__ __forceinline__ void begin_read(u64) {}
     __device__ __forceinline__ void slow_block(u32) { flush_rows(); }   // a rolled tile: 16 more windows per read, wave converged: drain the rings
-    __device__ __forceinline__ void tile_slow_begin(u64 read) { begin_read(read); }
-    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
-    __device__ __forceinline__ void tile_slow_end() { end_read(); }
     // slow path: up to W ids per lane since the last flush (what does not fit the rings went to the global table).
     // The final partial tile calls this with some lanes masked off; flush_rows needs the whole wave, so it waits.
     __device__ __forceinline__ void end_read() {
@@ -241,7 +236,6 @@ struct SinkHistPartT {
             flush_rows();   // a ring can hold two full half rows
         }
     }
-    __device__ __forceinline__ void tile_fast_done(u32) {}
     __device__ __forceinline__ void finish(const Params&) {
         flush_rows();
         flush_rows();
@@ -263,50 +257,39 @@ struct SinkHistPartT {
     }
 };
 
-// pass 2: block (partition q, group g) adds the segments of the waves w == g (mod gridDim.y) into an LDS table
-// SUB_BITS = 1 (2^22 buckets: a partition's 2^16-entry table does not fit the LDS): blockIdx.z picks the half of the partition's
-
-template <typename SinkHistPart, typename Pre, bool RAGGED>
+template <typename SinkHistPart, bool RAGGED>
 static hipError_t dispatch_part_mode(const uint8_t* bases, u64 n_reads, u32 L, u32 k, typename SinkHistPart::Params& p, unsigned long long* queue,
-                                     int n_cu, hipStream_t stream, Pre pre, const u64* offsets) {
+                                     int n_cu, hipStream_t stream, HistPartPre pre, const u64* offsets) {
     const bool big = L > 160 || (RAGGED && L == 0);
-#define KMX_PART(NW, V, DW) launch_one<NW, V, DW, SinkHistPart, typename SinkHistPart::Params, Pre, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets)
+#define KMX_PART(NW, V, DW) launch_one<NW, V, DW, SinkHistPart, typename SinkHistPart::Params, HistPartPre, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets)
     if (k <= 16) return big ? KMX_PART(16, 1, 1) : KMX_PART(10, 1, 1);
     if (k == 17) return big ? KMX_PART(16, 1, 2) : KMX_PART(10, 1, 2);
     return big ? KMX_PART(16, 2, 2) : KMX_PART(10, 2, 2);
 #undef KMX_PART
 }
 
-template <typename Pre, typename E = uint16_t, typename P = HistPartParams>
-static hipError_t dispatch_part(const uint8_t* bases, u64 n_reads, u32 L, u32 k, P& p, unsigned long long* queue,
-                                int n_cu, hipStream_t stream, Pre pre, const u64* offsets) {
+// the sink's MODE, picked once: 3 for SipHash (the parameter type says so), otherwise 0..2 from the call's hasher
+template <typename E, bool RAGGED, typename P>
+static hipError_t dispatch_part_as(const uint8_t* bases, u64 n_reads, u32 L, u32 k, P& p, unsigned long long* queue, int n_cu,
+                                   hipStream_t stream, HistPartPre pre, const u64* offsets) {
     if constexpr (std::is_same_v<P, HistPartSipParams>) {   // kmx_histogram_sip13
-        if (offsets) return dispatch_part_mode<SinkHistPartT<3, E>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-        return dispatch_part_mode<SinkHistPartT<3, E>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
+        return dispatch_part_mode<SinkHistPartT<3, E>, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
     } else {
-    const int mode = p.hasher != KMX_HASH_LEX ? 1 : p.hk == k ? 0 : 2;
-    if constexpr (sizeof(E) == 4) {   // first level of the two-level partition (2^23..2^28 buckets)
-        if (offsets) {
-            if (mode == 0) return dispatch_part_mode<SinkHistPartT<0, u32>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-            if (mode == 1) return dispatch_part_mode<SinkHistPartT<1, u32>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-            return dispatch_part_mode<SinkHistPartT<2, u32>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-        }
-        if (mode == 0) return dispatch_part_mode<SinkHistPartT<0, u32>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
-        if (mode == 1) return dispatch_part_mode<SinkHistPartT<1, u32>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
-        return dispatch_part_mode<SinkHistPartT<2, u32>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
-    }
-    if (offsets) {
-        if (mode == 0) return dispatch_part_mode<SinkHistPartT<0>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-        if (mode == 1) return dispatch_part_mode<SinkHistPartT<1>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-        return dispatch_part_mode<SinkHistPartT<2>, Pre, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
-    }
-    if (mode == 0) return dispatch_part_mode<SinkHistPartT<0>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
-    if (mode == 1) return dispatch_part_mode<SinkHistPartT<1>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
-    return dispatch_part_mode<SinkHistPartT<2>, Pre, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
+        const int mode = p.hasher != KMX_HASH_LEX ? 1 : p.hk == k ? 0 : 2;
+        if (mode == 0) return dispatch_part_mode<SinkHistPartT<0, E>, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
+        if (mode == 1) return dispatch_part_mode<SinkHistPartT<1, E>, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
+        return dispatch_part_mode<SinkHistPartT<2, E>, RAGGED>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
     }
 }
+// E = uint16_t: 2^15..2^22 buckets (kmx_hist.hip); u32: the first level of 2^23..2^28 (kmx_hist32.hip)
+template <typename E, typename P>
+static hipError_t dispatch_part(const uint8_t* bases, u64 n_reads, u32 L, u32 k, P& p, unsigned long long* queue,
+                                int n_cu, hipStream_t stream, HistPartPre pre, const u64* offsets) {
+    if (offsets) return dispatch_part_as<E, true>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, offsets);
+    return dispatch_part_as<E, false>(bases, n_reads, L, k, p, queue, n_cu, stream, pre, nullptr);
+}
 
-// Histogram over uniform or ragged reads.  2^b <= 2^14: block-private LDS tables (SinkHistLds).  2^15..2^22: two passes through
+// Histogram over uniform or ragged reads.  2^b <= 2^14: block-private LDS tables (SinkHistTable).  2^15..2^22: two passes through
 // 64 partitions (SinkHistPart + hist_part_reduce_kernel) in chunks of reads sized to `scratch_budget` bytes of
 // caller-provided scratch (`get_scratch(user, bytes)` returns a device buffer of at least `bytes`, or nullptr).
 // 2^23..2^28: the same with a second level of 64 partitions in between (hist_repartition_kernel).

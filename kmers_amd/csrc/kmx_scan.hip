@@ -36,15 +36,11 @@ struct ReduceParams {
     u32 want_hash, want_sumfw;
 };
 template <bool FULL>
-struct SinkReduce {
+struct SinkReduce : ScanSink<SinkReduce<FULL>> {
     Acc acc;
     u64 maskk;
     u32 k;
-    static constexpr u32 kLdsDwordsPerWave = 0;
-    static constexpr bool kRagged = true;
-    static u32 block_lds_dwords(const ReduceParams&) { return 0; }
     __device__ SinkReduce(const ReduceParams&, u32 k_, u32, u32*, u32, u32*, u32) : maskk(mask2k(k_)), k(k_) {}
-    __device__ __forceinline__ void block_done(u64, u32, u32) {}
     __device__ __forceinline__ void fast(u32, u64 fw, u64 rc) {
         const u64 canon = fw < rc ? fw : rc;  // canonical_kmer.rs:113-119
         acc.sum_canon += canon;
@@ -68,12 +64,6 @@ struct SinkReduce {
             acc.sum_fw += fw;
         }
     }
-    __device__ __forceinline__ void begin_read(u64) {}
-    __device__ __forceinline__ void slow_block(u32) {}   // a rolled tile: the wave has completed 16 more windows per read
-    __device__ __forceinline__ void tile_slow_begin(u64 read) { begin_read(read); }
-    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
-    __device__ __forceinline__ void tile_slow_end() { end_read(); }
-    __device__ __forceinline__ void end_read() {}
     __device__ __forceinline__ void tile_fast_done(u32 nwin) { acc.n_valid += nwin; }
     __device__ __forceinline__ void finish(const ReduceParams& p) { flush_acc(acc, p.out, FULL && p.want_hash, FULL && p.want_sumfw); }
 };
@@ -87,14 +77,10 @@ struct ReduceSipParams {
     SipKey key;
 };
 template <bool SUMFW>
-struct SinkReduceSip {
+struct SinkReduceSip : ScanSink<SinkReduceSip<SUMFW>> {
     Acc acc;
     SipKey key;
-    static constexpr u32 kLdsDwordsPerWave = 0;
-    static constexpr bool kRagged = true;
-    static u32 block_lds_dwords(const ReduceSipParams&) { return 0; }
     __device__ SinkReduceSip(const ReduceSipParams& p, u32, u32, u32*, u32, u32*, u32) : key(p.key) {}
-    __device__ __forceinline__ void block_done(u64, u32, u32) {}
     __device__ __forceinline__ void add(u64 fw, u64 rc) {
         const u64 canon = fw < rc ? fw : rc;  // canonical_kmer.rs:113-119
         acc.sum_canon += canon;
@@ -110,12 +96,6 @@ struct SinkReduceSip {
         acc.n_valid += 1;
         add(fw, rc);
     }
-    __device__ __forceinline__ void begin_read(u64) {}
-    __device__ __forceinline__ void slow_block(u32) {}
-    __device__ __forceinline__ void tile_slow_begin(u64) {}
-    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { slow(pos, fw, rc); }
-    __device__ __forceinline__ void tile_slow_end() {}
-    __device__ __forceinline__ void end_read() {}
     __device__ __forceinline__ void tile_fast_done(u32 nwin) { acc.n_valid += nwin; }
     __device__ __forceinline__ void finish(const ReduceSipParams& p) { flush_acc(acc, p.out, true, SUMFW); }
 };
@@ -133,13 +113,13 @@ struct WindowsParams {
 // slot (win_offsets[r] mod 16) instead of r*W, its window count from the offsets; a read's last pass writes what is left of
 // it.  No shared-line merge, no prefetch of the next tile (the tile's geometry is not known that early).
 template <bool ALIGNED, bool RG = false>
-struct SinkWindowsT {
+struct SinkWindowsT : ScanSink<SinkWindowsT<ALIGNED, RG>> {
     static_assert(!RG || ALIGNED, "the ragged ring is a mode of the line-aligned sink");
-    // (round 6) a tile with an invalid byte: fast path + marks (kmx_scan_kernel.h, SinkMarksDirty) -- launch_windows_* ends with the
+    // (round 6) a tile with an invalid byte: fast path + marks (kmx_scan_kernel.h, ScanSink::kMarksDirty) -- launch_windows_* ends with the
     // sweep that writes the spoiled windows' slots as the iterator leaves them, zeros (kmx_sweep.hip, ZERO); rolled per lane such a
     // tile cost 6 tiles' worth, and 2 % dirty reads the materialise 37 % (profiles/r06_windows_dirty.txt)
     static constexpr bool kMarksDirty = true;
-    static constexpr bool kMarksCoarse = true;     // (all reads of a dirty tile: kmx_scan_kernel.h, SinkMarksCoarse)
+    static constexpr bool kMarksCoarse = true;     // (all reads of a dirty tile: kmx_scan_kernel.h, ScanSink::kMarksCoarse)
     static constexpr u32 PITCH = 17;                        // u64 per lane row (16 + 1 pad: conflict-free both ways)
     static constexpr u32 PLANE = 64u * PITCH * 2u;          // dwords of one staged u64 array of a wave
     // staging sized by what the caller asked for (with all three u64 planes a block holds 108 KB = one block per CU and one
@@ -154,7 +134,6 @@ struct SinkWindowsT {
     // living in the ring, two blocks per CU up to 256 bases: 2.5 -> 4.5 TB/s)
     static constexpr int kWavesBig = ALIGNED ? 2 : 1;
     static constexpr bool kAliasPacked = ALIGNED;
-    static constexpr u32 kLdsDwordsPerWave = 0;
     // One u64 array and no flags (the usual call: the canonical words): write-back in units of whole, 128-byte ALIGNED
     // lines of the output.  The lines of read r are shifted by a = r*W mod 16 slots against its windows, so the windows
     // of two passes sit in a 32-slot ring per read and pass j writes windows [16j - a, 16j + 16 - a).  (Writing windows
@@ -430,8 +409,6 @@ struct SinkWindowsT {
     }
     __device__ __forceinline__ void tile_slow_end() {}
     __device__ __forceinline__ void end_read() { zero_to(nwr); }
-    __device__ __forceinline__ void tile_fast_done(u32) {}
-    __device__ __forceinline__ void finish(const WindowsParams&) {}
 };
 
 // The flags array alone (uniform reads, W >= 16): one byte per window, VALID | FW_CANONICAL -- two BITS per window.  A lane
@@ -446,11 +423,10 @@ struct FlagsParams {
     uint8_t* flags;
     u32 magic;       // floor(2^32 / W) + 1: b / W = umulhi(b, magic) for b < 2^16
 };
-struct SinkFlags {
+struct SinkFlags : ScanSink<SinkFlags> {
     static constexpr bool kMarksDirty = true;   // (as SinkWindowsT: the sweep behind the passes zeroes the spoiled windows' flags)
     static constexpr bool kMarksCoarse = true;
     static constexpr u32 NB = 8, BP = 9;        // mask dwords per read (W <= 256); LDS pitch (the ninth stays zero)
-    static constexpr u32 kLdsDwordsPerWave = 0;
     static constexpr bool kRagged = false;
     static constexpr int kWaves = 3;            // (four: 40-60 bytes of spills)
     static u32 block_lds_dwords(const FlagsParams&) { return 4u * 2u * 64u * BP; }
@@ -475,7 +451,6 @@ struct SinkFlags {
 #pragma unroll
         for (u32 j = 0; j < NB; ++j) lb[j] |= (o >> 5) == j ? bit : 0u;
     }
-    __device__ __forceinline__ void block_done(u64, u32, u32) {}
     // the tile's masks are in LDS: 4 W chunks of 16 flag bytes
     __device__ __forceinline__ void write_tile(u64 read0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -530,7 +505,6 @@ struct SinkFlags {
         VB[lane * BP + (pos >> 5)] |= 1u << (pos & 31u);
         if (fw < rc) LB[lane * BP + (pos >> 5)] |= 1u << (pos & 31u);
     }
-    __device__ __forceinline__ void slow_block(u32) {}
     __device__ __forceinline__ void tile_slow_end() { write_tile(tile_read0); }
     // the final partial tile: byte stores, window by window
     __device__ __forceinline__ void slow(u32 pos, u64 fw, u64 rc) {
@@ -541,7 +515,6 @@ struct SinkFlags {
     __device__ __forceinline__ void end_read() {
         for (; next < W; ++next) p.flags[base + next] = 0;
     }
-    __device__ __forceinline__ void finish(const FlagsParams&) {}
 };
 
 // Each returns hipSuccess and sets *handled=false when (L,k) is outside the fast kernel's domain.

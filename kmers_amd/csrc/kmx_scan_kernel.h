@@ -11,6 +11,68 @@ namespace kmx {
 // A sink consumes windows.  fast(o, fw, rc): window o of the lane's read on the all-valid fast path;
 // slow(pos, fw, rc): a window yielded by roll_read (invalid ones are skipped); begin/end bracket one read
 // on the slow path; tile_fast_done(nwin) closes a fast tile.
+// Every sink derives from ScanSink<itself>, which holds what the kernel assumes of a sink that does not say otherwise; a sink
+// restates only the constants and hooks it changes (its own members hide the base's).
+template <class S>
+struct ScanSink {
+    // waves per SIMD the register allocation of a sink is sized for (1: hipcc otherwise spends up to 256 VGPRs on hoisting)
+    static constexpr int kWaves = 1;
+    // ... and for the 16-word frame (without a value of its own: no cap -- most sinks would spill 1 KB there)
+    static constexpr int kWavesBig = 1;
+    // take the 16 windows of an unrolled block together (kBatch16 = true; fast_slot())
+    static constexpr bool kBatch16 = false;
+    // the block-level LDS region starts at a multiple of kBlockLdsAlign dwords
+    static constexpr u32 kBlockLdsAlign = 1u;
+    // complemented windows (fw ^ mask, rc ^ mask) from the kernel's fast path
+    static constexpr bool kComplement = false;
+    // the first 16 windows of every read once more after the last block (kRedoHead; wants_heads(), head(o, fw, rc),
+    // heads_done(read0)): the materialise sink writes the output line that two neighbouring reads share in one piece then
+    static constexpr bool kRedoHead = false;
+    // a sink that stores to global memory in bulk may ask for the NEXT tile's bytes early (kPrefetch).  On gfx9 loads and stores
+    // share one in-order counter: a tile's loads, issued behind the 150 stores of the tile before, return when the last of those
+    // has been acknowledged -- every tile began with a drain of the wave's store queue (materialise, one array: 2.04 ms per 1e7
+    // reads against 1.73 with the loads taken out).  With kPrefetch the loads of tile t + 1 are issued once tile t has built its
+    // F / G words -- behind the stores of tile t - 1 only, which have had a whole load-and-encode phase to drain -- and are
+    // encoded into ten registers right after the first window block, before that block's stores.
+    static constexpr bool kPrefetch = false;
+    // a sink whose block-level LDS is one region per wave, empty between two tiles (kAliasPacked; wave_dwords(params) >= the
+    // packed tile), lends it to the tile's packed words: they are dead once the lanes hold their F / G words, and a wave's LDS
+    // operations complete in order
+    static constexpr bool kAliasPacked = false;
+    // a sink whose windows a later pass can take back (kMarksDirty; round 6): a tile that holds an invalid byte is then NOT rolled
+    // per lane -- it takes the fast path as it is, an invalid byte counting as the base its bits (b >> 1) & 3 spell, and the reads
+    // that touch a bad chunk are marked in the array behind queue[KMX_Q_MASKS] exactly as the bit-sliced scan marks them
+    // (mark_dirty_rows, below); what the windows with an invalid byte added is subtracted by sweep_flagged_kernel (kmx_sweep.hip).
+    // The bucket histograms: a rolled tile cost 2-3 tiles, and with an N in 2 % of the reads 73 % of the tiles rolled (+62 %:
+    // profiles/r05_dirty_bench.txt).
+    static constexpr bool kMarksDirty = false;
+    // ... and a sink that marks COARSELY (kMarksCoarse): every read of a dirty tile -- one store of a constant, nothing computed --
+    // and leaves it to the sweep to look at the bytes.  The line-aligned window sinks: at 249-255 registers they have none to spare
+    // for finding the reads (inline or as a call, the block cost the CLEAN materialise 15-18 %: profiles/r06_windows_dirty.txt).
+    static constexpr bool kMarksCoarse = false;
+    // LDS dwords of the sink's own per wave, behind the wave's packed tile
+    static constexpr u32 kLdsDwordsPerWave = 0;
+    // the sink serves ragged reads (an offsets array) as well as uniform ones
+    static constexpr bool kRagged = true;
+    // LDS dwords of the sink's own per block, behind the waves' regions
+    template <class P>
+    static u32 block_lds_dwords(const P&) { return 0; }
+    // all 64 lanes are through windows [o0, o0 + cnt) of reads [read0, read0 + 64) on the fast path
+    __device__ __forceinline__ void block_done(u64, u32, u32) {}
+    __device__ __forceinline__ void begin_read(u64) {}
+    __device__ __forceinline__ void end_read() {}
+    __device__ __forceinline__ void slow_block(u32) {}   // a rolled tile: the wave has completed 16 more windows per read
+    // a rolled tile (all 64 lanes together): by default the same as the final partial tile's reads
+    __device__ __forceinline__ void tile_slow_begin(u64 read) { self().begin_read(read); }
+    __device__ __forceinline__ void tile_slow_emit(u32 pos, u64 fw, u64 rc) { self().slow(pos, fw, rc); }
+    __device__ __forceinline__ void tile_slow_end() { self().end_read(); }
+    __device__ __forceinline__ void tile_fast_done(u32) {}
+    template <class P>
+    __device__ __forceinline__ void finish(const P&) {}
+
+  private:
+    __device__ __forceinline__ S& self() { return static_cast<S&>(*this); }
+};
 
 // ----------------------------------------------------------------------------------------- kernel
 // NW  = packed dwords per read = ceil(L/16) rounded up to an instantiated size (L <= 16*NW)
@@ -20,50 +82,10 @@ namespace kmx {
 // one contiguous byte span, streamed from its 16-byte-aligned start; lanes carry their own start and window count,
 // windows past a lane's read are masked.  A tile whose span or longest read does not fit the NW-word frame, or that
 // would load past the end of the buffer, takes the per-lane rolling path.
-// SinkWaves / SinkWavesBig: waves per SIMD the register allocation of a sink is sized for (default 1: hipcc otherwise spends up to 256
-// VGPRs on hoisting)
-// a sink may ask for a register budget of its own (static constexpr int kWaves)
-template <typename S, typename = void> struct SinkWaves { static constexpr int value = 1; };
-template <typename S> struct SinkWaves<S, decltype((void)S::kWaves)> { static constexpr int value = S::kWaves; };
-// a sink may take the 16 windows of an unrolled block together (static constexpr bool kBatch16 = true; fast_slot())
-template <typename S, typename = void> struct SinkBatch16 { static constexpr bool value = false; };
-template <typename S> struct SinkBatch16<S, decltype((void)S::kBatch16)> { static constexpr bool value = S::kBatch16; };
-// a sink may want its block-level LDS region to start at a multiple of kBlockLdsAlign dwords (static constexpr u32)
-template <typename S, typename = void> struct SinkBlockAlign { static constexpr u32 value = 1u; };
-template <typename S> struct SinkBlockAlign<S, decltype((void)S::kBlockLdsAlign)> { static constexpr u32 value = S::kBlockLdsAlign; };
-// a sink may ask for complemented windows (fw ^ mask, rc ^ mask) from the kernel's fast path (static constexpr bool kComplement)
-template <typename S, typename = void> struct SinkComplement { static constexpr bool value = false; };
-template <typename S> struct SinkComplement<S, decltype((void)S::kComplement)> { static constexpr bool value = S::kComplement; };
-// a sink may ask for the first 16 windows of every read once more after the last block (static constexpr bool kRedoHead;
-// wants_heads(), head(o, fw, rc), heads_done(read0)): the materialise sink writes the output line that two neighbouring reads
-// share in one piece then
-template <typename S, typename = void> struct SinkRedoHead { static constexpr bool value = false; };
-template <typename S> struct SinkRedoHead<S, decltype((void)S::kRedoHead)> { static constexpr bool value = S::kRedoHead; };
-// a sink that stores to global memory in bulk may ask for the NEXT tile's bytes early (static constexpr bool kPrefetch).  On
-// gfx9 loads and stores share one in-order counter: a tile's loads, issued behind the 150 stores of the tile before, return
-// when the last of those has been acknowledged -- every tile began with a drain of the wave's store queue (materialise, one
-// array: 2.04 ms per 1e7 reads against 1.73 with the loads taken out).  With kPrefetch the loads of tile t + 1 are issued once
-// tile t has built its F / G words -- behind the stores of tile t - 1 only, which have had a whole load-and-encode phase to
-// drain -- and are encoded into ten registers right after the first window block, before that block's stores.
-template <typename S, typename = void> struct SinkPrefetch { static constexpr bool value = false; };
-template <typename S> struct SinkPrefetch<S, decltype((void)S::kPrefetch)> { static constexpr bool value = S::kPrefetch; };
-// ... and for the 16-word frame (static constexpr int kWavesBig; without it: no cap -- most sinks would spill 1 KB there)
-template <typename S, typename = void> struct SinkWavesBig { static constexpr int value = 1; };
-template <typename S> struct SinkWavesBig<S, decltype((void)S::kWavesBig)> { static constexpr int value = S::kWavesBig; };
-// a sink whose block-level LDS is one region per wave, empty between two tiles (static constexpr bool kAliasPacked;
-// wave_dwords(params) >= the packed tile), lends it to the tile's packed words: they are dead once the lanes hold their F / G
-// words, and a wave's LDS operations complete in order
-template <typename S, typename = void> struct SinkAliasPacked { static constexpr bool value = false; };
-template <typename S> struct SinkAliasPacked<S, decltype((void)S::kAliasPacked)> { static constexpr bool value = S::kAliasPacked; };
-// a sink whose windows a later pass can take back (static constexpr bool kMarksDirty; round 6): a tile that holds an invalid byte is
-// then NOT rolled per lane -- it takes the fast path as it is, an invalid byte counting as the base its bits (b >> 1) & 3 spell, and
-// the reads that touch a bad chunk are marked in the array behind queue[KMX_Q_MASKS] exactly as the bit-sliced scan marks them; what the
-// windows with an invalid byte added is subtracted by sweep_flagged_kernel (kmx_sweep.hip).  The bucket histograms: a rolled tile
-// cost 2-3 tiles, and with an N in 2 % of the reads 73 % of the tiles rolled (+62 %: profiles/r05_dirty_bench.txt).
-// The reads of a tile that touch a chunk with an invalid byte (a sink that marks, below): the tile's chunks once more (they are in the L2),
-// one ballot per row; every lane keeps the two rows' ballots its read's chunks lie in (a chunk shared by two reads marks both: the sweep
-// looks at the bytes).  NOT inlined: the line-aligned window sinks run at 249-255 registers, and inline this block's temporaries were 40
-// registers spilled in their window loop (round 6) -- as a call it costs the tiles that take it, and nobody else.
+// The reads of a tile that touch a chunk with an invalid byte (a sink that marks, kMarksDirty): the tile's chunks once more (they are
+// in the L2), one ballot per row; every lane keeps the two rows' ballots its read's chunks lie in (a chunk shared by two reads marks
+// both: the sweep looks at the bytes).  NOT inlined: the line-aligned window sinks run at 249-255 registers, and inline this block's
+// temporaries were 40 registers spilled in their window loop (round 6) -- as a call it costs the tiles that take it, and nobody else.
 template <int NW>
 __device__ __attribute__((noinline)) u64 mark_dirty_rows(const uint4* __restrict__ tb, u32 chunks, u32 rd_off, u32 rd_len) {
     const u32 lane = threadIdx.x & 63u;
@@ -84,14 +106,7 @@ __device__ __attribute__((noinline)) u64 mark_dirty_rows(const uint4* __restrict
     return __ballot(rd_len != 0u && (bits & ((1ull << (c1 - c0 + 1u)) - 1ull)) != 0ull);
 }
 
-template <typename S, typename = void> struct SinkMarksDirty { static constexpr bool value = false; };
-template <typename S> struct SinkMarksDirty<S, decltype((void)S::kMarksDirty)> { static constexpr bool value = S::kMarksDirty; };
-// ... and a sink that marks COARSELY (static constexpr bool kMarksCoarse): every read of a dirty tile -- one store of a constant, nothing
-// computed -- and leaves it to the sweep to look at the bytes.  The line-aligned window sinks: at 249-255 registers they have none to
-// spare for finding the reads (inline or as a call, the block cost the CLEAN materialise 15-18 %: profiles/r06_windows_dirty.txt).
-template <typename S, typename = void> struct SinkMarksCoarse { static constexpr bool value = false; };
-template <typename S> struct SinkMarksCoarse<S, decltype((void)S::kMarksCoarse)> { static constexpr bool value = S::kMarksCoarse; };
-template <typename S, int NW> constexpr int sink_waves() { return NW <= 10 ? SinkWaves<S>::value : SinkWavesBig<S>::value; }
+template <typename S, int NW> constexpr int sink_waves() { return NW <= 10 ? S::kWaves : S::kWavesBig; }
 template <int NW, int V, int DW, typename Sink, typename Params, bool RAGGED = false>
 __global__ void __launch_bounds__(256, (sink_waves<Sink, NW>()))
 scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k, Params params,
@@ -106,7 +121,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
     const u32 wib = threadIdx.x >> 6;
     const u32 chunks_u = RAGGED ? 64u * NW : 4u * L + (lead != 0u ? 1u : 0u);  // 16-byte chunks per 64-read tile (ragged: the most a tile may span)
     const u32 ldsw = (chunks_u + 1u + 6u + 3u) & ~3u; // front pad 1, tail pad >= 6
-    constexpr bool ALIAS = SinkAliasPacked<Sink>::value;
+    constexpr bool ALIAS = Sink::kAliasPacked;
     u32* P;
     if constexpr (ALIAS) P = lds + wib * Sink::wave_dwords(params);
     else P = lds + wib * (ldsw + Sink::kLdsDwordsPerWave);
@@ -130,7 +145,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
     u32 nwin = omax + 1u;       // windows of this lane's read
     u32 chunks = chunks_u;
 
-    constexpr u32 BAL = SinkBlockAlign<Sink>::value;
+    constexpr u32 BAL = Sink::kBlockLdsAlign;
     Sink sink(params, k, nwin, P + ldsw, lane, ALIAS ? lds : lds + (4u * (ldsw + Sink::kLdsDwordsPerWave) + BAL - 1u) / BAL * BAL, threadIdx.x);
 
     [[maybe_unused]] u32 nwin_min = nwin;   // ragged: the shortest read of the tile (blocks of windows below it need no per-lane mask)
@@ -150,7 +165,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
             fw = (u64)(alignbit(f1, f0, sf) & mlo);
             rc = (u64)(alignbit(g1, g0, sr) & mlo);
         }
-        if constexpr (SinkBatch16<Sink>::value) {
+        if constexpr (Sink::kBatch16) {
             if (slot >= 0) {
                 sink.fast_slot(slot, fw, rc);
                 return;
@@ -201,7 +216,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
     // waves of the SIMD have to cover.  (Ragged reads and the prefetching materialise sink want the next tile's number early: its
     // offsets / its bytes are requested under this tile's windows.)  BOTH words of the return stay live until then: with the high word
     // dead hipcc hands its register out behind an s_waitcnt vmcnt(0) (kmx_bitslice_kernel.h, "the atomic's return").
-    constexpr bool ASYNC_TICKET = !RAGGED && !(SinkPrefetch<Sink>::value && NW <= 10);
+    constexpr bool ASYNC_TICKET = !RAGGED && !(Sink::kPrefetch && NW <= 10);
     unsigned long long pend = 0;
     u32 pend_qid = 0;
     bool pend_any = false;
@@ -225,11 +240,11 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
         qid = (pend_qid + 1u) & (NQ - 1u);   // that head is drained: on, synchronously (rare)
         return dequeue();
     };
-    constexpr bool MARK = SinkMarksDirty<Sink>::value;
-    [[maybe_unused]] u64* const dirty_masks = (MARK && !SinkMarksCoarse<Sink>::value) ? reinterpret_cast<u64*>(queue[KMX_Q_MASKS]) : nullptr;
+    constexpr bool MARK = Sink::kMarksDirty;
+    [[maybe_unused]] u64* const dirty_masks = (MARK && !Sink::kMarksCoarse) ? reinterpret_cast<u64*>(queue[KMX_Q_MASKS]) : nullptr;
     [[maybe_unused]] u32 n_marked = 0;
     u64 next_tile = dequeue();
-    constexpr bool PF = SinkPrefetch<Sink>::value && !RAGGED && NW <= 10;   // (the 16-word frame: 80 more registers do not fit two waves)
+    constexpr bool PF = Sink::kPrefetch && !RAGGED && NW <= 10;   // (the 16-word frame: 80 more registers do not fit two waves)
     [[maybe_unused]] u32 E[NW];          // PF: the next tile, encoded (chunk it * 64 + lane)
     [[maybe_unused]] u32 bad_pf = 0;
     [[maybe_unused]] uint4 wpf[NW];
@@ -337,7 +352,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
         bool roll_tile = !tile_fits || __any(chunk_has_invalid(bad));
-        if constexpr (MARK && SinkMarksCoarse<Sink>::value) {
+        if constexpr (MARK && Sink::kMarksCoarse) {
             // (nothing of this is carried across the tile loop -- no pointer, no counter: the mask array's address is read here, and
             // what the sweep is told is "many", by a plain store that every marking wave agrees on; it fields all its waves then)
             if (roll_tile && tile_fits) {
@@ -387,7 +402,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
 #pragma unroll
             for (int j = 0; j <= NW; ++j) R[j] = P[qF + j];
 #pragma unroll
-            for (int i = 0; i < NW; ++i) F[i] = SinkComplement<Sink>::value ? ~alignbit(R[i + 1], R[i], aF) : alignbit(R[i + 1], R[i], aF);
+            for (int i = 0; i < NW; ++i) F[i] = Sink::kComplement ? ~alignbit(R[i + 1], R[i], aF) : alignbit(R[i + 1], R[i], aF);
             F[NW] = 0;
             F[NW + 1] = 0;
             u32 Rr[NW + 2];
@@ -395,7 +410,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
             for (int j = 0; j <= NW + 1; ++j) Rr[j] = P[qR + j];
 #pragma unroll
             for (int m = 0; m <= NW; ++m)
-                G[m] = SinkComplement<Sink>::value ? revgroups32(alignbit(Rr[NW - m + 1], Rr[NW - m], aR)) : revgroups32(~alignbit(Rr[NW - m + 1], Rr[NW - m], aR));
+                G[m] = Sink::kComplement ? revgroups32(alignbit(Rr[NW - m + 1], Rr[NW - m], aR)) : revgroups32(~alignbit(Rr[NW - m + 1], Rr[NW - m], aR));
             G[NW + 1] = 0;
         }
 
@@ -413,7 +428,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
                 // and keeps them all live -- 228-256 VGPRs, 1-2 waves per SIMD instead of 4.
                 u32 f0 = F[i], f1 = F[i + 1], f2 = F[i + 2], g0 = G[M], g1 = G[M + 1], g2 = G[M + 2];
                 asm volatile("" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(g0), "+v"(g1), "+v"(g2));
-                if constexpr (RAGGED && SinkBatch16<Sink>::value) {
+                if constexpr (RAGGED && Sink::kBatch16) {
                     // a sink that takes the windows of a block in batches (the partitioned histogram: its LDS round trips, paid
                     // once per batch instead of once per window, are what the ragged scan otherwise runs at): a second,
                     // unmasked copy of the block for the blocks that every read of the tile owns in full
@@ -442,7 +457,7 @@ scan_uniform_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32 k
                 sink.block_done(tile * 64u, 16u * i, smax + 1u);
             }
         }
-        if constexpr (SinkRedoHead<Sink>::value && !RAGGED) {
+        if constexpr (Sink::kRedoHead && !RAGGED) {
             if (sink.wants_heads()) {
                 constexpr int M0 = NW - V;
                 u32 f0 = F[0], f1 = F[1], f2 = F[2], g0 = G[M0], g1 = G[M0 + 1], g2 = G[M0 + 2];
@@ -505,9 +520,9 @@ static hipError_t launch_one(const uint8_t* bases, u64 n_reads, u32 L, u32 k, Pa
     }
     const u32 chunks = RAGGED ? 64u * NW : 4u * L + (lead != 0u ? 1u : 0u);
     const u32 ldsw = (chunks + 1u + 6u + 3u) & ~3u;
-    constexpr u32 BAL = SinkBlockAlign<Sink>::value;
+    constexpr u32 BAL = Sink::kBlockLdsAlign;
     size_t lds_bytes = (size_t)((4u * (ldsw + Sink::kLdsDwordsPerWave) + BAL - 1u) / BAL * BAL) * 4u + (size_t)Sink::block_lds_dwords(params) * 4u;
-    if constexpr (SinkAliasPacked<Sink>::value) {
+    if constexpr (Sink::kAliasPacked) {
         if (Sink::block_lds_dwords(params) < 4u * ldsw) return hipErrorInvalidValue;
         lds_bytes = (size_t)Sink::block_lds_dwords(params) * 4u;
     }

@@ -26,7 +26,7 @@ template <int NW, int V1> constexpr int sweep_pitch() {     // dwords of a lane'
     return ((NW + V1 + 4) + (NW + 4) + (NW / 2 + 1)) | 1;
 }
 // HIST: the windows are taken out of a bucket histogram instead of a summary (the word-domain scan's histogram sinks mark their dirty
-// reads the same way: kmx_scan_kernel.h, SinkMarksDirty) -- `out` = the counters, want_hash = the hasher, want_sumfw = hasher_k | log2_buckets << 8.
+// reads the same way: kmx_scan_kernel.h, ScanSink::kMarksDirty) -- `out` = the counters, want_hash = the hasher, want_sumfw = hasher_k | log2_buckets << 8.
 // MODE 2 (ZERO, round 6): behind a MATERIALISE pass (kmx_canonical_windows: the word-domain scan's window sinks mark their dirty reads too and
 // take the fast path on a dirty tile instead of rolling it per lane -- 2 % dirty reads cost the materialise 37 %): the slots of the windows
 // that hold an invalid byte are written as the reference's iterator leaves them -- words 0, flags 0 (kmx.h) -- in every array asked for.
@@ -340,7 +340,7 @@ __device__ __forceinline__ void sweep_body(const uint8_t* __restrict__ bases, u6
     // reads spent more time waiting for masks than sweeping)
     u64 m0 = 0, m1 = 0, m2 = 0, m3 = 0, t = 0;   // m0: the masks being taken apart, of the tiles t (this lane's) -- m1..m3: of the groups n_waves, 2 n_waves, 3 n_waves on
     u32 left = 0;
-    // ZERO: the window sinks mark COARSELY -- every read of a tile that holds an invalid byte (kmx_scan_kernel.h, SinkMarksCoarse) -- and a sweep
+    // ZERO: the window sinks mark COARSELY -- every read of a tile that holds an invalid byte (kmx_scan_kernel.h, ScanSink::kMarksCoarse) -- and a sweep
     // of 64 reads costs ~12 us: with an N in 2 % of the reads 73 % of the tiles are dirty, one sweep each, 0.7 ms per 1e7 reads.  So the wave first
     // looks at such a tile as the scan would have (its chunks in rows of 64, coalesced, one ballot per row) and keeps the reads that touch a chunk
     // with an invalid byte: ~1.5 us per tile, and one sweep per 64 DIRTY reads.  A tile whose chunks cannot be taken whole (the batch's last bytes,
