@@ -382,6 +382,36 @@ pub fn count_canonical(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, 
     Ok(n_distinct)
 }
 
+/// The same count for two-word k-mers, k in 33..=64 (`kmx_count_canonical2`): `d_kmers2` holds at least `2 * max_distinct` u64 --
+/// entry i is (low word, high word), ascending as a 2k-bit unsigned integer (high word first) -- and `d_counts` at least
+/// `max_distinct`; Err(KMX_E_NOMEM) if the batch has more distinct k-mers (or its working set is above the work buffer's cap).
+pub fn count_canonical2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, d_kmers2: &DeviceBuf<'_>,
+                        d_counts: &DeviceBuf<'_>, max_distinct: u64) -> Result<u64, KmxError> {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(max_distinct as u128 * 16 <= d_kmers2.len() as u128 && max_distinct as u128 * 8 <= d_counts.len() as u128,
+            "outputs shorter than max_distinct");
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    let mut n_distinct = 0u64;
+    ctx.ck(unsafe { kmx_count_canonical2(ctx.0, &r, k as u32, d_kmers2.as_mut_ptr::<u64>(), d_counts.as_mut_ptr::<u64>(), max_distinct,
+                                         &mut n_distinct) })?;
+    Ok(n_distinct)
+}
+
+/// Union of two tables of `count_canonical2` (`kmx_count_merge2`): `a` and `b` are (keys, counts, entries); equal k-mers are
+/// merged and their counts added.  `d_kmers2_out` holds at least `2 * max_out` u64, `d_counts_out` at least `max_out`.
+pub fn count_merge2(ctx: &HipContext, a: (&DeviceBuf<'_>, &DeviceBuf<'_>, u64), b: (&DeviceBuf<'_>, &DeviceBuf<'_>, u64),
+                    d_kmers2_out: &DeviceBuf<'_>, d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    for (keys, counts, n) in [a, b] {
+        assert!(n as u128 * 16 <= keys.len() as u128 && n as u128 * 8 <= counts.len() as u128, "table shorter than its entry count");
+    }
+    assert!(max_out as u128 * 16 <= d_kmers2_out.len() as u128 && max_out as u128 * 8 <= d_counts_out.len() as u128,
+            "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_merge2(ctx.0, a.0.as_ptr::<u64>(), a.1.as_ptr::<u64>(), a.2, b.0.as_ptr::<u64>(), b.1.as_ptr::<u64>(), b.2,
+                                     d_kmers2_out.as_mut_ptr::<u64>(), d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
 /// `Kmer::minimizer_word(word, k, width, &state)` (kmer.rs:170-192) with a std hasher state: `(minimizer, offset)` per word
 pub fn minimizer_words_sip13(ctx: &HipContext, words: &[u64], k: u8, width: u8, keys: (u64, u64)) -> Result<Vec<(u64, u32)>, KmxError> {
     let bytes = unsafe { std::slice::from_raw_parts(words.as_ptr() as *const u8, words.len() * 8) };

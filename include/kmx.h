@@ -229,6 +229,33 @@ int kmx_count_merge(kmx_ctx *ctx, const uint64_t *d_kmers_a, const uint64_t *d_c
                     const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers_out, uint64_t *d_counts_out, uint64_t max_out,
                     uint64_t *h_n_out);
 
+/* The same count for [u64;2] k-mers, k in [33,64] (k = 32 stays unsupported, as everywhere): the multiset kmx_canonical_windows2
+ * yields.  d_kmers2[2i], d_kmers2[2i+1] = low and high word of the i-th distinct canonical k-mer (the slot layout of
+ * kmx_canonical_windows2), ASCENDING as a 2k-bit unsigned integer -- high word first, then low, the order of [u64;2] above;
+ * d_counts[i] = how many windows yield it (u64).  Windows without KMX_WIN_VALID are skipped.  Every input kmx_canonical_windows2
+ * accepts is accepted (uniform reads of any length, ragged reads with any bound -- the window offsets are made on the device --, any
+ * d_bases alignment, invalid bytes, lower case).  Deterministic: bit-identical tables on repeated calls.
+ * d_kmers2 holds 2 * max_distinct u64 and must be 16-byte aligned (keys are moved as 16-byte elements; KMX_E_ARG otherwise).
+ * *h_n_distinct, max_distinct / KMX_E_NOMEM with nothing written, both outputs NULL = count only, one NULL = KMX_E_ARG: as
+ * kmx_count_canonical.
+ * Working set in the context's work buffer: at most 36 bytes per window + 1 MiB (16 canonical words, 1 flags, 16 keys, 1 mark,
+ * ~1.35 partition arrays; uniform reads: windows = n_reads * (read_len - k + 1); ragged reads: the batch's number of BASES stands
+ * for the windows, plus 9 bytes per read), and reads longer than 256 bases add their segment plan (24 bytes per segment of at most
+ * 257 - k windows).  A batch above the cap returns KMX_E_NOMEM BEFORE any kernel runs and writes nothing.  Split larger inputs and
+ * combine their tables with kmx_count_merge2: at k = 47 a 150 bp read has 104 windows (3744 bytes), so 2.2e6 such reads fit the
+ * 8 GiB floor of the automatic cap and 9.6e6 fit it on a device of 288 GB.  The call uses the work buffer (a following
+ * kmx_fastx_parse cannot reuse its chunk prefixes).
+ * Synchronous (one host round trip per 8 bits of key that a partition still needs, at most ceil(2k / 8) = 16, plus two or three;
+ * random reads need as many as at k = 31: the number of levels follows the number of keys, not k): not capturable in a HIP graph. */
+int kmx_count_canonical2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint64_t *d_kmers2, uint64_t *d_counts,
+                         uint64_t max_distinct, uint64_t *h_n_distinct);
+/* Union of two tables as kmx_count_canonical2 writes them (2 u64 per key, ascending, distinct; 16-byte aligned key arrays): equal
+ * k-mers are merged and their counts added.  Conventions of kmx_count_merge; outputs must not alias inputs.  Working set in the work
+ * buffer: 24 bytes per input entry + 1 MiB.  Synchronous. */
+int kmx_count_merge2(kmx_ctx *ctx, const uint64_t *d_kmers2_a, const uint64_t *d_counts_a, uint64_t n_a, const uint64_t *d_kmers2_b,
+                     const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers2_out, uint64_t *d_counts_out, uint64_t max_out,
+                     uint64_t *h_n_out);
+
 /* Deterministic synthetic reads (BUILD-DEFINED; the reference bench input is unseeded,
  * benches/simple_benchmark.rs:59-65): byte g of the stream = "ACGT"[(splitmix64(seed + g/32) >> 2*(g%32)) & 3].
  * Writes nbytes bytes for stream positions [first_byte, first_byte+nbytes). */

@@ -176,11 +176,7 @@ class Context:
         windows yield each (int64 device tensors holding u64 words, trimmed to the number of distinct k-mers).  Without
         `max_distinct` the buffers are sized to the batch's window count; with it, KmxError (KMX_E_NOMEM) if there are more."""
         if max_distinct is None:
-            if offsets is None:
-                max_distinct = int(n_reads) * max(int(read_len) - int(k) + 1, 0)
-            else:
-                lens = offsets[1:] - offsets[:-1]
-                max_distinct = int((lens - int(k) + 1).clamp_(min=0).sum().item()) if int(n_reads) > 0 else 0
+            max_distinct = self._max_windows(n_reads, read_len, k, offsets)
         kmers = self.empty(max(max_distinct, 1), torch.int64)
         counts = self.empty(max(max_distinct, 1), torch.int64)
         nd = C.c_uint64(0)
@@ -201,6 +197,41 @@ class Context:
                                           _ptr(kmers_b) if nb else None, _ptr(counts_b) if nb else None, nb, _ptr(kmers), _ptr(counts),
                                           int(max_out), C.byref(n)))
         return kmers[:n.value], counts[:n.value]
+
+    def _max_windows(self, n_reads, read_len, k, offsets):
+        if offsets is None:
+            return int(n_reads) * max(int(read_len) - int(k) + 1, 0)
+        lens = offsets[1:] - offsets[:-1]
+        return int((lens - int(k) + 1).clamp_(min=0).sum().item()) if int(n_reads) > 0 else 0
+
+    @_on_ctx_stream
+    def count_canonical2(self, bases, n_reads, read_len, k, offsets=None, max_distinct=None):
+        """kmx_count_canonical2 (k 33..64) -> (kmers, counts): the distinct canonical two-word k-mers of the batch, kmers int64[n, 2] =
+        (low word, high word) holding u64 words, ascending as 2k-bit unsigned integers (high word first), and counts int64[n].
+        Without `max_distinct` the buffers are sized to the batch's window count; with it, KmxError (KMX_E_NOMEM) if there are more."""
+        if max_distinct is None:
+            max_distinct = self._max_windows(n_reads, read_len, k, offsets)
+        kmers = self.empty(2 * max(max_distinct, 1), torch.int64)
+        counts = self.empty(max(max_distinct, 1), torch.int64)
+        nd = C.c_uint64(0)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_count_canonical2(self._h, C.byref(r), k, _ptr(kmers), _ptr(counts), int(max_distinct), C.byref(nd)))
+        return kmers[:2 * nd.value].view(-1, 2), counts[:nd.value]
+
+    @_on_ctx_stream
+    def count_merge2(self, kmers_a, counts_a, kmers_b, counts_b, max_out=None):
+        """kmx_count_merge2 -> (kmers int64[n, 2], counts): the union of two tables of count_canonical2, counts of equal k-mers added."""
+        na, nb = int(counts_a.numel()), int(counts_b.numel())
+        if max_out is None:
+            max_out = na + nb
+        kmers_a, kmers_b = kmers_a.contiguous(), kmers_b.contiguous()
+        kmers = self.empty(2 * max(max_out, 1), torch.int64)
+        counts = self.empty(max(max_out, 1), torch.int64)
+        n = C.c_uint64(0)
+        self._ck(self.lib.kmx_count_merge2(self._h, _ptr(kmers_a) if na else None, _ptr(counts_a) if na else None, na,
+                                           _ptr(kmers_b) if nb else None, _ptr(counts_b) if nb else None, nb, _ptr(kmers), _ptr(counts),
+                                           int(max_out), C.byref(n)))
+        return kmers[:2 * n.value].view(-1, 2), counts[:n.value]
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

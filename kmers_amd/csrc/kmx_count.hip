@@ -23,23 +23,18 @@
 // The table is then the kept entries in index order -- ascending, because partitions are laid out in digit order -- and
 // is compacted by a block count, a scan, and a write (one more host round trip for the number of distinct keys).
 // No block waits for another: cross-block results travel through kernel boundaries only.
-#include "kmx_device.h"
-#include "kmx_launch.h"
+// (what does not depend on the width of a key -- block scans, the Leaf / Counters records, the count of the marked bytes -- is in
+// kmx_count_common.h, shared with the two-word counter of kmx_count2.hip)
+#include "kmx_count_common.h"
 
 namespace kmx {
 
 namespace {
 
-constexpr u32 CT = 256;                       // threads per block
-constexpr u32 RBITS = 8, RADIX = 1u << RBITS; // digit width: 256 bins
 constexpr u32 TILE = 16384;                   // keys per block in the partition passes
 constexpr u32 LEAF = 4096;                    // keys a leaf block sorts in LDS (32 KiB of keys)
 constexpr u32 LEAF_SMALL = 512;               // leaf groups are gathered up to this size: a shorter bitonic network, more blocks per CU
-constexpr u32 COL_SERIAL = 64;                // levels above 0: a column of at most this many tiles is scanned by one thread
-constexpr u32 CHUNK = CT * 64;                // positions per block in the compaction passes
 constexpr u32 RCHUNK = CT * 16;               // reads per block in the window-offset passes
-constexpr u32 MCHUNK = CT * 16;               // positions per block in the merge's collapse passes
-constexpr u32 MERGE_IPT = 8;                  // merged items per thread
 
 struct Seg {
     u64 start;      // first index of the partition (output coordinates; level 0: the window array)
@@ -49,70 +44,6 @@ struct Seg {
     u32 hi_bit;     // bits not yet partitioned: the digit is bits [hi_bit - w, hi_bit), w = min(8, hi_bit)
     u32 skip;       // segfinal wrote the partition's runs itself: no scatter
 };
-
-struct Leaf {
-    u64 start, n;
-    u32 in_keys;    // the group's keys are in `keys` (1) or in the other array (0)
-    u32 pad;
-};
-
-// device counters of a level (one host read-back per level)
-struct Counters {
-    unsigned long long n_valid, n_next, n_next_tiles, n_leaf, overflow, n_leaf_small, n_next_big;
-    u64 n_distinct;
-};
-constexpr size_t LEVEL_COUNTERS = 7u * 8u;   // (n_valid .. n_next_big: cleared before and read back after every level)
-static_assert(LEVEL_COUNTERS <= KMX_PIN_BYTES, "the level counters are read back into the context's pinned words");
-
-__host__ __device__ __forceinline__ u64 ceil_div(u64 a, u64 b) { return (a + b - 1u) / b; }
-__device__ __forceinline__ u32 digit_width(u32 hi_bit) { return hi_bit < RBITS ? hi_bit : RBITS; }
-
-// exclusive scan of one value per thread over the block (256 threads); *total = the sum; `sh` holds CT u64
-__device__ __forceinline__ u64 block_exscan(u64 v, u64* sh, u64* total) {
-    const u32 t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (u32 d = 1; d < CT; d <<= 1) {
-        const u64 x = t >= d ? sh[t - d] : 0u;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    *total = sh[CT - 1];
-    const u64 ex = sh[t] - v;
-    __syncthreads();
-    return ex;
-}
-
-// exclusive scan in place of a[0..n) by one block, 8 contiguous entries per thread and step; *total = the sum
-__device__ void block_scan_array(u64* a, u64 n, u64* sh, u64* total) {
-    u64 carry = 0;
-    for (u64 base = 0; base < n; base += (u64)CT * 8u) {
-        const u64 i0 = base + (u64)threadIdx.x * 8u;
-        u64 v[8], s = 0;
-#pragma unroll
-        for (u32 j = 0; j < 8; ++j) {
-            v[j] = i0 + j < n ? a[i0 + j] : 0u;
-            s += v[j];
-        }
-        u64 tot;
-        u64 run = carry + block_exscan(s, sh, &tot);
-#pragma unroll
-        for (u32 j = 0; j < 8; ++j) {
-            if (i0 + j < n) a[i0 + j] = run;
-            run += v[j];
-        }
-        carry += tot;
-    }
-    *total = carry;
-}
-
-__global__ void __launch_bounds__(CT) scan_single_kernel(u64* __restrict__ a, u64 n, u64* __restrict__ total) {
-    __shared__ u64 sh[CT];
-    u64 t;
-    block_scan_array(a, n, sh, &t);
-    if (threadIdx.x == 0) *total = t;
-}
 
 // ---------------------------------------------------------------- window offsets of ragged reads
 // (a read of 2^31 bases or more owns no window: the scans skip it and report it, kmx.h "Limits")
@@ -421,24 +352,6 @@ __global__ void __launch_bounds__(CT) leaf_kernel(const Leaf* __restrict__ leave
 }
 
 // ---------------------------------------------------------------- compaction of the kept entries
-__device__ __forceinline__ u32 kept_in(const uint8_t* keep, u64 i0) {
-    const uint4* p = reinterpret_cast<const uint4*>(keep + i0);
-    u32 c = 0;
-#pragma unroll
-    for (u32 j = 0; j < 4; ++j) {
-        const uint4 v = p[j];
-        c += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);   // (bytes are 0 or 1)
-    }
-    return c;
-}
-
-__global__ void __launch_bounds__(CT) keep_count_kernel(const uint8_t* __restrict__ keep, u64* __restrict__ partial) {
-    __shared__ u64 sh[CT];
-    u64 tot;
-    (void)block_exscan(kept_in(keep, (u64)blockIdx.x * CHUNK + (u64)threadIdx.x * 64u), sh, &tot);
-    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
 // a wave per quarter of the block's positions, 64 at a time: the ballot of the kept bytes gives each lane its slot
 __global__ void __launch_bounds__(CT) keep_write_kernel(const uint8_t* __restrict__ keep, const u64* __restrict__ partial, const u64* __restrict__ keys,
                                                         const u64* __restrict__ counts, u64* __restrict__ out_k, u64* __restrict__ out_c) {
@@ -524,8 +437,6 @@ __global__ void __launch_bounds__(CT) head_write_kernel(const u64* __restrict__ 
         }
     }
 }
-
-size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
 // bounds of one level's arrays for n keys
 u64 max_segs(u64 n) { return n / (LEAF + 1u) + 2u; }

@@ -1,0 +1,107 @@
+// kmx_count_common.h -- what the exact counters share whatever the width of a key: kmx_count.hip (one-word keys, k <= 31) and
+// kmx_count2.hip (two-word keys, k = 33..64).  Block scans, the records a level leaves for the host and for the leaf kernels, the
+// count of the marked bytes the compaction starts with.  Everything here has internal linkage (each translation unit compiles
+// its own copy, as it did when kmx_count.hip was the only user); the kernels that touch keys stay with their key type.
+#pragma once
+#include "kmx_device.h"
+#include "kmx_launch.h"
+
+namespace kmx {
+
+namespace {
+
+constexpr u32 CT = 256;                       // threads per block
+constexpr u32 RBITS = 8, RADIX = 1u << RBITS; // digit width: 256 bins
+constexpr u32 COL_SERIAL = 64;                // levels above 0: a column of at most this many tiles is scanned by one thread
+constexpr u32 CHUNK = CT * 64;                // positions per block in the compaction passes
+constexpr u32 MCHUNK = CT * 16;               // positions per block in the merge's collapse passes
+constexpr u32 MERGE_IPT = 8;                  // merged items per thread
+
+struct Leaf {
+    u64 start, n;
+    u32 in_keys;    // the group's keys are in `keys` (1) or in the other array (0)
+    u32 pad;
+};
+
+// device counters of a level (one host read-back per level)
+struct Counters {
+    unsigned long long n_valid, n_next, n_next_tiles, n_leaf, overflow, n_leaf_small, n_next_big;
+    u64 n_distinct;
+};
+constexpr size_t LEVEL_COUNTERS = 7u * 8u;   // (n_valid .. n_next_big: cleared before and read back after every level)
+static_assert(LEVEL_COUNTERS <= KMX_PIN_BYTES, "the level counters are read back into the context's pinned words");
+
+__host__ __device__ __forceinline__ u64 ceil_div(u64 a, u64 b) { return (a + b - 1u) / b; }
+__device__ __forceinline__ u32 digit_width(u32 hi_bit) { return hi_bit < RBITS ? hi_bit : RBITS; }
+
+// exclusive scan of one value per thread over the block (256 threads); *total = the sum; `sh` holds CT u64
+__device__ __forceinline__ u64 block_exscan(u64 v, u64* sh, u64* total) {
+    const u32 t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (u32 d = 1; d < CT; d <<= 1) {
+        const u64 x = t >= d ? sh[t - d] : 0u;
+        __syncthreads();
+        sh[t] += x;
+        __syncthreads();
+    }
+    *total = sh[CT - 1];
+    const u64 ex = sh[t] - v;
+    __syncthreads();
+    return ex;
+}
+
+// exclusive scan in place of a[0..n) by one block, 8 contiguous entries per thread and step; *total = the sum
+__device__ void block_scan_array(u64* a, u64 n, u64* sh, u64* total) {
+    u64 carry = 0;
+    for (u64 base = 0; base < n; base += (u64)CT * 8u) {
+        const u64 i0 = base + (u64)threadIdx.x * 8u;
+        u64 v[8], s = 0;
+#pragma unroll
+        for (u32 j = 0; j < 8; ++j) {
+            v[j] = i0 + j < n ? a[i0 + j] : 0u;
+            s += v[j];
+        }
+        u64 tot;
+        u64 run = carry + block_exscan(s, sh, &tot);
+#pragma unroll
+        for (u32 j = 0; j < 8; ++j) {
+            if (i0 + j < n) a[i0 + j] = run;
+            run += v[j];
+        }
+        carry += tot;
+    }
+    *total = carry;
+}
+
+__global__ void __launch_bounds__(CT) scan_single_kernel(u64* __restrict__ a, u64 n, u64* __restrict__ total) {
+    __shared__ u64 sh[CT];
+    u64 t;
+    block_scan_array(a, n, sh, &t);
+    if (threadIdx.x == 0) *total = t;
+}
+
+// ---------------------------------------------------------------- compaction of the kept entries
+__device__ __forceinline__ u32 kept_in(const uint8_t* keep, u64 i0) {
+    const uint4* p = reinterpret_cast<const uint4*>(keep + i0);
+    u32 c = 0;
+#pragma unroll
+    for (u32 j = 0; j < 4; ++j) {
+        const uint4 v = p[j];
+        c += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);   // (bytes are 0 or 1)
+    }
+    return c;
+}
+
+__global__ void __launch_bounds__(CT) keep_count_kernel(const uint8_t* __restrict__ keep, u64* __restrict__ partial) {
+    __shared__ u64 sh[CT];
+    u64 tot;
+    (void)block_exscan(kept_in(keep, (u64)blockIdx.x * CHUNK + (u64)threadIdx.x * 64u), sh, &tot);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+}  // namespace
+
+}  // namespace kmx

@@ -137,4 +137,13 @@ size_t count_merge_bytes(u64 n);
 hipError_t launch_count_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
                               u64* h_out, hipStream_t st);
 hipError_t launch_count_merge_emit(u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
+// kmx_count2.hip: the same for two-word keys (2 u64 per key, low word first, 16-byte aligned)
+size_t count2_area_bytes(u64 n_win);
+hipError_t launch_count2_sort(u64* canon2, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
+                              u64* h_distinct, bool* bad, hipStream_t st);
+hipError_t launch_count2_emit(const u64* canon2, u64 n_win, u64 n_valid, void* area, u64* out_k2, u64* out_c, hipStream_t st);
+size_t count2_merge_bytes(u64 n);
+hipError_t launch_count2_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
+                               u64* h_out, hipStream_t st);
+hipError_t launch_count2_merge_emit(u64 n, const void* area, u64* out_k2, u64* out_c, hipStream_t st);
 }  // namespace kmx
