@@ -412,6 +412,111 @@ pub fn count_merge2(ctx: &HipContext, a: (&DeviceBuf<'_>, &DeviceBuf<'_>, u64), 
     Ok(n_out)
 }
 
+/// A count table on the device: `keys` (`words` u64 per entry: 1 for k <= 31, 2 for k in 33..=64; ascending, distinct), one u64
+/// count per entry in `counts` (`None`: membership only, where a call allows it), `n` entries.
+#[derive(Clone, Copy)]
+pub struct CountTable<'a> {
+    pub keys: &'a DeviceBuf<'a>,
+    pub counts: Option<&'a DeviceBuf<'a>>,
+    pub n: u64,
+}
+
+impl CountTable<'_> {
+    fn check(&self, words: u64) {
+        assert!(self.n as u128 * 8 * words as u128 <= self.keys.len() as u128, "table keys shorter than the entry count");
+        if let Some(c) = self.counts {
+            assert!(self.n as u128 * 8 <= c.len() as u128, "table counts shorter than the entry count");
+        }
+    }
+    fn counts_ptr(&self) -> *const u64 {
+        self.counts.map_or(ptr::null(), |c| c.as_ptr::<u64>())
+    }
+}
+
+/// The count of every query word in a table (`kmx_count_lookup`): `d_out[i]` = the count of `d_query[i]`, 0 if absent or if its
+/// flag (`d_flags`, one byte per query, optional) lacks `KMX_WIN_VALID`.  `d_out` may be `d_query` itself.
+pub fn count_lookup(ctx: &HipContext, table: CountTable<'_>, k: u8, d_query: &DeviceBuf<'_>, d_flags: Option<&DeviceBuf<'_>>, n_query: u64,
+                    d_out: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    table.check(1);
+    assert!(n_query as u128 * 8 <= d_query.len().min(d_out.len()) as u128, "queries or answers shorter than n_query");
+    assert!(d_flags.map_or(true, |f| n_query as u128 <= f.len() as u128), "flags shorter than n_query");
+    let flags = d_flags.map_or(ptr::null(), |f| f.as_ptr::<u8>());
+    ctx.ck(unsafe { kmx_count_lookup(ctx.0, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, k as u32, d_query.as_ptr::<u64>(), flags, n_query,
+                                     d_out.as_mut_ptr::<u64>()) })
+}
+
+/// The same for two-word keys (`kmx_count_lookup2`): 16 bytes per key and per query, 8 per answer.
+pub fn count_lookup2(ctx: &HipContext, table: CountTable<'_>, k: u8, d_query2: &DeviceBuf<'_>, d_flags: Option<&DeviceBuf<'_>>, n_query: u64,
+                     d_out: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    table.check(2);
+    assert!(n_query as u128 * 16 <= d_query2.len() as u128 && n_query as u128 * 8 <= d_out.len() as u128, "queries or answers shorter than n_query");
+    assert!(d_flags.map_or(true, |f| n_query as u128 <= f.len() as u128), "flags shorter than n_query");
+    let flags = d_flags.map_or(ptr::null(), |f| f.as_ptr::<u8>());
+    ctx.ck(unsafe { kmx_count_lookup2(ctx.0, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, k as u32, d_query2.as_ptr::<u64>(), flags, n_query,
+                                      d_out.as_mut_ptr::<u64>()) })
+}
+
+/// The count, in a table, of the canonical k-mer of every window of a uniform batch on the device (`kmx_count_lookup_reads`):
+/// `d_out[r * (read_len - k + 1) + p]`, 0 for a window with an invalid byte.  Returns the number of windows.
+pub fn count_lookup_reads(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>,
+                          d_out: &DeviceBuf<'_>) -> Result<u64, KmxError> {
+    table.check(1);
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    let n_win = n_reads * (read_len as u64 + 1).saturating_sub(k as u64);
+    assert!(n_win as u128 * 8 <= d_out.len() as u128, "answers shorter than the batch's windows");
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_lookup_reads(ctx.0, &r, ptr::null(), k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n,
+                                           d_out.as_mut_ptr::<u64>()) })?;
+    Ok(n_win)
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_lookup_reads2`).
+pub fn count_lookup_reads2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>,
+                           d_out: &DeviceBuf<'_>) -> Result<u64, KmxError> {
+    table.check(2);
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    let n_win = n_reads * (read_len as u64 + 1).saturating_sub(k as u64);
+    assert!(n_win as u128 * 8 <= d_out.len() as u128, "answers shorter than the batch's windows");
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_lookup_reads2(ctx.0, &r, ptr::null(), k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n,
+                                            d_out.as_mut_ptr::<u64>()) })?;
+    Ok(n_win)
+}
+
+/// The abundance spectrum of a table's counts (`kmx_count_spectrum`): `n_bins` bins, bin c = how many entries have count c, the last
+/// bin everything at or above it.
+pub fn count_spectrum(ctx: &HipContext, d_counts: &DeviceBuf<'_>, n: u64, n_bins: usize) -> Result<Vec<u64>, KmxError> {
+    assert!(n as u128 * 8 <= d_counts.len() as u128, "counts shorter than the entry count");
+    let d_bins = ctx.upload(&vec![0u8; 8 * n_bins.max(1)])?;
+    ctx.ck(unsafe { kmx_count_spectrum(ctx.0, d_counts.as_ptr::<u64>(), n, n_bins as u64, d_bins.as_mut_ptr::<u64>()) })?;
+    d_bins.download::<u64>(n_bins)
+}
+
+/// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
+/// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
+pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,
+                    d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    table.check(1);
+    let counts = table.counts.expect("count_filter needs the table's counts");
+    assert!(max_out as u128 * 8 <= d_kmers_out.len().min(d_counts_out.len()) as u128, "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_filter(ctx.0, table.keys.as_ptr::<u64>(), counts.as_ptr::<u64>(), table.n, min_count, max_count,
+                                     d_kmers_out.as_mut_ptr::<u64>(), d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
+/// The same for two-word keys (`kmx_count_filter2`): `d_kmers2_out` holds at least `2 * max_out` u64.
+pub fn count_filter2(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers2_out: &DeviceBuf<'_>,
+                     d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    table.check(2);
+    let counts = table.counts.expect("count_filter2 needs the table's counts");
+    assert!(max_out as u128 * 16 <= d_kmers2_out.len() as u128 && max_out as u128 * 8 <= d_counts_out.len() as u128, "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_filter2(ctx.0, table.keys.as_ptr::<u64>(), counts.as_ptr::<u64>(), table.n, min_count, max_count,
+                                      d_kmers2_out.as_mut_ptr::<u64>(), d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
 /// `Kmer::minimizer_word(word, k, width, &state)` (kmer.rs:170-192) with a std hasher state: `(minimizer, offset)` per word
 pub fn minimizer_words_sip13(ctx: &HipContext, words: &[u64], k: u8, width: u8, keys: (u64, u64)) -> Result<Vec<(u64, u32)>, KmxError> {
     let bytes = unsafe { std::slice::from_raw_parts(words.as_ptr() as *const u8, words.len() * 8) };

@@ -256,6 +256,64 @@ int kmx_count_merge2(kmx_ctx *ctx, const uint64_t *d_kmers2_a, const uint64_t *d
                      const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers2_out, uint64_t *d_counts_out, uint64_t max_out,
                      uint64_t *h_n_out);
 
+/* ---------------------------------------------------------------- queries on a count table ----
+ * BUILD-DEFINED, like the counters.  A TABLE is what kmx_count_canonical(2) / kmx_count_merge(2) / kmx_count_filter(2) write: n keys
+ * ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs, 16-byte aligned (KMX_E_ARG otherwise), ordered
+ * as 2k-bit integers.  The calls assume that and do not check it: a table that is not sorted gives wrong answers, never an access
+ * outside the arrays.  n and n_query up to 2^40 (KMX_E_ARG above). */
+
+/* d_out[i] (u64) = the count of d_query[i] in the table, 0 if it is absent.  Queries are taken as they are (the caller
+ * canonicalises: kmx_canonical_words, or the canon array of kmx_canonical_windows), in any order, with repeats; a query with a bit
+ * set at or above bit 2k is absent.  d_query_flags may be NULL; where given, a query whose flag lacks KMX_WIN_VALID answers 0
+ * whatever its word is, so the canon / flags pair of kmx_canonical_windows goes in unchanged.  d_counts == NULL = membership: 1 / 0.
+ * n == 0 is a valid empty table (all answers 0), n_query == 0 a no-op.  k in [1,31], KMX_E_K_RANGE otherwise.  d_out must not
+ * alias the table; it MAY be d_query itself (answers in place).
+ * Working set: none, or a prefix directory over the keys' top bits in the context's work buffer -- 4 bytes per 8 table entries
+ * (rounded up to a power of two, + 260 bytes; at most 1 GiB), built per call by one pass over the keys when n_query >= n / 64 (below
+ * that the pass costs more bytes than it saves), n < 2^32 and it fits under the work buffer's cap; otherwise every query is a plain
+ * binary search.  Same answers either way: the call never fails for lack of work buffer.
+ * Asynchronous: it only enqueues work on the context's stream unless the work buffer has to grow. */
+int kmx_count_lookup(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n, uint32_t k, const uint64_t *d_query,
+                     const uint8_t *d_query_flags, uint64_t n_query, uint64_t *d_out);
+/* The same for two-word keys, k in [33,64]: d_kmers2 and d_query2 hold two u64 per key (low, high; both 16-byte aligned, KMX_E_ARG
+ * otherwise), d_out one u64 per query (it may NOT alias d_query2).  Directory when n_query >= n / 32.  Working set and
+ * synchronisation as kmx_count_lookup. */
+int kmx_count_lookup2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, uint32_t k, const uint64_t *d_query2,
+                      const uint8_t *d_query_flags, uint64_t n_query, uint64_t *d_out);
+/* The same answer for every window of a batch of reads, in the dense slot layout of kmx_canonical_windows (r * (read_len - k + 1) + p,
+ * or d_win_offsets[r] + p): d_out[slot] = the count of the window's canonical k-mer in the table, 0 for a window the iterator skips
+ * (a byte outside ACGTacgt) and for one whose k-mer is absent.  It IS kmx_canonical_windows followed by the lookup: every input that
+ * call accepts is accepted (uniform reads of any length, ragged reads with their d_win_offsets and any bound, any d_bases
+ * alignment), with its routes and its synchronisation (ragged reads: two more words come back to the host first).  k in [1,31].
+ * Working set in the context's work buffer: 1 byte per window (the flags; the canonical words are written into d_out and looked up
+ * in place), rounded up to 256 -- uniform reads: windows = n_reads * (read_len - k + 1); ragged reads: the batch's number of BASES
+ * stands for the windows -- and reads longer than 256 bases add their segment plan (24 bytes per segment of at most 257 - k
+ * windows); the directory of kmx_count_lookup behind that when it pays and fits (it is left out, never refused).  Above the cap:
+ * KMX_E_NOMEM BEFORE any kernel runs, nothing written.  The call uses the work buffer (a following kmx_fastx_parse cannot reuse its
+ * chunk prefixes). */
+int kmx_count_lookup_reads(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_win_offsets, uint32_t k, const uint64_t *d_kmers,
+                           const uint64_t *d_counts, uint64_t n, uint64_t *d_out);
+/* The same for two-word keys, k in [33,64]: kmx_canonical_windows2 followed by the lookup; d_out one u64 per window.  Working set:
+ * 17 bytes per window (16 canonical words, 1 flags; each array rounded up to 256), windows counted as above, + the segment plan of
+ * long reads, + the directory when it pays and fits. */
+int kmx_count_lookup_reads2(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_win_offsets, uint32_t k, const uint64_t *d_kmers2,
+                            const uint64_t *d_counts, uint64_t n, uint64_t *d_out);
+/* The abundance spectrum of a table: d_spectrum[min(d_counts[i], n_bins - 1)] += 1 for every entry -- bin c = how many distinct
+ * k-mers occur c times, the last bin collects everything at or above it.  n_bins u64 bins, ACCUMULATED into as kmx_histogram
+ * accumulates into its buckets (the caller zeroes).  It reads counts only: one call for both key widths.  n_bins >= 2, KMX_E_ARG
+ * otherwise.  Working set: none (16 KiB of LDS per block).  Asynchronous: it only enqueues work on the context's stream. */
+int kmx_count_spectrum(kmx_ctx *ctx, const uint64_t *d_counts, uint64_t n, uint64_t n_bins, uint64_t *d_spectrum);
+/* The entries of a table with min_count <= count <= max_count, order kept: a table again (it feeds merge, lookup, spectrum and
+ * filter).  *h_n_out (host) = how many there are; max_out / KMX_E_NOMEM with nothing written and *h_n_out set, both outputs NULL =
+ * count only, one NULL = KMX_E_ARG: the conventions of kmx_count_merge.  Outputs must not alias inputs.  Working set in the work
+ * buffer: 1 byte per entry (rounded up to 16384) + 8 bytes per 16384 entries + 528 bytes; above the cap KMX_E_NOMEM before any
+ * kernel runs.  n up to 2^38 (KMX_E_ARG above).  Synchronous (the count comes back to the host: one round trip). */
+int kmx_count_filter(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n, uint64_t min_count, uint64_t max_count,
+                     uint64_t *d_kmers_out, uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
+/* The same for two-word keys (16-byte aligned key arrays, KMX_E_ARG otherwise).  Working set and synchronisation as kmx_count_filter. */
+int kmx_count_filter2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, uint64_t min_count, uint64_t max_count,
+                      uint64_t *d_kmers2_out, uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
+
 /* Deterministic synthetic reads (BUILD-DEFINED; the reference bench input is unseeded,
  * benches/simple_benchmark.rs:59-65): byte g of the stream = "ACGT"[(splitmix64(seed + g/32) >> 2*(g%32)) & 3].
  * Writes nbytes bytes for stream positions [first_byte, first_byte+nbytes). */

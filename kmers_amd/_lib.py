@@ -95,6 +95,13 @@ SIGNATURES = {
     "kmx_count_merge": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_canonical2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_merge2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_lookup": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_lookup2": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_lookup_reads": (_int, [_vp, _RP, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_lookup_reads2": (_int, [_vp, _RP, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_spectrum": (_int, [_vp, _vp, _u64, _u64, _vp]),
+    "kmx_count_filter": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_filter2": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_minimizer_words_sip13": (_int, [_vp, _vp, _u64, _u32, _u32, _u64, _u64, _vp, _vp]),
     "kmx_seqvec_minimizers_sip13": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u64, _vp, _vp]),
     "kmx_minimizers_sip13": (_int, [_vp, _RP, _vp, _u32, _u32, _u64, _u64, _vp, _vp, C.POINTER(C.c_uint64)]),

@@ -233,6 +233,90 @@ class Context:
                                            int(max_out), C.byref(n)))
         return kmers[:2 * n.value].view(-1, 2), counts[:n.value]
 
+    # ------------------------------------------------------------ queries on a count table
+    def _lookup(self, fn, words, kmers, counts, k, query, flags, out):
+        n = int(kmers.numel()) // words
+        nq = int(query.numel()) // words
+        kmers, query = kmers.contiguous(), query.contiguous()
+        if out is None:
+            out = self.empty(nq, torch.int64)
+        self._ck(fn(self._h, _ptr(kmers) if n else None, _ptr(counts) if counts is not None and n else None, n, k,
+                    _ptr(query) if nq else None, _ptr(flags) if flags is not None and nq else None, nq, _ptr(out) if nq else None))
+        return out
+
+    @_on_ctx_stream
+    def count_lookup(self, kmers, counts, k, query, flags=None, out=None):
+        """kmx_count_lookup -> int64[n_query] (u64 words): the count of every query word in the table (kmers, counts) of
+        count_canonical / count_merge / count_filter, 0 where it is absent or its flag lacks KMX_WIN_VALID.  counts=None: membership
+        (1 / 0).  `out` may be `query` itself: answers in place."""
+        return self._lookup(self.lib.kmx_count_lookup, 1, kmers, counts, k, query, flags, out)
+
+    @_on_ctx_stream
+    def count_lookup2(self, kmers, counts, k, query, flags=None, out=None):
+        """kmx_count_lookup2 (k 33..64): kmers int64[n, 2], query int64[n_query, 2] = (low, high) words -> int64[n_query]."""
+        return self._lookup(self.lib.kmx_count_lookup2, 2, kmers, counts, k, query, flags, out)
+
+    def _lookup_reads(self, fn, words, bases, n_reads, read_len, k, kmers, counts, offsets, win_offsets, out):
+        n = int(kmers.numel()) // words
+        kmers = kmers.contiguous()
+        if offsets is not None and win_offsets is None:
+            lens = offsets[1:] - offsets[:-1]
+            w = (lens - int(k) + 1).clamp_(min=0)
+            w[lens > 0x7FFFFFFF] = 0
+            win_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(w, 0)])
+        if out is None:
+            total = int(win_offsets[-1].item()) if win_offsets is not None else int(n_reads) * max(int(read_len) - int(k) + 1, 0)
+            out = self.empty(total, torch.int64)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), _ptr(win_offsets), k, _ptr(kmers) if n else None,
+                    _ptr(counts) if counts is not None and n else None, n, _ptr(out) if out.numel() else None))
+        return out
+
+    @_on_ctx_stream
+    def count_lookup_reads(self, bases, n_reads, read_len, k, kmers, counts, offsets=None, win_offsets=None, out=None):
+        """kmx_count_lookup_reads -> int64[windows]: the count, in the table, of the canonical k-mer of every window of the batch, in
+        the slot layout of canonical_windows; 0 for a window with an invalid byte.  Ragged reads: `win_offsets` (device, n_reads + 1)
+        is made from `offsets` when not given."""
+        return self._lookup_reads(self.lib.kmx_count_lookup_reads, 1, bases, n_reads, read_len, k, kmers, counts, offsets, win_offsets, out)
+
+    @_on_ctx_stream
+    def count_lookup_reads2(self, bases, n_reads, read_len, k, kmers, counts, offsets=None, win_offsets=None, out=None):
+        """kmx_count_lookup_reads2 (k 33..64; kmers int64[n, 2]) -> int64[windows]."""
+        return self._lookup_reads(self.lib.kmx_count_lookup_reads2, 2, bases, n_reads, read_len, k, kmers, counts, offsets, win_offsets, out)
+
+    @_on_ctx_stream
+    def count_spectrum(self, counts, n_bins, out=None):
+        """kmx_count_spectrum -> int64[n_bins]: out[min(count, n_bins - 1)] += 1 for every entry; zeroed bins unless handed some
+        (they are accumulated into)."""
+        if out is None:
+            out = torch.zeros(int(n_bins), dtype=torch.int64, device=self.device)
+        n = int(counts.numel())
+        self._ck(self.lib.kmx_count_spectrum(self._h, _ptr(counts) if n else None, n, int(n_bins), _ptr(out)))
+        return out
+
+    def _filter(self, fn, words, kmers, counts, min_count, max_count, max_out):
+        n = int(counts.numel())
+        kmers = kmers.contiguous()
+        if max_out is None:
+            max_out = n
+        ok = self.empty(words * max(max_out, 1), torch.int64)
+        oc = self.empty(max(max_out, 1), torch.int64)
+        m = C.c_uint64(0)
+        self._ck(fn(self._h, _ptr(kmers) if n else None, _ptr(counts) if n else None, n, int(min_count), int(max_count), _ptr(ok), _ptr(oc),
+                    int(max_out), C.byref(m)))
+        ok = ok[:words * m.value]
+        return (ok.view(-1, 2) if words == 2 else ok), oc[:m.value]
+
+    @_on_ctx_stream
+    def count_filter(self, kmers, counts, min_count=1, max_count=2**64 - 1, max_out=None):
+        """kmx_count_filter -> (kmers, counts): the entries with min_count <= count <= max_count, order kept (a table again)."""
+        return self._filter(self.lib.kmx_count_filter, 1, kmers, counts, min_count, max_count, max_out)
+
+    @_on_ctx_stream
+    def count_filter2(self, kmers, counts, min_count=1, max_count=2**64 - 1, max_out=None):
+        """kmx_count_filter2 -> (kmers int64[n, 2], counts) for the tables of count_canonical2."""
+        return self._filter(self.lib.kmx_count_filter2, 2, kmers, counts, min_count, max_count, max_out)
+
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:
         out = self.empty(5, torch.int64)

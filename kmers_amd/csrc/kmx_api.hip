@@ -825,6 +825,190 @@ int kmx_count_merge2(kmx_ctx* ctx, const uint64_t* d_kmers2_a, const uint64_t* d
     return merge_impl(ctx, kind, d_kmers2_a, d_counts_a, n_a, d_kmers2_b, d_counts_b, n_b, d_kmers2_out, d_counts_out, max_out, h_n_out);
 }
 
+// ---- queries on a count table (kmx_count_query.hip) ----
+// What the one-word and the two-word queries differ in: the words of a key, the domain of k, the windows call of the reads form.
+struct QueryKind {
+    const char* who;
+    uint32_t words, k_min, k_max;
+    int (*windows)(kmx_ctx*, const kmx_reads*, const uint64_t*, uint32_t, uint64_t*, uint64_t*, uint64_t*, uint8_t*);
+};
+static const QueryKind kQuery1{"kmx_count_lookup", 1u, 1u, 31u, kmx_canonical_windows};
+static const QueryKind kQuery2{"kmx_count_lookup2", 2u, 33u, 64u, kmx_canonical_windows2};
+
+// The lookup behind its argument checks.  `reserved` bytes at the start of the work buffer belong to the caller (the reads form keeps
+// its flags / canonical words there); the directory goes behind them when the byte counts say it pays (count_lookup_wants_dir) and it
+// fits under the cap -- otherwise the plain search, which needs no work buffer: never KMX_E_NOMEM from here.
+static int lookup_run(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k,
+                      const uint64_t* d_query, const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out, size_t reserved) {
+    if (n_query == 0) return KMX_OK;
+    if (n == 0) {
+        KMX_HIP(ctx, hipMemsetAsync(d_out, 0, 8u * n_query, ctx->stream));
+        return KMX_OK;
+    }
+    void* dir = nullptr;
+    uint32_t p = 0;
+    const size_t dir_bytes = kmx::count_lookup_dir_bytes(n, k, &p);
+    if (dir_bytes != 0 && kmx::count_lookup_wants_dir(n, n_query, kind.words) &&
+        reserved + dir_bytes <= hist_scratch_budget(ctx->big_bytes, ctx->big_limit)) {
+        if (reserved == 0) {
+            if (char* base = static_cast<char*>(big_scratch(ctx, dir_bytes))) {
+                ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+                dir = base;
+            }
+        } else if (reserved + dir_bytes <= ctx->big_bytes) {   // (the reads form reserved its buffer with room for the directory, or without)
+            dir = static_cast<char*>(ctx->d_big) + reserved;
+        }
+    }
+    KMX_HIP(ctx, kmx::launch_count_lookup(kind.words, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out, dir, p, ctx->stream));
+    return KMX_OK;
+}
+
+static int lookup_impl(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k,
+                       const uint64_t* d_query, const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out) {
+    if (!ctx || (n && !d_kmers) || (n_query && (!d_query || !d_out)) || n > (1ull << 40) || n_query > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && (!aligned16(d_kmers) || !aligned16(d_query))) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    DeviceGuard g(ctx->device);
+    return lookup_run(ctx, kind, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out, 0);
+}
+
+int kmx_count_lookup(kmx_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k, const uint64_t* d_query,
+                     const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out) {
+    return lookup_impl(ctx, kQuery1, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out);
+}
+
+int kmx_count_lookup2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n, uint32_t k, const uint64_t* d_query2,
+                      const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out) {
+    return lookup_impl(ctx, kQuery2, d_kmers2, d_counts, n, k, d_query2, d_query_flags, n_query, d_out);
+}
+
+// kmx_count_lookup_reads(2) = kmx_canonical_windows(2) followed by the lookup kernel.  The work buffer is laid out up front, as
+// count_impl lays its arrays out: [segment plan of long reads][two-word keys: canon 16 B/window][flags 1 B/window][directory, when
+// it pays and fits].  One-word keys: the windows call writes its canonical words into d_out and they are looked up in place.
+static int lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k,
+                             const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint64_t* d_out) {
+    if (!ctx || !reads_ok(reads) || (n && !d_kmers) || n > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    // the windows the arrays are sized for (as kmx_count_canonical counts them: the number of bases for ragged reads) and the
+    // windows there are
+    uint64_t n_bound = 0, n_bases = 0, n_win = 0;
+    if (reads->d_offsets) {
+        uint64_t o_first = 0, o_last = 0;
+        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
+        if (o_last < o_first) return KMX_E_ARG;
+        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
+        n_bases = n_bound = o_last - o_first;
+        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        n_win = ctx->h_pinned[KMX_PIN_READ];
+        if (n_win > n_bound) return KMX_E_ARG;   // (more windows than bases: not this batch's window offsets)
+    } else {
+        if (reads->read_len < k) return KMX_OK;   // no window
+        const uint64_t w = reads->read_len - k + 1u;
+        if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
+        n_win = n_bound = reads->n_reads * w;
+        if (d_win_offsets) {   // (uniform reads in slots of the caller's: kmx_canonical_windows serves them, so they are served)
+            KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->h_pinned[KMX_PIN_READ] != n_win) return KMX_E_ARG;
+        }
+    }
+    if (n_win == 0) return KMX_OK;
+    if (!d_out) return KMX_E_ARG;
+    const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
+    const size_t canon_at = plan, flags_at = canon_at + (kind.words == 2u ? a256(16u * n_bound) : 0u), reserved = flags_at + a256(n_bound);
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (reserved > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s_reads: %zu bytes of working set above the work buffer's cap of %zu", kind.who,
+                      reserved, budget);
+        return KMX_E_NOMEM;
+    }
+    // (room for the directory is asked for with the rest, so the buffer does not move between the windows and the lookup)
+    uint32_t p = 0;
+    const size_t dir_bytes = n ? kmx::count_lookup_dir_bytes(n, k, &p) : 0;
+    const bool with_dir = dir_bytes != 0 && kmx::count_lookup_wants_dir(n, n_win, kind.words) && reserved + dir_bytes <= budget;
+    char* base = static_cast<char*>(big_scratch(ctx, reserved + (with_dir ? dir_bytes : 0)));
+    if (!base && with_dir) base = static_cast<char*>(big_scratch(ctx, reserved));
+    if (!base) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s_reads: no memory for %zu bytes of working set", kind.who, reserved);
+        return KMX_E_NOMEM;
+    }
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    const unsigned long long allocs = ctx->big_allocs;
+    uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : d_out;
+    uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
+    if (int st = kind.windows(ctx, reads, d_win_offsets, k, nullptr, nullptr, canon, flags)) return st;
+    if (ctx->d_big != base || ctx->big_allocs != allocs) {
+        char msg[96];
+        std::snprintf(msg, sizeof msg, "%s_reads: work buffer moved", kind.who);
+        return fail_hip(ctx, hipErrorUnknown, msg);
+    }
+    return lookup_run(ctx, kind, d_kmers, d_counts, n, k, canon, flags, n_win, d_out, reserved);
+}
+
+int kmx_count_lookup_reads(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint64_t* d_kmers,
+                           const uint64_t* d_counts, uint64_t n, uint64_t* d_out) {
+    return lookup_reads_impl(ctx, kQuery1, reads, d_win_offsets, k, d_kmers, d_counts, n, d_out);
+}
+
+int kmx_count_lookup_reads2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint64_t* d_kmers2,
+                            const uint64_t* d_counts, uint64_t n, uint64_t* d_out) {
+    return lookup_reads_impl(ctx, kQuery2, reads, d_win_offsets, k, d_kmers2, d_counts, n, d_out);
+}
+
+int kmx_count_spectrum(kmx_ctx* ctx, const uint64_t* d_counts, uint64_t n, uint64_t n_bins, uint64_t* d_spectrum) {
+    if (!ctx || !d_spectrum || n_bins < 2 || (n && !d_counts) || n > (1ull << 40)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_spectrum(d_counts, n, n_bins, d_spectrum, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+static int filter_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n,
+                       uint64_t min_count, uint64_t max_count, uint64_t* d_kmers_out, uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
+    if (!ctx || !h_n_out || ((d_kmers_out == nullptr) != (d_counts_out == nullptr))) return KMX_E_ARG;
+    if ((n && (!d_kmers || !d_counts)) || n > (1ull << 38)) return KMX_E_ARG;   // (the mark pass is one grid of a thread per entry)
+    if (words == 2u && (!aligned16(d_kmers) || !aligned16(d_kmers_out))) return KMX_E_ARG;
+    *h_n_out = 0;
+    if (n == 0 || min_count > max_count) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    const size_t bytes = kmx::count_filter_bytes(n);
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (bytes > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes, budget);
+        return KMX_E_NOMEM;
+    }
+    void* area = big_scratch(ctx, bytes);
+    if (!area) return KMX_E_NOMEM;
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    uint64_t n_out = 0;
+    KMX_HIP(ctx, kmx::launch_count_filter_mark(d_counts, n, min_count, max_count, area, ctx->h_pinned, &n_out, ctx->stream));
+    *h_n_out = n_out;
+    if (!d_kmers_out || n_out == 0) return KMX_OK;
+    if (n_out > max_out) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu entries kept, room for %llu", who, (unsigned long long)n_out,
+                      (unsigned long long)max_out);
+        return KMX_E_NOMEM;
+    }
+    KMX_HIP(ctx, kmx::launch_count_filter_emit(words, d_kmers, d_counts, n, area, d_kmers_out, d_counts_out, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_filter(kmx_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint64_t min_count, uint64_t max_count,
+                     uint64_t* d_kmers_out, uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
+    return filter_impl(ctx, "kmx_count_filter", 1u, d_kmers, d_counts, n, min_count, max_count, d_kmers_out, d_counts_out, max_out, h_n_out);
+}
+
+int kmx_count_filter2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n, uint64_t min_count, uint64_t max_count,
+                      uint64_t* d_kmers2_out, uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
+    return filter_impl(ctx, "kmx_count_filter2", 2u, d_kmers2, d_counts, n, min_count, max_count, d_kmers2_out, d_counts_out, max_out, h_n_out);
+}
+
 int kmx_canonical_reduce2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t with_hash, kmx_summary2* d_out) {
     if (!ctx || !reads_ok(reads) || !d_out) return KMX_E_ARG;
     if (k < 33 || k > 64) return KMX_E_K_RANGE;

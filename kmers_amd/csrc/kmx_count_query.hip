@@ -1,0 +1,330 @@
+// kmx_count_query.hip -- what is done WITH a count table (kmx_count_canonical(2) / kmx_count_merge(2): keys ascending and distinct,
+// one u64 count per key): kmx_count_lookup(2) / kmx_count_lookup_reads(2), kmx_count_spectrum, kmx_count_filter(2).
+//
+// Lookup.  A batch of unrelated queries against a sorted array: nothing coalesces, every query is a chain of dependent loads, and
+// what hides the chain is the number of chains in flight.  Two routes, one kernel:
+//   directory  dir[j] = index of the first key whose top p bits (counted down from bit 2k, as the counter's MSD partition counts
+//              them) are >= j, j = 0 .. 2^p; p from n so that a bin holds about LINE keys when keys are evenly spread.  Built per
+//              call by one streaming pass over the keys (a wave per 64 keys: where the prefix steps from a to b the wave's lanes
+//              write dir[a + 1 .. b] together, so a run of empty bins -- canonical keys are skewed -- is not one lane's loop).
+//              Per query: dir[j], dir[j + 1], then the search confined to that bin.
+//   plain      the same search over [0, n): few queries against a large table (the pass over the keys would cost more than it
+//              saves), a directory above the work buffer's cap, a table of 2^32 entries or more (directory entries are 4 bytes).
+// The search is correct for a bin of any size (all n keys in one bin, empty bins): binary steps while the range is longer than LINE
+// keys, then the LINE keys of the range are loaded at once (independent loads, one latency) and compared.  QPL queries per lane run
+// in lockstep, so every step issues QPL independent loads.  Vector loads and stores only; no LDS, no atomics, no scratch.
+// A table that is not sorted gives wrong answers, never a wild access: directory entries are clamped to n before they are used.
+//
+// Spectrum.  Bins below SPEC_LDS in block-private LDS words (u32: a block sees fewer than 2^32 entries), the rest -- rare in a real
+// table, where small counts dominate -- straight to the output with device atomics; count == 1 (most rows of a real table) and the
+// last, collecting bin (most rows of a deep table with few bins) are tallied per thread and added once per wave.  The block's bins are added to the output with one device atomic per non-empty bin.
+//
+// Filter.  A mark byte per entry, then the counters' compaction: keep_count_kernel and the block scans of kmx_count_common.h, and
+// the wave-ballot copy of the marked entries (here for either key width).
+#include "kmx_count_common.h"
+
+namespace kmx {
+
+namespace {
+
+constexpr u32 LINE = 8;          // keys the last step of a search loads at once (one-word keys: a 64-byte line; two-word: 128 bytes)
+constexpr u32 QPL = 4;           // queries per lane, in lockstep
+constexpr u32 DIR_MAX_BITS = 28; // at most 2^28 + 1 directory entries (1 GiB)
+constexpr u32 SPEC_LDS = 4096;   // spectrum bins held in LDS per block (16 KiB)
+constexpr u32 SPEC_IPT = 16;     // entries per thread and grid step of the spectrum
+
+// ---------------------------------------------------------------- keys of one or two words
+template <u32 W> struct KeyOf;
+template <> struct KeyOf<1> {
+    u64 lo;
+    __device__ __forceinline__ static KeyOf load(const u64* a, u64 i) { return KeyOf{a[i]}; }
+    __device__ __forceinline__ static void store(u64* a, u64 i, const KeyOf& v) { a[i] = v.lo; }
+    __device__ __forceinline__ bool less(const KeyOf& o) const { return lo < o.lo; }
+    __device__ __forceinline__ bool equal(const KeyOf& o) const { return lo == o.lo; }
+    // a bit at or above bit 2k: no key of a table has one (2k <= 62)
+    __device__ __forceinline__ bool outside(u32 k) const { return (lo >> (2u * k)) != 0u; }
+    // the top p bits of the 2k-bit key (0 < p <= 2k)
+    __device__ __forceinline__ u64 prefix(u32 k, u32 p) const { return lo >> (2u * k - p); }
+};
+template <> struct KeyOf<2> {
+    u64 lo, hi;
+    __device__ __forceinline__ static KeyOf load(const u64* a, u64 i) {
+        const ulonglong2 v = reinterpret_cast<const ulonglong2*>(a)[i];   // (one 16-byte load)
+        return KeyOf{v.x, v.y};
+    }
+    __device__ __forceinline__ static void store(u64* a, u64 i, const KeyOf& v) { reinterpret_cast<ulonglong2*>(a)[i] = make_ulonglong2(v.lo, v.hi); }
+    __device__ __forceinline__ bool less(const KeyOf& o) const { return hi < o.hi || (hi == o.hi && lo < o.lo); }
+    __device__ __forceinline__ bool equal(const KeyOf& o) const { return hi == o.hi && lo == o.lo; }
+    __device__ __forceinline__ bool outside(u32 k) const { return k < 64u && (hi >> (2u * k - 64u)) != 0u; }   // (k >= 33)
+    // the field may straddle the word boundary: s = 2k - p bits lie below it, 36 <= s < 128
+    __device__ __forceinline__ u64 prefix(u32 k, u32 p) const {
+        const u32 s = 2u * k - p;
+        return s >= 64u ? hi >> (s - 64u) : (hi << (64u - s)) | (lo >> s);
+    }
+};
+
+// the bin of a key; anything a table should not hold (a bit at or above 2k) lands in the last bin instead of outside the directory
+template <u32 W>
+__device__ __forceinline__ u64 bin_of(const KeyOf<W>& key, u32 k, u32 p) {
+    if (p == 0u) return 0u;
+    const u64 last = (1ull << p) - 1ull;
+    if (key.outside(k)) return last;
+    const u64 j = key.prefix(k, p);
+    return j > last ? last : j;
+}
+
+// ---------------------------------------------------------------- the directory
+// One streaming pass: lane i compares the bin of key i with the bin of key i - 1 (key -1: bin "-1", so dir[0 .. bin(key 0)] = 0;
+// behind the last key: bin 2^p, so the tail of the directory = n).  Every entry is written exactly once when keys ascend.
+template <u32 W>
+__global__ void __launch_bounds__(CT) dir_build_kernel(const u64* __restrict__ keys, u64 n, u32 k, u32 p, u32* __restrict__ dir) {
+    const u64 i = (u64)blockIdx.x * CT + threadIdx.x;   // 0 .. n: position n closes the directory
+    const u32 lane = threadIdx.x & 63u;
+    u64 from = 1u, to = 0u;   // this lane's entries: dir[from .. to] = i
+    if (i <= n) {
+        to = i < n ? bin_of<W>(KeyOf<W>::load(keys, i), k, p) : (1ull << p);
+        from = i == 0u ? 0u : bin_of<W>(KeyOf<W>::load(keys, i - 1u), k, p) + 1u;
+    }
+    unsigned long long todo = __ballot(from <= to);
+    while (todo) {
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1ull;
+        const u64 f = __shfl(from, src), t = __shfl(to, src), v = __shfl(i, src);
+        for (u64 j = f + lane; j <= t; j += 64u) dir[j] = (u32)v;
+    }
+}
+
+// ---------------------------------------------------------------- the lookup
+// out[i] = count of query[i] (1 with counts == nullptr), 0 if absent or the query's flag lacks KMX_WIN_VALID.  `out` may be `query`
+// (one-word keys): a lane reads its own queries before it writes their answers, and nobody else's.
+template <u32 W, bool DIR>
+__global__ void __launch_bounds__(CT) lookup_kernel(const u64* __restrict__ keys, const u64* __restrict__ counts, u64 n, u32 k, u32 p,
+                                                    const u32* __restrict__ dir, const u64* query, const uint8_t* __restrict__ qflags, u64 n_query,
+                                                    u64* out) {
+    using Key = KeyOf<W>;
+    const u64 base = (u64)blockIdx.x * (CT * QPL) + threadIdx.x;
+    Key q[QPL];
+    u64 lo[QPL], hi[QPL];
+    bool live[QPL];
+#pragma unroll
+    for (u32 j = 0; j < QPL; ++j) {
+        const u64 i = base + (u64)j * CT;
+        live[j] = i < n_query;
+        q[j] = Key::load(query, live[j] ? i : 0u);
+        if (live[j] && qflags != nullptr) live[j] = (qflags[i] & KMX_WIN_VALID) != 0u;
+        if (q[j].outside(k)) live[j] = false;
+    }
+#pragma unroll
+    for (u32 j = 0; j < QPL; ++j) {
+        lo[j] = hi[j] = 0u;
+        if (!live[j]) continue;
+        if (DIR) {
+            const u64 b = bin_of<W>(q[j], k, p);
+            const u64 a0 = dir[b], a1 = dir[b + 1u];
+            lo[j] = a0 < n ? a0 : n;
+            hi[j] = a1 < n ? a1 : n;
+            if (hi[j] < lo[j]) hi[j] = lo[j];
+        } else {
+            hi[j] = n;
+        }
+    }
+    // binary steps while some range is longer than LINE keys; q, if the table holds it, stays inside [lo, hi): keys[mid] <= q keeps
+    // [mid, hi), q < keys[mid] keeps [lo, mid) (lo < mid < hi, so every step shortens the range)
+    for (;;) {
+        bool any = false;
+#pragma unroll
+        for (u32 j = 0; j < QPL; ++j) any |= hi[j] - lo[j] > LINE;
+        if (!any) break;
+        Key m[QPL];
+        u64 mid[QPL];
+#pragma unroll
+        for (u32 j = 0; j < QPL; ++j) {
+            mid[j] = lo[j] + ((hi[j] - lo[j]) >> 1);
+            m[j] = q[j];
+            if (hi[j] - lo[j] > LINE) m[j] = Key::load(keys, mid[j]);
+        }
+#pragma unroll
+        for (u32 j = 0; j < QPL; ++j) {
+            if (hi[j] - lo[j] > LINE) {
+                if (q[j].less(m[j])) hi[j] = mid[j];
+                else lo[j] = mid[j];
+            }
+        }
+    }
+    // at most LINE keys are left: load them all, the equal one (keys are distinct) is the answer
+    u64 hit[QPL];
+#pragma unroll
+    for (u32 j = 0; j < QPL; ++j) {
+        hit[j] = ~0ull;
+#pragma unroll
+        for (u32 s = 0; s < LINE; ++s) {
+            const u64 i = lo[j] + s;
+            if (i < hi[j] && Key::load(keys, i).equal(q[j])) hit[j] = i;
+        }
+    }
+#pragma unroll
+    for (u32 j = 0; j < QPL; ++j) {
+        const u64 i = base + (u64)j * CT;
+        if (i >= n_query) continue;
+        u64 v = 0u;
+        if (hit[j] != ~0ull) v = counts != nullptr ? counts[hit[j]] : 1u;
+        out[i] = v;
+    }
+}
+
+// ---------------------------------------------------------------- the spectrum
+__global__ void __launch_bounds__(CT) spectrum_kernel(const u64* __restrict__ counts, u64 n, u64 n_bins, unsigned long long* __restrict__ spectrum) {
+    __shared__ u32 bins[SPEC_LDS];
+    for (u32 b = threadIdx.x; b < SPEC_LDS; b += CT) bins[b] = 0u;
+    __syncthreads();
+    const u64 top = n_bins - 1u;
+    u32 ones = 0, tops = 0;
+    for (u64 i0 = (u64)blockIdx.x * (CT * SPEC_IPT) + threadIdx.x; i0 < n; i0 += (u64)gridDim.x * (CT * SPEC_IPT)) {
+        u64 c[SPEC_IPT];
+#pragma unroll
+        for (u32 j = 0; j < SPEC_IPT; ++j) {
+            const u64 i = i0 + (u64)j * CT;
+            c[j] = i < n ? counts[i] : 0u;
+        }
+#pragma unroll
+        for (u32 j = 0; j < SPEC_IPT; ++j) {
+            if (i0 + (u64)j * CT >= n) continue;
+            const u64 b = c[j] < top ? c[j] : top;
+            if (b == top) tops += 1u;   // (the collecting bin: most rows of a deep table with few bins; n_bins == 2: the singletons too)
+            else if (b == 1u) ones += 1u;
+            else if (b < SPEC_LDS) atomicAdd(&bins[b], 1u);
+            else atomicAdd(&spectrum[b], 1ull);
+        }
+    }
+    for (u32 o = 32; o > 0; o >>= 1) {
+        ones += __shfl_xor(ones, o);
+        tops += __shfl_xor(tops, o);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (ones != 0u) atomicAdd(&bins[1], ones);
+        if (tops != 0u) {
+            if (top < SPEC_LDS) atomicAdd(&bins[top], tops);
+            else atomicAdd(&spectrum[top], (unsigned long long)tops);
+        }
+    }
+    __syncthreads();
+    for (u32 b = threadIdx.x; b < SPEC_LDS; b += CT) {
+        const u32 v = bins[b];
+        if (v != 0u) atomicAdd(&spectrum[b], (unsigned long long)v);   // (b < n_bins: only clamped values were counted)
+    }
+}
+
+// ---------------------------------------------------------------- the filter
+// keep[i] = min <= counts[i] <= max over the whole padded range (the compaction reads whole CHUNKs)
+__global__ void __launch_bounds__(CT) filter_mark_kernel(const u64* __restrict__ counts, u64 n, u64 n_pad, u64 mn, u64 mx, uint8_t* __restrict__ keep) {
+    const u64 i = (u64)blockIdx.x * CT + threadIdx.x;
+    if (i >= n_pad) return;
+    const bool in = i < n;
+    const u64 c = in ? counts[i] : 0u;
+    keep[i] = in && c >= mn && c <= mx ? 1u : 0u;
+}
+
+// the counters' wave-ballot copy of the marked entries, for either key width
+template <u32 W>
+__global__ void __launch_bounds__(CT) filter_write_kernel(const uint8_t* __restrict__ keep, const u64* __restrict__ partial, const u64* __restrict__ keys,
+                                                          const u64* __restrict__ counts, u64* __restrict__ out_k, u64* __restrict__ out_c) {
+    constexpr u32 PER_WAVE = CHUNK / (CT / 64u);
+    static_assert(PER_WAVE == 64u * 64u, "a wave's range is its lanes' 64-byte pieces");
+    __shared__ u32 wsum[CT / 64];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u64 w0 = (u64)blockIdx.x * CHUNK + (u64)wv * PER_WAVE;
+    u32 c = kept_in(keep, w0 + (u64)lane * 64u);
+    for (u32 o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) wsum[wv] = c;
+    __syncthreads();
+    u64 o = partial[blockIdx.x];
+    for (u32 j = 0; j < wv; ++j) o += wsum[j];
+    for (u32 s0 = 0; s0 < PER_WAVE; s0 += 64u) {
+        const u64 i = w0 + s0 + lane;
+        const bool kp = keep[i] != 0;
+        const unsigned long long m = __ballot(kp);
+        if (kp) {
+            const u64 r = o + (u64)__popcll(m & ((1ull << lane) - 1ull));
+            KeyOf<W>::store(out_k, r, KeyOf<W>::load(keys, i));
+            out_c[r] = counts[i];
+        }
+        o += (u64)__popcll(m);
+    }
+}
+
+u64 filter_pad(u64 n) { return ceil_div(n, CHUNK) * CHUNK; }
+
+}  // namespace
+
+// ---------------------------------------------------------------- host side
+// The directory for a table of n keys of 2k bits: *p_out prefix bits, 4 * (2^p + 1) bytes; 0 = no directory for such a table.
+size_t count_lookup_dir_bytes(u64 n, u32 k, u32* p_out) {
+    *p_out = 0;
+    if (n == 0 || n >= (1ull << 32)) return 0;
+    u32 p = 0;
+    while (p < DIR_MAX_BITS && p < 2u * k && (n >> p) > LINE) ++p;   // n / 2^p <= LINE, or as many bits as there are
+    *p_out = p;
+    return align256(4u * ((1ull << p) + 1u));
+}
+
+// Is the directory worth its pass over the keys?  Building it streams 8 * words * n bytes; a query it serves touches one line of
+// the directory and one or two of its bin instead of the lines of a whole search's last steps that no cache holds: about four
+// 128-byte lines, 512 bytes, saved per query.
+bool count_lookup_wants_dir(u64 n, u64 n_query, u32 words) { return n > LINE && n_query >= (u64)words * n / 64u; }
+
+hipError_t launch_count_lookup(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, const u64* query, const uint8_t* qflags, u64 n_query,
+                               u64* out, void* dir_area, u32 p, hipStream_t st) {
+    u32* dir = static_cast<u32*>(dir_area);
+    if (dir) {
+        const unsigned nb = (unsigned)ceil_div(n + 1u, CT);
+        if (words == 1u) hipLaunchKernelGGL(dir_build_kernel<1>, dim3(nb), dim3(CT), 0, st, keys, n, k, p, dir);
+        else hipLaunchKernelGGL(dir_build_kernel<2>, dim3(nb), dim3(CT), 0, st, keys, n, k, p, dir);
+    }
+    const unsigned nq = (unsigned)ceil_div(n_query, (u64)CT * QPL);
+    if (words == 1u) {
+        if (dir) hipLaunchKernelGGL((lookup_kernel<1, true>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
+        else hipLaunchKernelGGL((lookup_kernel<1, false>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
+    } else {
+        if (dir) hipLaunchKernelGGL((lookup_kernel<2, true>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
+        else hipLaunchKernelGGL((lookup_kernel<2, false>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_count_spectrum(const u64* counts, u64 n, u64 n_bins, u64* spectrum, int n_cu, hipStream_t st) {
+    u64 nb = ceil_div(n, (u64)CT * SPEC_IPT);
+    const u64 cap = (u64)(n_cu > 0 ? n_cu : 256) * 8u;
+    if (nb > cap) nb = cap;
+    hipLaunchKernelGGL(spectrum_kernel, dim3((unsigned)nb), dim3(CT), 0, st, counts, n, n_bins, reinterpret_cast<unsigned long long*>(spectrum));
+    return hipGetLastError();
+}
+
+// the filter's working set: a mark byte per entry (whole CHUNKs) and a partial sum per CHUNK
+size_t count_filter_bytes(u64 n) { return align256(filter_pad(n)) + align256(8u * (ceil_div(n, CHUNK) + 2u)); }
+
+// marks and counts the entries of [min, max]; synchronous (one host round trip: how many there are)
+hipError_t launch_count_filter_mark(const u64* counts, u64 n, u64 mn, u64 mx, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st) {
+    uint8_t* keep = static_cast<uint8_t*>(area);
+    u64* partial = reinterpret_cast<u64*>(static_cast<char*>(area) + align256(filter_pad(n)));
+    const u64 nb = ceil_div(n, CHUNK);
+    hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)ceil_div(filter_pad(n), CT)), dim3(CT), 0, st, counts, n, filter_pad(n), mn, mx, keep);
+    hipLaunchKernelGGL(keep_count_kernel, dim3((unsigned)nb), dim3(CT), 0, st, keep, partial);
+    hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial, nb, partial + nb);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(h_pinned, partial + nb, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    *h_out = h_pinned[0];
+    return hipSuccess;
+}
+
+hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* counts, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st) {
+    const uint8_t* keep = static_cast<const uint8_t*>(area);
+    const u64* partial = reinterpret_cast<const u64*>(static_cast<const char*>(area) + align256(filter_pad(n)));
+    const unsigned nb = (unsigned)ceil_div(n, CHUNK);
+    if (words == 1u) hipLaunchKernelGGL(filter_write_kernel<1>, dim3(nb), dim3(CT), 0, st, keep, partial, keys, counts, out_k, out_c);
+    else hipLaunchKernelGGL(filter_write_kernel<2>, dim3(nb), dim3(CT), 0, st, keep, partial, keys, counts, out_k, out_c);
+    return hipGetLastError();
+}
+
+}  // namespace kmx

@@ -146,4 +146,13 @@ size_t count2_merge_bytes(u64 n);
 hipError_t launch_count2_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
                                u64* h_out, hipStream_t st);
 hipError_t launch_count2_merge_emit(u64 n, const void* area, u64* out_k2, u64* out_c, hipStream_t st);
+// kmx_count_query.hip: lookup, spectrum and filter of a count table (`words` u64 per key: 1 or 2)
+size_t count_lookup_dir_bytes(u64 n, u32 k, u32* p_out);
+bool count_lookup_wants_dir(u64 n, u64 n_query, u32 words);
+hipError_t launch_count_lookup(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, const u64* query, const uint8_t* qflags, u64 n_query,
+                               u64* out, void* dir_area, u32 p, hipStream_t st);
+hipError_t launch_count_spectrum(const u64* counts, u64 n, u64 n_bins, u64* spectrum, int n_cu, hipStream_t st);
+size_t count_filter_bytes(u64 n);
+hipError_t launch_count_filter_mark(const u64* counts, u64 n, u64 mn, u64 mx, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* counts, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
 }  // namespace kmx
