@@ -517,6 +517,54 @@ pub fn count_filter2(ctx: &HipContext, table: CountTable<'_>, min_count: u64, ma
     Ok(n_out)
 }
 
+/// Set algebra of two count tables (`kmx_count_setop`): `op` is one of `KMX_SETOP_*`, `rule` one of `KMX_RULE_*` (the count of a
+/// key both tables hold, for INTERSECT and UNION; 0 for the other operations).  The result is a table again; returns its size.
+/// A table's `counts` may be `None` where the operation never reads them (b's for SUBTRACT and INTERSECT / LEFT, a's for
+/// INTERSECT / RIGHT).  `d_kmers_out` and `d_counts_out` hold at least `max_out` u64 each.
+pub fn count_setop(ctx: &HipContext, op: u32, rule: u32, a: CountTable<'_>, b: CountTable<'_>, d_kmers_out: &DeviceBuf<'_>,
+                   d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    a.check(1);
+    b.check(1);
+    assert!(max_out as u128 * 8 <= d_kmers_out.len().min(d_counts_out.len()) as u128, "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_setop(ctx.0, op, rule, a.keys.as_ptr::<u64>(), a.counts_ptr(), a.n, b.keys.as_ptr::<u64>(), b.counts_ptr(), b.n,
+                                    d_kmers_out.as_mut_ptr::<u64>(), d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
+/// The same for two-word keys (`kmx_count_setop2`): `d_kmers2_out` holds at least `2 * max_out` u64.
+pub fn count_setop2(ctx: &HipContext, op: u32, rule: u32, a: CountTable<'_>, b: CountTable<'_>, d_kmers2_out: &DeviceBuf<'_>,
+                    d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    a.check(2);
+    b.check(2);
+    assert!(max_out as u128 * 16 <= d_kmers2_out.len() as u128 && max_out as u128 * 8 <= d_counts_out.len() as u128, "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_setop2(ctx.0, op, rule, a.keys.as_ptr::<u64>(), a.counts_ptr(), a.n, b.keys.as_ptr::<u64>(), b.counts_ptr(), b.n,
+                                     d_kmers2_out.as_mut_ptr::<u64>(), d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
+/// How two count tables relate (`kmx_count_compare`): keys shared / only in `a` / only in `b` and the sums of counts behind Jaccard,
+/// containment and weighted Jaccard.  Both tables without counts: the key sets alone (the sums are 0).
+pub fn count_compare(ctx: &HipContext, a: CountTable<'_>, b: CountTable<'_>) -> Result<kmx_table_compare, KmxError> {
+    a.check(1);
+    b.check(1);
+    let mut rec = kmx_table_compare::default();
+    ctx.ck(unsafe { kmx_count_compare(ctx.0, a.keys.as_ptr::<u64>(), a.counts_ptr(), a.n, b.keys.as_ptr::<u64>(), b.counts_ptr(), b.n,
+                                      &mut rec as *mut kmx_table_compare as *mut std::os::raw::c_void) })?;
+    Ok(rec)
+}
+
+/// The same for two-word keys (`kmx_count_compare2`).
+pub fn count_compare2(ctx: &HipContext, a: CountTable<'_>, b: CountTable<'_>) -> Result<kmx_table_compare, KmxError> {
+    a.check(2);
+    b.check(2);
+    let mut rec = kmx_table_compare::default();
+    ctx.ck(unsafe { kmx_count_compare2(ctx.0, a.keys.as_ptr::<u64>(), a.counts_ptr(), a.n, b.keys.as_ptr::<u64>(), b.counts_ptr(), b.n,
+                                       &mut rec as *mut kmx_table_compare as *mut std::os::raw::c_void) })?;
+    Ok(rec)
+}
+
 /// `Kmer::minimizer_word(word, k, width, &state)` (kmer.rs:170-192) with a std hasher state: `(minimizer, offset)` per word
 pub fn minimizer_words_sip13(ctx: &HipContext, words: &[u64], k: u8, width: u8, keys: (u64, u64)) -> Result<Vec<(u64, u32)>, KmxError> {
     let bytes = unsafe { std::slice::from_raw_parts(words.as_ptr() as *const u8, words.len() * 8) };

@@ -314,6 +314,69 @@ int kmx_count_filter(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_co
 int kmx_count_filter2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, uint64_t min_count, uint64_t max_count,
                       uint64_t *d_kmers2_out, uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
 
+/* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
+ * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
+ * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.
+ * The calls assume sorted tables and do not check: tables that are not sorted give wrong answers (a result that is not a table,
+ * even one longer than n_a + n_b, which max_out then refuses like any other), never an access outside the arrays.  n_a, n_b up to 2^40 (KMX_E_ARG above); an empty table on either side is valid and its pointers may be NULL. */
+#define KMX_SETOP_INTERSECT 0
+#define KMX_SETOP_UNION 1
+#define KMX_SETOP_SUBTRACT 2
+#define KMX_SETOP_SYMDIFF 3
+#define KMX_SETOP_COUNTER_SUBTRACT 4
+#define KMX_RULE_SUM 0
+#define KMX_RULE_MIN 1
+#define KMX_RULE_MAX 2
+#define KMX_RULE_LEFT 3
+#define KMX_RULE_RIGHT 4
+/* op:   KMX_SETOP_INTERSECT         the keys both tables hold
+ *       KMX_SETOP_UNION             the keys either table holds
+ *       KMX_SETOP_SUBTRACT          the keys of a that b does not hold, with a's counts
+ *       KMX_SETOP_SYMDIFF           the keys exactly one table holds, with that table's count
+ *       KMX_SETOP_COUNTER_SUBTRACT  the keys of a; count_a - count_b where b holds the key, the key dropped where count_a <= count_b
+ * rule: the count of a key BOTH tables hold, for INTERSECT and UNION -- KMX_RULE_SUM (count_a + count_b, wrapping mod 2^64 exactly
+ *       as kmx_count_merge adds), KMX_RULE_MIN, KMX_RULE_MAX, KMX_RULE_LEFT (count_a), KMX_RULE_RIGHT (count_b).  A key of UNION that
+ *       one table holds keeps that table's count whatever the rule.  The other three operations take no rule: it must be 0.
+ * An op or rule outside these lists, or a rule on an operation that takes none: KMX_E_ARG.  UNION with KMX_RULE_SUM is
+ * bit-identical to kmx_count_merge on the same inputs.
+ * A count array the operation never reads may be NULL: d_counts_b for SUBTRACT and for INTERSECT with KMX_RULE_LEFT ("the entries
+ * of a whose key is / is not in the key SET b"), d_counts_a for INTERSECT with KMX_RULE_RIGHT.  NULL anywhere else with n > 0:
+ * KMX_E_ARG.
+ * Outputs: the conventions of kmx_count_merge -- *h_n_out (host) is always set; both outputs NULL = count only; one NULL =
+ * KMX_E_ARG; n_out > max_out = KMX_E_NOMEM with nothing written; outputs must not alias inputs.  Deterministic: repeated calls
+ * are bit-identical.
+ * Working set in the context's work buffer, per TILE of 2048 merged entries, not per entry: with tiles = ceil((n_a + n_b) / 2048),
+ * 16 * (tiles + 1) bytes rounded up to 256 plus 8 * (tiles + 2) bytes rounded up to 256 (24 bytes per 2048 entries; 512 bytes for
+ * one tile).  Above the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM before any kernel runs.  The call uses the work buffer (a
+ * following kmx_fastx_parse cannot reuse its chunk prefixes).
+ * Synchronous (the size comes back to the host: one round trip): not capturable in a HIP graph. */
+int kmx_count_setop(kmx_ctx *ctx, uint32_t op, uint32_t rule, const uint64_t *d_kmers_a, const uint64_t *d_counts_a, uint64_t n_a,
+                    const uint64_t *d_kmers_b, const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers_out, uint64_t *d_counts_out,
+                    uint64_t max_out, uint64_t *h_n_out);
+/* The same for two-word keys (k = 33..64): d_kmers2_a, d_kmers2_b and d_kmers2_out hold two u64 per key and must be 16-byte
+ * aligned (KMX_E_ARG otherwise).  Working set and synchronisation as kmx_count_setop. */
+int kmx_count_setop2(kmx_ctx *ctx, uint32_t op, uint32_t rule, const uint64_t *d_kmers2_a, const uint64_t *d_counts_a, uint64_t n_a,
+                     const uint64_t *d_kmers2_b, const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers2_out, uint64_t *d_counts_out,
+                     uint64_t max_out, uint64_t *h_n_out);
+
+/* What kmx_count_compare(2) fills: all u64, sums wrap mod 2^64. */
+typedef struct kmx_table_compare {
+    uint64_t n_both, n_only_a, n_only_b; /* keys in both tables, in a only, in b only */
+    uint64_t sum_a, sum_b;               /* all counts of a / of b */
+    uint64_t sum_a_both, sum_b_both;     /* the counts of a / of b over the shared keys */
+    uint64_t sum_min, sum_max;           /* over the union: a key one table holds contributes min 0, max its count */
+} kmx_table_compare;
+/* How two tables relate, without writing a table: Jaccard = n_both / (n_both + n_only_a + n_only_b), containment of a in b =
+ * n_both / (n_both + n_only_a), weighted Jaccard = sum_min / sum_max.  h_out (host) points at a kmx_table_compare (declared
+ * void * so that bindings generated from the prototypes pass the record's address without a type of their own); NULL: KMX_E_ARG.
+ * With BOTH count arrays NULL the three n_* fields are filled and the sums are 0; one of them NULL with n > 0: KMX_E_ARG.
+ * Working set as kmx_count_setop.  Synchronous (the record comes back to the host: one round trip).  Deterministic. */
+int kmx_count_compare(kmx_ctx *ctx, const uint64_t *d_kmers_a, const uint64_t *d_counts_a, uint64_t n_a, const uint64_t *d_kmers_b,
+                      const uint64_t *d_counts_b, uint64_t n_b, void *h_out);
+/* The same for two-word keys (16-byte aligned key arrays, KMX_E_ARG otherwise). */
+int kmx_count_compare2(kmx_ctx *ctx, const uint64_t *d_kmers2_a, const uint64_t *d_counts_a, uint64_t n_a, const uint64_t *d_kmers2_b,
+                       const uint64_t *d_counts_b, uint64_t n_b, void *h_out);
+
 /* Deterministic synthetic reads (BUILD-DEFINED; the reference bench input is unseeded,
  * benches/simple_benchmark.rs:59-65): byte g of the stream = "ACGT"[(splitmix64(seed + g/32) >> 2*(g%32)) & 3].
  * Writes nbytes bytes for stream positions [first_byte, first_byte+nbytes). */

@@ -21,6 +21,12 @@ HASH_NONE, HASH_LEX, HASH_IDENTITY = 0, 1, 2
 NO_MATCH, IDENTITY_MATCH, TWIN_MATCH = 0, 1, 2
 WIN_VALID, WIN_FW_CANONICAL = 1, 2
 REDUCE_SUM_FW = 1
+# kmx_count_setop(2): the operation, and the count of a key both tables hold (INTERSECT and UNION)
+SETOP_INTERSECT, SETOP_UNION, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_COUNTER_SUBTRACT = range(5)
+RULE_SUM, RULE_MIN, RULE_MAX, RULE_LEFT, RULE_RIGHT = range(5)
+# merged entries per tile of kmx_count_setop(2) / kmx_count_compare(2) (kmx_count_setop.hip: SETOP_TILE): where the boundary tests
+# put their shared keys, and what the documented working set counts in
+SETOP_TILE = 2048
 
 
 class KmxError(RuntimeError):
@@ -40,6 +46,12 @@ class Summary(C.Structure):
 class Summary2(C.Structure):
     _fields_ = [("n_valid", C.c_uint64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_uint64), ("xor_lo", C.c_uint64),
                 ("xor_hi", C.c_uint64)]
+
+
+class TableCompare(C.Structure):
+    """kmx_table_compare: what kmx_count_compare(2) fills"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_both", "n_only_a", "n_only_b", "sum_a", "sum_b", "sum_a_both", "sum_b_both", "sum_min",
+                                          "sum_max")]
 
 
 _vp, _u64, _u32, _u8, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint8, C.c_int
@@ -102,6 +114,10 @@ SIGNATURES = {
     "kmx_count_spectrum": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "kmx_count_filter": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_filter2": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "kmx_count_compare2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
     "kmx_minimizer_words_sip13": (_int, [_vp, _vp, _u64, _u32, _u32, _u64, _u64, _vp, _vp]),
     "kmx_seqvec_minimizers_sip13": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u64, _vp, _vp]),
     "kmx_minimizers_sip13": (_int, [_vp, _RP, _vp, _u32, _u32, _u64, _u64, _vp, _vp, C.POINTER(C.c_uint64)]),

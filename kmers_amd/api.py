@@ -13,13 +13,16 @@ with `record_stream` so the caching allocator does not recycle them under a runn
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import functools
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, REDUCE_SUM_FW, KmxError, Reads, Summary, Summary2)
+from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, REDUCE_SUM_FW, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+                   SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
+                   TableCompare)
 
 SEED_DEFAULT = 0x6B6D6572735F7631  # "kmers_v1"
 
@@ -37,6 +40,47 @@ def _ptr(t):
 def u64_numpy(t: torch.Tensor) -> np.ndarray:
     """int64 CUDA tensor holding u64 words -> numpy uint64 (host)."""
     return t.detach().cpu().numpy().view(np.uint64)
+
+
+def _ratio(num: int, den: int) -> float:
+    return num / den if den else 0.0
+
+
+@dataclasses.dataclass(frozen=True)
+class TableComparison:
+    """kmx_table_compare on the host: how many keys two count tables share and the sums of their counts (u64 values, sums wrapped
+    mod 2^64 as the device adds them), and the similarity measures that follow (0.0 where a denominator is 0)."""
+    n_both: int
+    n_only_a: int
+    n_only_b: int
+    sum_a: int
+    sum_b: int
+    sum_a_both: int
+    sum_b_both: int
+    sum_min: int
+    sum_max: int
+
+    @property
+    def jaccard(self) -> float:
+        return _ratio(self.n_both, self.n_both + self.n_only_a + self.n_only_b)
+
+    @property
+    def containment_a(self) -> float:
+        """the share of a's keys that b holds"""
+        return _ratio(self.n_both, self.n_both + self.n_only_a)
+
+    @property
+    def containment_b(self) -> float:
+        return _ratio(self.n_both, self.n_both + self.n_only_b)
+
+    @property
+    def weighted_jaccard(self) -> float:
+        return _ratio(self.sum_min, self.sum_max)
+
+    @property
+    def bray_curtis(self) -> float:
+        """the Bray-Curtis dissimilarity 1 - 2 sum_min / (sum_a + sum_b)"""
+        return 1.0 - 2.0 * self.sum_min / (self.sum_a + self.sum_b) if self.sum_a + self.sum_b else 0.0
 
 
 def _on_ctx_stream(fn):
@@ -232,6 +276,85 @@ class Context:
                                            _ptr(kmers_b) if nb else None, _ptr(counts_b) if nb else None, nb, _ptr(kmers), _ptr(counts),
                                            int(max_out), C.byref(n)))
         return kmers[:2 * n.value].view(-1, 2), counts[:n.value]
+
+    # ------------------------------------------------------------ set algebra and comparison of two count tables
+    def _setop(self, fn, words, op, kmers_a, counts_a, kmers_b, counts_b, rule, max_out):
+        na, nb = int(kmers_a.numel()) // words, int(kmers_b.numel()) // words
+        kmers_a, kmers_b = kmers_a.contiguous(), kmers_b.contiguous()
+        if max_out is None:
+            max_out = min(na, nb) if op == SETOP_INTERSECT else na if op in (SETOP_SUBTRACT, SETOP_COUNTER_SUBTRACT) else na + nb
+        ok = self.empty(words * max(max_out, 1), torch.int64)
+        oc = self.empty(max(max_out, 1), torch.int64)
+        n = C.c_uint64(0)
+        self._ck(fn(self._h, int(op), int(rule), _ptr(kmers_a) if na else None, _ptr(counts_a) if counts_a is not None and na else None, na,
+                    _ptr(kmers_b) if nb else None, _ptr(counts_b) if counts_b is not None and nb else None, nb, _ptr(ok), _ptr(oc), int(max_out),
+                    C.byref(n)))
+        ok = ok[:words * n.value]
+        return (ok.view(-1, 2) if words == 2 else ok), oc[:n.value]
+
+    @_on_ctx_stream
+    def count_setop(self, op, kmers_a, counts_a, kmers_b, counts_b, rule=RULE_SUM, max_out=None):
+        """kmx_count_setop -> (kmers, counts): SETOP_INTERSECT / UNION / SUBTRACT / SYMDIFF / COUNTER_SUBTRACT of two count tables, a
+        table again.  `rule` (RULE_SUM / MIN / MAX / LEFT / RIGHT) is the count of a key both tables hold, for INTERSECT and UNION;
+        the other operations take none (0).  A count tensor the operation never reads may be None (counts_b for SUBTRACT and
+        INTERSECT / LEFT, counts_a for INTERSECT / RIGHT).  Without `max_out` the outputs are sized to the operation's own bound."""
+        return self._setop(self.lib.kmx_count_setop, 1, op, kmers_a, counts_a, kmers_b, counts_b, rule, max_out)
+
+    @_on_ctx_stream
+    def count_setop2(self, op, kmers_a, counts_a, kmers_b, counts_b, rule=RULE_SUM, max_out=None):
+        """kmx_count_setop2 (k 33..64): kmers int64[n, 2] = (low, high) words -> (kmers int64[n_out, 2], counts)."""
+        return self._setop(self.lib.kmx_count_setop2, 2, op, kmers_a, counts_a, kmers_b, counts_b, rule, max_out)
+
+    def count_intersect(self, kmers_a, counts_a, kmers_b, counts_b, rule=RULE_SUM, max_out=None):
+        return self.count_setop(SETOP_INTERSECT, kmers_a, counts_a, kmers_b, counts_b, rule, max_out)
+
+    def count_intersect2(self, kmers_a, counts_a, kmers_b, counts_b, rule=RULE_SUM, max_out=None):
+        return self.count_setop2(SETOP_INTERSECT, kmers_a, counts_a, kmers_b, counts_b, rule, max_out)
+
+    def count_union(self, kmers_a, counts_a, kmers_b, counts_b, rule=RULE_SUM, max_out=None):
+        return self.count_setop(SETOP_UNION, kmers_a, counts_a, kmers_b, counts_b, rule, max_out)
+
+    def count_union2(self, kmers_a, counts_a, kmers_b, counts_b, rule=RULE_SUM, max_out=None):
+        return self.count_setop2(SETOP_UNION, kmers_a, counts_a, kmers_b, counts_b, rule, max_out)
+
+    def count_subtract(self, kmers_a, counts_a, kmers_b, counts_b=None, max_out=None):
+        """the entries of a whose key b does not hold (counts_b is not read)"""
+        return self.count_setop(SETOP_SUBTRACT, kmers_a, counts_a, kmers_b, counts_b, 0, max_out)
+
+    def count_subtract2(self, kmers_a, counts_a, kmers_b, counts_b=None, max_out=None):
+        return self.count_setop2(SETOP_SUBTRACT, kmers_a, counts_a, kmers_b, counts_b, 0, max_out)
+
+    def count_symdiff(self, kmers_a, counts_a, kmers_b, counts_b, max_out=None):
+        return self.count_setop(SETOP_SYMDIFF, kmers_a, counts_a, kmers_b, counts_b, 0, max_out)
+
+    def count_symdiff2(self, kmers_a, counts_a, kmers_b, counts_b, max_out=None):
+        return self.count_setop2(SETOP_SYMDIFF, kmers_a, counts_a, kmers_b, counts_b, 0, max_out)
+
+    def count_counter_subtract(self, kmers_a, counts_a, kmers_b, counts_b, max_out=None):
+        """a's entries with b's counts taken off; a key is dropped where count_a <= count_b"""
+        return self.count_setop(SETOP_COUNTER_SUBTRACT, kmers_a, counts_a, kmers_b, counts_b, 0, max_out)
+
+    def count_counter_subtract2(self, kmers_a, counts_a, kmers_b, counts_b, max_out=None):
+        return self.count_setop2(SETOP_COUNTER_SUBTRACT, kmers_a, counts_a, kmers_b, counts_b, 0, max_out)
+
+    def _compare(self, fn, words, kmers_a, counts_a, kmers_b, counts_b):
+        na, nb = int(kmers_a.numel()) // words, int(kmers_b.numel()) // words
+        kmers_a, kmers_b = kmers_a.contiguous(), kmers_b.contiguous()
+        rec = TableCompare()
+        self._ck(fn(self._h, _ptr(kmers_a) if na else None, _ptr(counts_a) if counts_a is not None and na else None, na,
+                    _ptr(kmers_b) if nb else None, _ptr(counts_b) if counts_b is not None and nb else None, nb, C.byref(rec)))
+        return TableComparison(*[int(getattr(rec, f)) for f, _ in TableCompare._fields_])
+
+    @_on_ctx_stream
+    def count_compare(self, kmers_a, counts_a, kmers_b, counts_b):
+        """kmx_count_compare -> TableComparison: keys shared / only in a / only in b and the sums of counts behind Jaccard,
+        containment and weighted Jaccard.  Both count tensors None: the key sets alone (the sums are 0)."""
+        return self._compare(self.lib.kmx_count_compare, 1, kmers_a, counts_a, kmers_b, counts_b)
+
+    @_on_ctx_stream
+    def count_compare2(self, kmers_a, counts_a, kmers_b, counts_b):
+        """kmx_count_compare2 (k 33..64): kmers int64[n, 2]."""
+        return self._compare(self.lib.kmx_count_compare2, 2, kmers_a, counts_a, kmers_b, counts_b)
 
     # ------------------------------------------------------------ queries on a count table
     def _lookup(self, fn, words, kmers, counts, k, query, flags, out):

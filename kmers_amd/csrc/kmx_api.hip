@@ -1009,6 +1009,107 @@ int kmx_count_filter2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_
     return filter_impl(ctx, "kmx_count_filter2", 2u, d_kmers2, d_counts, n, min_count, max_count, d_kmers2_out, d_counts_out, max_out, h_n_out);
 }
 
+// ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
+// The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
+static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,
+                      void** area) {
+    if ((n_a && !d_kmers_a) || (n_b && !d_kmers_b) || n_a > (1ull << 40) || n_b > (1ull << 40)) return KMX_E_ARG;
+    if (words == 2u && (!aligned16(d_kmers_a) || !aligned16(d_kmers_b))) return KMX_E_ARG;
+    *area = nullptr;
+    if (n_a + n_b == 0) return KMX_OK;
+    const size_t bytes = kmx::count_setop_bytes(n_a + n_b);
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (bytes > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes, budget);
+        return KMX_E_NOMEM;
+    }
+    if (!(*area = big_scratch(ctx, bytes))) return KMX_E_NOMEM;
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    return KMX_OK;
+}
+
+static int setop_impl(kmx_ctx* ctx, const char* who, uint32_t words, uint32_t op, uint32_t rule, const uint64_t* d_kmers_a, const uint64_t* d_counts_a,
+                      uint64_t n_a, const uint64_t* d_kmers_b, const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers_out, uint64_t* d_counts_out,
+                      uint64_t max_out, uint64_t* h_n_out) {
+    if (!ctx || !h_n_out || ((d_kmers_out == nullptr) != (d_counts_out == nullptr))) return KMX_E_ARG;
+    if (op > KMX_SETOP_COUNTER_SUBTRACT || rule > KMX_RULE_RIGHT) return KMX_E_ARG;
+    const bool ruled = op == KMX_SETOP_INTERSECT || op == KMX_SETOP_UNION;
+    if (!ruled && rule != 0u) return KMX_E_ARG;
+    // the count arrays the operation reads
+    const bool reads_a = !(op == KMX_SETOP_INTERSECT && rule == KMX_RULE_RIGHT);
+    const bool reads_b = !(op == KMX_SETOP_SUBTRACT || (op == KMX_SETOP_INTERSECT && rule == KMX_RULE_LEFT));
+    if ((n_a && reads_a && !d_counts_a) || (n_b && reads_b && !d_counts_b)) return KMX_E_ARG;
+    if (words == 2u && !aligned16(d_kmers_out)) return KMX_E_ARG;
+    *h_n_out = 0;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = setop_area(ctx, who, words, d_kmers_a, n_a, d_kmers_b, n_b, &area)) return st;
+    if (!area) return KMX_OK;   // (both tables empty)
+    uint64_t n_out = 0;
+    KMX_HIP(ctx, kmx::launch_count_setop(words, op, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, ctx->h_pinned, &n_out, ctx->stream));
+    *h_n_out = n_out;
+    if (!d_kmers_out || n_out == 0) return KMX_OK;
+    if (n_out > max_out) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu k-mers in the result, room for %llu", who, (unsigned long long)n_out,
+                      (unsigned long long)max_out);
+        return KMX_E_NOMEM;
+    }
+    KMX_HIP(ctx, kmx::launch_count_setop_emit(words, op, rule, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, d_kmers_out, d_counts_out,
+                                              ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_setop(kmx_ctx* ctx, uint32_t op, uint32_t rule, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a,
+                    const uint64_t* d_kmers_b, const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers_out, uint64_t* d_counts_out, uint64_t max_out,
+                    uint64_t* h_n_out) {
+    return setop_impl(ctx, "kmx_count_setop", 1u, op, rule, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, d_kmers_out, d_counts_out, max_out,
+                      h_n_out);
+}
+
+int kmx_count_setop2(kmx_ctx* ctx, uint32_t op, uint32_t rule, const uint64_t* d_kmers2_a, const uint64_t* d_counts_a, uint64_t n_a,
+                     const uint64_t* d_kmers2_b, const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers2_out, uint64_t* d_counts_out,
+                     uint64_t max_out, uint64_t* h_n_out) {
+    return setop_impl(ctx, "kmx_count_setop2", 2u, op, rule, d_kmers2_a, d_counts_a, n_a, d_kmers2_b, d_counts_b, n_b, d_kmers2_out, d_counts_out,
+                      max_out, h_n_out);
+}
+
+static int compare_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a,
+                        const uint64_t* d_kmers_b, const uint64_t* d_counts_b, uint64_t n_b, void* h_out) {
+    if (!ctx || !h_out) return KMX_E_ARG;
+    // counts of both tables, or of neither (an empty table has none to give)
+    const bool with_counts = d_counts_a != nullptr || d_counts_b != nullptr;
+    if (with_counts && ((n_a && !d_counts_a) || (n_b && !d_counts_b))) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = setop_area(ctx, who, words, d_kmers_a, n_a, d_kmers_b, n_b, &area)) return st;
+    uint64_t rec[6] = {0, 0, 0, 0, 0, 0};   // n_both, sum_a, sum_b, sum_a_both, sum_b_both, sum_min
+    if (area)
+        KMX_HIP(ctx, kmx::launch_count_compare(words, d_kmers_a, with_counts ? d_counts_a : nullptr, n_a, d_kmers_b, with_counts ? d_counts_b : nullptr,
+                                               n_b, area, ctx->h_pinned, rec, ctx->stream));
+    kmx_table_compare* out = static_cast<kmx_table_compare*>(h_out);
+    out->n_both = rec[0];
+    out->n_only_a = n_a - rec[0];
+    out->n_only_b = n_b - rec[0];
+    out->sum_a = rec[1];
+    out->sum_b = rec[2];
+    out->sum_a_both = rec[3];
+    out->sum_b_both = rec[4];
+    out->sum_min = rec[5];
+    out->sum_max = rec[1] + rec[2] - rec[5];   // (per key max + min = count_a + count_b; all of it mod 2^64)
+    return KMX_OK;
+}
+
+int kmx_count_compare(kmx_ctx* ctx, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a, const uint64_t* d_kmers_b,
+                      const uint64_t* d_counts_b, uint64_t n_b, void* h_out) {
+    return compare_impl(ctx, "kmx_count_compare", 1u, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, h_out);
+}
+
+int kmx_count_compare2(kmx_ctx* ctx, const uint64_t* d_kmers2_a, const uint64_t* d_counts_a, uint64_t n_a, const uint64_t* d_kmers2_b,
+                       const uint64_t* d_counts_b, uint64_t n_b, void* h_out) {
+    return compare_impl(ctx, "kmx_count_compare2", 2u, d_kmers2_a, d_counts_a, n_a, d_kmers2_b, d_counts_b, n_b, h_out);
+}
+
 int kmx_canonical_reduce2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t with_hash, kmx_summary2* d_out) {
     if (!ctx || !reads_ok(reads) || !d_out) return KMX_E_ARG;
     if (k < 33 || k > 64) return KMX_E_K_RANGE;

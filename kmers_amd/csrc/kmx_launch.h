@@ -155,4 +155,12 @@ hipError_t launch_count_spectrum(const u64* counts, u64 n, u64 n_bins, u64* spec
 size_t count_filter_bytes(u64 n);
 hipError_t launch_count_filter_mark(const u64* counts, u64 n, u64 mn, u64 mx, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
 hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* counts, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
+// kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
+size_t count_setop_bytes(u64 n);
+hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
+                              unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+hipError_t launch_count_setop_emit(u32 words, u32 op, u32 rule, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb,
+                                   const void* area, u64* out_k, u64* out_c, hipStream_t st);
+hipError_t launch_count_compare(u32 words, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
+                                unsigned long long* h_pinned, u64* h_rec, hipStream_t st);
 }  // namespace kmx
