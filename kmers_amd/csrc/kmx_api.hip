@@ -662,15 +662,11 @@ static size_t count_plan_bytes(const kmx_reads* reads, uint32_t k, uint64_t n_ba
 
 static size_t a256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
-// What the one-word and the two-word counter differ in: the words of a key, the windows call that fills canon / flags, the
-// sort / emit of their kernel file.
+// What the one-word and the two-word counter differ in: the words of a key and the windows call that fills canon / flags.
 struct CountKind {
     const char* who;
     uint32_t words;
-    size_t (*area_bytes)(kmx::u64);
     int (*windows)(kmx_ctx*, const kmx_reads*, const uint64_t*, uint32_t, uint64_t*, uint64_t*, uint64_t*, uint8_t*);
-    hipError_t (*sort)(kmx::u64*, const uint8_t*, kmx::u64, kmx::u32, void*, unsigned long long*, kmx::u64*, kmx::u64*, bool*, hipStream_t);
-    hipError_t (*emit)(const kmx::u64*, kmx::u64, kmx::u64, void*, kmx::u64*, kmx::u64*, hipStream_t);
 };
 
 // The body of kmx_count_canonical / kmx_count_canonical2 behind their argument checks: sizing, cap, work buffer, window offsets,
@@ -698,7 +694,7 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
     const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
     const size_t wo_bytes = reads->d_offsets ? a256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
     const size_t canon_at = plan + wo_bytes, flags_at = canon_at + a256(8u * kind.words * n_bound), area_at = flags_at + a256(n_bound);
-    const size_t bytes = area_at + kind.area_bytes(n_bound);
+    const size_t bytes = area_at + kmx::count_area_bytes(kind.words, n_bound);
     const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
     if (bytes > budget) {
         std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", kind.who, bytes,
@@ -734,7 +730,7 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
     bool bad = false;
     // (the count area is laid out for the n_win windows there are, inside the bytes reserved for n_bound >= n_win)
     void* area = base + area_at;
-    KMX_HIP(ctx, kind.sort(canon, flags, n_win, k, area, ctx->h_pinned, &n_valid, &n_distinct, &bad, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_count_sort(kind.words, canon, flags, n_win, k, area, ctx->h_pinned, &n_valid, &n_distinct, &bad, ctx->stream));
     if (bad) {
         std::snprintf(msg, sizeof msg, "%s: partition arrays above their bounds", kind.who);
         return fail_hip(ctx, hipErrorUnknown, msg);
@@ -746,7 +742,7 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
                       (unsigned long long)max_distinct);
         return KMX_E_NOMEM;
     }
-    KMX_HIP(ctx, kind.emit(canon, n_win, n_valid, area, d_kmers, d_counts, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_count_emit(kind.words, canon, n_win, n_valid, area, d_kmers, d_counts, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
 }
@@ -755,7 +751,7 @@ int kmx_count_canonical(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64
                         uint64_t* h_n_distinct) {
     if (!ctx || !reads_ok(reads) || !h_n_distinct || ((d_kmers == nullptr) != (d_counts == nullptr))) return KMX_E_ARG;
     if (k < 1 || k > 31) return KMX_E_K_RANGE;
-    static const CountKind kind{"kmx_count_canonical", 1u, kmx::count_area_bytes, kmx_canonical_windows, kmx::launch_count_sort, kmx::launch_count_emit};
+    static const CountKind kind{"kmx_count_canonical", 1u, kmx_canonical_windows};
     return count_impl(ctx, reads, k, kind, d_kmers, d_counts, max_distinct, h_n_distinct);
 }
 
@@ -764,21 +760,11 @@ int kmx_count_canonical2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint6
                          uint64_t* h_n_distinct) {
     if (!ctx || !reads_ok(reads) || !h_n_distinct || ((d_kmers2 == nullptr) != (d_counts == nullptr)) || !aligned16(d_kmers2)) return KMX_E_ARG;
     if (k < 33 || k > 64) return KMX_E_K_RANGE;
-    static const CountKind kind{"kmx_count_canonical2", 2u, kmx::count2_area_bytes, kmx_canonical_windows2, kmx::launch_count2_sort,
-                                kmx::launch_count2_emit};
+    static const CountKind kind{"kmx_count_canonical2", 2u, kmx_canonical_windows2};
     return count_impl(ctx, reads, k, kind, d_kmers2, d_counts, max_distinct, h_n_distinct);
 }
 
-// What the two merges differ in: the working set and the kernels.
-struct MergeKind {
-    const char* who;
-    size_t (*bytes)(kmx::u64);
-    hipError_t (*merge)(const kmx::u64*, const kmx::u64*, kmx::u64, const kmx::u64*, const kmx::u64*, kmx::u64, void*, unsigned long long*, kmx::u64*,
-                        hipStream_t);
-    hipError_t (*emit)(kmx::u64, const void*, kmx::u64*, kmx::u64*, hipStream_t);
-};
-
-static int merge_impl(kmx_ctx* ctx, const MergeKind& kind, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a,
+static int merge_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a,
                       const uint64_t* d_kmers_b, const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers_out, uint64_t* d_counts_out,
                       uint64_t max_out, uint64_t* h_n_out) {
     if (!ctx || !h_n_out || ((d_kmers_out == nullptr) != (d_counts_out == nullptr))) return KMX_E_ARG;
@@ -788,10 +774,10 @@ static int merge_impl(kmx_ctx* ctx, const MergeKind& kind, const uint64_t* d_kme
     const uint64_t n = n_a + n_b;
     if (n == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    const size_t bytes = kind.bytes(n);
+    const size_t bytes = kmx::count_merge_bytes(words, n);
     const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
     if (bytes > budget) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", kind.who, bytes,
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes,
                       budget);
         return KMX_E_NOMEM;
     }
@@ -799,30 +785,28 @@ static int merge_impl(kmx_ctx* ctx, const MergeKind& kind, const uint64_t* d_kme
     if (!area) return KMX_E_NOMEM;
     ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
     uint64_t n_out = 0;
-    KMX_HIP(ctx, kind.merge(d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, ctx->h_pinned, &n_out, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_count_merge(words, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, ctx->h_pinned, &n_out, ctx->stream));
     *h_n_out = n_out;
     if (!d_kmers_out) return KMX_OK;
     if (n_out > max_out) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu distinct k-mers, room for %llu", kind.who, (unsigned long long)n_out,
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu distinct k-mers, room for %llu", who, (unsigned long long)n_out,
                       (unsigned long long)max_out);
         return KMX_E_NOMEM;
     }
-    KMX_HIP(ctx, kind.emit(n, area, d_kmers_out, d_counts_out, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_count_merge_emit(words, n, area, d_kmers_out, d_counts_out, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
 }
 
 int kmx_count_merge(kmx_ctx* ctx, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a, const uint64_t* d_kmers_b,
                     const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers_out, uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
-    static const MergeKind kind{"kmx_count_merge", kmx::count_merge_bytes, kmx::launch_count_merge, kmx::launch_count_merge_emit};
-    return merge_impl(ctx, kind, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, d_kmers_out, d_counts_out, max_out, h_n_out);
+    return merge_impl(ctx, "kmx_count_merge", 1u, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, d_kmers_out, d_counts_out, max_out, h_n_out);
 }
 
 int kmx_count_merge2(kmx_ctx* ctx, const uint64_t* d_kmers2_a, const uint64_t* d_counts_a, uint64_t n_a, const uint64_t* d_kmers2_b,
                      const uint64_t* d_counts_b, uint64_t n_b, uint64_t* d_kmers2_out, uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
     if (!aligned16(d_kmers2_a) || !aligned16(d_kmers2_b) || !aligned16(d_kmers2_out)) return KMX_E_ARG;
-    static const MergeKind kind{"kmx_count_merge2", kmx::count2_merge_bytes, kmx::launch_count2_merge, kmx::launch_count2_merge_emit};
-    return merge_impl(ctx, kind, d_kmers2_a, d_counts_a, n_a, d_kmers2_b, d_counts_b, n_b, d_kmers2_out, d_counts_out, max_out, h_n_out);
+    return merge_impl(ctx, "kmx_count_merge2", 2u, d_kmers2_a, d_counts_a, n_a, d_kmers2_b, d_counts_b, n_b, d_kmers2_out, d_counts_out, max_out, h_n_out);
 }
 
 // ---- queries on a count table (kmx_count_query.hip) ----

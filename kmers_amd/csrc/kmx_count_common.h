@@ -1,7 +1,8 @@
-// kmx_count_common.h -- what the exact counters share whatever the width of a key: kmx_count.hip (one-word keys, k <= 31) and
-// kmx_count2.hip (two-word keys, k = 33..64).  Block scans, the records a level leaves for the host and for the leaf kernels, the
+// kmx_count_common.h -- what the count family shares: kmx_count.hip (the counter and the merge, one source for one-word keys,
+// k <= 31, and two-word keys, k = 33..64), kmx_count_query.hip and kmx_count_setop.hip.  The key of W words (Key<W>: the one type
+// every kernel of the family is templated on), block scans, the records a level leaves for the host and for the leaf kernels, the
 // count of the marked bytes the compaction starts with.  Everything here has internal linkage (each translation unit compiles
-// its own copy, as it did when kmx_count.hip was the only user); the kernels that touch keys stay with their key type.
+// its own copy, as it did when kmx_count.hip was the only user).
 #pragma once
 #include "kmx_device.h"
 #include "kmx_launch.h"
@@ -16,6 +17,62 @@ constexpr u32 COL_SERIAL = 64;                // levels above 0: a column of at 
 constexpr u32 CHUNK = CT * 64;                // positions per block in the compaction passes
 constexpr u32 MCHUNK = CT * 16;               // positions per block in the merge's collapse passes
 constexpr u32 MERGE_IPT = 8;                  // merged items per thread
+
+// ---------------------------------------------------------------- a key of W words
+// One u64 for k <= 31; {lo, hi} for k = 33..64: one 16-byte element everywhere (the slot layout of kmx_canonical_windows2: a dwordx4
+// access per lane in global memory, a b128 element in LDS), ordered as the 2k-bit integer -- high word first, then low.  Arrays of
+// keys are passed as u64* (W words per key) and read and written through load / store.
+template <u32 W> struct Key;
+template <> struct Key<1> {
+    u64 lo;
+    __device__ __forceinline__ static Key load(const u64* a, u64 i) { return Key{a[i]}; }
+    __device__ __forceinline__ static void store(u64* a, u64 i, const Key& v) { a[i] = v.lo; }
+    __device__ __forceinline__ static void copy(u64* dst, u64 i, const u64* src, u64 j) { dst[i] = src[j]; }   // (element to element)
+    __device__ __forceinline__ static Key sentinel() { return Key{~0ull}; }   // above every key: pads a leaf's sort
+    // a run's count in the slot of the array that does not hold its key (read back as .lo)
+    __device__ __forceinline__ static Key count(u64 c) { return Key{c}; }
+    __device__ __forceinline__ bool less(const Key& o) const { return lo < o.lo; }
+    __device__ __forceinline__ bool equal(const Key& o) const { return lo == o.lo; }
+    __device__ __forceinline__ bool differs(const Key& o) const { return lo != o.lo; }
+    __device__ __forceinline__ bool greater(const Key& o) const { return lo > o.lo; }
+    // bits [sh, sh + 8) of the key at the bottom of the result (the caller masks): sh is uniform over the block
+    __device__ __forceinline__ u32 bits(u32 sh) const { return (u32)(lo >> sh); }
+    // the key with its lowest w bits (w <= 8) replaced by d
+    __device__ __forceinline__ Key with_low(u32 w, u32 d) const { return Key{((lo >> w) << w) | d}; }
+    // a bit at or above bit 2k: no key of a table has one (2k <= 62)
+    __device__ __forceinline__ bool outside(u32 k) const { return (lo >> (2u * k)) != 0u; }
+    // the top p bits of the 2k-bit key (0 < p <= 2k)
+    __device__ __forceinline__ u64 prefix(u32 k, u32 p) const { return lo >> (2u * k - p); }
+};
+template <> struct alignas(16) Key<2> {
+    u64 lo, hi;
+    __device__ __forceinline__ static Key load(const u64* a, u64 i) { return reinterpret_cast<const Key*>(a)[i]; }   // (one 16-byte load)
+    __device__ __forceinline__ static void store(u64* a, u64 i, const Key& v) { reinterpret_cast<Key*>(a)[i] = v; }
+    __device__ __forceinline__ static void copy(u64* dst, u64 i, const u64* src, u64 j) { reinterpret_cast<Key*>(dst)[i] = reinterpret_cast<const Key*>(src)[j]; }
+    __device__ __forceinline__ static Key sentinel() { return Key{~0ull, ~0ull}; }
+    __device__ __forceinline__ static Key count(u64 c) { return Key{c, 0u}; }
+    __device__ __forceinline__ bool less(const Key& o) const { return hi < o.hi || (hi == o.hi && lo < o.lo); }
+    // equal and differs are one question spelled twice, on purpose: `equal` is the compare the query and set-operation kernels were
+    // built with (high word first), `differs` the one the counter's kernels were built with (word-wise xor, or).  The compiler keeps
+    // the order of the two word compares it is given, so one spelling for both would change the instructions of one family.
+    __device__ __forceinline__ bool equal(const Key& o) const { return hi == o.hi && lo == o.lo; }
+    __device__ __forceinline__ bool differs(const Key& o) const { return ((lo ^ o.lo) | (hi ^ o.hi)) != 0; }
+    __device__ __forceinline__ bool greater(const Key& o) const { return o.less(*this); }
+    // (the field may straddle the two words: 2k mod 8 != 0)
+    __device__ __forceinline__ u32 bits(u32 sh) const {
+        if (sh >= 64u) return (u32)(hi >> (sh - 64u));
+        if (sh == 0u) return (u32)lo;
+        return (u32)((lo >> sh) | (hi << (64u - sh)));
+    }
+    __device__ __forceinline__ Key with_low(u32 w, u32 d) const { return Key{((lo >> w) << w) | d, hi}; }
+    __device__ __forceinline__ bool outside(u32 k) const { return k < 64u && (hi >> (2u * k - 64u)) != 0u; }   // (k >= 33)
+    // the field may straddle the word boundary: s = 2k - p bits lie below it, 36 <= s < 128
+    __device__ __forceinline__ u64 prefix(u32 k, u32 p) const {
+        const u32 s = 2u * k - p;
+        return s >= 64u ? hi >> (s - 64u) : (hi << (64u - s)) | (lo >> s);
+    }
+};
+static_assert(sizeof(Key<1>) == 8 && sizeof(Key<2>) == 16, "a key is one element of W words");
 
 struct Leaf {
     u64 start, n;

@@ -33,39 +33,9 @@ constexpr u32 DIR_MAX_BITS = 28; // at most 2^28 + 1 directory entries (1 GiB)
 constexpr u32 SPEC_LDS = 4096;   // spectrum bins held in LDS per block (16 KiB)
 constexpr u32 SPEC_IPT = 16;     // entries per thread and grid step of the spectrum
 
-// ---------------------------------------------------------------- keys of one or two words
-template <u32 W> struct KeyOf;
-template <> struct KeyOf<1> {
-    u64 lo;
-    __device__ __forceinline__ static KeyOf load(const u64* a, u64 i) { return KeyOf{a[i]}; }
-    __device__ __forceinline__ static void store(u64* a, u64 i, const KeyOf& v) { a[i] = v.lo; }
-    __device__ __forceinline__ bool less(const KeyOf& o) const { return lo < o.lo; }
-    __device__ __forceinline__ bool equal(const KeyOf& o) const { return lo == o.lo; }
-    // a bit at or above bit 2k: no key of a table has one (2k <= 62)
-    __device__ __forceinline__ bool outside(u32 k) const { return (lo >> (2u * k)) != 0u; }
-    // the top p bits of the 2k-bit key (0 < p <= 2k)
-    __device__ __forceinline__ u64 prefix(u32 k, u32 p) const { return lo >> (2u * k - p); }
-};
-template <> struct KeyOf<2> {
-    u64 lo, hi;
-    __device__ __forceinline__ static KeyOf load(const u64* a, u64 i) {
-        const ulonglong2 v = reinterpret_cast<const ulonglong2*>(a)[i];   // (one 16-byte load)
-        return KeyOf{v.x, v.y};
-    }
-    __device__ __forceinline__ static void store(u64* a, u64 i, const KeyOf& v) { reinterpret_cast<ulonglong2*>(a)[i] = make_ulonglong2(v.lo, v.hi); }
-    __device__ __forceinline__ bool less(const KeyOf& o) const { return hi < o.hi || (hi == o.hi && lo < o.lo); }
-    __device__ __forceinline__ bool equal(const KeyOf& o) const { return hi == o.hi && lo == o.lo; }
-    __device__ __forceinline__ bool outside(u32 k) const { return k < 64u && (hi >> (2u * k - 64u)) != 0u; }   // (k >= 33)
-    // the field may straddle the word boundary: s = 2k - p bits lie below it, 36 <= s < 128
-    __device__ __forceinline__ u64 prefix(u32 k, u32 p) const {
-        const u32 s = 2u * k - p;
-        return s >= 64u ? hi >> (s - 64u) : (hi << (64u - s)) | (lo >> s);
-    }
-};
-
 // the bin of a key; anything a table should not hold (a bit at or above 2k) lands in the last bin instead of outside the directory
 template <u32 W>
-__device__ __forceinline__ u64 bin_of(const KeyOf<W>& key, u32 k, u32 p) {
+__device__ __forceinline__ u64 bin_of(const Key<W>& key, u32 k, u32 p) {
     if (p == 0u) return 0u;
     const u64 last = (1ull << p) - 1ull;
     if (key.outside(k)) return last;
@@ -82,8 +52,8 @@ __global__ void __launch_bounds__(CT) dir_build_kernel(const u64* __restrict__ k
     const u32 lane = threadIdx.x & 63u;
     u64 from = 1u, to = 0u;   // this lane's entries: dir[from .. to] = i
     if (i <= n) {
-        to = i < n ? bin_of<W>(KeyOf<W>::load(keys, i), k, p) : (1ull << p);
-        from = i == 0u ? 0u : bin_of<W>(KeyOf<W>::load(keys, i - 1u), k, p) + 1u;
+        to = i < n ? bin_of<W>(Key<W>::load(keys, i), k, p) : (1ull << p);
+        from = i == 0u ? 0u : bin_of<W>(Key<W>::load(keys, i - 1u), k, p) + 1u;
     }
     unsigned long long todo = __ballot(from <= to);
     while (todo) {
@@ -101,16 +71,16 @@ template <u32 W, bool DIR>
 __global__ void __launch_bounds__(CT) lookup_kernel(const u64* __restrict__ keys, const u64* __restrict__ counts, u64 n, u32 k, u32 p,
                                                     const u32* __restrict__ dir, const u64* query, const uint8_t* __restrict__ qflags, u64 n_query,
                                                     u64* out) {
-    using Key = KeyOf<W>;
+    using K = Key<W>;
     const u64 base = (u64)blockIdx.x * (CT * QPL) + threadIdx.x;
-    Key q[QPL];
+    K q[QPL];
     u64 lo[QPL], hi[QPL];
     bool live[QPL];
 #pragma unroll
     for (u32 j = 0; j < QPL; ++j) {
         const u64 i = base + (u64)j * CT;
         live[j] = i < n_query;
-        q[j] = Key::load(query, live[j] ? i : 0u);
+        q[j] = K::load(query, live[j] ? i : 0u);
         if (live[j] && qflags != nullptr) live[j] = (qflags[i] & KMX_WIN_VALID) != 0u;
         if (q[j].outside(k)) live[j] = false;
     }
@@ -135,13 +105,13 @@ __global__ void __launch_bounds__(CT) lookup_kernel(const u64* __restrict__ keys
 #pragma unroll
         for (u32 j = 0; j < QPL; ++j) any |= hi[j] - lo[j] > LINE;
         if (!any) break;
-        Key m[QPL];
+        K m[QPL];
         u64 mid[QPL];
 #pragma unroll
         for (u32 j = 0; j < QPL; ++j) {
             mid[j] = lo[j] + ((hi[j] - lo[j]) >> 1);
             m[j] = q[j];
-            if (hi[j] - lo[j] > LINE) m[j] = Key::load(keys, mid[j]);
+            if (hi[j] - lo[j] > LINE) m[j] = K::load(keys, mid[j]);
         }
 #pragma unroll
         for (u32 j = 0; j < QPL; ++j) {
@@ -159,7 +129,7 @@ __global__ void __launch_bounds__(CT) lookup_kernel(const u64* __restrict__ keys
 #pragma unroll
         for (u32 s = 0; s < LINE; ++s) {
             const u64 i = lo[j] + s;
-            if (i < hi[j] && Key::load(keys, i).equal(q[j])) hit[j] = i;
+            if (i < hi[j] && K::load(keys, i).equal(q[j])) hit[j] = i;
         }
     }
 #pragma unroll
@@ -245,7 +215,7 @@ __global__ void __launch_bounds__(CT) filter_write_kernel(const uint8_t* __restr
         const unsigned long long m = __ballot(kp);
         if (kp) {
             const u64 r = o + (u64)__popcll(m & ((1ull << lane) - 1ull));
-            KeyOf<W>::store(out_k, r, KeyOf<W>::load(keys, i));
+            Key<W>::store(out_k, r, Key<W>::load(keys, i));
             out_c[r] = counts[i];
         }
         o += (u64)__popcll(m);

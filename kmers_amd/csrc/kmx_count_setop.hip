@@ -34,32 +34,12 @@ constexpr u32 SETOP_WALK = SETOP_IPT + 1;     // steps of a thread's walk
 constexpr u32 SETOP_NONE = 0xFFFFu;           // "no entry of this table" in a descriptor
 static_assert(SETOP_SLOTS < SETOP_NONE, "a tile's indices fit 16 bits");
 
-// ---------------------------------------------------------------- keys of one or two words
-template <u32 W> struct SKey;
-template <> struct SKey<1> {
-    u64 lo;
-    __device__ __forceinline__ static SKey load(const u64* a, u64 i) { return SKey{a[i]}; }
-    __device__ __forceinline__ static void store(u64* a, u64 i, const SKey& v) { a[i] = v.lo; }
-    __device__ __forceinline__ bool less(const SKey& o) const { return lo < o.lo; }
-    __device__ __forceinline__ bool equal(const SKey& o) const { return lo == o.lo; }
-};
-template <> struct alignas(16) SKey<2> {
-    u64 lo, hi;
-    __device__ __forceinline__ static SKey load(const u64* a, u64 i) {
-        const ulonglong2 v = reinterpret_cast<const ulonglong2*>(a)[i];   // (one 16-byte load)
-        return SKey{v.x, v.y};
-    }
-    __device__ __forceinline__ static void store(u64* a, u64 i, const SKey& v) { reinterpret_cast<ulonglong2*>(a)[i] = make_ulonglong2(v.lo, v.hi); }
-    __device__ __forceinline__ bool less(const SKey& o) const { return hi < o.hi || (hi == o.hi && lo < o.lo); }
-    __device__ __forceinline__ bool equal(const SKey& o) const { return hi == o.hi && lo == o.lo; }
-};
-
 // ---------------------------------------------------------------- the partition
 // split[2 m], split[2 m + 1] = how many entries of a / of b lie before cut m, m = 0 .. n_tiles
 template <u32 W>
 __global__ void __launch_bounds__(CT) setop_partition_kernel(const u64* __restrict__ ka, u64 na, const u64* __restrict__ kb, u64 nb, u64 n_tiles,
                                                              u64* __restrict__ split) {
-    using Key = SKey<W>;
+    using K = Key<W>;
     const u64 m = (u64)blockIdx.x * CT + threadIdx.x;
     if (m > n_tiles) return;
     const u64 n = na + nb;
@@ -68,11 +48,11 @@ __global__ void __launch_bounds__(CT) setop_partition_kernel(const u64* __restri
     u64 lo = d > nb ? d - nb : 0u, hi = d < na ? d : na;
     while (lo < hi) {
         const u64 mid = (lo + hi) >> 1;   // (lo <= mid < hi: d - nb <= mid <= d - 1, so 0 <= d - 1 - mid < nb)
-        if (!Key::load(kb, d - 1u - mid).less(Key::load(ka, mid))) lo = mid + 1u;   // a[mid] <= b[d - 1 - mid]
+        if (!K::load(kb, d - 1u - mid).less(K::load(ka, mid))) lo = mid + 1u;   // a[mid] <= b[d - 1 - mid]
         else hi = mid;
     }
     u64 i = lo, j = d - lo;
-    if (i > 0u && j < nb && Key::load(ka, i - 1u).equal(Key::load(kb, j))) ++j;   // the pair stays with a's entry
+    if (i > 0u && j < nb && K::load(ka, i - 1u).equal(K::load(kb, j))) ++j;   // the pair stays with a's entry
     split[2u * m] = i;
     split[2u * m + 1u] = j;
 }
@@ -97,13 +77,13 @@ __device__ __forceinline__ TileRange tile_range(const u64* __restrict__ split, u
 // keys[0 .. na) = a's range, keys[na .. na + nb) = b's; cnt likewise where the walk decides by counts (a NULL count array reads as 0)
 template <u32 W, bool CNT>
 __device__ __forceinline__ void tile_load(const TileRange& r, const u64* __restrict__ ka, const u64* __restrict__ ca, const u64* __restrict__ kb,
-                                          const u64* __restrict__ cb, SKey<W>* keys, u64* cnt) {
+                                          const u64* __restrict__ cb, Key<W>* keys, u64* cnt) {
     for (u32 s = threadIdx.x; s < r.na; s += CT) {
-        keys[s] = SKey<W>::load(ka, r.a0 + s);
+        keys[s] = Key<W>::load(ka, r.a0 + s);
         if (CNT) cnt[s] = ca != nullptr ? ca[r.a0 + s] : 0u;
     }
     for (u32 s = threadIdx.x; s < r.nb; s += CT) {
-        keys[r.na + s] = SKey<W>::load(kb, r.b0 + s);
+        keys[r.na + s] = Key<W>::load(kb, r.b0 + s);
         if (CNT) cnt[r.na + s] = cb != nullptr ? cb[r.b0 + s] : 0u;
     }
     __syncthreads();
@@ -112,7 +92,7 @@ __device__ __forceinline__ void tile_load(const TileRange& r, const u64* __restr
 // Every thread's split at its diagonal threadIdx.x * SETOP_IPT of the tile (the partition's search and step, in LDS), left in
 // splits[0 .. CT] as i | j << 16 with splits[CT] = the tile's end; returns with the splits visible to the block.
 template <u32 W>
-__device__ __forceinline__ void thread_splits(const SKey<W>* A, u32 na, const SKey<W>* B, u32 nb, u32* splits) {
+__device__ __forceinline__ void thread_splits(const Key<W>* A, u32 na, const Key<W>* B, u32 nb, u32* splits) {
     u32 d = threadIdx.x * SETOP_IPT;
     if (d > na + nb) d = na + nb;
     u32 lo = d > nb ? d - nb : 0u, hi = d < na ? d : na;
@@ -131,12 +111,12 @@ __device__ __forceinline__ void thread_splits(const SKey<W>* A, u32 na, const SK
 // One step of a thread's walk over [i, ie) of A and [j, je) of B: the next distinct key, ascending, as (*ai, *bj) = its index in A /
 // in B or SETOP_NONE; false when both ranges are used up.  A walk is at most SETOP_WALK steps (sorted tables need no more).
 template <u32 W>
-__device__ __forceinline__ bool walk_step(const SKey<W>* A, const SKey<W>* B, u32& i, u32 ie, u32& j, u32 je, u32* ai, u32* bj) {
+__device__ __forceinline__ bool walk_step(const Key<W>* A, const Key<W>* B, u32& i, u32 ie, u32& j, u32 je, u32* ai, u32* bj) {
     const bool ha = i < ie, hb = j < je;
     if (!ha && !hb) return false;
     bool ta = ha, tb = hb;
     if (ha && hb) {
-        const SKey<W> x = A[i], y = B[j];
+        const Key<W> x = A[i], y = B[j];
         ta = !y.less(x);   // a's key <= b's
         tb = !x.less(y);
     }
@@ -181,13 +161,13 @@ template <u32 W, u32 OP>
 __global__ void __launch_bounds__(CT) setop_count_kernel(const u64* __restrict__ ka, const u64* __restrict__ ca, const u64* __restrict__ kb,
                                                          const u64* __restrict__ cb, const u64* __restrict__ split, u64* __restrict__ partial) {
     constexpr bool CNT = OP == KMX_SETOP_COUNTER_SUBTRACT;
-    __shared__ SKey<W> keys[SETOP_SLOTS];
+    __shared__ Key<W> keys[SETOP_SLOTS];
     __shared__ u64 cnt[CNT ? SETOP_SLOTS : 1];
     __shared__ u32 splits[CT + 1];
     __shared__ u64 sh[CT / 64];
     const TileRange r = tile_range(split, blockIdx.x);
     tile_load<W, CNT>(r, ka, ca, kb, cb, keys, cnt);
-    const SKey<W>*A = keys, *B = keys + r.na;
+    const Key<W>*A = keys, *B = keys + r.na;
     thread_splits<W>(A, r.na, B, r.nb, splits);
     const u32 s0 = splits[threadIdx.x], s1 = splits[threadIdx.x + 1];
     const u32 ie = s1 & 0xFFFFu, je = s1 >> 16;
@@ -219,14 +199,14 @@ __global__ void __launch_bounds__(CT) setop_write_kernel(const u64* __restrict__
                                                          const u64* __restrict__ cb, const u64* __restrict__ split, const u64* __restrict__ partial,
                                                          u32 rule, u64* __restrict__ out_k, u64* __restrict__ out_c) {
     constexpr bool CNT = OP == KMX_SETOP_COUNTER_SUBTRACT;
-    __shared__ SKey<W> keys[SETOP_SLOTS];
+    __shared__ Key<W> keys[SETOP_SLOTS];
     __shared__ u64 cnt[CNT ? SETOP_SLOTS : 1];
     __shared__ u32 splits[CT + 1];
     __shared__ u32 desc[CT * SETOP_WALK];   // (what the walks of a block can emit at most, whatever the keys)
     __shared__ u64 sh[CT];
     const TileRange r = tile_range(split, blockIdx.x);
     tile_load<W, CNT>(r, ka, ca, kb, cb, keys, cnt);
-    const SKey<W>*A = keys, *B = keys + r.na;
+    const Key<W>*A = keys, *B = keys + r.na;
     thread_splits<W>(A, r.na, B, r.nb, splits);
     const u32 s0 = splits[threadIdx.x], s1 = splits[threadIdx.x + 1];
     const u32 ie = s1 & 0xFFFFu, je = s1 >> 16;
@@ -246,7 +226,7 @@ __global__ void __launch_bounds__(CT) setop_write_kernel(const u64* __restrict__
         if (a && b) v = CNT ? cnt[ai] - cnt[r.na + bj] : ruled(rule, ca, r.a0 + ai, cb, r.b0 + bj);
         else if (a) v = ca[r.a0 + ai];
         else v = cb[r.b0 + bj];
-        SKey<W>::store(out_k, base + s, a ? A[ai] : B[bj]);
+        Key<W>::store(out_k, base + s, a ? A[ai] : B[bj]);
         out_c[base + s] = v;
     }
 }
@@ -259,13 +239,13 @@ template <u32 W>
 __global__ void __launch_bounds__(CT) setop_compare_kernel(const u64* __restrict__ ka, const u64* __restrict__ ca, const u64* __restrict__ kb,
                                                            const u64* __restrict__ cb, const u64* __restrict__ split,
                                                            unsigned long long* __restrict__ rec) {
-    __shared__ SKey<W> keys[SETOP_SLOTS];
+    __shared__ Key<W> keys[SETOP_SLOTS];
     __shared__ u64 cnt[SETOP_SLOTS];
     __shared__ u32 splits[CT + 1];
     __shared__ u64 red[CT / 64][CMP_WORDS];
     const TileRange r = tile_range(split, blockIdx.x);
     tile_load<W, true>(r, ka, ca, kb, cb, keys, cnt);
-    const SKey<W>*A = keys, *B = keys + r.na;
+    const Key<W>*A = keys, *B = keys + r.na;
     thread_splits<W>(A, r.na, B, r.nb, splits);
     const u32 s0 = splits[threadIdx.x], s1 = splits[threadIdx.x + 1];
     u64 n_both = 0, sum_a = 0, sum_b = 0, sum_ab = 0, sum_bb = 0, sum_min = 0;

@@ -125,27 +125,18 @@ hipError_t launch_minimizers_reads_sip(const uint8_t* bases, const u64* offsets,
                                        u64 k0, u64 k1, u64* out_word, u32* out_pos, unsigned long long* first_bad, int n_cu, hipStream_t st);
 hipError_t launch_seqvec_minimizers_sip(const u64* words, u64 n_reads, u32 L, u32 k, u32 w, u64 k0, u64 k1, u64* out_word, u32* out_pos,
                                         int n_cu, hipStream_t st);
-// kmx_count.hip
-size_t count_area_bytes(u64 n_win);
+// kmx_count.hip: the counter and the merge (`words` u64 per key: 1 or 2; two-word keys low word first, their arrays 16-byte aligned)
+size_t count_area_bytes(u32 words, u64 n_win);
 size_t win_offsets_bytes(u64 n_reads);
 hipError_t launch_count_win_offsets(const u64* offsets, u64 n_reads, u32 k, void* area, u64** wo_out, unsigned long long* h_pinned,
                                     u64* h_total, hipStream_t st);
-hipError_t launch_count_sort(u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
+hipError_t launch_count_sort(u32 words, u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
                              u64* h_distinct, bool* bad, hipStream_t st);
-hipError_t launch_count_emit(const u64* canon, u64 n_win, u64 n_valid, void* area, u64* out_k, u64* out_c, hipStream_t st);
-size_t count_merge_bytes(u64 n);
-hipError_t launch_count_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
-                              u64* h_out, hipStream_t st);
-hipError_t launch_count_merge_emit(u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
-// kmx_count2.hip: the same for two-word keys (2 u64 per key, low word first, 16-byte aligned)
-size_t count2_area_bytes(u64 n_win);
-hipError_t launch_count2_sort(u64* canon2, const uint8_t* flags, u64 n_win, u32 k, void* area, unsigned long long* h_pinned, u64* h_valid,
-                              u64* h_distinct, bool* bad, hipStream_t st);
-hipError_t launch_count2_emit(const u64* canon2, u64 n_win, u64 n_valid, void* area, u64* out_k2, u64* out_c, hipStream_t st);
-size_t count2_merge_bytes(u64 n);
-hipError_t launch_count2_merge(const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area, unsigned long long* h_pinned,
-                               u64* h_out, hipStream_t st);
-hipError_t launch_count2_merge_emit(u64 n, const void* area, u64* out_k2, u64* out_c, hipStream_t st);
+hipError_t launch_count_emit(u32 words, const u64* canon, u64 n_win, u64 n_valid, void* area, u64* out_k, u64* out_c, hipStream_t st);
+size_t count_merge_bytes(u32 words, u64 n);
+hipError_t launch_count_merge(u32 words, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
+                              unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+hipError_t launch_count_merge_emit(u32 words, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
 // kmx_count_query.hip: lookup, spectrum and filter of a count table (`words` u64 per key: 1 or 2)
 size_t count_lookup_dir_bytes(u64 n, u32 k, u32* p_out);
 bool count_lookup_wants_dir(u64 n, u64 n_query, u32 words);

@@ -1,4 +1,4 @@
-"""Exact counting of two-word canonical k-mers, k = 33..64 (kmx_count_canonical2, kmx_count_merge2; kmx_count2.hip) on the GPU.
+"""Exact counting of two-word canonical k-mers, k = 33..64 (kmx_count_canonical2, kmx_count_merge2; kmx_count.hip) on the GPU.
 
 The table is pinned to the multiset kmx_canonical_windows2 yields, as the oracle states it: canonical_windows2 -> valid windows ->
 sorted as 2k-bit unsigned integers (high word first) -> run heads and lengths; bit-equal keys and counts, compared as uint64

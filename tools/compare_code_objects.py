@@ -1,11 +1,15 @@
 """dev tool: do two builds of the library hold the same device code?  For a refactor that must not change a kernel.
-    python tools/compare_code_objects.py OLD_OBJ_DIR NEW_OBJ_DIR [--map OLD=NEW ...]
+    python tools/compare_code_objects.py OLD_OBJ_DIR NEW_OBJ_DIR [--map OLD=NEW ...] [--pooled]
 
 Both directories are kmers_amd/csrc/_obj of a `python -m kmers_amd.build --force`.  For every object in both, the gfx950 code object
 is unbundled and disassembled; each function's instructions (addresses dropped, encodings kept; the pc-relative offset of a call resolved to its target) and each kernel's
 resource line (<src>.usage.txt) are compared by DEMANGLED name, after the --map substitutions (plain text, applied to the old
 names: a renamed type, e.g. --map 'kmx::SinkHist,=kmx::SinkHistTable<kmx::HashLex, false>,').  Prints one line per object and
 exits 1 if anything differs.
+
+--pooled: for a refactor that moves kernels between source files.  The functions and usage lines of ALL objects of a build are pooled
+and compared by demangled name alone; a name several objects define (an anonymous-namespace kernel of a shared header) counts as the
+set of its bodies.  Prints one line for the pool and one per name that differs.
 """
 from __future__ import annotations
 
@@ -90,15 +94,39 @@ def _mapped(d: dict, maps: list[tuple[str, str]]) -> dict:
     return out
 
 
+def _pool(d: str, tmp: str, maps: list[tuple[str, str]]) -> tuple[dict[str, set], dict[str, set]]:
+    """every object of a build: demangled name -> the set of its bodies, demangled name -> the set of its usage lines"""
+    funcs: dict[str, set] = {}
+    usage: dict[str, set] = {}
+    os.makedirs(tmp, exist_ok=True)
+    for f in sorted(os.listdir(d)):
+        if f.endswith(".o"):
+            for n, body in _mapped(_functions(os.path.join(d, f), tmp), maps).items():
+                funcs.setdefault(n, set()).add(tuple(body))
+            for n, u in _mapped(_usage(os.path.join(d, f[:-2] + ".usage.txt")), maps).items():
+                usage.setdefault(n, set()).add(u)
+    return funcs, usage
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--map", action="append", default=[], help="OLD=NEW text substitution on the old build's demangled names")
+    ap.add_argument("--pooled", action="store_true", help="compare by name over all objects of each build, not object by object")
     a = ap.parse_args()
     maps = [tuple(m.split("=", 1)) for m in a.map]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
+        if a.pooled:
+            (fo, uo), (fn, un) = _pool(a.old, os.path.join(tmp, "o"), maps), _pool(a.new, os.path.join(tmp, "n"), [])
+            diff = [n for n in sorted(set(fo) | set(fn)) if fo.get(n) != fn.get(n)]
+            udiff = [n for n in sorted(set(uo) | set(un)) if uo.get(n) != un.get(n)]
+            print(f"{'pooled':34s} {len(fn):4d} functions  {'DIFFERENT' if diff or udiff else 'same code'}")
+            for kind, names, old, new in (("code ", diff, fo, fn), ("usage", udiff, uo, un)):
+                for n in names:
+                    print(f"    {kind} {'missing in new' if n not in new else 'missing in old' if n not in old else 'differs'}: {n[:160]}")
+            return 1 if diff or udiff else 0
         for f in sorted(os.listdir(a.old)):
             if not f.endswith(".o") or not os.path.exists(os.path.join(a.new, f)):
                 continue
