@@ -483,6 +483,31 @@ pub fn count_lookup_reads2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u
     Ok(n_win)
 }
 
+/// Per-read abundance statistics of a uniform batch against a table (`kmx_count_read_stats`): `KMX_RS_WORDS` u64 per read in
+/// `d_stats` (row `r` at word `8 * r`; the words are `KMX_RS_N_VALID` .. `KMX_RS_SPAN`) -- the valid, present and solid
+/// (count >= `solid_min`) windows, min, max, sum and upper median of the counts, and the longest run of solid windows.  Every row is
+/// written.
+pub fn count_read_stats(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>, solid_min: u64,
+                        d_stats: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    table.check(1);
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(n_reads as u128 * 8 * KMX_RS_WORDS as u128 <= d_stats.len() as u128, "rows shorter than the batch's reads");
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_read_stats(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, solid_min,
+                                         d_stats.as_mut_ptr::<u64>()) })
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_read_stats2`).
+pub fn count_read_stats2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>, solid_min: u64,
+                         d_stats: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    table.check(2);
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(n_reads as u128 * 8 * KMX_RS_WORDS as u128 <= d_stats.len() as u128, "rows shorter than the batch's reads");
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_read_stats2(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, solid_min,
+                                          d_stats.as_mut_ptr::<u64>()) })
+}
+
 /// The abundance spectrum of a table's counts (`kmx_count_spectrum`): `n_bins` bins, bin c = how many entries have count c, the last
 /// bin everything at or above it.
 pub fn count_spectrum(ctx: &HipContext, d_counts: &DeviceBuf<'_>, n: u64, n_bins: usize) -> Result<Vec<u64>, KmxError> {

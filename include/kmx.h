@@ -314,6 +314,45 @@ int kmx_count_filter(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_co
 int kmx_count_filter2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, uint64_t min_count, uint64_t max_count,
                       uint64_t *d_kmers2_out, uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
 
+/* ---- per-read abundance statistics against a table ----
+ * One row of KMX_RS_WORDS u64 per read, row r at d_stats + KMX_RS_WORDS * r; the words of a row: */
+#define KMX_RS_WORDS 8u
+#define KMX_RS_N_VALID 0u   /* windows of the read the iterator yields (no byte outside ACGTacgt in the window) */
+#define KMX_RS_N_PRESENT 1u /* valid windows whose canonical k-mer is in the table (its count is not 0) */
+#define KMX_RS_N_SOLID 2u   /* valid windows with count >= solid_min */
+#define KMX_RS_MIN 3u       /* smallest count over the valid windows (an absent k-mer counts 0); 0 when there is no valid window */
+#define KMX_RS_MAX 4u       /* largest count over the valid windows; 0 when there is none */
+#define KMX_RS_SUM 5u       /* sum of the counts over the valid windows, wrapping mod 2^64 */
+#define KMX_RS_MEDIAN 6u    /* c[n_valid / 2] of the valid windows' counts sorted ascending as u64 (the upper median); 0 when n_valid == 0 */
+#define KMX_RS_SPAN 7u      /* the longest run of consecutive window positions that are all valid with count >= solid_min: low 32 bits =
+                             * the position of its first window in the read, high 32 bits = its length in windows; the earliest such run
+                             * on ties; 0 when there is none.  The bases to keep are [start, start + length + k - 1). */
+/* The count of a window is what kmx_count_lookup_reads answers for it: d_counts == NULL = membership (1 / 0); n == 0 = a valid empty
+ * table (N_VALID is counted, everything else is 0 -- except with solid_min == 0, where every valid window is solid, so N_SOLID and
+ * SPAN describe the valid windows: the longest stretch free of invalid bytes).  A table entry whose count is 0 reads as absent.  An
+ * invalid window breaks a run of SPAN and contributes to nothing else.  Compares are unsigned; exact for any count up to 2^64 - 1.
+ * Every input kmx_canonical_windows accepts is accepted, through its routes and with its synchronisation: uniform reads of any
+ * length and d_bases alignment; ragged reads with any bound -- NO window offsets are asked of the caller: they are made on the
+ * device, which costs one host round trip.  Uniform reads of at most 256 bases only enqueue work unless the work buffer grows.
+ * EVERY row is written: a read without a window (shorter than k, empty, uniform read_len < k, a ragged read of 2^31 bases or more,
+ * which the scans skip) gets eight zeros; only n_reads == 0 is a no-op.  Deterministic: repeated calls give identical bytes.
+ * k in [1,31], KMX_E_K_RANGE otherwise; NULL ctx / reads, n > 2^40, d_stats == NULL with n_reads > 0: KMX_E_ARG.
+ * Working set in the context's work buffer, each array rounded up to 256 bytes (a256), laid out before any kernel runs.  With
+ * windows = n_reads * (read_len - k + 1) for uniform reads and the batch's number of BASES for ragged ones:
+ *     a256(8 * windows) + a256(windows)                                                  the counts and the flags
+ *   + ragged reads:  a256(8 * (n_reads + 1)) + a256(8 * (ceil(n_reads / 4096) + 2))      the window offsets
+ *   + reads longer than 256 bases: the segment plan (24 bytes per segment of at most 257 - k windows; 16-byte aligned d_bases)
+ * and, behind that, the directory of kmx_count_lookup when it pays and fits (left out, never refused).  The canonical words are
+ * written into the counts array and looked up in place.  150 bp reads at k = 31: 1080 bytes per read here, 64 bytes per read out.
+ * Above the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM BEFORE any kernel runs, nothing written.  The call uses the work
+ * buffer (a following kmx_fastx_parse cannot reuse its chunk prefixes). */
+int kmx_count_read_stats(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n,
+                         uint64_t solid_min, uint64_t *d_stats);
+/* The same for two-word keys, k in [33,64] (d_kmers2 16-byte aligned, KMX_E_ARG otherwise): kmx_canonical_windows2 and its routes.
+ * Working set: as above + a256(16 * windows) for the canonical words. */
+int kmx_count_read_stats2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n,
+                          uint64_t solid_min, uint64_t *d_stats);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

@@ -27,6 +27,9 @@ RULE_SUM, RULE_MIN, RULE_MAX, RULE_LEFT, RULE_RIGHT = range(5)
 # merged entries per tile of kmx_count_setop(2) / kmx_count_compare(2) (kmx_count_setop.hip: SETOP_TILE): where the boundary tests
 # put their shared keys, and what the documented working set counts in
 SETOP_TILE = 2048
+# kmx_count_read_stats(2): the words of a read's row
+RS_N_VALID, RS_N_PRESENT, RS_N_SOLID, RS_MIN, RS_MAX, RS_SUM, RS_MEDIAN, RS_SPAN = range(8)
+RS_WORDS = 8
 
 
 class KmxError(RuntimeError):
@@ -111,6 +114,8 @@ SIGNATURES = {
     "kmx_count_lookup2": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_lookup_reads": (_int, [_vp, _RP, _vp, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_lookup_reads2": (_int, [_vp, _RP, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_read_stats": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _vp]),
+    "kmx_count_read_stats2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _vp]),
     "kmx_count_spectrum": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "kmx_count_filter": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_filter2": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, REDUCE_SUM_FW, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -40,6 +40,15 @@ def _ptr(t):
 def u64_numpy(t: torch.Tensor) -> np.ndarray:
     """int64 CUDA tensor holding u64 words -> numpy uint64 (host)."""
     return t.detach().cpu().numpy().view(np.uint64)
+
+
+def read_stats_span(stats: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """column RS_SPAN of count_read_stats' rows -> (first_base, end_base), int64 per read: the bases [first_base, end_base) of the
+    longest run of solid windows (a run of `len` windows from window `start` covers start .. start + len + k - 1); (0, 0) for a read
+    without a solid window.  Works on host and device tensors."""
+    word = stats.reshape(-1, RS_WORDS)[:, RS_SPAN]
+    start, length = word & 0xFFFFFFFF, (word >> 32) & 0xFFFFFFFF
+    return start, torch.where(length > 0, start + length + (int(k) - 1), torch.zeros_like(start))
 
 
 def _ratio(num: int, den: int) -> float:
@@ -406,6 +415,30 @@ class Context:
     def count_lookup_reads2(self, bases, n_reads, read_len, k, kmers, counts, offsets=None, win_offsets=None, out=None):
         """kmx_count_lookup_reads2 (k 33..64; kmers int64[n, 2]) -> int64[windows]."""
         return self._lookup_reads(self.lib.kmx_count_lookup_reads2, 2, bases, n_reads, read_len, k, kmers, counts, offsets, win_offsets, out)
+
+    def _read_stats(self, fn, words, bases, n_reads, read_len, k, kmers, counts, solid_min, offsets, out):
+        n = int(kmers.numel()) // words if kmers is not None else 0
+        if n:
+            kmers = kmers.contiguous()
+        if out is None:
+            out = self.empty(RS_WORDS * int(n_reads), torch.int64)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), k, _ptr(kmers) if n else None, _ptr(counts) if counts is not None and n else None, n,
+                    int(solid_min), _ptr(out) if out.numel() else None))
+        return out.view(-1, RS_WORDS)
+
+    @_on_ctx_stream
+    def count_read_stats(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, offsets=None, out=None):
+        """kmx_count_read_stats -> int64[n_reads, 8] (u64 words, columns _lib.RS_*): per read, over the counts its windows have in
+        the table (kmers, counts) -- valid / present / solid (count >= solid_min) windows, min, max, sum, upper median, and the
+        longest run of solid windows (column RS_SPAN: read_stats_span decodes it).  counts=None: membership (1 / 0).  Ragged reads
+        (`offsets`) need no window offsets.  `out` (int64, 8 * n_reads elements) is overwritten: every row is written."""
+        return self._read_stats(self.lib.kmx_count_read_stats, 1, bases, n_reads, read_len, k, kmers, counts, solid_min, offsets, out)
+
+    @_on_ctx_stream
+    def count_read_stats2(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, offsets=None, out=None):
+        """kmx_count_read_stats2 (k 33..64; kmers int64[n, 2]) -> int64[n_reads, 8]."""
+        return self._read_stats(self.lib.kmx_count_read_stats2, 2, bases, n_reads, read_len, k, kmers, counts, solid_min, offsets, out)
 
     @_on_ctx_stream
     def count_spectrum(self, counts, n_bins, out=None):

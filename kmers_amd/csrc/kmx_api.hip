@@ -866,6 +866,57 @@ int kmx_count_lookup2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_
     return lookup_impl(ctx, kQuery2, d_kmers2, d_counts, n, k, d_query2, d_query_flags, n_query, d_out);
 }
 
+// ---- the reads forms of the queries: kmx_count_lookup_reads(2) and kmx_count_read_stats(2) ----
+// The windows their arrays are sized for, as kmx_count_canonical counts them: exact for uniform reads (*n_bound = 0: no window), the
+// number of bases -- a bound, also in *n_bases -- for ragged ones.
+static int query_window_bound(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t* n_bound, uint64_t* n_bases) {
+    *n_bound = *n_bases = 0;
+    if (reads->d_offsets) {
+        uint64_t o_first = 0, o_last = 0;
+        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
+        if (o_last < o_first) return KMX_E_ARG;
+        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
+        *n_bases = *n_bound = o_last - o_first;
+        return KMX_OK;
+    }
+    if (reads->read_len < k) return KMX_OK;
+    const uint64_t w = reads->read_len - k + 1u;
+    if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
+    *n_bound = reads->n_reads * w;
+    return KMX_OK;
+}
+
+// Their work buffer: `reserved` bytes for the caller's arrays, refused above the cap, and room for the lookup's directory behind them
+// when it pays for n_query windows and fits (asked for with the rest, so the buffer does not move between the windows call and the
+// lookup; left out, never refused).
+static int query_scratch(kmx_ctx* ctx, const char* who, uint32_t words, size_t reserved, uint64_t n, uint32_t k, uint64_t n_query, char** base_out) {
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (reserved > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, reserved, budget);
+        return KMX_E_NOMEM;
+    }
+    uint32_t p = 0;
+    const size_t dir_bytes = n ? kmx::count_lookup_dir_bytes(n, k, &p) : 0;
+    const bool with_dir = dir_bytes != 0 && kmx::count_lookup_wants_dir(n, n_query, words) && reserved + dir_bytes <= budget;
+    char* base = static_cast<char*>(big_scratch(ctx, reserved + (with_dir ? dir_bytes : 0)));
+    if (!base && with_dir) base = static_cast<char*>(big_scratch(ctx, reserved));
+    if (!base) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: no memory for %zu bytes of working set", who, reserved);
+        return KMX_E_NOMEM;
+    }
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    *base_out = base;
+    return KMX_OK;
+}
+
+// (the windows call took a route that grew the work buffer under the arrays laid out in it: a bug, never expected)
+static int query_scratch_kept(kmx_ctx* ctx, const char* who, const char* base, unsigned long long allocs) {
+    if (ctx->d_big == base && ctx->big_allocs == allocs) return KMX_OK;
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "%s: work buffer moved", who);
+    return fail_hip(ctx, hipErrorUnknown, msg);
+}
+
 // kmx_count_lookup_reads(2) = kmx_canonical_windows(2) followed by the lookup kernel.  The work buffer is laid out up front, as
 // count_impl lays its arrays out: [segment plan of long reads][two-word keys: canon 16 B/window][flags 1 B/window][directory, when
 // it pays and fits].  One-word keys: the windows call writes its canonical words into d_out and they are looked up in place.
@@ -877,24 +928,17 @@ static int lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_read
     if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
     if (reads->n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    // the windows the arrays are sized for (as kmx_count_canonical counts them: the number of bases for ragged reads) and the
-    // windows there are
+    // the windows the arrays are sized for and the windows there are
     uint64_t n_bound = 0, n_bases = 0, n_win = 0;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
     if (reads->d_offsets) {
-        uint64_t o_first = 0, o_last = 0;
-        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
-        if (o_last < o_first) return KMX_E_ARG;
-        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
-        n_bases = n_bound = o_last - o_first;
         KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         n_win = ctx->h_pinned[KMX_PIN_READ];
         if (n_win > n_bound) return KMX_E_ARG;   // (more windows than bases: not this batch's window offsets)
     } else {
-        if (reads->read_len < k) return KMX_OK;   // no window
-        const uint64_t w = reads->read_len - k + 1u;
-        if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
-        n_win = n_bound = reads->n_reads * w;
+        if (n_bound == 0) return KMX_OK;   // no window
+        n_win = n_bound;
         if (d_win_offsets) {   // (uniform reads in slots of the caller's: kmx_canonical_windows serves them, so they are served)
             KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
             KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -905,32 +949,15 @@ static int lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_read
     if (!d_out) return KMX_E_ARG;
     const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
     const size_t canon_at = plan, flags_at = canon_at + (kind.words == 2u ? a256(16u * n_bound) : 0u), reserved = flags_at + a256(n_bound);
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
-    if (reserved > budget) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s_reads: %zu bytes of working set above the work buffer's cap of %zu", kind.who,
-                      reserved, budget);
-        return KMX_E_NOMEM;
-    }
-    // (room for the directory is asked for with the rest, so the buffer does not move between the windows and the lookup)
-    uint32_t p = 0;
-    const size_t dir_bytes = n ? kmx::count_lookup_dir_bytes(n, k, &p) : 0;
-    const bool with_dir = dir_bytes != 0 && kmx::count_lookup_wants_dir(n, n_win, kind.words) && reserved + dir_bytes <= budget;
-    char* base = static_cast<char*>(big_scratch(ctx, reserved + (with_dir ? dir_bytes : 0)));
-    if (!base && with_dir) base = static_cast<char*>(big_scratch(ctx, reserved));
-    if (!base) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s_reads: no memory for %zu bytes of working set", kind.who, reserved);
-        return KMX_E_NOMEM;
-    }
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    char who[48];
+    std::snprintf(who, sizeof who, "%s_reads", kind.who);
+    char* base = nullptr;
+    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_win, &base)) return st;
     const unsigned long long allocs = ctx->big_allocs;
     uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : d_out;
     uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
     if (int st = kind.windows(ctx, reads, d_win_offsets, k, nullptr, nullptr, canon, flags)) return st;
-    if (ctx->d_big != base || ctx->big_allocs != allocs) {
-        char msg[96];
-        std::snprintf(msg, sizeof msg, "%s_reads: work buffer moved", kind.who);
-        return fail_hip(ctx, hipErrorUnknown, msg);
-    }
+    if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
     return lookup_run(ctx, kind, d_kmers, d_counts, n, k, canon, flags, n_win, d_out, reserved);
 }
 
@@ -942,6 +969,69 @@ int kmx_count_lookup_reads(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t*
 int kmx_count_lookup_reads2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint64_t* d_kmers2,
                             const uint64_t* d_counts, uint64_t n, uint64_t* d_out) {
     return lookup_reads_impl(ctx, kQuery2, reads, d_win_offsets, k, d_kmers2, d_counts, n, d_out);
+}
+
+// kmx_count_read_stats(2) = kmx_canonical_windows(2), the lookup kernel and the per-read reduction of kmx_count_read_stats.hip over its
+// answers.  The work buffer, laid out up front: [segment plan of long reads][ragged reads: window offsets][two-word keys: canon
+// 16 B/window][counts 8 B/window][flags 1 B/window][directory, when it pays and fits].  One-word keys: the windows call writes its
+// canonical words into the counts array and they are looked up in place.
+static int read_stats_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers,
+                           const uint64_t* d_counts, uint64_t n, uint64_t solid_min, uint64_t* d_stats) {
+    if (!ctx || !reads_ok(reads) || (n && !d_kmers) || n > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    if (reads->n_reads == 0) return KMX_OK;
+    if (!d_stats) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    const char* who = kind.words == 2u ? "kmx_count_read_stats2" : "kmx_count_read_stats";
+    const size_t stats_bytes = 8u * KMX_RS_WORDS * reads->n_reads;
+    uint64_t n_bound = 0, n_bases = 0;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
+    if (n_bound == 0) {   // no window in the batch: every row is eight zeros
+        KMX_HIP(ctx, hipMemsetAsync(d_stats, 0, stats_bytes, ctx->stream));
+        return KMX_OK;
+    }
+    const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
+    const size_t wo_bytes = reads->d_offsets ? a256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
+    const size_t canon_at = plan + wo_bytes, counts_at = canon_at + (kind.words == 2u ? a256(16u * n_bound) : 0u);
+    const size_t flags_at = counts_at + a256(8u * n_bound), reserved = flags_at + a256(n_bound);
+    char* base = nullptr;
+    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &base)) return st;
+    const unsigned long long allocs = ctx->big_allocs;
+    uint64_t n_win = n_bound;
+    uint64_t* wo = nullptr;
+    if (reads->d_offsets) {
+        KMX_HIP(ctx, kmx::launch_count_win_offsets(reads->d_offsets, reads->n_reads, k, base + plan, &wo, ctx->h_pinned, &n_win, ctx->stream));
+        if (n_win > n_bound) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "%s: window count above its bound", who);
+            return fail_hip(ctx, hipErrorUnknown, msg);
+        }
+        if (n_win == 0) {
+            KMX_HIP(ctx, hipMemsetAsync(d_stats, 0, stats_bytes, ctx->stream));
+            return KMX_OK;
+        }
+    }
+    uint64_t* counts = reinterpret_cast<uint64_t*>(base + counts_at);
+    uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : counts;
+    uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
+    if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
+    if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
+    if (int st = lookup_run(ctx, kind, d_kmers, d_counts, n, k, canon, flags, n_win, counts, reserved)) return st;
+    // uniform reads: the windows of a read; ragged reads: the most a read within the bound has (0 = no bound given)
+    const uint32_t w = reads->read_len >= k ? reads->read_len - k + 1u : 0u;
+    KMX_HIP(ctx, kmx::launch_count_read_stats(counts, flags, wo, reads->n_reads, w, solid_min, d_stats, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_read_stats(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n,
+                         uint64_t solid_min, uint64_t* d_stats) {
+    return read_stats_impl(ctx, kQuery1, reads, k, d_kmers, d_counts, n, solid_min, d_stats);
+}
+
+int kmx_count_read_stats2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n,
+                          uint64_t solid_min, uint64_t* d_stats) {
+    return read_stats_impl(ctx, kQuery2, reads, k, d_kmers2, d_counts, n, solid_min, d_stats);
 }
 
 int kmx_count_spectrum(kmx_ctx* ctx, const uint64_t* d_counts, uint64_t n, uint64_t n_bins, uint64_t* d_spectrum) {

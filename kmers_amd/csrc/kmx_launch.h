@@ -146,6 +146,10 @@ hipError_t launch_count_spectrum(const u64* counts, u64 n, u64 n_bins, u64* spec
 size_t count_filter_bytes(u64 n);
 hipError_t launch_count_filter_mark(const u64* counts, u64 n, u64 mn, u64 mx, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
 hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* counts, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st);
+// kmx_count_read_stats.hip: KMX_RS_WORDS u64 per read out of the counts / flags of its windows (win_offsets == nullptr: uniform reads of
+// W windows; ragged reads: W = the most windows a read is expected to have, 0 = unknown)
+hipError_t launch_count_read_stats(const u64* counts, const uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u64 solid_min, u64* stats,
+                                   int n_cu, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
