@@ -660,7 +660,30 @@ static size_t count_plan_bytes(const kmx_reads* reads, uint32_t k, uint64_t n_ba
     return kmx::segments_scratch_bytes(reads->n_reads, kmx::segments_capacity(reads->n_reads, n_bases, 257u - k), true);
 }
 
-static size_t a256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+// The work buffer of a count-family call, `bytes` of working set: refused above the cap (kmx_ctx_set_work_buffer_limit, or what
+// the device has to spare), grown if need be, and the call's to overwrite.
+static int work_area(kmx_ctx* ctx, const char* who, size_t bytes, void** area) {
+    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+    if (bytes > budget) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes,
+                      budget);
+        return KMX_E_NOMEM;
+    }
+    if (!(*area = big_scratch(ctx, bytes))) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: no memory for %zu bytes of working set", who, bytes);
+        return KMX_E_NOMEM;
+    }
+    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    return KMX_OK;
+}
+
+// A result of n_out entries (`what` they are, for the message) for arrays of max_out: KMX_E_NOMEM when it is larger than the room.
+static int room_for(kmx_ctx* ctx, const char* who, uint64_t n_out, const char* what, uint64_t max_out) {
+    if (n_out <= max_out) return KMX_OK;
+    std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu %s, room for %llu", who, (unsigned long long)n_out, what,
+                  (unsigned long long)max_out);
+    return KMX_E_NOMEM;
+}
 
 // What the one-word and the two-word counter differ in: the words of a key and the windows call that fills canon / flags.
 struct CountKind {
@@ -691,22 +714,13 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
         n_bound = reads->n_reads * w;
     }
     if (n_bound == 0) return KMX_OK;
-    const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
-    const size_t wo_bytes = reads->d_offsets ? a256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
-    const size_t canon_at = plan + wo_bytes, flags_at = canon_at + a256(8u * kind.words * n_bound), area_at = flags_at + a256(n_bound);
+    const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
+    const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
+    const size_t canon_at = plan + wo_bytes, flags_at = canon_at + align256(8u * kind.words * n_bound), area_at = flags_at + align256(n_bound);
     const size_t bytes = area_at + kmx::count_area_bytes(kind.words, n_bound);
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
-    if (bytes > budget) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", kind.who, bytes,
-                      budget);
-        return KMX_E_NOMEM;
-    }
-    char* base = static_cast<char*>(big_scratch(ctx, bytes));
-    if (!base) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: no memory for %zu bytes of working set", kind.who, bytes);
-        return KMX_E_NOMEM;
-    }
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    void* buf = nullptr;
+    if (int st = work_area(ctx, kind.who, bytes, &buf)) return st;
+    char* base = static_cast<char*>(buf);
     const unsigned long long allocs = ctx->big_allocs;
     char msg[96];
     uint64_t n_win = n_bound;
@@ -737,11 +751,7 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
     }
     *h_n_distinct = n_distinct;
     if (!d_kmers || n_distinct == 0) return KMX_OK;
-    if (n_distinct > max_distinct) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu distinct k-mers, room for %llu", kind.who, (unsigned long long)n_distinct,
-                      (unsigned long long)max_distinct);
-        return KMX_E_NOMEM;
-    }
+    if (int st = room_for(ctx, kind.who, n_distinct, "distinct k-mers", max_distinct)) return st;
     KMX_HIP(ctx, kmx::launch_count_emit(kind.words, canon, n_win, n_valid, area, d_kmers, d_counts, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
@@ -774,25 +784,13 @@ static int merge_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint6
     const uint64_t n = n_a + n_b;
     if (n == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    const size_t bytes = kmx::count_merge_bytes(words, n);
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
-    if (bytes > budget) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes,
-                      budget);
-        return KMX_E_NOMEM;
-    }
-    void* area = big_scratch(ctx, bytes);
-    if (!area) return KMX_E_NOMEM;
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::count_merge_bytes(words, n), &area)) return st;
     uint64_t n_out = 0;
     KMX_HIP(ctx, kmx::launch_count_merge(words, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, ctx->h_pinned, &n_out, ctx->stream));
     *h_n_out = n_out;
     if (!d_kmers_out) return KMX_OK;
-    if (n_out > max_out) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu distinct k-mers, room for %llu", who, (unsigned long long)n_out,
-                      (unsigned long long)max_out);
-        return KMX_E_NOMEM;
-    }
+    if (int st = room_for(ctx, who, n_out, "distinct k-mers", max_out)) return st;
     KMX_HIP(ctx, kmx::launch_count_merge_emit(words, n, area, d_kmers_out, d_counts_out, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
@@ -947,8 +945,8 @@ static int lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_read
     }
     if (n_win == 0) return KMX_OK;
     if (!d_out) return KMX_E_ARG;
-    const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
-    const size_t canon_at = plan, flags_at = canon_at + (kind.words == 2u ? a256(16u * n_bound) : 0u), reserved = flags_at + a256(n_bound);
+    const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
+    const size_t canon_at = plan, flags_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u), reserved = flags_at + align256(n_bound);
     char who[48];
     std::snprintf(who, sizeof who, "%s_reads", kind.who);
     char* base = nullptr;
@@ -991,10 +989,10 @@ static int read_stats_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads*
         KMX_HIP(ctx, hipMemsetAsync(d_stats, 0, stats_bytes, ctx->stream));
         return KMX_OK;
     }
-    const size_t plan = a256(count_plan_bytes(reads, k, n_bases));
-    const size_t wo_bytes = reads->d_offsets ? a256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
-    const size_t canon_at = plan + wo_bytes, counts_at = canon_at + (kind.words == 2u ? a256(16u * n_bound) : 0u);
-    const size_t flags_at = counts_at + a256(8u * n_bound), reserved = flags_at + a256(n_bound);
+    const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
+    const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
+    const size_t canon_at = plan + wo_bytes, counts_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u);
+    const size_t flags_at = counts_at + align256(8u * n_bound), reserved = flags_at + align256(n_bound);
     char* base = nullptr;
     if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &base)) return st;
     const unsigned long long allocs = ctx->big_allocs;
@@ -1050,24 +1048,13 @@ static int filter_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint
     *h_n_out = 0;
     if (n == 0 || min_count > max_count) return KMX_OK;
     DeviceGuard g(ctx->device);
-    const size_t bytes = kmx::count_filter_bytes(n);
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
-    if (bytes > budget) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes, budget);
-        return KMX_E_NOMEM;
-    }
-    void* area = big_scratch(ctx, bytes);
-    if (!area) return KMX_E_NOMEM;
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::count_filter_bytes(n), &area)) return st;
     uint64_t n_out = 0;
     KMX_HIP(ctx, kmx::launch_count_filter_mark(d_counts, n, min_count, max_count, area, ctx->h_pinned, &n_out, ctx->stream));
     *h_n_out = n_out;
     if (!d_kmers_out || n_out == 0) return KMX_OK;
-    if (n_out > max_out) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu entries kept, room for %llu", who, (unsigned long long)n_out,
-                      (unsigned long long)max_out);
-        return KMX_E_NOMEM;
-    }
+    if (int st = room_for(ctx, who, n_out, "entries kept", max_out)) return st;
     KMX_HIP(ctx, kmx::launch_count_filter_emit(words, d_kmers, d_counts, n, area, d_kmers_out, d_counts_out, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
@@ -1091,15 +1078,7 @@ static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint6
     if (words == 2u && (!aligned16(d_kmers_a) || !aligned16(d_kmers_b))) return KMX_E_ARG;
     *area = nullptr;
     if (n_a + n_b == 0) return KMX_OK;
-    const size_t bytes = kmx::count_setop_bytes(n_a + n_b);
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
-    if (bytes > budget) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes, budget);
-        return KMX_E_NOMEM;
-    }
-    if (!(*area = big_scratch(ctx, bytes))) return KMX_E_NOMEM;
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
-    return KMX_OK;
+    return work_area(ctx, who, kmx::count_setop_bytes(n_a + n_b), area);
 }
 
 static int setop_impl(kmx_ctx* ctx, const char* who, uint32_t words, uint32_t op, uint32_t rule, const uint64_t* d_kmers_a, const uint64_t* d_counts_a,
@@ -1123,11 +1102,7 @@ static int setop_impl(kmx_ctx* ctx, const char* who, uint32_t words, uint32_t op
     KMX_HIP(ctx, kmx::launch_count_setop(words, op, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, ctx->h_pinned, &n_out, ctx->stream));
     *h_n_out = n_out;
     if (!d_kmers_out || n_out == 0) return KMX_OK;
-    if (n_out > max_out) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu k-mers in the result, room for %llu", who, (unsigned long long)n_out,
-                      (unsigned long long)max_out);
-        return KMX_E_NOMEM;
-    }
+    if (int st = room_for(ctx, who, n_out, "k-mers in the result", max_out)) return st;
     KMX_HIP(ctx, kmx::launch_count_setop_emit(words, op, rule, d_kmers_a, d_counts_a, n_a, d_kmers_b, d_counts_b, n_b, area, d_kmers_out, d_counts_out,
                                               ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));

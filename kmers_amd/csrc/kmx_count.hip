@@ -23,8 +23,8 @@
 // run's key is written to `keys` and its count to the other array at the same index (Key<W>::count: the low word of the slot),
 // and a byte at that index is set in `keep`; the ranges of different partitions never overlap, so nothing is ordered across
 // blocks but by kernel boundaries.  The table is then the kept entries in index order -- ascending, because partitions are laid
-// out in digit order -- and is compacted by a block count, a scan, and a write (one more host round trip for the number of
-// distinct keys).  No block waits for another: cross-block results travel through kernel boundaries only.
+// out in digit order -- and is compacted by a block count, a scan, and a write (keep_count_kernel, scan_single_kernel and
+// compact_write_kernel of kmx_count_common.h, which the filter shares; one more host round trip for the number of distinct keys).  No block waits for another: cross-block results travel through kernel boundaries only.
 // What the width changes, beside the key itself:
 //   - a digit is bits [hi_bit - 8, hi_bit) of the whole key and, with two words, may straddle them (2k mod 8 != 0): Key<W>::bits;
 //   - how a partition learns that all its keys are equal: the per-width policy Same<W>;
@@ -488,35 +488,6 @@ __global__ void __launch_bounds__(CT) leaf_kernel(const Leaf* __restrict__ leave
     }
 }
 
-// ---------------------------------------------------------------- compaction of the kept entries
-// a wave per quarter of the block's positions, 64 at a time: the ballot of the kept bytes gives each lane its slot
-template <u32 W>
-__global__ void __launch_bounds__(CT) keep_write_kernel(const uint8_t* __restrict__ keep, const u64* __restrict__ partial, const u64* __restrict__ keys,
-                                                        const u64* __restrict__ counts, u64* __restrict__ out_k, u64* __restrict__ out_c) {
-    constexpr u32 PER_WAVE = CHUNK / (CT / 64u);
-    static_assert(PER_WAVE == 64u * 64u, "a wave's range is its lanes' 64-byte pieces");
-    __shared__ u32 wsum[CT / 64];
-    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const u64 w0 = (u64)blockIdx.x * CHUNK + (u64)wv * PER_WAVE;
-    u32 c = kept_in(keep, w0 + (u64)lane * 64u);
-    for (u32 o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if (lane == 0) wsum[wv] = c;
-    __syncthreads();
-    u64 o = partial[blockIdx.x];
-    for (u32 j = 0; j < wv; ++j) o += wsum[j];
-    for (u32 s0 = 0; s0 < PER_WAVE; s0 += 64u) {
-        const u64 i = w0 + s0 + lane;
-        const bool kp = keep[i] != 0;
-        const unsigned long long m = __ballot(kp);
-        if (kp) {
-            const u64 r = o + (u64)__popcll(m & ((1ull << lane) - 1ull));
-            Key<W>::store(out_k, r, Key<W>::load(keys, i));
-            out_c[r] = Key<W>::load(counts, i).lo;
-        }
-        o += (u64)__popcll(m);
-    }
-}
-
 // ---------------------------------------------------------------- merge of two tables
 // merge path: thread t writes outputs [8 t, 8 t + 8); on equal keys the item of `a` goes first
 // ka[i] <= kb[j].  Spelled per width, as each kernel was built: the compiler keeps the order of the loads and of the operands it
@@ -704,12 +675,11 @@ hipError_t count_sort(u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* 
                            src_is_keys ? 0u : 1u, a.keys, canon, a.keep, l0 ? 1u : 0u, a.tkeys);
         if (l0) hipLaunchKernelGGL((scatter_kernel<W, true>), dim3((unsigned)n_tiles), dim3(CT), 0, st, cur, a.tile_seg, src, flags, a.hist, a.coltot, dst);
         else hipLaunchKernelGGL((scatter_kernel<W, false>), dim3((unsigned)n_tiles), dim3(CT), 0, st, cur, a.tile_seg, src, flags, a.hist, a.coltot, dst);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(h_pinned, a.cnt, LEVEL_COUNTERS, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-        if (l0) *h_valid = h_pinned[0];
-        const u64 n_next = h_pinned[1], n_next_tiles = h_pinned[2], n_leaf = h_pinned[3], n_small = h_pinned[5], n_next_big = h_pinned[6];
-        if (h_pinned[4] != 0 || n_next > ms || n_leaf > ml || n_small > mls || n_next_tiles > mt || n_next_big > mb) {
+        u64 c[LEVEL_COUNTERS / 8u];   // (in the order of Counters)
+        if ((e = read_back(h_pinned, a.cnt, LEVEL_COUNTERS / 8u, c, st)) != hipSuccess) return e;
+        if (l0) *h_valid = c[0];
+        const u64 n_next = c[1], n_next_tiles = c[2], n_leaf = c[3], n_small = c[5], n_next_big = c[6];
+        if (c[4] != 0 || n_next > ms || n_leaf > ml || n_small > mls || n_next_tiles > mt || n_next_big > mb) {
             *bad = true;
             return hipSuccess;
         }
@@ -726,11 +696,7 @@ hipError_t count_sort(u64* canon, const uint8_t* flags, u64 n_win, u32 k, void* 
     if (nb == 0) return hipSuccess;
     hipLaunchKernelGGL(keep_count_kernel, dim3((unsigned)nb), dim3(CT), 0, st, a.keep, a.partial);
     hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, a.partial, nb, &a.cnt->n_distinct);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(h_pinned, &a.cnt->n_distinct, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    *h_distinct = h_pinned[0];
-    return hipSuccess;
+    return read_back(h_pinned, &a.cnt->n_distinct, 1u, h_distinct, st);
 }
 
 template <u32 W>
@@ -738,7 +704,7 @@ hipError_t count_emit(const u64* canon, u64 n_win, u64 n_valid, void* area, u64*
     CountArea<W> a;
     area_layout<W>(n_win, &a, area);
     const u64 nb = ceil_div(n_valid, CHUNK);
-    if (nb) hipLaunchKernelGGL(keep_write_kernel<W>, dim3((unsigned)nb), dim3(CT), 0, st, a.keep, a.partial, a.keys, canon, out_k, out_c);
+    if (nb) hipLaunchKernelGGL((compact_write_kernel<W, W>), dim3((unsigned)nb), dim3(CT), 0, st, a.keep, a.partial, a.keys, canon, out_k, out_c);
     return hipGetLastError();
 }
 
@@ -768,13 +734,8 @@ hipError_t launch_count_win_offsets(const u64* offsets, u64 n_reads, u32 k, void
     hipLaunchKernelGGL(win_count_kernel, dim3((unsigned)nb), dim3(CT), 0, st, offsets, n_reads, k, partial);
     hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial, nb, partial + nb);
     hipLaunchKernelGGL(win_fill_kernel, dim3((unsigned)nb), dim3(CT), 0, st, offsets, n_reads, k, partial, wo);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(h_pinned, wo + n_reads, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     *wo_out = wo;
-    *h_total = h_pinned[0];
-    return hipSuccess;
+    return read_back(h_pinned, wo + n_reads, 1u, h_total, st);
 }
 
 // Sort and tally the n_win windows (canon / flags) of a batch of k-mers; the table is left in `area` (keys in a.keys, counts
@@ -799,20 +760,12 @@ hipError_t launch_count_merge(u32 words, const u64* ka, const u64* ca, u64 na, c
     const u64 n = na + nb, nblk = ceil_div(n, MCHUNK);
     const MergeArea a = merge_layout(words, n, area);
     const dim3 gm((unsigned)ceil_div(n, (u64)CT * MERGE_IPT)), gh((unsigned)nblk), b(CT);
-    if (words == 1u) {
-        hipLaunchKernelGGL(merge_kernel<1>, gm, b, 0, st, ka, ca, na, kb, cb, nb, a.mk, a.mc);
-        hipLaunchKernelGGL(head_count_kernel<1>, gh, b, 0, st, (const u64*)a.mk, n, a.partial);
-    } else {
-        hipLaunchKernelGGL(merge_kernel<2>, gm, b, 0, st, ka, ca, na, kb, cb, nb, a.mk, a.mc);
-        hipLaunchKernelGGL(head_count_kernel<2>, gh, b, 0, st, (const u64*)a.mk, n, a.partial);
-    }
+    with_width(words, [&](auto w) {
+        hipLaunchKernelGGL(merge_kernel<decltype(w)::value>, gm, b, 0, st, ka, ca, na, kb, cb, nb, a.mk, a.mc);
+        hipLaunchKernelGGL(head_count_kernel<decltype(w)::value>, gh, b, 0, st, (const u64*)a.mk, n, a.partial);
+    });
     hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, a.partial, nblk, a.partial + nblk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(h_pinned, a.partial + nblk, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    *h_out = h_pinned[0];
-    return hipSuccess;
+    return read_back(h_pinned, a.partial + nblk, 1u, h_out, st);
 }
 
 hipError_t launch_count_merge_emit(u32 words, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st) {

@@ -1,9 +1,13 @@
 // kmx_count_common.h -- what the count family shares: kmx_count.hip (the counter and the merge, one source for one-word keys,
-// k <= 31, and two-word keys, k = 33..64), kmx_count_query.hip and kmx_count_setop.hip.  The key of W words (Key<W>: the one type
-// every kernel of the family is templated on), block scans, the records a level leaves for the host and for the leaf kernels, the
-// count of the marked bytes the compaction starts with.  Everything here has internal linkage (each translation unit compiles
-// its own copy, as it did when kmx_count.hip was the only user).
+// k <= 31, and two-word keys, k = 33..64), kmx_count_query.hip, kmx_count_setop.hip and kmx_count_read_stats.hip.  On the device: the
+// key of W words (Key<W>: the one type every kernel of the family is templated on), block scans and the block sum, the records a
+// level leaves for the host and for the leaf kernels, and the compaction of marked entries (the count of the marked bytes and the
+// wave-ballot copy, compact_write_kernel: the counter's and the filter's).  On the host: the launchers' tail that brings one record
+// back (read_back) and the dispatch on the key width (with_width).  Everything here has internal linkage (each translation unit
+// compiles its own copy, as it did when kmx_count.hip was the only user).
 #pragma once
+#include <type_traits>
+
 #include "kmx_device.h"
 #include "kmx_launch.h"
 
@@ -131,6 +135,25 @@ __device__ void block_scan_array(u64* a, u64 n, u64* sh, u64* total) {
     *total = carry;
 }
 
+// the shuffle sum the set-operation kernels were built with: the DPP wave_sum of kmx_device.h is not timed in them yet
+__device__ __forceinline__ u64 wave_sum_shfl(u64 v) {
+#pragma unroll
+    for (u32 o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// sum of one value per thread over the block, valid in thread 0; `sh` holds CT / 64 u64
+__device__ __forceinline__ u64 block_sum(u64 v, u64* sh) {
+    v = wave_sum_shfl(v);
+    if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 t = 0;
+    if (threadIdx.x == 0)
+        for (u32 w = 0; w < CT / 64u; ++w) t += sh[w];
+    __syncthreads();
+    return t;
+}
+
 __global__ void __launch_bounds__(CT) scan_single_kernel(u64* __restrict__ a, u64 n, u64* __restrict__ total) {
     __shared__ u64 sh[CT];
     u64 t;
@@ -157,7 +180,54 @@ __global__ void __launch_bounds__(CT) keep_count_kernel(const uint8_t* __restric
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+// The copy: a wave per quarter of the block's positions, 64 at a time: the ballot of the kept bytes gives each lane its slot.  A
+// count is the low word of a slot of CW words: the counter leaves a run's count in a key-sized slot (CW = W, Key<W>::count), a
+// table holds plain u64 (CW = 1, the filter).
+template <u32 W, u32 CW>
+__global__ void __launch_bounds__(CT) compact_write_kernel(const uint8_t* __restrict__ keep, const u64* __restrict__ partial,
+                                                           const u64* __restrict__ keys, const u64* __restrict__ counts, u64* __restrict__ out_k,
+                                                           u64* __restrict__ out_c) {
+    constexpr u32 PER_WAVE = CHUNK / (CT / 64u);
+    static_assert(PER_WAVE == 64u * 64u, "a wave's range is its lanes' 64-byte pieces");
+    __shared__ u32 wsum[CT / 64];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u64 w0 = (u64)blockIdx.x * CHUNK + (u64)wv * PER_WAVE;
+    u32 c = kept_in(keep, w0 + (u64)lane * 64u);
+    for (u32 o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) wsum[wv] = c;
+    __syncthreads();
+    u64 o = partial[blockIdx.x];
+    for (u32 j = 0; j < wv; ++j) o += wsum[j];
+    for (u32 s0 = 0; s0 < PER_WAVE; s0 += 64u) {
+        const u64 i = w0 + s0 + lane;
+        const bool kp = keep[i] != 0;
+        const unsigned long long m = __ballot(kp);
+        if (kp) {
+            const u64 r = o + (u64)__popcll(m & ((1ull << lane) - 1ull));
+            Key<W>::store(out_k, r, Key<W>::load(keys, i));
+            out_c[r] = Key<CW>::load(counts, i).lo;
+        }
+        o += (u64)__popcll(m);
+    }
+}
+
+// ---------------------------------------------------------------- host side
+// The tail of a launcher that needs one record on the host: the launches' error, then n_words u64 at d_src through the context's
+// pinned words into h_out.  Synchronous: one host round trip.
+hipError_t read_back(unsigned long long* h_pinned, const void* d_src, u32 n_words, u64* h_out, hipStream_t st) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(h_pinned, d_src, 8u * n_words, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    for (u32 q = 0; q < n_words; ++q) h_out[q] = h_pinned[q];
+    return hipSuccess;
+}
+
+// f(std::integral_constant<u32, words>{}), words = 1 or 2: the one place a launcher turns `words` into the W of its kernels
+template <typename F>
+auto with_width(u32 words, F&& f) {
+    return words == 1u ? f(std::integral_constant<u32, 1>{}) : f(std::integral_constant<u32, 2>{});
+}
 
 }  // namespace
 

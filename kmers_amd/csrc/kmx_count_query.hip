@@ -19,8 +19,8 @@
 // table, where small counts dominate -- straight to the output with device atomics; count == 1 (most rows of a real table) and the
 // last, collecting bin (most rows of a deep table with few bins) are tallied per thread and added once per wave.  The block's bins are added to the output with one device atomic per non-empty bin.
 //
-// Filter.  A mark byte per entry, then the counters' compaction: keep_count_kernel and the block scans of kmx_count_common.h, and
-// the wave-ballot copy of the marked entries (here for either key width).
+// Filter.  A mark byte per entry, then the counters' compaction, all of it in kmx_count_common.h: keep_count_kernel, the block
+// scans, and the wave-ballot copy of the marked entries (compact_write_kernel<W, 1>: a table's counts are plain u64).
 #include "kmx_count_common.h"
 
 namespace kmx {
@@ -194,34 +194,6 @@ __global__ void __launch_bounds__(CT) filter_mark_kernel(const u64* __restrict__
     keep[i] = in && c >= mn && c <= mx ? 1u : 0u;
 }
 
-// the counters' wave-ballot copy of the marked entries, for either key width
-template <u32 W>
-__global__ void __launch_bounds__(CT) filter_write_kernel(const uint8_t* __restrict__ keep, const u64* __restrict__ partial, const u64* __restrict__ keys,
-                                                          const u64* __restrict__ counts, u64* __restrict__ out_k, u64* __restrict__ out_c) {
-    constexpr u32 PER_WAVE = CHUNK / (CT / 64u);
-    static_assert(PER_WAVE == 64u * 64u, "a wave's range is its lanes' 64-byte pieces");
-    __shared__ u32 wsum[CT / 64];
-    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const u64 w0 = (u64)blockIdx.x * CHUNK + (u64)wv * PER_WAVE;
-    u32 c = kept_in(keep, w0 + (u64)lane * 64u);
-    for (u32 o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if (lane == 0) wsum[wv] = c;
-    __syncthreads();
-    u64 o = partial[blockIdx.x];
-    for (u32 j = 0; j < wv; ++j) o += wsum[j];
-    for (u32 s0 = 0; s0 < PER_WAVE; s0 += 64u) {
-        const u64 i = w0 + s0 + lane;
-        const bool kp = keep[i] != 0;
-        const unsigned long long m = __ballot(kp);
-        if (kp) {
-            const u64 r = o + (u64)__popcll(m & ((1ull << lane) - 1ull));
-            Key<W>::store(out_k, r, Key<W>::load(keys, i));
-            out_c[r] = counts[i];
-        }
-        o += (u64)__popcll(m);
-    }
-}
-
 u64 filter_pad(u64 n) { return ceil_div(n, CHUNK) * CHUNK; }
 
 }  // namespace
@@ -245,19 +217,13 @@ bool count_lookup_wants_dir(u64 n, u64 n_query, u32 words) { return n > LINE && 
 hipError_t launch_count_lookup(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, const u64* query, const uint8_t* qflags, u64 n_query,
                                u64* out, void* dir_area, u32 p, hipStream_t st) {
     u32* dir = static_cast<u32*>(dir_area);
-    if (dir) {
-        const unsigned nb = (unsigned)ceil_div(n + 1u, CT);
-        if (words == 1u) hipLaunchKernelGGL(dir_build_kernel<1>, dim3(nb), dim3(CT), 0, st, keys, n, k, p, dir);
-        else hipLaunchKernelGGL(dir_build_kernel<2>, dim3(nb), dim3(CT), 0, st, keys, n, k, p, dir);
-    }
-    const unsigned nq = (unsigned)ceil_div(n_query, (u64)CT * QPL);
-    if (words == 1u) {
-        if (dir) hipLaunchKernelGGL((lookup_kernel<1, true>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
-        else hipLaunchKernelGGL((lookup_kernel<1, false>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
-    } else {
-        if (dir) hipLaunchKernelGGL((lookup_kernel<2, true>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
-        else hipLaunchKernelGGL((lookup_kernel<2, false>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
-    }
+    const unsigned nb = (unsigned)ceil_div(n + 1u, CT), nq = (unsigned)ceil_div(n_query, (u64)CT * QPL);
+    with_width(words, [&](auto w) {
+        constexpr u32 W = decltype(w)::value;
+        if (dir) hipLaunchKernelGGL(dir_build_kernel<W>, dim3(nb), dim3(CT), 0, st, keys, n, k, p, dir);
+        if (dir) hipLaunchKernelGGL((lookup_kernel<W, true>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
+        else hipLaunchKernelGGL((lookup_kernel<W, false>), dim3(nq), dim3(CT), 0, st, keys, counts, n, k, p, dir, query, qflags, n_query, out);
+    });
     return hipGetLastError();
 }
 
@@ -280,20 +246,15 @@ hipError_t launch_count_filter_mark(const u64* counts, u64 n, u64 mn, u64 mx, vo
     hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)ceil_div(filter_pad(n), CT)), dim3(CT), 0, st, counts, n, filter_pad(n), mn, mx, keep);
     hipLaunchKernelGGL(keep_count_kernel, dim3((unsigned)nb), dim3(CT), 0, st, keep, partial);
     hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial, nb, partial + nb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(h_pinned, partial + nb, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    *h_out = h_pinned[0];
-    return hipSuccess;
+    return read_back(h_pinned, partial + nb, 1u, h_out, st);
 }
 
 hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* counts, u64 n, const void* area, u64* out_k, u64* out_c, hipStream_t st) {
     const uint8_t* keep = static_cast<const uint8_t*>(area);
     const u64* partial = reinterpret_cast<const u64*>(static_cast<const char*>(area) + align256(filter_pad(n)));
     const unsigned nb = (unsigned)ceil_div(n, CHUNK);
-    if (words == 1u) hipLaunchKernelGGL(filter_write_kernel<1>, dim3(nb), dim3(CT), 0, st, keep, partial, keys, counts, out_k, out_c);
-    else hipLaunchKernelGGL(filter_write_kernel<2>, dim3(nb), dim3(CT), 0, st, keep, partial, keys, counts, out_k, out_c);
+    if (words == 1u) hipLaunchKernelGGL((compact_write_kernel<1, 1>), dim3(nb), dim3(CT), 0, st, keep, partial, keys, counts, out_k, out_c);
+    else hipLaunchKernelGGL((compact_write_kernel<2, 1>), dim3(nb), dim3(CT), 0, st, keep, partial, keys, counts, out_k, out_c);
     return hipGetLastError();
 }
 

@@ -11,13 +11,14 @@
 //   entry, so 16-byte loads of one-word keys would need a peeled head; 16 bytes per lane for two-word keys), each thread finds the
 //   split of its own diagonal in LDS -- the same search and the same step along `b` -- and walks at most SETOP_IPT + 1 entries.
 //   Counts go to LDS as well only where the DECISION needs them (COUNTER_SUBTRACT, compare).
-// Count pass: the walk counts what the operation emits; per-tile totals, scan_single_kernel, the host reads n_out.
+// Count pass: the walk counts what the operation emits; per-tile totals (block_sum of kmx_count_common.h), scan_single_kernel,
+//   the host reads n_out.
 // Write pass: the walk again, leaving one 32-bit descriptor (index in a's range, index in b's range; 0xFFFF = none) per emitted
 //   entry at its scanned place in LDS; then the block writes the tile's output in order -- keys from LDS, counts gathered from the
 //   two count arrays at ascending indices, the rule applied -- so what leaves is whole lines of keys and counts.
-// Compare: the count pass with counts, six sums per thread folded per block and added to the record with six device atomics
-//   (integer adds: any order gives the same record).  The host derives the other three (n_only_* from n_a, n_b; sum_max from
-//   sum_a + sum_b - sum_min).
+// Compare: the count pass with counts, six sums per thread folded per block (wave_sum_shfl of kmx_count_common.h, then LDS) and
+//   added to the record with six device atomics (integer adds: any order gives the same record).  The host derives the other
+//   three (n_only_* from n_a, n_b; sum_max from sum_a + sum_b - sum_min).
 // Tables that are not sorted give wrong answers, never an access outside the arrays: every range is clamped to what LDS holds
 // before it is used, a walk is at most SETOP_IPT + 1 steps whatever the keys say, and both passes make the same decisions, so the
 // write pass stays inside the n_out the count pass reported.  No scratch, no pass waits on another block.
@@ -138,24 +139,6 @@ __device__ __forceinline__ bool emits(u32 ai, u32 bj, const u64* cnt, u32 na) {
     return a && (!b || cnt[ai] > cnt[na + bj]);   // KMX_SETOP_COUNTER_SUBTRACT
 }
 
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (u32 o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sum of one value per thread over the block, valid in thread 0; `sh` holds CT / 64 u64
-__device__ __forceinline__ u64 block_sum(u64 v, u64* sh) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 t = 0;
-    if (threadIdx.x == 0)
-        for (u32 w = 0; w < CT / 64u; ++w) t += sh[w];
-    __syncthreads();
-    return t;
-}
-
 // ---------------------------------------------------------------- the count pass
 template <u32 W, u32 OP>
 __global__ void __launch_bounds__(CT) setop_count_kernel(const u64* __restrict__ ka, const u64* __restrict__ ca, const u64* __restrict__ kb,
@@ -264,8 +247,8 @@ __global__ void __launch_bounds__(CT) setop_compare_kernel(const u64* __restrict
             sum_min += x < y ? x : y;
         }
     }
-    n_both = wave_sum(n_both), sum_a = wave_sum(sum_a), sum_b = wave_sum(sum_b);
-    sum_ab = wave_sum(sum_ab), sum_bb = wave_sum(sum_bb), sum_min = wave_sum(sum_min);
+    n_both = wave_sum_shfl(n_both), sum_a = wave_sum_shfl(sum_a), sum_b = wave_sum_shfl(sum_b);
+    sum_ab = wave_sum_shfl(sum_ab), sum_bb = wave_sum_shfl(sum_bb), sum_min = wave_sum_shfl(sum_min);
     if ((threadIdx.x & 63u) == 0u) {
         u64* w = red[threadIdx.x >> 6];
         w[0] = n_both, w[1] = sum_a, w[2] = sum_b, w[3] = sum_ab, w[4] = sum_bb, w[5] = sum_min;
@@ -282,38 +265,15 @@ __global__ void __launch_bounds__(CT) setop_compare_kernel(const u64* __restrict
 u64 setop_tiles(u64 n) { return ceil_div(n, SETOP_TILE); }
 size_t setop_split_bytes(u64 n) { return align256(16u * (setop_tiles(n) + 1u)); }
 
-template <u32 W>
-void count_pass(u32 op, const u64* ka, const u64* ca, const u64* kb, const u64* cb, const u64* split, u64* partial, unsigned nt, hipStream_t st) {
-    const dim3 g(nt), b(CT);
+// f(std::integral_constant<u32, op>{}): the one place `op` becomes the OP of the count and the write kernel
+template <typename F>
+void with_op(u32 op, F&& f) {
     switch (op) {
-        case KMX_SETOP_INTERSECT: hipLaunchKernelGGL((setop_count_kernel<W, KMX_SETOP_INTERSECT>), g, b, 0, st, ka, ca, kb, cb, split, partial); break;
-        case KMX_SETOP_UNION: hipLaunchKernelGGL((setop_count_kernel<W, KMX_SETOP_UNION>), g, b, 0, st, ka, ca, kb, cb, split, partial); break;
-        case KMX_SETOP_SUBTRACT: hipLaunchKernelGGL((setop_count_kernel<W, KMX_SETOP_SUBTRACT>), g, b, 0, st, ka, ca, kb, cb, split, partial); break;
-        case KMX_SETOP_SYMDIFF: hipLaunchKernelGGL((setop_count_kernel<W, KMX_SETOP_SYMDIFF>), g, b, 0, st, ka, ca, kb, cb, split, partial); break;
-        default: hipLaunchKernelGGL((setop_count_kernel<W, KMX_SETOP_COUNTER_SUBTRACT>), g, b, 0, st, ka, ca, kb, cb, split, partial); break;
-    }
-}
-
-template <u32 W>
-void write_pass(u32 op, const u64* ka, const u64* ca, const u64* kb, const u64* cb, const u64* split, const u64* partial, u32 rule, u64* out_k,
-                u64* out_c, unsigned nt, hipStream_t st) {
-    const dim3 g(nt), b(CT);
-    switch (op) {
-        case KMX_SETOP_INTERSECT:
-            hipLaunchKernelGGL((setop_write_kernel<W, KMX_SETOP_INTERSECT>), g, b, 0, st, ka, ca, kb, cb, split, partial, rule, out_k, out_c);
-            break;
-        case KMX_SETOP_UNION:
-            hipLaunchKernelGGL((setop_write_kernel<W, KMX_SETOP_UNION>), g, b, 0, st, ka, ca, kb, cb, split, partial, rule, out_k, out_c);
-            break;
-        case KMX_SETOP_SUBTRACT:
-            hipLaunchKernelGGL((setop_write_kernel<W, KMX_SETOP_SUBTRACT>), g, b, 0, st, ka, ca, kb, cb, split, partial, rule, out_k, out_c);
-            break;
-        case KMX_SETOP_SYMDIFF:
-            hipLaunchKernelGGL((setop_write_kernel<W, KMX_SETOP_SYMDIFF>), g, b, 0, st, ka, ca, kb, cb, split, partial, rule, out_k, out_c);
-            break;
-        default:
-            hipLaunchKernelGGL((setop_write_kernel<W, KMX_SETOP_COUNTER_SUBTRACT>), g, b, 0, st, ka, ca, kb, cb, split, partial, rule, out_k, out_c);
-            break;
+        case KMX_SETOP_INTERSECT: return f(std::integral_constant<u32, KMX_SETOP_INTERSECT>{});
+        case KMX_SETOP_UNION: return f(std::integral_constant<u32, KMX_SETOP_UNION>{});
+        case KMX_SETOP_SUBTRACT: return f(std::integral_constant<u32, KMX_SETOP_SUBTRACT>{});
+        case KMX_SETOP_SYMDIFF: return f(std::integral_constant<u32, KMX_SETOP_SYMDIFF>{});
+        default: return f(std::integral_constant<u32, KMX_SETOP_COUNTER_SUBTRACT>{});
     }
 }
 
@@ -335,20 +295,15 @@ hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u
     u64* split = static_cast<u64*>(area);
     u64* partial = reinterpret_cast<u64*>(static_cast<char*>(area) + setop_split_bytes(na + nb));
     const u64 nt = setop_tiles(na + nb);
-    if (words == 1u) {
-        partition<1>(ka, na, kb, nb, split, st);
-        count_pass<1>(op, ka, ca, kb, cb, split, partial, (unsigned)nt, st);
-    } else {
-        partition<2>(ka, na, kb, nb, split, st);
-        count_pass<2>(op, ka, ca, kb, cb, split, partial, (unsigned)nt, st);
-    }
+    with_width(words, [&](auto w) {
+        constexpr u32 W = decltype(w)::value;
+        partition<W>(ka, na, kb, nb, split, st);
+        with_op(op, [&](auto o) {
+            hipLaunchKernelGGL((setop_count_kernel<W, decltype(o)::value>), dim3((unsigned)nt), dim3(CT), 0, st, ka, ca, kb, cb, split, partial);
+        });
+    });
     hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial, nt, partial + nt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(h_pinned, partial + nt, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    *h_out = h_pinned[0];
-    return hipSuccess;
+    return read_back(h_pinned, partial + nt, 1u, h_out, st);
 }
 
 hipError_t launch_count_setop_emit(u32 words, u32 op, u32 rule, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb,
@@ -356,8 +311,12 @@ hipError_t launch_count_setop_emit(u32 words, u32 op, u32 rule, const u64* ka, c
     const u64* split = static_cast<const u64*>(area);
     const u64* partial = reinterpret_cast<const u64*>(static_cast<const char*>(area) + setop_split_bytes(na + nb));
     const unsigned nt = (unsigned)setop_tiles(na + nb);
-    if (words == 1u) write_pass<1>(op, ka, ca, kb, cb, split, partial, rule, out_k, out_c, nt, st);
-    else write_pass<2>(op, ka, ca, kb, cb, split, partial, rule, out_k, out_c, nt, st);
+    with_width(words, [&](auto w) {
+        with_op(op, [&](auto o) {
+            hipLaunchKernelGGL((setop_write_kernel<decltype(w)::value, decltype(o)::value>), dim3(nt), dim3(CT), 0, st, ka, ca, kb, cb, split, partial,
+                               rule, out_k, out_c);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -369,18 +328,11 @@ hipError_t launch_count_compare(u32 words, const u64* ka, const u64* ca, u64 na,
     const unsigned nt = (unsigned)setop_tiles(na + nb);
     hipError_t e = hipMemsetAsync(rec, 0, 8u * CMP_WORDS, st);
     if (e != hipSuccess) return e;
-    if (words == 1u) {
-        partition<1>(ka, na, kb, nb, split, st);
-        hipLaunchKernelGGL(setop_compare_kernel<1>, dim3(nt), dim3(CT), 0, st, ka, ca, kb, cb, split, rec);
-    } else {
-        partition<2>(ka, na, kb, nb, split, st);
-        hipLaunchKernelGGL(setop_compare_kernel<2>, dim3(nt), dim3(CT), 0, st, ka, ca, kb, cb, split, rec);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(h_pinned, rec, 8u * CMP_WORDS, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    for (u32 q = 0; q < CMP_WORDS; ++q) h_rec[q] = h_pinned[q];
-    return hipSuccess;
+    with_width(words, [&](auto w) {
+        partition<decltype(w)::value>(ka, na, kb, nb, split, st);
+        hipLaunchKernelGGL(setop_compare_kernel<decltype(w)::value>, dim3(nt), dim3(CT), 0, st, ka, ca, kb, cb, split, rec);
+    });
+    return read_back(h_pinned, rec, CMP_WORDS, h_rec, st);
 }
 
 }  // namespace kmx

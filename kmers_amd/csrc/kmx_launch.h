@@ -12,6 +12,8 @@
 namespace kmx {
 typedef uint32_t u32;
 typedef uint64_t u64;
+// every array of a work-buffer layout starts on a 256-byte boundary (the working-set formulas of kmx.h round with it)
+inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 // kmx_scan.hip
 hipError_t launch_scan_uniform(const uint8_t* bases, u64 n_reads, u32 L, u32 k, bool want_hash, bool want_sumfw,
                                kmx_summary* out, unsigned long long* queue, int n_cu, hipStream_t stream, bool* handled, const u64* offsets);

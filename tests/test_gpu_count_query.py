@@ -594,6 +594,43 @@ def test_filter_contract(ctx, k):
     assert (ok_[w * m:] == sentinel).all() and (oc[m:] == sentinel).all()
 
 
+# the compaction's boundaries: a ballot step (64 entries), a wave's range (4096) and a block's (16384), each minus one, exact, plus one
+COMPACT_SIZES = (1, 63, 64, 65, 4095, 4096, 4097, 16383, 16384, 16385, 2 * 16384 + 1)
+
+
+@pytest.mark.parametrize("w", (1, 2))
+def test_filter_compaction_boundaries(ctx, w):
+    """Synthetic tables (ascending keys; two-word keys differ in the low word only), counts chosen so that [1, 1] keeps every
+    entry, none, only the last, every other one from entry 1 on.  Expected: boolean indexing; the slack behind n_out stays poisoned."""
+    import torch
+
+    from kmers_amd import _lib
+    from kmers_amd.api import _ptr
+
+    fn = ctx.lib.kmx_count_filter if w == 1 else ctx.lib.kmx_count_filter2
+    sentinel = -0x5A5A5A5A5A5A5A5B
+    dev = lambda a: torch.from_numpy(a.view(np.int64).reshape(-1)).to(ctx.device)
+    for n in COMPACT_SIZES:
+        i = np.arange(n, dtype=np.uint64)
+        hk = (i + np.uint64(7)).reshape(n, 1)
+        if w == 2:
+            hk = np.concatenate([hk, np.full((n, 1), 0x1234, np.uint64)], axis=1)   # (low word first)
+        hk = np.ascontiguousarray(hk)
+        km = dev(hk)
+        other = np.uint64(2) + (i % np.uint64(3)) * np.uint64(2**40)               # never 1
+        last, odd = i == np.uint64(n - 1), (i & np.uint64(1)) == np.uint64(1)
+        for name, keep in (("all", np.ones(n, bool)), ("none", np.zeros(n, bool)), ("last", last), ("odd", odd)):
+            hc = np.where(keep, np.uint64(1), other)
+            m, cnt = int(keep.sum()), dev(hc)
+            ok_ = torch.full((w * (m + 8),), sentinel, dtype=torch.int64, device=ctx.device)
+            oc = torch.full((m + 8,), sentinel, dtype=torch.int64, device=ctx.device)
+            got = C.c_uint64(12345)
+            st = fn(ctx._h, _ptr(km), _ptr(cnt), n, 1, 1, _ptr(ok_), _ptr(oc), m + 8, C.byref(got))
+            assert (st, got.value) == (_lib.OK, m), (w, n, name)
+            assert (_u64(ok_[:w * m]).reshape(m, w) == hk[keep]).all() and (_u64(oc[:m]) == hc[keep]).all(), (w, n, name)
+            assert (ok_[w * m:] == sentinel).all() and (oc[m:] == sentinel).all(), (w, n, name)
+
+
 # ---------------------------------------------------------------- at a size the oracle cannot reach
 def _big_batches(ctx, n, L, k):
     import torch
