@@ -4,31 +4,18 @@ The table is pinned to the multiset CanonicalKmerIterator yields (canonical_kmer
 np.unique(canon[flags & 1], return_counts=True), bit-equal keys and counts -- for every k-mer width, uniform and ragged
 reads, odd base addresses, invalid bytes, FASTQ end to end, heavy hitters and layout edges.  At a size the oracle cannot
 reach, the table is checked against the composition of already-pinned calls (kmx_canonical_windows -> mask -> torch.unique)
-and against kmx_canonical_reduce's n_valid / sum_canon."""
+and against kmx_canonical_reduce's n_valid / sum_canon.  The read batches come from tests/count_np.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
+from tests.count_np import dirty, random_reads, u64
+
 pytestmark = pytest.mark.gpu
 
 KS = (1, 2, 5, 9, 12, 13, 21, 31)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from kmers_amd.api import Context
-
-    c = Context()
-    yield c
-    c.close()
-
-
-def _u64(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 def _expect(orc, host, n, L, k, offsets=None):
@@ -43,30 +30,18 @@ def _check(ctx, orc, host, n, L, k, offsets=None, shift=0):
     d_off = None if offsets is None else ctx.to_device(np.asarray(offsets, np.uint64))
     km, cnt = ctx.count_canonical(bases if len(host) else buf, n, L, k, offsets=d_off)
     ek, ec = _expect(orc, host, n, L, k, offsets)
-    gk, gc = _u64(km), _u64(cnt)
+    gk, gc = u64(km), u64(cnt)
     assert gk.shape == ek.shape, (k, L, n, shift, gk.shape, ek.shape)
     assert (gk == ek).all(), (k, L, n, shift)
     assert (gc == ec.astype(np.uint64)).all(), (k, L, n, shift)
     return gk, gc
 
 
-def _random_reads(rng, nbytes):
-    return rng.choice(np.frombuffer(b"ACGT", np.uint8), nbytes).astype(np.uint8)
-
-
-def _dirty(host, rng, share, n, L):
-    h = host.copy()
-    for r in np.nonzero(rng.random(n) < share)[0]:
-        p = int(rng.integers(0, L))
-        h[r * L + p] = ord("N") if r % 3 else ord(">")
-    return h
-
-
 @pytest.mark.parametrize("k", KS)
 def test_uniform_reads(ctx, orc, k):
     rng = np.random.default_rng(100 + k)
     for L, n in ((k, 5000), (150, 3000), (300, 700), (1000, 200)):
-        host = _random_reads(rng, n * L)
+        host = random_reads(rng, n * L)
         _check(ctx, orc, host, n, L, k)
         _check(ctx, orc, host, n, L, k, shift=1)   # odd d_bases
 
@@ -75,10 +50,10 @@ def test_uniform_reads(ctx, orc, k):
 def test_invalid_bytes_and_lower_case(ctx, orc, k):
     rng = np.random.default_rng(200 + k)
     for L, n in ((150, 4000), (300, 600)):
-        host = _random_reads(rng, n * L)
+        host = random_reads(rng, n * L)
         for share in (0.005, 0.10):
-            _check(ctx, orc, _dirty(host, rng, share, n, L), n, L, k)
-        h = _dirty(host, rng, 0.10, n, L)
+            _check(ctx, orc, dirty(host, rng, share, n, L), n, L, k)
+        h = dirty(host, rng, 0.10, n, L)
         h[7 * L:8 * L] = ord("N")                              # a read that is all N
         low = rng.random(n * L) < 0.3
         h[low & (h != ord("N")) & (h != ord(">"))] |= 0x20     # lower-case bases
@@ -96,7 +71,7 @@ def test_ragged_reads(ctx, orc, k, bound):
     lens[::17] = 0                             # empty reads
     lens[5::13] = max(k - 1, 0)                # reads shorter than k
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    host = _random_reads(rng, int(offsets[-1]))
+    host = random_reads(rng, int(offsets[-1]))
     bad = rng.random(len(host)) < 0.002
     host[bad] = ord("N")
     _check(ctx, orc, host, n, bound, k, offsets=offsets)
@@ -114,7 +89,7 @@ def test_fastq_end_to_end(ctx, orc, k):
         km, cnt = ctx.count_canonical(bases, n, 300, k, offsets=offsets)
         eb, eo = orc.fastx_parse(text)
         ek, ec = _expect(orc, np.asarray(eb, np.uint8), n, 300, k, np.asarray(eo, np.uint64))
-        assert (_u64(km) == ek).all() and (_u64(cnt) == ec.astype(np.uint64)).all()
+        assert (u64(km) == ek).all() and (u64(cnt) == ec.astype(np.uint64)).all()
 
 
 def test_all_a_is_one_kmer(ctx, orc):
@@ -128,7 +103,7 @@ def test_all_a_is_one_kmer(ctx, orc):
 def test_heavy_hitter_and_shared_top_digits(ctx, orc):
     rng = np.random.default_rng(5)
     n, L = 20000, 150
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     poly = rng.random(n) < 0.9                 # one k-mer ~90 % of the windows
     host.reshape(n, L)[poly] = ord("A")
     for k in (9, 21, 31):
@@ -136,7 +111,7 @@ def test_heavy_hitter_and_shared_top_digits(ctx, orc):
     # poly-A with sparse substitutions: many distinct keys that share their top digits -> partitions far above a block's LDS
     h = np.full(n * L, ord("A"), np.uint8)
     sub = rng.random(n * L) < 0.01
-    h[sub] = _random_reads(rng, int(sub.sum()))
+    h[sub] = random_reads(rng, int(sub.sum()))
     for k in (13, 21, 31):
         _check(ctx, orc, h, n, L, k)
 
@@ -152,7 +127,7 @@ def test_even_k_palindromes(ctx, orc):
 def test_big_random_batch_needs_every_level(ctx, orc):
     rng = np.random.default_rng(6)
     n, L = 40000, 150                           # 4.8e6 windows: level-0 partitions of ~19k keys, then leaves
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     for k in (12, 31):
         _check(ctx, orc, host, n, L, k)
 
@@ -195,7 +170,7 @@ def test_many_large_leaf_groups(ctx, orc):
 def test_deep_coverage_of_a_small_genome(ctx, orc):
     """1.5e5 reads of 150 bases from a 30 kb genome (~600x): children of one k-mer with hundreds of copies, many of them"""
     rng = np.random.default_rng(13)
-    g = _random_reads(rng, 30_000)
+    g = random_reads(rng, 30_000)
     n, L = 150_000, 150
     starts = rng.integers(0, len(g) - L + 1, n)
     host = g[starts[:, None] + np.arange(L)[None, :]].reshape(-1).copy()
@@ -237,7 +212,7 @@ def test_contract(ctx, orc):
 
     rng = np.random.default_rng(7)
     n, L, k = 3000, 150, 13
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     host[rng.random(n * L) < 0.001] = ord("N")
     bases = ctx.to_device(host)
     ek, ec = _expect(orc, host, n, L, k)
@@ -262,11 +237,11 @@ def test_contract(ctx, orc):
     # exactly the answer: written, and the slots behind it untouched
     st, got = _raw_count(ctx, bases, n, L, k, ok_, oc, nd)
     assert st == _lib.OK and got == nd
-    assert (_u64(ok_[:nd]) == ek).all() and (_u64(oc[:nd]) == ec.astype(np.uint64)).all()
+    assert (u64(ok_[:nd]) == ek).all() and (u64(oc[:nd]) == ec.astype(np.uint64)).all()
     assert (ok_[nd:] == sentinel).all()
     # two calls, identical tables
-    a = [_u64(t) for t in ctx.count_canonical(bases, n, L, k)]
-    b = [_u64(t) for t in ctx.count_canonical(bases, n, L, k)]
+    a = [u64(t) for t in ctx.count_canonical(bases, n, L, k)]
+    b = [u64(t) for t in ctx.count_canonical(bases, n, L, k)]
     assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
 
 
@@ -277,7 +252,7 @@ def test_work_buffer_cap(ctx, orc):
 
     rng = np.random.default_rng(8)
     n, L, k = 4000, 150, 31
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     bases = ctx.to_device(host)
     n_win = n * (L - k + 1)
     ok_ = torch.full((n_win,), -1, dtype=torch.int64, device=ctx.device)
@@ -295,7 +270,7 @@ def test_work_buffer_cap(ctx, orc):
         st, got = _raw_count(ctx, bases, n, L, k, ok_, oc, n_win)
         assert st == _lib.OK
         ek, ec = _expect(orc, host, n, L, k)
-        assert got == len(ek) and (_u64(ok_[:got]) == ek).all() and (_u64(oc[:got]) == ec.astype(np.uint64)).all()
+        assert got == len(ek) and (u64(ok_[:got]) == ek).all() and (u64(oc[:got]) == ec.astype(np.uint64)).all()
     finally:
         ctx.set_work_buffer_limit(0)
 
@@ -311,7 +286,7 @@ def _merge_check(ctx, orc, ha, hb, n, L, k):
     mk, mc = ctx.count_merge(ka, ca, kb, cb)
     both = np.concatenate([ha, hb])
     ek, ec = _table(orc, both, len(both) // L, L, k)
-    assert (_u64(mk) == ek).all() and (_u64(mc) == ec).all()
+    assert (u64(mk) == ek).all() and (u64(mc) == ec).all()
     return mk, mc, ka, ca, kb, cb
 
 
@@ -320,8 +295,8 @@ def test_merge(ctx, orc):
 
     rng = np.random.default_rng(9)
     n, L, k = 3000, 150, 21
-    a = _random_reads(rng, n * L)
-    b = _random_reads(rng, n * L)
+    a = random_reads(rng, n * L)
+    b = random_reads(rng, n * L)
     _merge_check(ctx, orc, a, b, n, L, k)                                  # (almost surely) disjoint
     _merge_check(ctx, orc, a, a.copy(), n, L, k)                           # identical
     _merge_check(ctx, orc, a, np.zeros(0, np.uint8), n, L, k)              # one empty

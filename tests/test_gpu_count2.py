@@ -6,31 +6,19 @@ sorted as 2k-bit unsigned integers (high word first) -> run heads and lengths; b
 alignment (2k mod 8 = 0, 2, 4, 6), uniform and ragged reads, odd base addresses, invalid bytes, FASTQ end to end, heavy hitters
 and long shared prefixes (levels past the word boundary), keys that differ in one word only, layout edges, the contract.  At a size
 the oracle cannot reach the table is checked against the composition of pinned calls on the device (kmx_canonical_windows2 ->
-mask -> two stable sorts) and against kmx_canonical_reduce2's n_valid and word sums."""
+mask -> two stable sorts) and against kmx_canonical_reduce2's n_valid and word sums.  The read batches come from
+tests/count_np.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
+from tests.count_np import dirty, random_reads, u64
+
 pytestmark = pytest.mark.gpu
 
 KS2 = (33, 34, 35, 40, 47, 48, 49, 56, 63, 64)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from kmers_amd.api import Context
-
-    c = Context()
-    yield c
-    c.close()
-
-
-def _u64(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 def _expect2(orc, host, n, L, k, offsets=None):
@@ -50,7 +38,7 @@ def _check(ctx, orc, host, n, L, k, offsets=None, shift=0, expect=None):
     d_off = None if offsets is None else ctx.to_device(np.asarray(offsets, np.uint64))
     km, cnt = ctx.count_canonical2(bases if len(host) else buf, n, L, k, offsets=d_off)
     ek, ec = expect if expect is not None else _expect2(orc, host, n, L, k, offsets)
-    gk, gc = _u64(km), _u64(cnt)
+    gk, gc = u64(km), u64(cnt)
     assert gk.shape == ek.shape, (k, L, n, shift, gk.shape, ek.shape)
     assert (gk == ek).all(), (k, L, n, shift)
     assert (gc == ec).all(), (k, L, n, shift)
@@ -64,23 +52,11 @@ def _check_shifts(ctx, orc, host, n, L, k, shifts, offsets=None):
     return out
 
 
-def _random_reads(rng, nbytes):
-    return rng.choice(np.frombuffer(b"ACGT", np.uint8), nbytes).astype(np.uint8)
-
-
-def _dirty(host, rng, share, n, L):
-    h = host.copy()
-    for r in np.nonzero(rng.random(n) < share)[0]:
-        p = int(rng.integers(0, L))
-        h[r * L + p] = ord("N") if r % 3 else ord(">")
-    return h
-
-
 @pytest.mark.parametrize("k", KS2)
 def test_uniform_reads(ctx, orc, k):
     rng = np.random.default_rng(1100 + k)
     for L, n in ((k, 5000), (150, 3000), (300, 700), (1000, 200)):
-        host = _random_reads(rng, n * L)
+        host = random_reads(rng, n * L)
         _check_shifts(ctx, orc, host, n, L, k, (0, 1))   # aligned and odd d_bases
 
 
@@ -88,10 +64,10 @@ def test_uniform_reads(ctx, orc, k):
 def test_invalid_bytes_and_lower_case(ctx, orc, k):
     rng = np.random.default_rng(1200 + k)
     for L, n in ((150, 4000), (300, 600)):
-        host = _random_reads(rng, n * L)
+        host = random_reads(rng, n * L)
         for share in (0.005, 0.10):
-            _check(ctx, orc, _dirty(host, rng, share, n, L), n, L, k)
-        h = _dirty(host, rng, 0.10, n, L)
+            _check(ctx, orc, dirty(host, rng, share, n, L), n, L, k)
+        h = dirty(host, rng, 0.10, n, L)
         h[7 * L:8 * L] = ord("N")                              # a read that is all N
         low = rng.random(n * L) < 0.3
         h[low & (h != ord("N")) & (h != ord(">"))] |= 0x20     # lower-case bases
@@ -108,7 +84,7 @@ def test_ragged_reads(ctx, orc, k, bound):
     lens[::17] = 0                             # empty reads
     lens[5::13] = k - 1                        # reads one base short of a window
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    host = _random_reads(rng, int(offsets[-1]))
+    host = random_reads(rng, int(offsets[-1]))
     bad = rng.random(len(host)) < 0.002
     host[bad] = ord("N")
     _check_shifts(ctx, orc, host, n, bound, k, (0, 5), offsets=offsets)   # (5: misaligned d_bases, the per-read kernels)
@@ -125,8 +101,8 @@ def test_fastq_end_to_end(ctx, orc, k):
         km, cnt = ctx.count_canonical2(bases, n, 300, k, offsets=offsets)
         eb, eo = orc.fastx_parse(text)
         ek, ec = _expect2(orc, np.asarray(eb, np.uint8), n, 300, k, np.asarray(eo, np.uint64))
-        assert _u64(km).shape == ek.shape
-        assert (_u64(km) == ek).all() and (_u64(cnt) == ec).all()
+        assert u64(km).shape == ek.shape
+        assert (u64(km) == ek).all() and (u64(cnt) == ec).all()
 
 
 @pytest.mark.parametrize("base", (b"A", b"T"))
@@ -142,7 +118,7 @@ def test_one_base_is_one_kmer(ctx, orc, base):
 def test_heavy_hitter_and_shared_top_digits(ctx, orc):
     rng = np.random.default_rng(15)
     n, L = 20000, 150
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     poly = rng.random(n) < 0.9                 # one k-mer ~90 % of the windows
     host.reshape(n, L)[poly] = ord("A")
     for k in (33, 47, 63):
@@ -151,7 +127,7 @@ def test_heavy_hitter_and_shared_top_digits(ctx, orc):
     # start leaves the whole high word zero) -> partitions that stay large through the levels past the word boundary
     h = np.full(n * L, ord("A"), np.uint8)
     sub = rng.random(n * L) < 0.01
-    h[sub] = _random_reads(rng, int(sub.sum()))
+    h[sub] = random_reads(rng, int(sub.sum()))
     for k in (33, 47, 63):
         _check(ctx, orc, h, n, L, k)
 
@@ -214,7 +190,7 @@ def test_even_k_palindromes(ctx, orc):
 def test_big_random_batch_needs_every_level(ctx, orc):
     rng = np.random.default_rng(16)
     n, L = 40000, 150                           # ~4e6 windows: level-0 partitions of ~16k keys, then leaves
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     for k in (33, 63):
         _check(ctx, orc, host, n, L, k)
 
@@ -222,7 +198,7 @@ def test_big_random_batch_needs_every_level(ctx, orc):
 def test_deep_coverage_of_a_small_genome(ctx, orc):
     """1.5e5 reads of 150 bases from a 30 kb genome (~600x): children of one k-mer with hundreds of copies, many of them"""
     rng = np.random.default_rng(113)
-    g = _random_reads(rng, 30_000)
+    g = random_reads(rng, 30_000)
     n, L = 150_000, 150
     starts = rng.integers(0, len(g) - L + 1, n)
     host = g[starts[:, None] + np.arange(L)[None, :]].reshape(-1).copy()
@@ -264,7 +240,7 @@ def test_contract(ctx, orc):
 
     rng = np.random.default_rng(17)
     n, L, k = 3000, 150, 47
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     host[rng.random(n * L) < 0.001] = ord("N")
     bases = ctx.to_device(host)
     ek, ec = _expect2(orc, host, n, L, k)
@@ -297,11 +273,11 @@ def test_contract(ctx, orc):
     # exactly the answer: written, and the slots behind it untouched
     st, got = _raw_count(ctx, bases, n, L, k, ok_, oc, nd)
     assert st == _lib.OK and got == nd
-    assert (_u64(ok_[:2 * nd]).reshape(-1, 2) == ek).all() and (_u64(oc[:nd]) == ec).all()
+    assert (u64(ok_[:2 * nd]).reshape(-1, 2) == ek).all() and (u64(oc[:nd]) == ec).all()
     assert (ok_[2 * nd:] == sentinel).all() and (oc[nd:] == sentinel).all()
     # two calls, identical tables
-    a = [_u64(t) for t in ctx.count_canonical2(bases, n, L, k)]
-    b = [_u64(t) for t in ctx.count_canonical2(bases, n, L, k)]
+    a = [u64(t) for t in ctx.count_canonical2(bases, n, L, k)]
+    b = [u64(t) for t in ctx.count_canonical2(bases, n, L, k)]
     assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
 
 
@@ -312,7 +288,7 @@ def test_work_buffer_cap(ctx, orc):
 
     rng = np.random.default_rng(18)
     n, L, k = 4000, 150, 47
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     bases = ctx.to_device(host)
     n_win = n * (L - k + 1)
     ok_ = torch.full((2 * n_win,), -1, dtype=torch.int64, device=ctx.device)
@@ -330,7 +306,7 @@ def test_work_buffer_cap(ctx, orc):
         st, got = _raw_count(ctx, bases, n, L, k, ok_, oc, n_win)
         assert st == _lib.OK
         ek, ec = _expect2(orc, host, n, L, k)
-        assert got == len(ek) and (_u64(ok_[:2 * got]).reshape(-1, 2) == ek).all() and (_u64(oc[:got]) == ec).all()
+        assert got == len(ek) and (u64(ok_[:2 * got]).reshape(-1, 2) == ek).all() and (u64(oc[:got]) == ec).all()
     finally:
         ctx.set_work_buffer_limit(0)
 
@@ -341,8 +317,8 @@ def _merge_check(ctx, orc, ha, hb, n, L, k):
     mk, mc = ctx.count_merge2(ka, ca, kb, cb)
     both = np.concatenate([ha, hb])
     ek, ec = _expect2(orc, both, len(both) // L, L, k)
-    assert _u64(mk).shape == ek.shape
-    assert (_u64(mk) == ek).all() and (_u64(mc) == ec).all()
+    assert u64(mk).shape == ek.shape
+    assert (u64(mk) == ek).all() and (u64(mc) == ec).all()
     return mk, mc, ka, ca, kb, cb
 
 
@@ -352,8 +328,8 @@ def test_merge(ctx, orc, k):
 
     rng = np.random.default_rng(1900 + k)
     n, L = 3000, 150
-    a = _random_reads(rng, n * L)
-    b = _random_reads(rng, n * L)
+    a = random_reads(rng, n * L)
+    b = random_reads(rng, n * L)
     _merge_check(ctx, orc, a, b, n, L, k)                                  # disjoint
     _merge_check(ctx, orc, a, a.copy(), n, L, k)                           # identical
     _merge_check(ctx, orc, a, np.zeros(0, np.uint8), n, L, k)              # one empty

@@ -3,7 +3,7 @@
 
 Everything is exact (u64 equality).  The lookup is pinned to the oracle: table = np.unique of the oracle's valid canonical words of
 batch A (thinned on the host), queries = the oracle's canonical words and flags of batch B, expected = np.searchsorted + equality on
-the host (two-word keys: a numpy search over (high, low) pairs written here, not the code under test).  Every such test asserts of
+the host (tests/count_np.py: table_of and host_lookup, numpy and not the code under test).  Every such test asserts of
 its own input that at least a tenth of the valid queries hit and at least a tenth miss.  The reads form is pinned to the
 composition canonical_windows(2) -> count_lookup(2) and to the oracle route; spectrum to np.bincount; filter to boolean indexing.
 At a size the oracle cannot reach: the composition of pinned calls on the device (k = 31), a host search of 10^6 sampled windows
@@ -13,6 +13,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
+from tests.count_np import dirty, host_lookup, orc_windows, random_reads, table_of, two_batches, u64, words
+
 pytestmark = pytest.mark.gpu
 
 KS1 = (1, 2, 5, 9, 12, 13, 21, 31)
@@ -20,98 +23,10 @@ KS2 = (33, 34, 35, 47, 63, 64)
 U64_MAX = 2**64 - 1
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from kmers_amd.api import Context
-
-    c = Context()
-    yield c
-    c.close()
-
-
-def _u64(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def _random_reads(rng, nbytes):
-    return rng.choice(np.frombuffer(b"ACGT", np.uint8), nbytes).astype(np.uint8)
-
-
-def _dirty(host, rng, share, n, L):
-    h = host.copy()
-    for r in np.nonzero(rng.random(n) < share)[0]:
-        p = int(rng.integers(0, L))
-        h[r * L + p] = ord("N") if r % 3 else ord(">")
-    return h
-
-
-def _words(k):
-    return 1 if k <= 31 else 2
-
-
-def _orc_windows(orc, host, n, L, k, offsets=None):
-    """the oracle's canonical words ((windows,) or (windows, 2) uint64) and flags of a batch"""
-    f = orc.canonical_windows if k <= 31 else orc.canonical_windows2
-    _, _, canon, flags = f(host, n, L, k, offsets=offsets)
-    return np.asarray(canon, np.uint64), np.asarray(flags, np.uint8)
-
-
-def _table_of(canon, flags):
-    """sorted distinct valid canonical words and their counts, on the host"""
-    c = canon[(flags & 1) != 0]
-    if c.ndim == 1:
-        k_, c_ = np.unique(c, return_counts=True)
-        return k_, c_.astype(np.uint64)
-    c = c[np.lexsort((c[:, 0], c[:, 1]))]
-    head = np.ones(len(c), bool)
-    head[1:] = (c[1:] != c[:-1]).any(axis=1)
-    idx = np.nonzero(head)[0]
-    return c[head], np.diff(np.append(idx, len(c))).astype(np.uint64)
-
-
-def _host_lookup(tk, tc, q, qflags=None, k=None):
-    """expected answers on the host: lower bound + equality; tc None = membership"""
-    n = len(tk)
-    out = np.zeros(len(q), np.uint64)
-    if n == 0 or len(q) == 0:
-        return out
-    if tk.ndim == 1:
-        i = np.searchsorted(tk, q)
-        ic = np.minimum(i, n - 1)
-        found = (i < n) & (tk[ic] == q)
-    else:
-        thi, tlo, qhi, qlo = tk[:, 1], tk[:, 0], q[:, 1], q[:, 0]
-        lo = np.searchsorted(thi, qhi, "left")
-        hi = np.searchsorted(thi, qhi, "right")
-        for _ in range(44):                      # lower bound of the low word inside the run of equal high words
-            act = lo < hi
-            mid = (lo + hi) // 2
-            less = tlo[np.minimum(mid, n - 1)] < qlo
-            lo = np.where(act & less, mid + 1, lo)
-            hi = np.where(act & ~less, mid, hi)
-        ic = np.minimum(lo, n - 1)
-        found = (lo < n) & (thi[ic] == qhi) & (tlo[ic] == qlo)
-    if qflags is not None:
-        found &= (qflags & 1) != 0
-    out[found] = tc[ic[found]] if tc is not None else 1
-    return out
-
-
 def _dev_lookup(ctx, tk, tc, k, q, qflags=None, out=None):
     f = ctx.count_lookup if k <= 31 else ctx.count_lookup2
-    return _u64(f(ctx.to_device(tk), None if tc is None else ctx.to_device(tc), k, q if not isinstance(q, np.ndarray) else ctx.to_device(q),
-                  None if qflags is None else ctx.to_device(qflags), out=out))
-
-
-def _two_batches(rng, n, L):
-    """A and B: every second read of B is a read of A"""
-    a = _random_reads(rng, n * L)
-    b = _random_reads(rng, n * L)
-    b.reshape(n, L)[::2] = a.reshape(n, L)[::2]
-    return a, b
+    return u64(f(ctx.to_device(tk), None if tc is None else ctx.to_device(tc), k, q if not isinstance(q, np.ndarray) else ctx.to_device(q),
+                 None if qflags is None else ctx.to_device(qflags), out=out))
 
 
 def _thin(tk, tc):
@@ -131,14 +46,14 @@ def _assert_hits_and_misses(expect, qflags):
 def test_lookup_against_the_oracle(ctx, orc, k):
     rng = np.random.default_rng(2100 + k)
     n, L = 3000, 150
-    a, b = _two_batches(rng, n, L)
-    tk, tc = _thin(*_table_of(*_orc_windows(orc, a, n, L, k)))
-    q, qf = _orc_windows(orc, b, n, L, k)
-    expect = _host_lookup(tk, tc, q, qf)
+    a, b = two_batches(rng, n, L)
+    tk, tc = _thin(*table_of(*orc_windows(orc, a, n, L, k)))
+    q, qf = orc_windows(orc, b, n, L, k)
+    expect = host_lookup(tk, tc, q, qf)
     _assert_hits_and_misses(expect, qf)
     got = _dev_lookup(ctx, tk, tc, k, q, qf)
     assert (got == expect).all(), k
-    assert (_dev_lookup(ctx, tk, tc, k, q, None) == _host_lookup(tk, tc, q, None)).all()      # no flags
+    assert (_dev_lookup(ctx, tk, tc, k, q, None) == host_lookup(tk, tc, q, None)).all()      # no flags
     assert (_dev_lookup(ctx, tk, None, k, q, qf) == (expect != 0).astype(np.uint64)).all()    # membership
     # determinism: two calls, bit-identical
     assert (_dev_lookup(ctx, tk, tc, k, q, qf) == got).all()
@@ -148,16 +63,16 @@ def test_lookup_against_the_oracle(ctx, orc, k):
 def test_lookup_flags_of_a_dirty_batch(ctx, orc, k):
     rng = np.random.default_rng(2200 + k)
     n, L = 3000, 150
-    a, b = _two_batches(rng, n, L)
-    b = _dirty(b, rng, 0.2, n, L)
-    tk, tc = _thin(*_table_of(*_orc_windows(orc, a, n, L, k)))
-    q, qf = _orc_windows(orc, b, n, L, k)
+    a, b = two_batches(rng, n, L)
+    b = dirty(b, rng, 0.2, n, L)
+    tk, tc = _thin(*table_of(*orc_windows(orc, a, n, L, k)))
+    q, qf = orc_windows(orc, b, n, L, k)
     bad = np.nonzero((qf & 1) == 0)[0]
     assert len(bad) > 1000
     q = q.copy()
     q[bad] = tk[rng.integers(0, len(tk), len(bad))]     # words that ARE in the table, in slots that are not valid
-    expect = _host_lookup(tk, tc, q, qf)
-    assert (expect[bad] == 0).all() and (_host_lookup(tk, tc, q, None)[bad] != 0).all()
+    expect = host_lookup(tk, tc, q, qf)
+    assert (expect[bad] == 0).all() and (host_lookup(tk, tc, q, None)[bad] != 0).all()
     _assert_hits_and_misses(expect, qf)
     assert (_dev_lookup(ctx, tk, tc, k, q, qf) == expect).all()
 
@@ -166,21 +81,21 @@ def test_lookup_flags_of_a_dirty_batch(ctx, orc, k):
 def test_lookup_in_place(ctx, orc, k):
     rng = np.random.default_rng(2300 + k)
     n, L = 3000, 150
-    a, b = _two_batches(rng, n, L)
-    tk, tc = _thin(*_table_of(*_orc_windows(orc, a, n, L, k)))
-    q, qf = _orc_windows(orc, b, n, L, k)
-    expect = _host_lookup(tk, tc, q, qf)
+    a, b = two_batches(rng, n, L)
+    tk, tc = _thin(*table_of(*orc_windows(orc, a, n, L, k)))
+    q, qf = orc_windows(orc, b, n, L, k)
+    expect = host_lookup(tk, tc, q, qf)
     _assert_hits_and_misses(expect, qf)
     d_q = ctx.to_device(q)
     out = ctx.count_lookup(ctx.to_device(tk), ctx.to_device(tc), k, d_q, ctx.to_device(qf), out=d_q)
     assert out.data_ptr() == d_q.data_ptr()
-    assert (_u64(d_q) == expect).all()
+    assert (u64(d_q) == expect).all()
 
 
 def _synthetic_table(rng, k, n, lo_bits=None, prefixes=None):
     """n distinct sorted keys of 2k bits: all bits random, or only the low `lo_bits` (every key in ONE directory bin), or a few
     values of the top 24 bits (most bins empty)"""
-    w = _words(k)
+    w = words(k)
     bits = 2 * k
     vals = set()
     while len(vals) < n:
@@ -221,7 +136,7 @@ def test_lookup_skewed_tables(ctx, k, shape):
     else:
         tk, tc = _synthetic_table(rng, k, n)
     q = _queries_from(rng, tk, 200000)                             # enough queries for the directory
-    expect = _host_lookup(tk, tc, q)
+    expect = host_lookup(tk, tc, q)
     assert 10 * int((expect != 0).sum()) >= len(q) and 10 * int((expect == 0).sum()) >= len(q)
     assert (_dev_lookup(ctx, tk, tc, k, q) == expect).all()
     # the same with a batch small enough for the plain search, and with no room for a directory: same answers, no KMX_E_NOMEM
@@ -239,7 +154,7 @@ def test_lookup_edges(ctx, k):
     import torch
 
     rng = np.random.default_rng(2500 + k)
-    w = _words(k)
+    w = words(k)
     n = min(3000, 4 ** k // 2)
     tk, tc = _synthetic_table(rng, k, n)
     shape = (0,) if w == 1 else (0, 2)
@@ -287,13 +202,13 @@ def test_lookup_all_a_table(ctx, orc):
     n, L = 2000, 150
     host = np.full(n * L, ord("A"), np.uint8)
     for k in (31, 47):
-        tk, tc = _table_of(*_orc_windows(orc, host, n, L, k))
+        tk, tc = table_of(*orc_windows(orc, host, n, L, k))
         assert len(tk) == 1 and int(tc[0]) == n * (L - k + 1)
         rng = np.random.default_rng(k)
-        b = _random_reads(rng, n * L)
+        b = random_reads(rng, n * L)
         b.reshape(n, L)[::2] = ord("T")                  # poly-T: canonical form all A
-        q, qf = _orc_windows(orc, b, n, L, k)
-        expect = _host_lookup(tk, tc, q, qf)
+        q, qf = orc_windows(orc, b, n, L, k)
+        expect = host_lookup(tk, tc, q, qf)
         _assert_hits_and_misses(expect, qf)
         assert (_dev_lookup(ctx, tk, tc, k, q, qf) == expect).all()
 
@@ -330,13 +245,13 @@ def _lookup_reads_check(ctx, orc, table_host, host, n, L, k, offsets=None, shift
     bases = buf[shift:shift + len(host)]
     d_off = None if offsets is None else ctx.to_device(np.asarray(offsets, np.uint64))
     one = k <= 31
-    got = _u64((ctx.count_lookup_reads if one else ctx.count_lookup_reads2)(bases, n, L, k, d_tk, d_tc, offsets=d_off))
+    got = u64((ctx.count_lookup_reads if one else ctx.count_lookup_reads2)(bases, n, L, k, d_tk, d_tc, offsets=d_off))
     w = (ctx.canonical_windows(bases, n, L, k, offsets=d_off, host_offsets=offsets, want=("canon", "flags")) if one else
          ctx.canonical_windows2(bases, n, L, k, offsets=d_off, host_offsets=offsets))
-    comp = _u64((ctx.count_lookup if one else ctx.count_lookup2)(d_tk, d_tc, k, w["canon"] if one else w["canon"].view(-1, 2), w["flags"]))
+    comp = u64((ctx.count_lookup if one else ctx.count_lookup2)(d_tk, d_tc, k, w["canon"] if one else w["canon"].view(-1, 2), w["flags"]))
     assert got.shape == comp.shape and (got == comp).all(), (k, L, n, shift)
-    q, qf = _orc_windows(orc, host, n, L, k, offsets)
-    expect = _host_lookup(tk, tc, q, qf)
+    q, qf = orc_windows(orc, host, n, L, k, offsets)
+    expect = host_lookup(tk, tc, q, qf)
     assert got.shape == expect.shape and (got == expect).all(), (k, L, n, shift)
     return got, expect, qf
 
@@ -345,14 +260,14 @@ def _lookup_reads_check(ctx, orc, table_host, host, n, L, k, offsets=None, shift
 def test_lookup_reads_uniform(ctx, orc, k):
     rng = np.random.default_rng(3100 + k)
     for L, n in ((k, 5000), (150, 3000), (300, 700), (1000, 200)):
-        a, b = _two_batches(rng, n, L)
-        table = _thin(*_table_of(*_orc_windows(orc, a, n, L, k)))
+        a, b = two_batches(rng, n, L)
+        table = _thin(*table_of(*orc_windows(orc, a, n, L, k)))
         for shift in (0, 1):                                        # aligned and odd d_bases
             _, expect, qf = _lookup_reads_check(ctx, orc, table, b, n, L, k, shift=shift)
         if L > k:
             _assert_hits_and_misses(expect, qf)
         # dirty and lower-case bytes
-        h = _dirty(b, rng, 0.10, n, L)
+        h = dirty(b, rng, 0.10, n, L)
         low = rng.random(n * L) < 0.3
         h[low & (h != ord("N")) & (h != ord(">"))] |= 0x20
         _lookup_reads_check(ctx, orc, table, h, n, L, k, shift=3 if L == 150 else 0)
@@ -368,12 +283,12 @@ def test_lookup_reads_ragged(ctx, orc, k, bound):
     lens[::17] = 0                             # empty reads
     lens[5::13] = k - 1                        # reads one base short of a window
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    a = _random_reads(rng, int(offsets[-1]))
-    b = _random_reads(rng, int(offsets[-1]))
+    a = random_reads(rng, int(offsets[-1]))
+    b = random_reads(rng, int(offsets[-1]))
     half = int(offsets[n // 2])
     b[:half] = a[:half]                        # the first half of the reads shared
     b[rng.random(len(b)) < 0.002] = ord("N")
-    table = _thin(*_table_of(*_orc_windows(orc, a, n, bound, k, offsets)))
+    table = _thin(*table_of(*orc_windows(orc, a, n, bound, k, offsets)))
     for shift in (0, 5):                       # (5: misaligned d_bases, the per-read kernels)
         _, expect, qf = _lookup_reads_check(ctx, orc, table, b, n, bound, k, offsets=offsets, shift=shift)
     _assert_hits_and_misses(expect, qf)
@@ -384,20 +299,20 @@ def test_lookup_reads_in_own_table(ctx, k):
     """a batch looked up in ITS OWN table: sum(d_out) == sum(count ** 2), and no valid window answers 0"""
     rng = np.random.default_rng(3300 + k)
     n, L = 20000, 150
-    g = _random_reads(rng, 50_000)             # reads of a small genome: counts well above 1
+    g = random_reads(rng, 50_000)             # reads of a small genome: counts well above 1
     starts = rng.integers(0, len(g) - L + 1, n)
-    host = _dirty(g[starts[:, None] + np.arange(L)[None, :]].reshape(-1).copy(), rng, 0.05, n, L)
+    host = dirty(g[starts[:, None] + np.arange(L)[None, :]].reshape(-1).copy(), rng, 0.05, n, L)
     bases = ctx.to_device(host)
     one = k <= 31
     km, cnt = (ctx.count_canonical if one else ctx.count_canonical2)(bases, n, L, k)
     out = (ctx.count_lookup_reads if one else ctx.count_lookup_reads2)(bases, n, L, k, km, cnt)
     flags = (ctx.canonical_windows(bases, n, L, k, want=("flags",)) if one else ctx.canonical_windows2(bases, n, L, k))["flags"]
-    o, f, c = _u64(out), flags.cpu().numpy(), _u64(cnt)
+    o, f, c = u64(out), flags.cpu().numpy(), u64(cnt)
     assert ((o != 0) == ((f & 1) != 0)).all()
     assert sum(int(x) for x in o.tolist()) == sum(int(x) ** 2 for x in c.tolist())
     # determinism
     again = (ctx.count_lookup_reads if one else ctx.count_lookup_reads2)(bases, n, L, k, km, cnt)
-    assert (_u64(again) == o).all()
+    assert (u64(again) == o).all()
 
 
 @pytest.mark.parametrize("k", (31, 47))
@@ -409,8 +324,8 @@ def test_lookup_reads_work_buffer_cap(ctx, orc, k):
 
     rng = np.random.default_rng(3400 + k)
     n, L = 4000, 150
-    a, b = _two_batches(rng, n, L)
-    tk, tc = _thin(*_table_of(*_orc_windows(orc, a, n, L, k)))
+    a, b = two_batches(rng, n, L)
+    tk, tc = _thin(*table_of(*orc_windows(orc, a, n, L, k)))
     d_tk, d_tc, bases = ctx.to_device(tk), ctx.to_device(tc), ctx.to_device(b)
     n_win = n * (L - k + 1)
     a256 = lambda x: (x + 255) & ~255
@@ -430,8 +345,8 @@ def test_lookup_reads_work_buffer_cap(ctx, orc, k):
         ctx.set_work_buffer_limit(need)                      # exactly the documented size: served (without a directory)
         st = fn(ctx._h, C.byref(r), None, k, _ptr(d_tk), _ptr(d_tc), len(tc), _ptr(out))
         assert st == _lib.OK
-        q, qf = _orc_windows(orc, b, n, L, k)
-        assert (_u64(out) == _host_lookup(tk, tc, q, qf)).all()
+        q, qf = orc_windows(orc, b, n, L, k)
+        assert (u64(out) == host_lookup(tk, tc, q, qf)).all()
     finally:
         ctx.set_work_buffer_limit(0)
 
@@ -451,12 +366,12 @@ def test_fastq_end_to_end(ctx, orc, k):
     km, cnt = ctx.count_canonical(b1, int(o1.numel()) - 1, 300, k, offsets=o1)
     b2, o2 = ctx.fastx_parse(ctx.to_device(t2))
     n2 = int(o2.numel()) - 1
-    got = _u64(ctx.count_lookup_reads(b2, n2, 300, k, km, cnt, offsets=o2))
+    got = u64(ctx.count_lookup_reads(b2, n2, 300, k, km, cnt, offsets=o2))
     e1b, e1o = orc.fastx_parse(t1)
-    tk, tc = _table_of(*_orc_windows(orc, np.asarray(e1b, np.uint8), len(e1o) - 1, 300, k, np.asarray(e1o, np.uint64)))
+    tk, tc = table_of(*orc_windows(orc, np.asarray(e1b, np.uint8), len(e1o) - 1, 300, k, np.asarray(e1o, np.uint64)))
     e2b, e2o = orc.fastx_parse(t2)
-    q, qf = _orc_windows(orc, np.asarray(e2b, np.uint8), n2, 300, k, np.asarray(e2o, np.uint64))
-    expect = _host_lookup(tk, tc, q, qf)
+    q, qf = orc_windows(orc, np.asarray(e2b, np.uint8), n2, 300, k, np.asarray(e2o, np.uint64))
+    expect = host_lookup(tk, tc, q, qf)
     _assert_hits_and_misses(expect, qf)
     assert got.shape == expect.shape and (got == expect).all()
 
@@ -471,32 +386,32 @@ def _spectrum_check(ctx, counts):
     d = ctx.to_device(counts)
     for nb in BINS:
         expect = np.bincount(np.minimum(counts, np.uint64(nb - 1)).astype(np.int64), minlength=nb).astype(np.uint64)
-        got = _u64(ctx.count_spectrum(d, nb))
+        got = u64(ctx.count_spectrum(d, nb))
         assert got.shape == (nb,) and (got == expect).all(), nb
         assert int(got.sum()) == len(counts)
         bins = torch.zeros(nb, dtype=torch.int64, device=ctx.device)       # accumulation: two calls, the sum
         ctx.count_spectrum(d, nb, out=bins)
         ctx.count_spectrum(d, nb, out=bins)
-        assert (_u64(bins) == 2 * expect).all(), nb
+        assert (u64(bins) == 2 * expect).all(), nb
 
 
 def test_spectrum_of_tables(ctx):
     rng = np.random.default_rng(41)
     n, L, k = 20000, 150, 31
-    host = _random_reads(rng, n * L)
+    host = random_reads(rng, n * L)
     bases = ctx.to_device(host)
     _, cnt = ctx.count_canonical(bases, n, L, k)                           # nearly all singletons
-    c = _u64(cnt)
+    c = u64(cnt)
     assert (c == 1).mean() > 0.99
     _spectrum_check(ctx, c)
-    s = _u64(ctx.count_spectrum(cnt, 65536))
+    s = u64(ctx.count_spectrum(cnt, 65536))
     assert int(s[-1]) == 0
     assert sum(i * int(v) for i, v in enumerate(s.tolist())) == ctx.canonical_reduce(bases, n, L, k).n_valid
     poly = rng.random(n) < 0.9                                             # one huge count among singletons
     host.reshape(n, L)[poly] = ord("A")
     for kk, f in ((31, ctx.count_canonical), (47, ctx.count_canonical2)):
         _, cnt = f(ctx.to_device(host), n, L, kk)
-        c = _u64(cnt)
+        c = u64(cnt)
         assert int(c.max()) > 1_000_000
         _spectrum_check(ctx, c)
 
@@ -516,11 +431,11 @@ RANGES = ((1, U64_MAX), (2, U64_MAX), (1, 1), (3, 10), (5, 4))
 
 
 def _genome_table(ctx, rng, k, n=20000, L=150):
-    g = _random_reads(rng, 100_000)
+    g = random_reads(rng, 100_000)
     starts = rng.integers(0, len(g) - L + 1, n)
     host = g[starts[:, None] + np.arange(L)[None, :]].reshape(-1).copy()
     err = rng.random(len(host)) < 0.01                                     # sequencing errors: singletons
-    host[err] = _random_reads(rng, int(err.sum()))
+    host[err] = random_reads(rng, int(err.sum()))
     return (ctx.count_canonical if k <= 31 else ctx.count_canonical2)(ctx.to_device(host), n, L, k)
 
 
@@ -531,21 +446,21 @@ def test_filter(ctx, k):
     rng = np.random.default_rng(5100 + k)
     one = k <= 31
     km, cnt = _genome_table(ctx, rng, k)
-    hk, hc = _u64(km), _u64(cnt)
+    hk, hc = u64(km), u64(cnt)
     filt = ctx.count_filter if one else ctx.count_filter2
     for mn, mx in RANGES:
         keep = (hc >= np.uint64(mn)) & (hc <= np.uint64(mx))
         fk, fc = filt(km, cnt, mn, mx)
-        assert _u64(fk).shape == hk[keep].shape
-        assert (_u64(fk) == hk[keep]).all() and (_u64(fc) == hc[keep]).all(), (k, mn, mx)
+        assert u64(fk).shape == hk[keep].shape
+        assert (u64(fk) == hk[keep]).all() and (u64(fc) == hc[keep]).all(), (k, mn, mx)
     assert 0 < int(((hc >= 3) & (hc <= 10)).sum()) < len(hc)
     # the output is a table: merge(filter(t, 1, 1), filter(t, 2, max)) == t, and it goes into lookup unchanged
     k1, c1 = filt(km, cnt, 1, 1)
     k2, c2 = filt(km, cnt, 2, U64_MAX)
     assert 0 < c1.numel() < cnt.numel()
     mk, mc = (ctx.count_merge if one else ctx.count_merge2)(k1, c1, k2, c2)
-    assert (_u64(mk) == hk).all() and (_u64(mc) == hc).all()
-    got = _u64((ctx.count_lookup if one else ctx.count_lookup2)(k2, c2, k, km))
+    assert (u64(mk) == hk).all() and (u64(mc) == hc).all()
+    got = u64((ctx.count_lookup if one else ctx.count_lookup2)(k2, c2, k, km))
     assert (got == np.where(hc >= 2, hc, 0)).all()
     # an empty table
     e = filt(km[:0], cnt[:0], 1, U64_MAX)
@@ -563,11 +478,11 @@ def test_filter_contract(ctx, k):
     from kmers_amd.api import _ptr
 
     rng = np.random.default_rng(5200 + k)
-    w = _words(k)
+    w = words(k)
     km, cnt = _genome_table(ctx, rng, k)
     km = km.contiguous().view(-1)
     n = int(cnt.numel())
-    hk, hc = _u64(km).reshape(n, w), _u64(cnt)
+    hk, hc = u64(km).reshape(n, w), u64(cnt)
     keep = (hc >= 3) & (hc <= 10)
     m = int(keep.sum())
     fn = ctx.lib.kmx_count_filter if w == 1 else ctx.lib.kmx_count_filter2
@@ -590,7 +505,7 @@ def test_filter_contract(ctx, k):
         assert call(km, ok_[1:], oc, m)[0] == _lib.E_ARG
     assert (ok_ == sentinel).all() and (oc == sentinel).all()
     assert call(km, ok_, oc, m) == (_lib.OK, m)                          # exactly the answer; the slots behind it untouched
-    assert (_u64(ok_[:w * m]).reshape(m, w) == hk[keep]).all() and (_u64(oc[:m]) == hc[keep]).all()
+    assert (u64(ok_[:w * m]).reshape(m, w) == hk[keep]).all() and (u64(oc[:m]) == hc[keep]).all()
     assert (ok_[w * m:] == sentinel).all() and (oc[m:] == sentinel).all()
 
 
@@ -627,7 +542,7 @@ def test_filter_compaction_boundaries(ctx, w):
             got = C.c_uint64(12345)
             st = fn(ctx._h, _ptr(km), _ptr(cnt), n, 1, 1, _ptr(ok_), _ptr(oc), m + 8, C.byref(got))
             assert (st, got.value) == (_lib.OK, m), (w, n, name)
-            assert (_u64(ok_[:w * m]).reshape(m, w) == hk[keep]).all() and (_u64(oc[:m]) == hc[keep]).all(), (w, n, name)
+            assert (u64(ok_[:w * m]).reshape(m, w) == hk[keep]).all() and (u64(oc[:m]) == hc[keep]).all(), (w, n, name)
             assert (ok_[w * m:] == sentinel).all() and (oc[m:] == sentinel).all(), (w, n, name)
 
 
@@ -676,12 +591,12 @@ def test_at_size_two_word(ctx):
     w = ctx.canonical_windows2(b, n, L, k)
     g = torch.Generator(device=ctx.device).manual_seed(7)
     pick = torch.randint(0, got.numel(), (1_000_000,), device=ctx.device, generator=g)
-    q = _u64(w["canon"].view(-1, 2)[:, 0][pick]), _u64(w["canon"].view(-1, 2)[:, 1][pick])
+    q = u64(w["canon"].view(-1, 2)[:, 0][pick]), u64(w["canon"].view(-1, 2)[:, 1][pick])
     qf = w["flags"][pick].cpu().numpy()
-    tk = np.stack([_u64(km[:, 0].contiguous()), _u64(km[:, 1].contiguous())], axis=1)
-    expect = _host_lookup(tk, _u64(cnt), np.stack(q, axis=1), qf)
+    tk = np.stack([u64(km[:, 0].contiguous()), u64(km[:, 1].contiguous())], axis=1)
+    expect = host_lookup(tk, u64(cnt), np.stack(q, axis=1), qf)
     _assert_hits_and_misses(expect, qf)
-    assert (_u64(got[pick]) == expect).all()
+    assert (u64(got[pick]) == expect).all()
     del w
     own = ctx.count_lookup_reads2(a, n, L, k, km, cnt)
     assert int(own.sum().item()) == int((cnt * cnt).sum().item())

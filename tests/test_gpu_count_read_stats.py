@@ -1,8 +1,8 @@
 """Per-read abundance statistics against a count table on the GPU: kmx_count_read_stats(2) (kmx_count_read_stats.hip).
 
 Every comparison is u64 equality of whole (n_reads, 8) arrays.  Expected values are made on the host: the oracle's canonical words
-and flags of the batch, a host lookup (lower bound + equality, written here), and a plain per-read loop over the eight fields as
-kmx.h defines them.  Tables are np.unique of the oracle's valid words of a batch A with every third entry dropped -- except the
+and flags of the batch, a host lookup (lower bound + equality: tests/count_np.py), and a plain per-read loop over the eight fields
+as kmx.h defines them, written here.  Tables are np.unique of the oracle's valid words of a batch A with every third entry dropped -- except the
 k-mers of a few reads that both batches hold, so that some reads are wholly in the table; batch B shares every second read with A.
 Every table-driven test asserts of its own input: at least a tenth of the valid windows hit and a tenth miss, one read has a span
 shorter than its window count, one has a span over all its windows, n_valid is even in one read and odd in another.
@@ -13,77 +13,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
+from tests.count_np import host_lookup, orc_windows, random_reads, table_of, u64
+
 pytestmark = pytest.mark.gpu
 
 U64_MAX = 2**64 - 1
 POISON = -0x5A5A5A5A5A5A5A5B
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from kmers_amd.api import Context
-
-    c = Context()
-    yield c
-    c.close()
-
-
-def _u64(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def _random_reads(rng, nbytes):
-    return rng.choice(np.frombuffer(b"ACGT", np.uint8), nbytes).astype(np.uint8)
-
-
-def _orc_windows(orc, host, n, L, k, offsets=None):
-    f = orc.canonical_windows if k <= 31 else orc.canonical_windows2
-    _, _, canon, flags = f(host, n, L, k, offsets=offsets)
-    return np.asarray(canon, np.uint64), np.asarray(flags, np.uint8)
-
-
-def _table_of(canon, flags):
-    """sorted distinct valid canonical words and their counts, on the host"""
-    c = canon[(flags & 1) != 0]
-    if c.ndim == 1:
-        k_, c_ = np.unique(c, return_counts=True)
-        return k_, c_.astype(np.uint64)
-    c = c[np.lexsort((c[:, 0], c[:, 1]))]
-    head = np.ones(len(c), bool)
-    head[1:] = (c[1:] != c[:-1]).any(axis=1)
-    idx = np.nonzero(head)[0]
-    return c[head], np.diff(np.append(idx, len(c))).astype(np.uint64)
-
-
-def _host_lookup(tk, tc, q, qflags=None):
-    """expected answers on the host: lower bound + equality; tc None = membership"""
-    n = len(tk)
-    out = np.zeros(len(q), np.uint64)
-    if n == 0 or len(q) == 0:
-        return out
-    if tk.ndim == 1:
-        i = np.searchsorted(tk, q)
-        ic = np.minimum(i, n - 1)
-        found = (i < n) & (tk[ic] == q)
-    else:
-        thi, tlo, qhi, qlo = tk[:, 1], tk[:, 0], q[:, 1], q[:, 0]
-        lo = np.searchsorted(thi, qhi, "left")
-        hi = np.searchsorted(thi, qhi, "right")
-        for _ in range(44):                      # lower bound of the low word inside the run of equal high words
-            act = lo < hi
-            mid = (lo + hi) // 2
-            less = tlo[np.minimum(mid, n - 1)] < qlo
-            lo = np.where(act & less, mid + 1, lo)
-            hi = np.where(act & ~less, mid, hi)
-        ic = np.minimum(lo, n - 1)
-        found = (lo < n) & (thi[ic] == qhi) & (tlo[ic] == qlo)
-    if qflags is not None:
-        found &= (qflags & 1) != 0
-    out[found] = tc[ic[found]] if tc is not None else 1
-    return out
 
 
 def _host_stats(cnt, flags, wo, solid_min):
@@ -164,8 +100,8 @@ def _thin(tk, tc, protect):
 def _uniform_batches(rng, n, L):
     """A and B.  Every second read of B is a read of A; read 0 (shared) is A / T only, so that it is whole in a table of one key at
     k = 1; read 1 of B has an N at base 0 (one window fewer than its neighbours: both parities of n_valid)."""
-    a = _random_reads(rng, n * L)
-    b = _random_reads(rng, n * L)
+    a = random_reads(rng, n * L)
+    b = random_reads(rng, n * L)
     a.reshape(n, L)[0] = rng.choice(np.frombuffer(b"AT", np.uint8), L)
     b.reshape(n, L)[::2] = a.reshape(n, L)[::2]
     b.reshape(n, L)[1, 0] = ord("N")
@@ -174,11 +110,11 @@ def _uniform_batches(rng, n, L):
 
 def _table_for(orc, a, b, n, L, k, offsets=None, protect_reads=(0,)):
     """the thinned table of batch A that keeps the k-mers of B's `protect_reads` (reads both batches hold)"""
-    q, qf = _orc_windows(orc, b, n, L, k, offsets)
+    q, qf = orc_windows(orc, b, n, L, k, offsets)
     wo = orc.win_offsets_for(n, L, k, None if offsets is None else np.asarray(offsets, np.uint64))
     rows = np.concatenate([np.arange(int(wo[r]), int(wo[r + 1])) for r in protect_reads]).astype(np.int64)
     rows = rows[(qf[rows] & 1) != 0]
-    tk, tc = _table_of(*_orc_windows(orc, a, n, L, k, offsets))
+    tk, tc = table_of(*orc_windows(orc, a, n, L, k, offsets))
     return _thin(tk, tc, q[rows]), (q, qf, wo)
 
 
@@ -191,7 +127,7 @@ def _check(ctx, table, windows, host, n, L, k, offsets=None, solid_mins=(1,), sh
     """the device rows against the host loop for every solid_min; returns the expectation of the first"""
     tk, tc = table
     q, qf, wo = windows
-    cnt = _host_lookup(tk, tc, q, qf)
+    cnt = host_lookup(tk, tc, q, qf)
     d_tk = ctx.to_device(tk)
     d_tc = None if tc is None else ctx.to_device(tc)
     buf = ctx.to_device(np.concatenate([np.zeros(shift, np.uint8), host, np.zeros(16, np.uint8)]))
@@ -200,7 +136,7 @@ def _check(ctx, table, windows, host, n, L, k, offsets=None, solid_mins=(1,), sh
     first = None
     for sm in solid_mins:
         expect = _host_stats(cnt, qf, wo, sm)
-        got = _u64(_call(ctx, k, bases, n, L, d_tk, d_tc, sm, d_off))
+        got = u64(_call(ctx, k, bases, n, L, d_tk, d_tc, sm, d_off))
         assert got.shape == expect.shape
         bad = np.nonzero((got != expect).any(axis=1))[0]
         assert len(bad) == 0, (k, L, n, sm, shift, bad[:5], got[bad[:2]], expect[bad[:2]])
@@ -306,8 +242,8 @@ def _ragged_batches(rng, lens, k):
     read but two kept clean"""
     n = len(lens)
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    a = _random_reads(rng, int(offsets[-1]))
-    b = _random_reads(rng, int(offsets[-1]))
+    a = random_reads(rng, int(offsets[-1]))
+    b = random_reads(rng, int(offsets[-1]))
     half = int(offsets[n // 2])
     b[:half] = a[:half]
     order = np.argsort(lens, kind="stable")
@@ -396,7 +332,7 @@ def test_solid_min_values(ctx, orc, k):
 def _runs_by_invalid_bytes(rng, L, k, bad_windows):
     """a read whose windows are valid except `bad_windows` (each made invalid by an N at its first base, which also takes the k - 1
     windows before it)"""
-    r = _random_reads(rng, L)
+    r = random_reads(rng, L)
     for w in bad_windows:
         r[w] = ord("N")
     return r
@@ -411,12 +347,12 @@ def test_span_ties_and_boundaries(ctx, orc):
     def run(reads, L):
         n = len(reads)
         host = np.concatenate(reads)
-        q, qf = _orc_windows(orc, host, n, L, k)
+        q, qf = orc_windows(orc, host, n, L, k)
         wo = orc.win_offsets_for(n, L, k, None)
         return _check(ctx, empty, (q, qf, wo), host, n, L, k, solid_mins=(0,), conditions=False)
 
     # W = 45 windows, windows 20 .. 24 invalid: two runs of 20, the earlier one is reported
-    e = run([_runs_by_invalid_bytes(rng, 49, k, [24]), _random_reads(rng, 49)], 49)
+    e = run([_runs_by_invalid_bytes(rng, 49, k, [24]), random_reads(rng, 49)], 49)
     assert int(e[0, 7]) == (20 << 32) | 0 and int(e[1, 7]) == (45 << 32) | 0
     # the later run longer by one: it wins
     e = run([_runs_by_invalid_bytes(rng, 50, k, [24])], 50)
@@ -454,7 +390,7 @@ def test_empty_table_and_membership(ctx, orc, k):
     f = ctx.count_read_stats if k <= 31 else ctx.count_read_stats2
     bases = ctx.to_device(b)
     for sm in (1, 0):                                                              # n == 0, null pointers
-        got = _u64(f(bases, n, L, k, None, None, solid_min=sm))
+        got = u64(f(bases, n, L, k, None, None, solid_min=sm))
         expect = _host_stats(np.zeros(len(q), np.uint64), qf, wo, sm)
         assert (got == expect).all(), sm
         assert (got[:, 1] == 0).all() and (got[:, 3:7] == 0).all() and (got[:, 0] > 0).all()
@@ -480,12 +416,12 @@ def test_against_the_pinned_composition_at_size(ctx, k):
     b[rows * L + pos] = ord("N")
     one = k <= 31
     km, cnt = (ctx.count_canonical if one else ctx.count_canonical2)(a, n, L, k)
-    per_window = _u64((ctx.count_lookup_reads if one else ctx.count_lookup_reads2)(b, n, L, k, km, cnt))
+    per_window = u64((ctx.count_lookup_reads if one else ctx.count_lookup_reads2)(b, n, L, k, km, cnt))
     flags = (ctx.canonical_windows(b, n, L, k, want=("flags",)) if one else ctx.canonical_windows2(b, n, L, k))["flags"].cpu().numpy()
     wo = np.arange(n + 1, dtype=np.uint64) * np.uint64(W)
     for sm in (1, 2):
         expect = _dense_stats(per_window, flags, n, W, sm)
-        got = _u64(_call(ctx, k, b, n, L, km, cnt, sm))
+        got = u64(_call(ctx, k, b, n, L, km, cnt, sm))
         assert (got == expect).all(), (k, sm)
         if sm == 1:
             _assert_input(expect, per_window, flags, wo)
@@ -520,8 +456,8 @@ def test_work_buffer_cap(ctx, orc, k):
         assert (out == POISON).all()
         ctx.set_work_buffer_limit(need)                      # exactly the documented size: served (without a directory)
         assert fn(ctx._h, C.byref(r), k, _ptr(d_tk), _ptr(d_tc), len(tc), 1, _ptr(out)) == _lib.OK
-        expect = _host_stats(_host_lookup(tk, tc, q, qf), qf, wo, 1)
-        assert (_u64(out).reshape(n, 8) == expect).all()
+        expect = _host_stats(host_lookup(tk, tc, q, qf), qf, wo, 1)
+        assert (u64(out).reshape(n, 8) == expect).all()
     finally:
         ctx.set_work_buffer_limit(0)
 
@@ -537,12 +473,12 @@ def test_determinism_and_out_reuse(ctx, orc, k):
         a, b = _uniform_batches(rng, n, L)
         (tk, tc), (q, qf, wo) = _table_for(orc, a, b, n, L, k)
         d_tk, d_tc, bases = ctx.to_device(tk), ctx.to_device(tc), ctx.to_device(b)
-        expect = _host_stats(_host_lookup(tk, tc, q, qf), qf, wo, 1)
+        expect = _host_stats(host_lookup(tk, tc, q, qf), qf, wo, 1)
         got = _call(ctx, k, bases, n, L, d_tk, d_tc, 1, out=out)
         assert got.data_ptr() == out.data_ptr()
-        first = _u64(got).copy()
+        first = u64(got).copy()
         assert (first == expect).all()
-        again = _u64(_call(ctx, k, bases, n, L, d_tk, d_tc, 1))
+        again = u64(_call(ctx, k, bases, n, L, d_tk, d_tc, 1))
         assert first.tobytes() == again.tobytes()
 
 
@@ -554,7 +490,7 @@ def test_argument_errors(ctx):
 
     rng = np.random.default_rng(86)
     n, L = 16, 150
-    bases = ctx.to_device(_random_reads(rng, n * L))
+    bases = ctx.to_device(random_reads(rng, n * L))
     keys = ctx.to_device(np.arange(1, 2001, dtype=np.uint64))     # a sorted table either way: 1000 two-word keys, or 2000 one-word
     cnts = ctx.to_device(np.ones(2000, np.uint64))
     out = torch.zeros(8 * n, dtype=torch.int64, device=ctx.device)

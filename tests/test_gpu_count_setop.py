@@ -1,12 +1,12 @@
 """Set algebra and comparison of two count tables on the GPU: kmx_count_setop(2), kmx_count_compare(2) (kmx_count_setop.hip).
 
 Everything is exact (u64 equality, no tolerance).  Pinned to the oracle: two read batches, tables built on the host from the
-oracle's canonical words and flags, thinned independently, one table's counts multiplied by 1..3; the expected tables are numpy
-written here (keys of both tables ranked in their union -- two-word keys by np.unique over (high, low) columns -- and the five
-operations stated on boolean masks over that union).  Every such test asserts of its own inputs that a tenth of the union lies in
-both tables, a tenth only in a, a tenth only in b, and that shared keys fall on both sides of count_a <= count_b.  Then hand-built
-tables around the tile boundaries (the tile is _lib.SETOP_TILE merged entries), the edges of the ABI, and identities between
-device calls at a size the oracle cannot reach."""
+oracle's canonical words and flags (batches and table_of from tests/count_np.py), thinned independently, one table's counts
+multiplied by 1..3; the expected tables are numpy written here (keys of both tables ranked in their union -- two-word keys by
+np.unique over (high, low) columns -- and the five operations stated on boolean masks over that union).  Every such test asserts
+of its own inputs that a tenth of the union lies in both tables, a tenth only in a, a tenth only in b, and that shared keys fall on
+both sides of count_a <= count_b.  Then hand-built tables around the tile boundaries (the tile is _lib.SETOP_TILE merged entries),
+the edges of the ABI, and identities between device calls at a size the oracle cannot reach."""
 import ctypes as C
 
 import numpy as np
@@ -15,6 +15,8 @@ import pytest
 from kmers_amd import _lib
 from kmers_amd._lib import (RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM, SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT,
                             SETOP_SYMDIFF, SETOP_TILE, SETOP_UNION)
+from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
+from tests.count_np import dirty, table_of, two_batches, u64
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +28,6 @@ RULES = (RULE_SUM, RULE_MIN, RULE_MAX, RULE_LEFT, RULE_RIGHT)
 COMBOS = [(SETOP_INTERSECT, r) for r in RULES] + [(SETOP_UNION, r) for r in RULES] + [(SETOP_SUBTRACT, 0), (SETOP_SYMDIFF, 0),
                                                                                        (SETOP_COUNTER_SUBTRACT, 0)]
 T = SETOP_TILE
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    from kmers_amd.api import Context
-
-    c = Context()
-    yield c
-    c.close()
-
-
-def _u64(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 # ---------------------------------------------------------------- the expected results, on the host
@@ -103,7 +89,7 @@ def _dev(ctx, x):
 def _dev_setop(ctx, op, rule, ka, ca, kb, cb, max_out=None):
     f = ctx.count_setop if _words(ka) == 1 else ctx.count_setop2
     ok, oc = f(op, _dev(ctx, ka), _dev(ctx, ca), _dev(ctx, kb), _dev(ctx, cb), rule, max_out)
-    return _u64(ok), _u64(oc)
+    return u64(ok), u64(oc)
 
 
 def _raw(ctx, op, rule, da, dca, na, db, dcb, nb, ok, oc, max_out, words=1):
@@ -134,14 +120,14 @@ def _check_all(ctx, ka, ca, kb, cb, tag):
     for op, rule in COMBOS:
         wk, wc = _host_setop(op, rule, ka, ca, kb, cb)
         ok, oc = f(op, da, dca, db, dcb, rule)
-        assert _same((_u64(ok), _u64(oc)), (wk, wc)), (tag, op, rule, len(wk), int(oc.numel()))
+        assert _same((u64(ok), u64(oc)), (wk, wc)), (tag, op, rule, len(wk), int(oc.numel()))
         st, n = _raw(ctx, op, rule, da if len(ka) else None, dca if len(ka) else None, len(ka), db if len(kb) else None,
                      dcb if len(kb) else None, len(kb), None, None, 0, w)
         assert (st, n) == (_lib.OK, len(wk)), (tag, op, rule, "count only")
     # a count array the operation never reads may be missing
     for op, rule, xa, xb in ((SETOP_SUBTRACT, 0, dca, None), (SETOP_INTERSECT, RULE_LEFT, dca, None), (SETOP_INTERSECT, RULE_RIGHT, None, dcb)):
         ok, oc = f(op, da, xa, db, xb, rule)
-        assert _same((_u64(ok), _u64(oc)), _host_setop(op, rule, ka, ca, kb, cb)), (tag, op, rule, "without counts")
+        assert _same((u64(ok), u64(oc)), _host_setop(op, rule, ka, ca, kb, cb)), (tag, op, rule, "without counts")
     fc = ctx.count_compare if w == 1 else ctx.count_compare2
     want = _host_compare(ka, ca, kb, cb)
     got = fc(da, dca, db, dcb)
@@ -152,51 +138,18 @@ def _check_all(ctx, ka, ca, kb, cb, tag):
 
 
 # ---------------------------------------------------------------- 1. pinned to the oracle
-def _random_reads(rng, nbytes):
-    return rng.choice(np.frombuffer(b"ACGT", np.uint8), nbytes).astype(np.uint8)
-
-
-def _two_batches(rng, n, L):
-    """A and B: every second read of B is a read of A (as tests/test_gpu_count_query.py makes them)"""
-    a = _random_reads(rng, n * L)
-    b = _random_reads(rng, n * L)
-    b.reshape(n, L)[::2] = a.reshape(n, L)[::2]
-    return a, b
-
-
-def _dirty(host, rng, share, n, L):
-    h = host.copy()
-    for r in np.nonzero(rng.random(n) < share)[0]:
-        p = int(rng.integers(0, L))
-        h[r * L + p] = ord("N") if r % 3 else ord(">")
-    return h
-
-
-def _table_of(canon, flags):
-    """sorted distinct valid canonical words and their counts, on the host (as tests/test_gpu_count_query.py)"""
-    c = canon[(flags & 1) != 0]
-    if c.ndim == 1:
-        k_, c_ = np.unique(c, return_counts=True)
-        return k_, c_.astype(np.uint64)
-    c = c[np.lexsort((c[:, 0], c[:, 1]))]
-    head = np.ones(len(c), bool)
-    head[1:] = (c[1:] != c[:-1]).any(axis=1)
-    idx = np.nonzero(head)[0]
-    return c[head], np.diff(np.append(idx, len(c))).astype(np.uint64)
-
-
 def oracle_tables(orc, k, n=3000, L=150):
     """the two tables of the oracle tests at this k: ((keys_a, counts_a), (keys_b, counts_b))"""
     rng = np.random.default_rng(2100 + k)
-    a, b = _two_batches(rng, n, L)
+    a, b = two_batches(rng, n, L)
     rng2 = np.random.default_rng(4200 + k)   # (thinning, dirt and factors from a stream of their own: the batches are those of the seed)
     if k in DIRTY_KS:
-        a, b = _dirty(a, rng2, 0.02, n, L), _dirty(b, rng2, 0.02, n, L)
+        a, b = dirty(a, rng2, 0.02, n, L), dirty(b, rng2, 0.02, n, L)
     f = orc.canonical_windows if k <= 31 else orc.canonical_windows2
     out = []
     for host in (a, b):
         _, _, canon, flags = f(host, n, L, k, offsets=None)
-        tk, tc = _table_of(np.asarray(canon, np.uint64), np.asarray(flags, np.uint8))
+        tk, tc = table_of(np.asarray(canon, np.uint64), np.asarray(flags, np.uint8))
         keep = rng2.random(len(tk)) < 2.0 / 3.0
         out.append((np.ascontiguousarray(tk[keep]), tc[keep]))
     (ka, ca), (kb, cb) = out
@@ -350,7 +303,7 @@ def test_max_out_and_sentinels(ctx, shape):
         assert (ok == -1).all() and (oc == -1).all()
         # exactly enough: served, and nothing behind the result is touched
         assert _raw(ctx, op, rule, da, dca, len(ka), db, dcb, len(kb), ok, oc, n_out, w) == (_lib.OK, n_out)
-        assert (_u64(ok[:w * n_out]).reshape(wk.shape) == wk).all() and (_u64(oc[:n_out]) == wc).all()
+        assert (u64(ok[:w * n_out]).reshape(wk.shape) == wk).all() and (u64(oc[:n_out]) == wc).all()
         assert (ok[w * n_out:] == -1).all() and (oc[n_out:] == -1).all()
         # one output without the other; a count array the operation reads missing
         assert _raw(ctx, op, rule, da, dca, len(ka), db, dcb, len(kb), ok, None, n_out, w)[0] == _lib.E_ARG
@@ -403,7 +356,7 @@ def test_sum_wraps_exactly_as_count_merge(ctx, shape):
     assert _same(_dev_setop(ctx, SETOP_UNION, RULE_SUM, ka, ca, kb, cb), want)
     merge = ctx.count_merge if _words(ka) == 1 else ctx.count_merge2
     mk, mc = merge(_dev(ctx, ka), _dev(ctx, ca), _dev(ctx, kb), _dev(ctx, cb))
-    assert _same((_u64(mk), _u64(mc)), want)
+    assert _same((u64(mk), u64(mc)), want)
     got = _dev_compare(ctx, ka, ca, kb, cb)
     assert {k: getattr(got, k) for k in ("sum_a", "sum_max", "sum_min")} == {k: _host_compare(ka, ca, kb, cb)[k] for k in ("sum_a", "sum_max", "sum_min")}
 
@@ -443,7 +396,7 @@ def test_work_buffer_limit_is_the_documented_formula(ctx, shape):
         ctx.set_work_buffer_limit(need)
         wk, wc = _host_setop(SETOP_UNION, RULE_SUM, ka, ca, kb, cb)
         assert _raw(ctx, SETOP_UNION, RULE_SUM, da, dca, len(ka), db, dcb, len(kb), ok, oc, n, w) == (_lib.OK, len(wk))
-        assert (_u64(ok[:w * len(wk)]).reshape(wk.shape) == wk).all() and (_u64(oc[:len(wk)]) == wc).all()
+        assert (u64(ok[:w * len(wk)]).reshape(wk.shape) == wk).all() and (u64(oc[:len(wk)]) == wc).all()
         assert fc(ctx._h, p(da), p(dca), len(ka), p(db), p(dcb), len(kb), C.byref(rec)) == _lib.OK
         assert rec.n_both == _host_compare(ka, ca, kb, cb)["n_both"]
     finally:
@@ -479,7 +432,7 @@ def test_unsorted_tables_stay_inside_the_arrays(ctx):
         oc = torch.full((room + 64,), -1, dtype=torch.int64, device=ctx.device)
         st, n_out = _raw(ctx, op, rule, da, dca, n, db, dcb, n, ok, oc, room, 1)
         assert st == _lib.OK and n_out <= room, (op, rule, st, n_out)
-        assert np.isin(_u64(ok[:n_out]), np.concatenate([ka, kb])).all()
+        assert np.isin(u64(ok[:n_out]), np.concatenate([ka, kb])).all()
         assert (ok[n_out:] == -1).all() and (oc[n_out:] == -1).all()
         ok.fill_(-1)
         oc.fill_(-1)
