@@ -517,6 +517,52 @@ pub fn count_spectrum(ctx: &HipContext, d_counts: &DeviceBuf<'_>, n: u64, n_bins
     d_bins.download::<u64>(n_bins)
 }
 
+/// The table as the node set of a de Bruijn graph (`kmx_count_adjacency`, k in 2..=31): `d_edges[i]` = one bit per neighbour of
+/// entry i that is a present entry (bit c: the successor ending in base c, bit 4 + c: the predecessor starting with it); optional
+/// `d_flips` (the same bits: the neighbour is stored as the reverse complement) and `d_nbr` (8 u64 per entry: the neighbour's
+/// table index, `KMX_NO_ENTRY` where there is no edge).  An entry is present if its count is at least `min_count`.
+pub fn count_adjacency(ctx: &HipContext, table: CountTable<'_>, k: u8, min_count: u64, d_edges: &DeviceBuf<'_>, d_flips: Option<&DeviceBuf<'_>>,
+                       d_nbr: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    table.check(1);
+    let (flips, nbr) = adjacency_outputs(table.n, d_edges, d_flips, d_nbr);
+    ctx.ck(unsafe { kmx_count_adjacency(ctx.0, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, k as u32, min_count,
+                                        d_edges.as_mut_ptr::<u8>(), flips, nbr) })
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_adjacency2`).
+pub fn count_adjacency2(ctx: &HipContext, table: CountTable<'_>, k: u8, min_count: u64, d_edges: &DeviceBuf<'_>, d_flips: Option<&DeviceBuf<'_>>,
+                        d_nbr: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    table.check(2);
+    let (flips, nbr) = adjacency_outputs(table.n, d_edges, d_flips, d_nbr);
+    ctx.ck(unsafe { kmx_count_adjacency2(ctx.0, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, k as u32, min_count,
+                                         d_edges.as_mut_ptr::<u8>(), flips, nbr) })
+}
+
+fn adjacency_outputs(n: u64, d_edges: &DeviceBuf<'_>, d_flips: Option<&DeviceBuf<'_>>, d_nbr: Option<&DeviceBuf<'_>>) -> (*mut u8, *mut u64) {
+    assert!(n as u128 <= d_edges.len() as u128, "edge bytes shorter than the entry count");
+    assert!(d_flips.map_or(true, |f| n as u128 <= f.len() as u128), "flip bytes shorter than the entry count");
+    assert!(d_nbr.map_or(true, |b| n as u128 * 64 <= b.len() as u128), "neighbour indices shorter than 8 per entry");
+    (d_flips.map_or(ptr::null_mut(), |f| f.as_mut_ptr::<u8>()), d_nbr.map_or(ptr::null_mut(), |b| b.as_mut_ptr::<u64>()))
+}
+
+/// How many entries have each edge byte (`kmx_count_edge_histogram`): 256 bins, from which every degree statistic follows.
+pub fn count_edge_histogram(ctx: &HipContext, d_edges: &DeviceBuf<'_>, n: u64) -> Result<Vec<u64>, KmxError> {
+    assert!(n as u128 <= d_edges.len() as u128, "edge bytes shorter than the entry count");
+    let d_bins = ctx.upload(&vec![0u8; 8 * 256])?;
+    ctx.ck(unsafe { kmx_count_edge_histogram(ctx.0, d_edges.as_ptr::<u8>(), n, d_bins.as_mut_ptr::<u64>()) })?;
+    d_bins.download::<u64>(256)
+}
+
+/// Where the non-branching paths end (`kmx_count_unitig_ends`), from the three outputs of `count_adjacency(2)`: bit 0 of
+/// `d_ends[i]` = the successor side of entry i is an end, bit 1 = its predecessor side is.
+pub fn count_unitig_ends(ctx: &HipContext, d_edges: &DeviceBuf<'_>, d_flips: &DeviceBuf<'_>, d_nbr: &DeviceBuf<'_>, n: u64,
+                         d_ends: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    assert!(n as u128 <= d_edges.len().min(d_flips.len()).min(d_ends.len()) as u128, "a byte array shorter than the entry count");
+    assert!(n as u128 * 64 <= d_nbr.len() as u128, "neighbour indices shorter than 8 per entry");
+    ctx.ck(unsafe { kmx_count_unitig_ends(ctx.0, d_edges.as_ptr::<u8>(), d_flips.as_ptr::<u8>(), d_nbr.as_ptr::<u64>(), n,
+                                          d_ends.as_mut_ptr::<u8>()) })
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -353,6 +353,52 @@ int kmx_count_read_stats(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const
 int kmx_count_read_stats2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n,
                           uint64_t solid_min, uint64_t *d_stats);
 
+/* ---------------------------------------------------------------- a count table as the node set of a de Bruijn graph ----
+ * BUILD-DEFINED (the crate has no graph).  A TABLE as above.  With x the key of entry i read as the forward strand and
+ * mask = 2^(2k) - 1, its eight possible neighbours are, for a base c in 0..3,
+ *     edge slot c:      the successor   S_c(x) = (x >> 2) | (c << (2k - 2))     (Kmer::append_base)
+ *     edge slot 4 + c:  the predecessor P_c(x) = ((x << 2) | c) & mask          (Kmer::prepend_base)
+ * and the NODE of a neighbouring word w is canon(w) = min(w, rc(w)) as 2k-bit integers: the word the counters store.  An entry is
+ * PRESENT if d_counts == NULL or d_counts[i] >= min_count; an entry that is not present has no edges and is nobody's neighbour. */
+#define KMX_NO_ENTRY 0xFFFFFFFFFFFFFFFFu /* d_nbr: no such edge (a u64, ~0) */
+
+/* d_edges[i] (one byte per entry): bit e is set iff entry i is present, canon(w_e) is a key of the table and that entry is present.
+ * A self-loop is an edge like any other (the all-A k-mer: S_0(x) = P_0(x) = x).
+ * d_flips[i] (may be NULL): bit e is set iff edge e exists and rc(w_e) < w_e -- the neighbour's stored key is the reverse complement
+ * of the word as spelled on x's strand.  A palindromic neighbour (even k, w == rc(w)) is not flipped; bits of absent edges are 0.
+ * d_nbr[8 * i + e] (may be NULL): the table index of that neighbour, KMX_NO_ENTRY where the edge is absent.
+ * Every byte and word of every output asked for is written.  k in [2,31], KMX_E_K_RANGE otherwise (k = 1 included).  n up to 2^40;
+ * n == 0 is a no-op.  d_edges == NULL with n > 0: KMX_E_ARG.  Outputs must not alias the table.  A table that is not sorted gives
+ * wrong answers, never an access outside the arrays.
+ * Per side four of the eight spellings are four consecutive integers: one search and the keys behind it answer them, and a further
+ * search is made only for a spelling that is the smaller of its pair -- about five searches per entry, not eight.
+ * Working set: the prefix directory of kmx_count_lookup (4 bytes per 8 entries rounded up to a power of two, + 260 bytes), built by
+ * one pass over the keys when n > 8, n < 2^32 and it fits under the work buffer's cap; otherwise it is left out and every search is
+ * a plain binary search.  Same answers either way: the call never fails for lack of work buffer.  With the directory the call uses
+ * the work buffer (a following kmx_fastx_parse cannot reuse its chunk prefixes).
+ * Asynchronous: it only enqueues work on the context's stream unless the work buffer has to grow. */
+int kmx_count_adjacency(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                        uint8_t *d_edges, uint8_t *d_flips, uint64_t *d_nbr);
+/* The same for two-word keys, k in [33,64] (k = 32 is KMX_E_K_RANGE for both calls); d_kmers2 16-byte aligned, KMX_E_ARG otherwise. */
+int kmx_count_adjacency2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                         uint8_t *d_edges, uint8_t *d_flips, uint64_t *d_nbr);
+/* d_hist[b] += the number of entries whose edge byte is b: 256 u64 bins, ACCUMULATED into as kmx_count_spectrum accumulates (the
+ * caller zeroes).  Every degree statistic follows on the host: the low nibble of b holds the successor edges, the high nibble the
+ * predecessor edges -- directed edge slots, isolated entries (b == 0), tips, branching entries, (in = 1, out = 1) interiors.  It
+ * reads edge bytes only: one call for both key widths.  Working set: none (4 KiB of LDS per block).  Asynchronous. */
+int kmx_count_edge_histogram(kmx_ctx *ctx, const uint8_t *d_edges, uint64_t n, uint64_t *d_hist);
+/* Where the non-branching paths (unitigs) end, from the three outputs of kmx_count_adjacency(2) -- it reads indices, not keys: one
+ * call for both key widths.  Bit 0 of d_ends[i] = the successor side of entry i (edge slots 0..3, the low nibble of its edge byte)
+ * is an END, bit 1 = its predecessor side (slots 4..7, the high nibble) is.  A side is an END iff its nibble does not have exactly
+ * one bit set, or its one neighbour j is i itself, or the nibble of j at the side the edge ENTERS does not have exactly one bit set.
+ * A successor edge enters j at its predecessor side, a predecessor edge at its successor side; a flipped edge (its bit in
+ * d_flips[i]) at the other one.  A d_nbr value >= n under a set edge bit (inconsistent inputs) makes that side an END; nothing is
+ * read there.  Entries with edge byte 0 -- isolated, or not present: the counts tell -- have both bits set.  The set bits are twice
+ * the number of unitigs that have an end (a cycle without a branch has none).  All four arrays are required for n > 0 (KMX_E_ARG).
+ * Working set: none.  Asynchronous. */
+int kmx_count_unitig_ends(kmx_ctx *ctx, const uint8_t *d_edges, const uint8_t *d_flips, const uint64_t *d_nbr, uint64_t n,
+                          uint8_t *d_ends);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

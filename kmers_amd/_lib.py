@@ -30,6 +30,8 @@ SETOP_TILE = 2048
 # kmx_count_read_stats(2): the words of a read's row
 RS_N_VALID, RS_N_PRESENT, RS_N_SOLID, RS_MIN, RS_MAX, RS_SUM, RS_MEDIAN, RS_SPAN = range(8)
 RS_WORDS = 8
+# kmx_count_adjacency(2): the word of d_nbr where an edge is absent (KMX_NO_ENTRY; -1 in the int64 tensors of kmers_amd.api)
+NO_ENTRY = 2**64 - 1
 
 
 class KmxError(RuntimeError):
@@ -119,6 +121,10 @@ SIGNATURES = {
     "kmx_count_spectrum": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "kmx_count_filter": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_filter2": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_adjacency": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
+    "kmx_count_adjacency2": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
+    "kmx_count_edge_histogram": (_int, [_vp, _vp, _u64, _vp]),
+    "kmx_count_unitig_ends": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

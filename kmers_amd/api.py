@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -90,6 +90,56 @@ class TableComparison:
     def bray_curtis(self) -> float:
         """the Bray-Curtis dissimilarity 1 - 2 sum_min / (sum_a + sum_b)"""
         return 1.0 - 2.0 * self.sum_min / (self.sum_a + self.sum_b) if self.sum_a + self.sum_b else 0.0
+
+
+_POPCOUNT4 = [bin(v).count("1") for v in range(16)]
+
+
+@dataclasses.dataclass(frozen=True)
+class GraphSummary:
+    """The 256 bins of kmx_count_edge_histogram on the host -- bins[b] = entries whose edge byte is b: the low nibble of b holds the
+    successor edges (out), the high nibble the predecessor edges (in) -- and the degree statistics that follow from them."""
+    bins: tuple
+
+    def _sum(self, pred) -> int:
+        return sum(v for b, v in enumerate(self.bins) if pred(_POPCOUNT4[b >> 4], _POPCOUNT4[b & 15]))
+
+    @property
+    def n_entries(self) -> int:
+        return sum(self.bins)
+
+    @property
+    def n_edges(self) -> int:
+        """directed edge slots: an edge between two entries is listed by both (a self-loop by both sides of one)"""
+        return sum(v * (_POPCOUNT4[b >> 4] + _POPCOUNT4[b & 15]) for b, v in enumerate(self.bins))
+
+    @property
+    def n_isolated(self) -> int:
+        """entries without an edge (entries that are not present among them)"""
+        return self.bins[0]
+
+    @property
+    def n_tips(self) -> int:
+        """entries with edges on one side only: dead ends"""
+        return self._sum(lambda i, o: (i == 0) != (o == 0))
+
+    @property
+    def n_branching(self) -> int:
+        """entries with more than one edge on a side"""
+        return self._sum(lambda i, o: i > 1 or o > 1)
+
+    @property
+    def n_interior(self) -> int:
+        """entries with exactly one predecessor and one successor"""
+        return self._sum(lambda i, o: i == 1 and o == 1)
+
+    @property
+    def degrees(self) -> np.ndarray:
+        """int64[5, 5]: degrees[i, o] = entries with i predecessor edges and o successor edges"""
+        m = np.zeros((5, 5), np.int64)
+        for b, v in enumerate(self.bins):
+            m[_POPCOUNT4[b >> 4], _POPCOUNT4[b & 15]] += v
+        return m
 
 
 def _on_ctx_stream(fn):
@@ -472,6 +522,52 @@ class Context:
     def count_filter2(self, kmers, counts, min_count=1, max_count=2**64 - 1, max_out=None):
         """kmx_count_filter2 -> (kmers int64[n, 2], counts) for the tables of count_canonical2."""
         return self._filter(self.lib.kmx_count_filter2, 2, kmers, counts, min_count, max_count, max_out)
+
+    # ------------------------------------------------------------ a count table as a de Bruijn graph
+    def _adjacency(self, fn, words, kmers, counts, k, min_count, flips, neighbors):
+        n = int(kmers.numel()) // words
+        kmers = kmers.contiguous()
+        edges = self.empty(n, torch.uint8)
+        fl = self.empty(n, torch.uint8) if flips else None
+        nb = self.empty(8 * n, torch.int64) if neighbors else None
+        self._ck(fn(self._h, _ptr(kmers) if n else None, _ptr(counts) if counts is not None and n else None, n, k, int(min_count),
+                    _ptr(edges) if n else None, _ptr(fl) if n else None, _ptr(nb) if n else None))
+        out = (edges,) + ((fl,) if flips else ()) + ((nb.view(-1, 8),) if neighbors else ())
+        return out if len(out) > 1 else edges
+
+    @_on_ctx_stream
+    def count_adjacency(self, kmers, counts, k, min_count=1, flips=False, neighbors=False):
+        """kmx_count_adjacency -> edges uint8[n][, flips uint8[n]][, nbr int64[n, 8]]: the table (kmers, counts) as the node set of a de
+        Bruijn graph.  Bit c of edges[i] = the successor of entry i that ends in base c is a present entry, bit 4 + c = the predecessor
+        that starts with base c is; the same bit of flips[i] = that neighbour is stored as the reverse complement of the word as
+        spelled on entry i's strand; nbr[i, e] = its table index, -1 (the u64 KMX_NO_ENTRY) where there is no edge.  An entry is
+        present if its count is at least min_count (counts=None: every entry is).  k 2..31."""
+        return self._adjacency(self.lib.kmx_count_adjacency, 1, kmers, counts, k, min_count, flips, neighbors)
+
+    @_on_ctx_stream
+    def count_adjacency2(self, kmers, counts, k, min_count=1, flips=False, neighbors=False):
+        """kmx_count_adjacency2 (k 33..64): kmers int64[n, 2] = (low, high) words."""
+        return self._adjacency(self.lib.kmx_count_adjacency2, 2, kmers, counts, k, min_count, flips, neighbors)
+
+    @_on_ctx_stream
+    def count_edge_histogram(self, edges, out=None) -> GraphSummary:
+        """kmx_count_edge_histogram -> GraphSummary of the 256 bins; `out` (int64[256], device) is accumulated into and summarised."""
+        if out is None:
+            out = torch.zeros(256, dtype=torch.int64, device=self.device)
+        n = int(edges.numel())
+        self._ck(self.lib.kmx_count_edge_histogram(self._h, _ptr(edges) if n else None, n, _ptr(out)))
+        return GraphSummary(tuple(int(v) for v in u64_numpy(out)))
+
+    @_on_ctx_stream
+    def count_unitig_ends(self, edges, flips, nbr):
+        """kmx_count_unitig_ends -> uint8[n] from the three outputs of count_adjacency(2): bit 0 = the successor side of the entry ends
+        a non-branching path, bit 1 = its predecessor side does (both for an entry without edges)."""
+        n = int(edges.numel())
+        nbr = nbr.contiguous()
+        ends = self.empty(n, torch.uint8)
+        self._ck(self.lib.kmx_count_unitig_ends(self._h, _ptr(edges) if n else None, _ptr(flips) if n else None, _ptr(nbr) if n else None, n,
+                                                _ptr(ends) if n else None))
+        return ends
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

@@ -1070,6 +1070,53 @@ int kmx_count_filter2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_
     return filter_impl(ctx, "kmx_count_filter2", 2u, d_kmers2, d_counts, n, min_count, max_count, d_kmers2_out, d_counts_out, max_out, h_n_out);
 }
 
+// ---- a count table as the node set of a de Bruijn graph (kmx_count_graph.hip) ----
+// One body for both key widths.  8 * n neighbour words are asked of n keys, so the directory is built whenever the lookup would build
+// one for that many queries (n above one line of keys, n < 2^32) and it fits under the cap; otherwise the plain search, which needs no
+// work buffer: never KMX_E_NOMEM from here.
+static int adjacency_impl(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k,
+                          uint64_t min_count, uint8_t* d_edges, uint8_t* d_flips, uint64_t* d_nbr) {
+    if (!ctx || (n && (!d_kmers || !d_edges)) || n > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < (kind.words == 1u ? 2u : kind.k_min) || k > kind.k_max) return KMX_E_K_RANGE;   // (a word of one base has no overlap to share)
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    void* dir = nullptr;
+    uint32_t p = 0;
+    const size_t dir_bytes = kmx::count_lookup_dir_bytes(n, k, &p);
+    if (dir_bytes != 0 && kmx::count_lookup_wants_dir(n, 8u * n, kind.words) && dir_bytes <= hist_scratch_budget(ctx->big_bytes, ctx->big_limit)) {
+        if ((dir = big_scratch(ctx, dir_bytes))) ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    }
+    KMX_HIP(ctx, kmx::launch_count_adjacency(kind.words, d_kmers, d_counts, n, k, min_count, d_edges, d_flips, d_nbr, dir, p, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_adjacency(kmx_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                        uint8_t* d_edges, uint8_t* d_flips, uint64_t* d_nbr) {
+    return adjacency_impl(ctx, kQuery1, d_kmers, d_counts, n, k, min_count, d_edges, d_flips, d_nbr);
+}
+
+int kmx_count_adjacency2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                         uint8_t* d_edges, uint8_t* d_flips, uint64_t* d_nbr) {
+    return adjacency_impl(ctx, kQuery2, d_kmers2, d_counts, n, k, min_count, d_edges, d_flips, d_nbr);
+}
+
+int kmx_count_edge_histogram(kmx_ctx* ctx, const uint8_t* d_edges, uint64_t n, uint64_t* d_hist) {
+    if (!ctx || !d_hist || (n && !d_edges) || n > (1ull << 40)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_edge_histogram(d_edges, n, d_hist, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_unitig_ends(kmx_ctx* ctx, const uint8_t* d_edges, const uint8_t* d_flips, const uint64_t* d_nbr, uint64_t n, uint8_t* d_ends) {
+    if (!ctx || (n && (!d_edges || !d_flips || !d_nbr || !d_ends)) || n > (1ull << 40)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_unitig_ends(d_edges, d_flips, d_nbr, n, d_ends, ctx->stream));
+    return KMX_OK;
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

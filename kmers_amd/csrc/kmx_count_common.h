@@ -1,5 +1,6 @@
 // kmx_count_common.h -- what the count family shares: kmx_count.hip (the counter and the merge, one source for one-word keys,
-// k <= 31, and two-word keys, k = 33..64), kmx_count_query.hip, kmx_count_setop.hip and kmx_count_read_stats.hip.  On the device: the
+// k <= 31, and two-word keys, k = 33..64), kmx_count_query.hip, kmx_count_setop.hip, kmx_count_read_stats.hip and kmx_count_graph.hip
+// (the query and the graph source through kmx_count_dir.h, the directory their searches share).  On the device: the
 // key of W words (Key<W>: the one type every kernel of the family is templated on), block scans and the block sum, the records a
 // level leaves for the host and for the leaf kernels, and the compaction of marked entries (the count of the marked bytes and the
 // wave-ballot copy, compact_write_kernel: the counter's and the filter's).  On the host: the launchers' tail that brings one record
@@ -47,6 +48,14 @@ template <> struct Key<1> {
     __device__ __forceinline__ bool outside(u32 k) const { return (lo >> (2u * k)) != 0u; }
     // the top p bits of the 2k-bit key (0 < p <= 2k)
     __device__ __forceinline__ u64 prefix(u32 k, u32 p) const { return lo >> (2u * k - p); }
+    // The key as a word of k bases (the graph layer, k >= 2): one base up with the top base dropped (Kmer::prepend_base with base 0),
+    // one base down (Kmer::append_base before the new base goes in), the top base, base c at a top position that holds 0, and the
+    // reverse complement (the element-wise kernels' revcomp_word).
+    __device__ __forceinline__ Key shl_base(u32 k) const { return Key{(lo << 2) & mask2k(k)}; }
+    __device__ __forceinline__ Key shr_base() const { return Key{lo >> 2}; }
+    __device__ __forceinline__ u32 top_base(u32 k) const { return (u32)(lo >> (2u * k - 2u)) & 3u; }
+    __device__ __forceinline__ Key with_top(u32 k, u32 c) const { return Key{lo | ((u64)c << (2u * k - 2u))}; }
+    __device__ __forceinline__ Key revcomp(u32 k) const { return Key{revcomp_word(lo, k)}; }
 };
 template <> struct alignas(16) Key<2> {
     u64 lo, hi;
@@ -74,6 +83,18 @@ template <> struct alignas(16) Key<2> {
     __device__ __forceinline__ u64 prefix(u32 k, u32 p) const {
         const u32 s = 2u * k - p;
         return s >= 64u ? hi >> (s - 64u) : (hi << (64u - s)) | (lo >> s);
+    }
+    // (as above; the high word holds 2k - 64 bits, 2 .. 64 of them; the reverse complement is the 128-bit group reversal of the scans)
+    __device__ __forceinline__ Key shl_base(u32 k) const {
+        const u64 m = k >= 64u ? ~0ull : (1ull << (2u * k - 64u)) - 1ull;
+        return Key{lo << 2, ((hi << 2) | (lo >> 62)) & m};
+    }
+    __device__ __forceinline__ Key shr_base() const { return Key{(lo >> 2) | (hi << 62), hi >> 2}; }
+    __device__ __forceinline__ u32 top_base(u32 k) const { return (u32)(hi >> (2u * k - 66u)) & 3u; }
+    __device__ __forceinline__ Key with_top(u32 k, u32 c) const { return Key{lo, hi | ((u64)c << (2u * k - 66u))}; }
+    __device__ __forceinline__ Key revcomp(u32 k) const {
+        const U128 r = lex_hash128(U128{~lo, ~hi}, k);
+        return Key{r.lo, r.hi};
     }
 };
 static_assert(sizeof(Key<1>) == 8 && sizeof(Key<2>) == 16, "a key is one element of W words");

@@ -5,8 +5,7 @@
 // what hides the chain is the number of chains in flight.  Two routes, one kernel:
 //   directory  dir[j] = index of the first key whose top p bits (counted down from bit 2k, as the counter's MSD partition counts
 //              them) are >= j, j = 0 .. 2^p; p from n so that a bin holds about LINE keys when keys are evenly spread.  Built per
-//              call by one streaming pass over the keys (a wave per 64 keys: where the prefix steps from a to b the wave's lanes
-//              write dir[a + 1 .. b] together, so a run of empty bins -- canonical keys are skewed -- is not one lane's loop).
+//              call by one streaming pass over the keys (kmx_count_dir.h: bin_of, dir_build_kernel, shared with the adjacency).
 //              Per query: dir[j], dir[j + 1], then the search confined to that bin.
 //   plain      the same search over [0, n): few queries against a large table (the pass over the keys would cost more than it
 //              saves), a directory above the work buffer's cap, a table of 2^32 entries or more (directory entries are 4 bytes).
@@ -21,48 +20,15 @@
 //
 // Filter.  A mark byte per entry, then the counters' compaction, all of it in kmx_count_common.h: keep_count_kernel, the block
 // scans, and the wave-ballot copy of the marked entries (compact_write_kernel<W, 1>: a table's counts are plain u64).
-#include "kmx_count_common.h"
+#include "kmx_count_dir.h"
 
 namespace kmx {
 
 namespace {
 
-constexpr u32 LINE = 8;          // keys the last step of a search loads at once (one-word keys: a 64-byte line; two-word: 128 bytes)
 constexpr u32 QPL = 4;           // queries per lane, in lockstep
-constexpr u32 DIR_MAX_BITS = 28; // at most 2^28 + 1 directory entries (1 GiB)
 constexpr u32 SPEC_LDS = 4096;   // spectrum bins held in LDS per block (16 KiB)
 constexpr u32 SPEC_IPT = 16;     // entries per thread and grid step of the spectrum
-
-// the bin of a key; anything a table should not hold (a bit at or above 2k) lands in the last bin instead of outside the directory
-template <u32 W>
-__device__ __forceinline__ u64 bin_of(const Key<W>& key, u32 k, u32 p) {
-    if (p == 0u) return 0u;
-    const u64 last = (1ull << p) - 1ull;
-    if (key.outside(k)) return last;
-    const u64 j = key.prefix(k, p);
-    return j > last ? last : j;
-}
-
-// ---------------------------------------------------------------- the directory
-// One streaming pass: lane i compares the bin of key i with the bin of key i - 1 (key -1: bin "-1", so dir[0 .. bin(key 0)] = 0;
-// behind the last key: bin 2^p, so the tail of the directory = n).  Every entry is written exactly once when keys ascend.
-template <u32 W>
-__global__ void __launch_bounds__(CT) dir_build_kernel(const u64* __restrict__ keys, u64 n, u32 k, u32 p, u32* __restrict__ dir) {
-    const u64 i = (u64)blockIdx.x * CT + threadIdx.x;   // 0 .. n: position n closes the directory
-    const u32 lane = threadIdx.x & 63u;
-    u64 from = 1u, to = 0u;   // this lane's entries: dir[from .. to] = i
-    if (i <= n) {
-        to = i < n ? bin_of<W>(Key<W>::load(keys, i), k, p) : (1ull << p);
-        from = i == 0u ? 0u : bin_of<W>(Key<W>::load(keys, i - 1u), k, p) + 1u;
-    }
-    unsigned long long todo = __ballot(from <= to);
-    while (todo) {
-        const int src = __ffsll(todo) - 1;
-        todo &= todo - 1ull;
-        const u64 f = __shfl(from, src), t = __shfl(to, src), v = __shfl(i, src);
-        for (u64 j = f + lane; j <= t; j += 64u) dir[j] = (u32)v;
-    }
-}
 
 // ---------------------------------------------------------------- the lookup
 // out[i] = count of query[i] (1 with counts == nullptr), 0 if absent or the query's flag lacks KMX_WIN_VALID.  `out` may be `query`

@@ -152,6 +152,12 @@ hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* count
 // W windows; ragged reads: W = the most windows a read is expected to have, 0 = unknown)
 hipError_t launch_count_read_stats(const u64* counts, const uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u64 solid_min, u64* stats,
                                    int n_cu, hipStream_t st);
+// kmx_count_graph.hip: a count table as the node set of a de Bruijn graph (dir_area: room for count_lookup_dir_bytes(n, k, &p), or
+// nullptr = the plain search; flips and nbr may be nullptr)
+hipError_t launch_count_adjacency(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, u64 min_count, uint8_t* edges, uint8_t* flips,
+                                  u64* nbr, void* dir_area, u32 p, hipStream_t st);
+hipError_t launch_count_edge_histogram(const uint8_t* edges, u64 n, u64* hist, int n_cu, hipStream_t st);
+hipError_t launch_count_unitig_ends(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, uint8_t* ends, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
