@@ -563,6 +563,83 @@ pub fn count_unitig_ends(ctx: &HipContext, d_edges: &DeviceBuf<'_>, d_flips: &De
                                           d_ends.as_mut_ptr::<u8>()) })
 }
 
+/// The device arrays `count_unitigs(2)` fills: `d_nodes` (n u64), `d_offsets` (n + 1 u64), optional `d_circular` (n bytes) and
+/// `d_count_sums` (n u64).
+pub struct UnitigOutputs<'a> {
+    pub d_nodes: &'a DeviceBuf<'a>,
+    pub d_offsets: &'a DeviceBuf<'a>,
+    pub d_circular: Option<&'a DeviceBuf<'a>>,
+    pub d_count_sums: Option<&'a DeviceBuf<'a>>,
+}
+
+impl UnitigOutputs<'_> {
+    fn check(&self, n: u64) -> (*mut u8, *mut u64) {
+        assert!(n as u128 * 8 <= self.d_nodes.len() as u128, "unitig nodes shorter than the entry count");
+        assert!((n as u128 + 1) * 8 <= self.d_offsets.len() as u128, "unitig offsets shorter than the entry count + 1");
+        assert!(self.d_circular.map_or(true, |c| n as u128 <= c.len() as u128), "circular flags shorter than the entry count");
+        assert!(self.d_count_sums.map_or(true, |c| n as u128 * 8 <= c.len() as u128), "count sums shorter than the entry count");
+        (self.d_circular.map_or(ptr::null_mut(), |c| c.as_mut_ptr::<u8>()), self.d_count_sums.map_or(ptr::null_mut(), |c| c.as_mut_ptr::<u64>()))
+    }
+}
+
+fn unitig_inputs(n: u64, d_edges: &DeviceBuf<'_>, d_flips: &DeviceBuf<'_>, d_nbr: &DeviceBuf<'_>) {
+    assert!(n as u128 <= d_edges.len().min(d_flips.len()) as u128, "a byte array shorter than the entry count");
+    assert!(n as u128 * 64 <= d_nbr.len() as u128, "neighbour indices shorter than 8 per entry");
+}
+
+/// The unitigs of the table's de Bruijn graph (`kmx_count_unitigs`, k in 2..=31) from the three outputs of `count_adjacency` made
+/// with the same `min_count`: the oriented nodes `2 * entry + o` of the canonical unitigs one after another, their offsets, circular
+/// flags and count sums (include/kmx.h has the definitions).  Returns (unitigs, nodes).  Synchronous.
+pub fn count_unitigs(ctx: &HipContext, table: CountTable<'_>, k: u8, min_count: u64, d_edges: &DeviceBuf<'_>, d_flips: &DeviceBuf<'_>,
+                     d_nbr: &DeviceBuf<'_>, out: &UnitigOutputs<'_>) -> Result<(u64, u64), KmxError> {
+    table.check(1);
+    unitig_inputs(table.n, d_edges, d_flips, d_nbr);
+    let (circular, sums) = out.check(table.n);
+    let (mut n_unitigs, mut n_nodes) = (0u64, 0u64);
+    ctx.ck(unsafe { kmx_count_unitigs(ctx.0, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, k as u32, min_count, d_edges.as_ptr::<u8>(),
+                                      d_flips.as_ptr::<u8>(), d_nbr.as_ptr::<u64>(), out.d_nodes.as_mut_ptr::<u64>(),
+                                      out.d_offsets.as_mut_ptr::<u64>(), circular, sums, &mut n_unitigs, &mut n_nodes) })?;
+    Ok((n_unitigs, n_nodes))
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_unitigs2`).
+pub fn count_unitigs2(ctx: &HipContext, table: CountTable<'_>, k: u8, min_count: u64, d_edges: &DeviceBuf<'_>, d_flips: &DeviceBuf<'_>,
+                      d_nbr: &DeviceBuf<'_>, out: &UnitigOutputs<'_>) -> Result<(u64, u64), KmxError> {
+    table.check(2);
+    unitig_inputs(table.n, d_edges, d_flips, d_nbr);
+    let (circular, sums) = out.check(table.n);
+    let (mut n_unitigs, mut n_nodes) = (0u64, 0u64);
+    ctx.ck(unsafe { kmx_count_unitigs2(ctx.0, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, k as u32, min_count, d_edges.as_ptr::<u8>(),
+                                       d_flips.as_ptr::<u8>(), d_nbr.as_ptr::<u64>(), out.d_nodes.as_mut_ptr::<u64>(),
+                                       out.d_offsets.as_mut_ptr::<u64>(), circular, sums, &mut n_unitigs, &mut n_nodes) })?;
+    Ok((n_unitigs, n_nodes))
+}
+
+/// The bases of the unitigs, ASCII (`kmx_count_unitig_sequences`): unitig u starts at byte `offsets[u] + u * (k - 1)` of `d_seq`,
+/// which holds `n_nodes + n_unitigs * (k - 1)` bytes.  Asynchronous.
+pub fn count_unitig_sequences(ctx: &HipContext, table: CountTable<'_>, k: u8, d_nodes: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64,
+                              n_nodes: u64, d_seq: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    table.check(1);
+    unitig_sequence_arrays(k, d_nodes, d_offsets, n_unitigs, n_nodes, d_seq);
+    ctx.ck(unsafe { kmx_count_unitig_sequences(ctx.0, table.keys.as_ptr::<u64>(), table.n, k as u32, d_nodes.as_ptr::<u64>(),
+                                               d_offsets.as_ptr::<u64>(), n_unitigs, d_seq.as_mut_ptr::<u8>()) })
+}
+
+/// The same for two-word keys (`kmx_count_unitig_sequences2`).
+pub fn count_unitig_sequences2(ctx: &HipContext, table: CountTable<'_>, k: u8, d_nodes: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64,
+                               n_nodes: u64, d_seq: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    table.check(2);
+    unitig_sequence_arrays(k, d_nodes, d_offsets, n_unitigs, n_nodes, d_seq);
+    ctx.ck(unsafe { kmx_count_unitig_sequences2(ctx.0, table.keys.as_ptr::<u64>(), table.n, k as u32, d_nodes.as_ptr::<u64>(),
+                                                d_offsets.as_ptr::<u64>(), n_unitigs, d_seq.as_mut_ptr::<u8>()) })
+}
+
+fn unitig_sequence_arrays(k: u8, d_nodes: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64, n_nodes: u64, d_seq: &DeviceBuf<'_>) {
+    assert!(n_nodes as u128 * 8 <= d_nodes.len() as u128, "unitig nodes shorter than the node count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!(n_nodes as u128 + n_unitigs as u128 * (k as u128 - 1) <= d_seq.len() as u128, "sequence bytes shorter than nodes + unitigs * (k - 1)");
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

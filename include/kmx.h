@@ -399,6 +399,50 @@ int kmx_count_edge_histogram(kmx_ctx *ctx, const uint8_t *d_edges, uint64_t n, u
 int kmx_count_unitig_ends(kmx_ctx *ctx, const uint8_t *d_edges, const uint8_t *d_flips, const uint64_t *d_nbr, uint64_t n,
                           uint8_t *d_ends);
 
+/* ---------------------------------------------------------------- the unitigs of that graph ----
+ * BUILD-DEFINED.  From a table and the three outputs of kmx_count_adjacency(2) (same d_counts / min_count: PRESENT as above) to the
+ * maximal non-branching paths, as lists of oriented nodes, and to their bases.
+ * The ORIENTED NODE v = 2 i + o is entry i read forward (o = 0: its word is the key x, it is left through the successor side) or
+ * reverse (o = 1: its word is rc(x), it is left through the predecessor side); mirror(v) = v ^ 1.
+ * next(v) = 2 j + (o ^ f) exists iff entry i is present; side o of i is not an END by the rule of kmx_count_unitig_ends; the one
+ * set edge slot e of that side has d_nbr[8 i + e] = j < n, with flip bit f; neither i nor j is a palindrome (x == rc(x), even k
+ * only: without this rule a path y -> palindrome z -> rc(y) makes next non-injective); and the link is mutual,
+ * next(mirror(next(v))) == mirror(v).  For inputs that are the adjacency of the table mutuality follows from the rest; it is there
+ * so that ANY bytes in d_edges / d_flips / d_nbr give disjoint simple paths and cycles: the call ends, succeeds and reads nothing
+ * outside its arrays.  prev(v) = mirror(next(mirror(v))).  A palindromic entry is a unitig of its own.
+ * A chain runs from a head (no prev) along next to a tail; its mirror chain has head mirror(tail) and tail mirror(head).  Of the
+ * two the CANONICAL one has the smaller head entry index, at equal indices (one node) the one with o = 0.  Oriented nodes on no
+ * chain lie on cycles, which come in mirror pairs too: the canonical one contains 2 i*, i* the cycle's smallest entry index, and
+ * is written starting there.  Unitigs are ordered by ascending head entry index (an entry heads at most one); every present entry
+ * lies in exactly one, entries that are not present in none.
+ * d_nodes (room for n u64): the oriented nodes of the canonical unitigs, one unitig after another.  d_offsets (room for n + 1):
+ * U + 1 offsets into d_nodes.  d_circular (may be NULL; room for n bytes): 1 for a cycle.  d_count_sums (may be NULL; room for n
+ * u64): the wrapping sum of the counts of the unitig's entries; with d_counts == NULL every entry counts 1.  Only the first
+ * *h_n_nodes, U + 1, U and U elements are written, U = *h_n_unitigs.  Exact and deterministic.
+ * d_kmers is read at even k only (it may be NULL at odd k).  k in [2,31] (KMX_E_K_RANGE); n up to 2^40; n == 0 is a no-op with both
+ * host counts 0.  A required array missing with n > 0: KMX_E_ARG.  Outputs must not alias inputs.
+ * Working set: 64 bytes per entry + n / 16 + 2 KiB in the work buffer -- two 16-byte rank records per oriented node (pointer
+ * jumping reads one set and writes the other) -- KMX_E_NOMEM above the cap (kmx_ctx_set_work_buffer_limit), nothing written then.
+ * ceil(log2(longest unitig)) + 2 rounds at most, each a pass over the records with one 16-byte gather per unfinished node and one
+ * host read-back.  Synchronous, as kmx_count_canonical is. */
+int kmx_count_unitigs(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                      const uint8_t *d_edges, const uint8_t *d_flips, const uint64_t *d_nbr, uint64_t *d_nodes, uint64_t *d_offsets,
+                      uint8_t *d_circular, uint64_t *d_count_sums, uint64_t *h_n_unitigs, uint64_t *h_n_nodes);
+/* The same for two-word keys, k in [33,64]; d_kmers2 16-byte aligned, KMX_E_ARG otherwise. */
+int kmx_count_unitigs2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                       const uint8_t *d_edges, const uint8_t *d_flips, const uint64_t *d_nbr, uint64_t *d_nodes, uint64_t *d_offsets,
+                       uint8_t *d_circular, uint64_t *d_count_sums, uint64_t *h_n_unitigs, uint64_t *h_n_nodes);
+/* The bases of the unitigs, ASCII ACGT.  A unitig of m nodes spells m + k - 1 bases: the k bases of its first oriented node's word
+ * (base 0 = the lowest two bits), then the top base of each following oriented word (o = 1: the complement of the key's lowest
+ * base).  A circular unitig is spelled the same way from its start; the wrap-around is not repeated.  Unitig u starts at byte
+ * d_offsets[u] + u (k - 1) of d_seq -- a closed form, there is no second offsets array -- and d_seq holds
+ * d_offsets[n_unitigs] + n_unitigs (k - 1) bytes.  n is the table's entry count (nodes naming an entry >= n are skipped).
+ * n_unitigs == 0 is a no-op; n_unitigs > n or a missing array: KMX_E_ARG.  Working set: none.  Asynchronous. */
+int kmx_count_unitig_sequences(kmx_ctx *ctx, const uint64_t *d_kmers, uint64_t n, uint32_t k, const uint64_t *d_nodes, const uint64_t *d_offsets,
+                               uint64_t n_unitigs, uint8_t *d_seq);
+int kmx_count_unitig_sequences2(kmx_ctx *ctx, const uint64_t *d_kmers2, uint64_t n, uint32_t k, const uint64_t *d_nodes, const uint64_t *d_offsets,
+                                uint64_t n_unitigs, uint8_t *d_seq);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

@@ -125,6 +125,10 @@ SIGNATURES = {
     "kmx_count_adjacency2": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "kmx_count_edge_histogram": (_int, [_vp, _vp, _u64, _vp]),
     "kmx_count_unitig_ends": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "kmx_count_unitigs": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_count_unitigs2": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_count_unitig_sequences": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_unitig_sequences2": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

@@ -142,6 +142,47 @@ class GraphSummary:
         return m
 
 
+@dataclasses.dataclass
+class Unitigs:
+    """What kmx_count_unitigs(2) returns: the canonical unitigs of a count table's de Bruijn graph, in order of their head entries.
+    nodes int64[n_nodes]: the oriented nodes 2 * entry + o (o = 1: the entry read as its reverse complement), one unitig after
+    another; offsets int64[n_unitigs + 1] into nodes; circular uint8[n_unitigs]; count_sums int64[n_unitigs] (the u64 wrapping sums of
+    the entries' counts).  `kmers` is the table's key tensor, kept for the sequences."""
+    nodes: "torch.Tensor"
+    offsets: "torch.Tensor"
+    circular: "torch.Tensor"
+    count_sums: "torch.Tensor"
+    n_unitigs: int
+    k: int
+    kmers: "torch.Tensor" = dataclasses.field(repr=False, default=None)
+    _ctx: "Context" = dataclasses.field(repr=False, default=None)
+    _seq: "torch.Tensor" = dataclasses.field(repr=False, default=None)
+
+    @property
+    def n_nodes(self) -> int:
+        return int(self.nodes.numel())
+
+    @property
+    def lengths(self):
+        """int64[n_unitigs]: nodes per unitig (its sequence has k - 1 bases more)"""
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def sequences(self):
+        """kmx_count_unitig_sequences(2) -> uint8[n_nodes + n_unitigs * (k - 1)], ASCII ACGT: unitig u starts at byte
+        offsets[u] + u * (k - 1) and has lengths[u] + k - 1 bases.  Computed once and kept."""
+        if self._seq is None:
+            self._seq = self._ctx._unitig_sequences(self)
+        return self._seq
+
+    def sequence(self, u: int) -> bytes:
+        """the bases of unitig u, on the host"""
+        if not 0 <= u < self.n_unitigs:
+            raise IndexError(u)
+        lo, hi = (int(v) for v in self.offsets[u:u + 2].cpu())
+        at = lo + u * (self.k - 1)
+        return bytes(self.sequences()[at:at + (hi - lo) + self.k - 1].cpu().numpy())
+
+
 def _on_ctx_stream(fn):
     """Run a Context method with Context.stream as torch's current stream (see "Stream discipline" above)."""
     @functools.wraps(fn)
@@ -568,6 +609,47 @@ class Context:
         self._ck(self.lib.kmx_count_unitig_ends(self._h, _ptr(edges) if n else None, _ptr(flips) if n else None, _ptr(nbr) if n else None, n,
                                                 _ptr(ends) if n else None))
         return ends
+
+    def _unitigs(self, words, kmers, counts, k, min_count, adjacency):
+        n = int(kmers.numel()) // words
+        kmers = kmers.contiguous()
+        if adjacency is None:
+            adjacency = (self.count_adjacency if words == 1 else self.count_adjacency2)(kmers, counts, k, min_count, flips=True, neighbors=True)
+        edges, flips, nbr = adjacency
+        nbr = nbr.contiguous()
+        nodes, offsets = self.empty(n, torch.int64), self.empty(n + 1, torch.int64)
+        circular, sums = self.empty(n, torch.uint8), self.empty(n, torch.int64)
+        n_unitigs, n_nodes = C.c_uint64(0), C.c_uint64(0)
+        fn = self.lib.kmx_count_unitigs if words == 1 else self.lib.kmx_count_unitigs2
+        self._ck(fn(self._h, _ptr(kmers) if n else None, _ptr(counts) if counts is not None and n else None, n, k, int(min_count),
+                    _ptr(edges) if n else None, _ptr(flips) if n else None, _ptr(nbr) if n else None, _ptr(nodes) if n else None, _ptr(offsets),
+                    _ptr(circular) if n else None, _ptr(sums) if n else None, C.byref(n_unitigs), C.byref(n_nodes)))
+        u = int(n_unitigs.value)
+        if n == 0:
+            offsets.zero_()
+        return Unitigs(nodes[:int(n_nodes.value)], offsets[:u + 1], circular[:u], sums[:u], u, k, kmers, self)
+
+    @_on_ctx_stream
+    def count_unitigs(self, kmers, counts, k, min_count=1, adjacency=None) -> Unitigs:
+        """kmx_count_unitigs -> Unitigs: the maximal non-branching paths of the table's de Bruijn graph as ordered lists of oriented
+        nodes (include/kmx.h has the definitions).  adjacency = (edges, flips, nbr) as count_adjacency(..., flips=True,
+        neighbors=True) returns them for the same counts and min_count; without it that call is made here.  k 2..31."""
+        return self._unitigs(1, kmers, counts, k, min_count, adjacency)
+
+    @_on_ctx_stream
+    def count_unitigs2(self, kmers, counts, k, min_count=1, adjacency=None) -> Unitigs:
+        """kmx_count_unitigs2 (k 33..64): kmers int64[n, 2] = (low, high) words."""
+        return self._unitigs(2, kmers, counts, k, min_count, adjacency)
+
+    @_on_ctx_stream
+    def _unitig_sequences(self, u: Unitigs):
+        words = 1 if u.kmers.dim() == 1 else 2
+        n = int(u.kmers.numel()) // words
+        seq = self.empty(u.n_nodes + u.n_unitigs * (u.k - 1), torch.uint8)
+        fn = self.lib.kmx_count_unitig_sequences if words == 1 else self.lib.kmx_count_unitig_sequences2
+        if u.n_unitigs:
+            self._ck(fn(self._h, _ptr(u.kmers), n, u.k, _ptr(u.nodes), _ptr(u.offsets), u.n_unitigs, _ptr(seq)))
+        return seq
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

@@ -1117,6 +1117,72 @@ int kmx_count_unitig_ends(kmx_ctx* ctx, const uint8_t* d_edges, const uint8_t* d
     return KMX_OK;
 }
 
+// ---- the unitigs of that graph (kmx_count_unitigs.hip) ----
+// One body for both key widths.  The keys are read at even k only (the palindromes), so they may be NULL at odd k.
+static int unitigs_impl(kmx_ctx* ctx, const QueryKind& kind, const char* who, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k,
+                        uint64_t min_count, const uint8_t* d_edges, const uint8_t* d_flips, const uint64_t* d_nbr, uint64_t* d_nodes, uint64_t* d_offsets,
+                        uint8_t* d_circular, uint64_t* d_count_sums, uint64_t* h_n_unitigs, uint64_t* h_n_nodes) {
+    if (!ctx || !h_n_unitigs || !h_n_nodes || n > (1ull << 40)) return KMX_E_ARG;
+    if (n && (!d_edges || !d_flips || !d_nbr || !d_nodes || !d_offsets)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < (kind.words == 1u ? 2u : kind.k_min) || k > kind.k_max) return KMX_E_K_RANGE;
+    if (n && (k & 1u) == 0u && !d_kmers) return KMX_E_ARG;
+    *h_n_unitigs = *h_n_nodes = 0;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::count_unitigs_bytes(n), &area)) return st;
+    uint64_t n_unitigs = 0, n_nodes = 0;
+    uint32_t rounds = 0;
+    bool bad = false;
+    KMX_HIP(ctx, kmx::launch_count_unitigs(kind.words, d_kmers, d_counts, n, k, min_count, d_edges, d_flips, d_nbr, d_nodes, d_offsets, d_circular,
+                                           d_count_sums, area, ctx->h_pinned, &n_unitigs, &n_nodes, &rounds, &bad, ctx->stream));
+    if (bad) {
+        char msg[96];
+        std::snprintf(msg, sizeof msg, "%s: ranking did not end", who);
+        return fail_hip(ctx, hipErrorUnknown, msg);
+    }
+    *h_n_unitigs = n_unitigs;
+    *h_n_nodes = n_nodes;
+    return KMX_OK;
+}
+
+int kmx_count_unitigs(kmx_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                      const uint8_t* d_edges, const uint8_t* d_flips, const uint64_t* d_nbr, uint64_t* d_nodes, uint64_t* d_offsets,
+                      uint8_t* d_circular, uint64_t* d_count_sums, uint64_t* h_n_unitigs, uint64_t* h_n_nodes) {
+    return unitigs_impl(ctx, kQuery1, "kmx_count_unitigs", d_kmers, d_counts, n, k, min_count, d_edges, d_flips, d_nbr, d_nodes, d_offsets, d_circular,
+                        d_count_sums, h_n_unitigs, h_n_nodes);
+}
+
+int kmx_count_unitigs2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n, uint32_t k, uint64_t min_count,
+                       const uint8_t* d_edges, const uint8_t* d_flips, const uint64_t* d_nbr, uint64_t* d_nodes, uint64_t* d_offsets,
+                       uint8_t* d_circular, uint64_t* d_count_sums, uint64_t* h_n_unitigs, uint64_t* h_n_nodes) {
+    return unitigs_impl(ctx, kQuery2, "kmx_count_unitigs2", d_kmers2, d_counts, n, k, min_count, d_edges, d_flips, d_nbr, d_nodes, d_offsets, d_circular,
+                        d_count_sums, h_n_unitigs, h_n_nodes);
+}
+
+static int unitig_sequences_impl(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kmers, uint64_t n, uint32_t k, const uint64_t* d_nodes,
+                                 const uint64_t* d_offsets, uint64_t n_unitigs, uint8_t* d_seq) {
+    if (!ctx || n > (1ull << 40) || n_unitigs > n) return KMX_E_ARG;
+    if (n_unitigs && (!d_kmers || !d_nodes || !d_offsets || !d_seq)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < (kind.words == 1u ? 2u : kind.k_min) || k > kind.k_max) return KMX_E_K_RANGE;
+    if (n_unitigs == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_unitig_sequences(kind.words, d_kmers, n, k, d_nodes, d_offsets, n_unitigs, d_seq, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_unitig_sequences(kmx_ctx* ctx, const uint64_t* d_kmers, uint64_t n, uint32_t k, const uint64_t* d_nodes, const uint64_t* d_offsets,
+                               uint64_t n_unitigs, uint8_t* d_seq) {
+    return unitig_sequences_impl(ctx, kQuery1, d_kmers, n, k, d_nodes, d_offsets, n_unitigs, d_seq);
+}
+
+int kmx_count_unitig_sequences2(kmx_ctx* ctx, const uint64_t* d_kmers2, uint64_t n, uint32_t k, const uint64_t* d_nodes, const uint64_t* d_offsets,
+                                uint64_t n_unitigs, uint8_t* d_seq) {
+    return unitig_sequences_impl(ctx, kQuery2, d_kmers2, n, k, d_nodes, d_offsets, n_unitigs, d_seq);
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

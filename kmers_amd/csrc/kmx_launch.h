@@ -158,6 +158,14 @@ hipError_t launch_count_adjacency(u32 words, const u64* keys, const u64* counts,
                                   u64* nbr, void* dir_area, u32 p, hipStream_t st);
 hipError_t launch_count_edge_histogram(const uint8_t* edges, u64 n, u64* hist, int n_cu, hipStream_t st);
 hipError_t launch_count_unitig_ends(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, uint8_t* ends, hipStream_t st);
+// kmx_count_unitigs.hip: the unitigs of that graph (keys is read at even k only; circular and sums may be nullptr; *bad: the rounds
+// ran out) and their bases
+size_t count_unitigs_bytes(u64 n);
+hipError_t launch_count_unitigs(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, u64 min_count, const uint8_t* edges, const uint8_t* flips,
+                                const u64* nbr, u64* nodes, u64* offsets, uint8_t* circular, u64* sums, void* area, unsigned long long* h_pinned,
+                                u64* n_unitigs, u64* n_nodes, u32* rounds, bool* bad, hipStream_t st);
+hipError_t launch_count_unitig_sequences(u32 words, const u64* keys, u64 n, u32 k, const u64* nodes, const u64* offsets, u64 n_unitigs, uint8_t* seq,
+                                         hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
