@@ -640,6 +640,66 @@ fn unitig_sequence_arrays(k: u8, d_nodes: &DeviceBuf<'_>, d_offsets: &DeviceBuf<
     assert!(n_nodes as u128 + n_unitigs as u128 * (k as u128 - 1) <= d_seq.len() as u128, "sequence bytes shorter than nodes + unitigs * (k - 1)");
 }
 
+/// Where each of the table's `n` entries sits in the unitigs (`kmx_count_unitig_index`): `d_place[i]` =
+/// `((p + 1) << 3) | (last << 2) | (first << 1) | o` for the entry `d_nodes[p]` names, `KMX_PLACE_NONE` for an entry in no unitig.
+/// It serves the lookups as their counts array.  One call for both key widths.  Asynchronous.
+pub fn count_unitig_index(ctx: &HipContext, d_nodes: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64, n_nodes: u64, n: u64,
+                          d_place: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    assert!(n_nodes as u128 * 8 <= d_nodes.len() as u128, "unitig nodes shorter than the node count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!(n as u128 * 8 <= d_place.len() as u128, "places shorter than the entry count");
+    ctx.ck(unsafe { kmx_count_unitig_index(ctx.0, d_nodes.as_ptr::<u64>(), d_offsets.as_ptr::<u64>(), n_unitigs, n, d_place.as_mut_ptr::<u64>()) })
+}
+
+/// The device arrays `count_read_paths(2)` fills: `d_path_offsets` (n_reads + 1 u64) and `d_segments` (`KMX_PATH_WORDS` u64 per
+/// segment, room for `max_segments`).
+pub struct PathOutputs<'a> {
+    pub d_path_offsets: &'a DeviceBuf<'a>,
+    pub d_segments: &'a DeviceBuf<'a>,
+    pub max_segments: u64,
+}
+
+fn path_arrays(table: &CountTable<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_place: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>,
+               n_unitigs: u64, out: Option<&PathOutputs<'_>>) -> (*mut u64, *mut u64, u64) {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(table.n as u128 * 8 <= d_place.len() as u128, "places shorter than the entry count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    out.map_or((ptr::null_mut(), ptr::null_mut(), 0), |o| {
+        assert!((n_reads as u128 + 1) * 8 <= o.d_path_offsets.len() as u128, "path offsets shorter than the batch's reads + 1");
+        assert!(o.max_segments as u128 * 8 * KMX_PATH_WORDS as u128 <= o.d_segments.len() as u128, "segments shorter than max_segments");
+        (o.d_path_offsets.as_mut_ptr::<u64>(), o.d_segments.as_mut_ptr::<u64>(), o.max_segments)
+    })
+}
+
+/// The segments of every read of a uniform batch over the unitigs of a table (`kmx_count_read_paths`, k in 2..=31): one record of
+/// `KMX_PATH_WORDS` u64 (`KMX_PATH_READ` .. `KMX_PATH_POS`) per maximal run of consecutive windows that walk one unitig in one
+/// direction, ordered by read, then by start; read r owns the segments `path_offsets[r] .. path_offsets[r + 1]`.  `table.counts` is
+/// not read; `d_place` is what `count_unitig_index` wrote for `d_offsets` / `n_unitigs`.  `out = None` counts only.  Returns the
+/// number of segments; Err(KMX_E_NOMEM) if there are more than `max_segments` (the path offsets are written all the same).
+/// Synchronous.
+pub fn count_read_paths(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>,
+                        d_place: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64, out: Option<&PathOutputs<'_>>) -> Result<u64, KmxError> {
+    table.check(1);
+    let (path_offsets, segments, max_segments) = path_arrays(&table, d_reads, n_reads, read_len, d_place, d_offsets, n_unitigs, out);
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    let mut n_segments = 0u64;
+    ctx.ck(unsafe { kmx_count_read_paths(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.n, d_place.as_ptr::<u64>(), d_offsets.as_ptr::<u64>(),
+                                         n_unitigs, path_offsets, segments, max_segments, &mut n_segments) })?;
+    Ok(n_segments)
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_read_paths2`).
+pub fn count_read_paths2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>,
+                         d_place: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64, out: Option<&PathOutputs<'_>>) -> Result<u64, KmxError> {
+    table.check(2);
+    let (path_offsets, segments, max_segments) = path_arrays(&table, d_reads, n_reads, read_len, d_place, d_offsets, n_unitigs, out);
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    let mut n_segments = 0u64;
+    ctx.ck(unsafe { kmx_count_read_paths2(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.n, d_place.as_ptr::<u64>(), d_offsets.as_ptr::<u64>(),
+                                          n_unitigs, path_offsets, segments, max_segments, &mut n_segments) })?;
+    Ok(n_segments)
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -443,6 +443,74 @@ int kmx_count_unitig_sequences(kmx_ctx *ctx, const uint64_t *d_kmers, uint64_t n
 int kmx_count_unitig_sequences2(kmx_ctx *ctx, const uint64_t *d_kmers2, uint64_t n, uint32_t k, const uint64_t *d_nodes, const uint64_t *d_offsets,
                                 uint64_t n_unitigs, uint8_t *d_seq);
 
+/* ---------------------------------------------------------------- reads threaded through the unitigs ----
+ * BUILD-DEFINED.  The way back from the unitigs to the reads: where every window of a read lies on them. */
+#define KMX_PLACE_NONE 0u /* d_place: the entry lies in no unitig */
+/* d_place[i] (one u64 per table entry, n of them) = KMX_PLACE_NONE for an entry no node of d_nodes names (an entry that was not
+ * present when the unitigs were made), otherwise
+ *     ((p + 1) << 3) | (last << 2) | (first << 1) | o
+ * with p the index into d_nodes with d_nodes[p] >> 1 == i, o = d_nodes[p] & 1, and first / last set when p is the first / last node
+ * of its unitig AS WRITTEN (both for a one-node unitig; for a circular unitig they mark the written start and end).  A place is
+ * never 0 for a placed entry, so d_place can be handed to kmx_count_lookup(2) / kmx_count_lookup_reads(2) as the counts array:
+ * "count 0 reads as absent" then means "in no unitig".
+ * d_nodes / d_offsets / n_unitigs as kmx_count_unitigs(2) wrote them (d_nodes holds d_offsets[n_unitigs] nodes); n = the table's
+ * entry count.  Every word of d_place[0 .. n) is written.  Nodes naming an entry >= n are skipped, as
+ * kmx_count_unitig_sequences skips them.  It reads indices only: one call for both key widths.  n_unitigs == 0 writes n zeros;
+ * n == 0 is a no-op; a missing array with n > 0 (d_place; d_nodes / d_offsets with n_unitigs > 0), n or n_unitigs above 2^40:
+ * KMX_E_ARG.  Working set: none.  Asynchronous. */
+int kmx_count_unitig_index(kmx_ctx *ctx, const uint64_t *d_nodes, const uint64_t *d_offsets, uint64_t n_unitigs, uint64_t n,
+                           uint64_t *d_place);
+
+/* The segments of every read over the unitigs: KMX_PATH_WORDS u64 per segment, segment s at d_segments + KMX_PATH_WORDS * s. */
+#define KMX_PATH_WORDS 4u
+#define KMX_PATH_READ 0u   /* the read index */
+#define KMX_PATH_SPAN 1u   /* low 32 bits = the position of the segment's first window in the read, high 32 bits = its length in windows
+                            * (the packing of KMX_RS_SPAN); its bases are [start, start + length + k - 1) */
+#define KMX_PATH_UNITIG 2u /* u, the unitig */
+#define KMX_PATH_POS 3u    /* (q << 1) | d, q = p - d_offsets[u] of the FIRST window: window start + t of the read sits at node q + t of
+                            * the unitig for d = 0 and at node q - t for d = 1 */
+/* Window j of a read is MAPPED if it is valid (KMX_WIN_VALID), its canonical word is entry i of the table (d_kmers, n) and
+ * d_place[i] != 0.  It then has p, o, first, last from the place, the read's strand s (0 if KMX_WIN_FW_CANONICAL is set, else 1) and
+ * the direction d = s ^ o: d = 0, the read walks the unitig as written; d = 1, it walks the mirror.  (A palindromic window has
+ * fw == rc, so s = 1; it is a one-node unitig with o = 0, so it reads d = 1 -- and is a segment of its own either way.)
+ * Window j + 1 CONTINUES window j (consecutive positions of ONE read) iff both are mapped, their d is equal, and
+ *     d = 0:  p' == p + 1 and first' is clear        d = 1:  p' + 1 == p and last' is clear.
+ * A SEGMENT is a maximal run of such windows.  So a run never crosses a unitig boundary, never crosses an unmapped or invalid
+ * window, never crosses from one read into the next, and never crosses the written start of a cycle: a read going round a circular
+ * unitig starts a new segment at each passage.
+ * Segments are ordered by read, then by start.  d_path_offsets (n_reads + 1 u64): read r owns the segments
+ * [d_path_offsets[r], d_path_offsets[r + 1]); every read gets its offset, one without a window too.  *h_n_segments (host) is always
+ * set.  Both output arrays NULL = count only; one NULL = KMX_E_ARG.  More segments than max_segments: KMX_E_NOMEM with d_segments
+ * untouched and d_path_offsets STILL WRITTEN in full -- its size does not depend on the count, and it says how to batch.
+ * Deterministic: repeated calls give identical bytes.
+ * d_place as kmx_count_unitig_index writes it for the unitigs d_offsets / n_unitigs describe (the node list itself is not read).
+ * Places that are inconsistent with d_offsets give meaningless records, never an access outside the arrays; a p at or beyond
+ * d_offsets[n_unitigs] reads as unmapped.
+ * Every input kmx_count_read_stats accepts is accepted, through the same routes and with the same synchronisation: uniform reads of
+ * any length and d_bases alignment, ragged reads with any bound (the window offsets are made on the device), reads longer than 256
+ * bases through the segment plan.  k in [2,31], the unitig calls' domain: KMX_E_K_RANGE otherwise (k = 1 included).  n == 0 or
+ * n_unitigs == 0 is valid and gives zero segments (every offset 0); n_reads == 0 is a no-op with *h_n_segments = 0.  NULL ctx /
+ * reads / h_n_segments, n or n_unitigs above 2^40, d_kmers or d_place NULL with n > 0, d_offsets NULL with n_unitigs > 0: KMX_E_ARG.
+ * Working set in the context's work buffer, each array rounded up to 256 bytes (a256), laid out before any kernel runs.  With
+ * windows = n_reads * (read_len - k + 1) for uniform reads and the batch's number of BASES for ragged ones, g = ceil(windows / 64):
+ *     a256(8 * windows) + a256(windows)                                                  the places and the flags
+ *   + 2 * a256(8 * g) + a256(4 * g) + a256(8 * (ceil(windows / 4096) + 2))               head / tail ballots, counts, scan partials
+ *   + ragged reads:  a256(8 * (n_reads + 1)) + a256(8 * (ceil(n_reads / 4096) + 2))      the window offsets
+ *   + reads longer than 256 bases: the segment plan (24 bytes per segment of at most 257 - k windows; 16-byte aligned d_bases)
+ * and, behind that, the directory of kmx_count_lookup when it pays and fits (left out, never refused).  The canonical words are
+ * written into the places array and looked up in place.  150 bp reads at k = 31: 1118 bytes per read here; out, 8 bytes per read
+ * and 32 per segment.  Above the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM BEFORE any kernel runs, nothing written.  The call
+ * uses the work buffer (a following kmx_fastx_parse cannot reuse its chunk prefixes).
+ * Synchronous (the count comes back to the host: one round trip, after those of the windows route). */
+int kmx_count_read_paths(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers, uint64_t n, const uint64_t *d_place,
+                         const uint64_t *d_offsets, uint64_t n_unitigs, uint64_t *d_path_offsets, uint64_t *d_segments,
+                         uint64_t max_segments, uint64_t *h_n_segments);
+/* The same for two-word keys, k in [33,64] (d_kmers2 16-byte aligned, KMX_E_ARG otherwise; k = 32 is KMX_E_K_RANGE for both calls):
+ * kmx_canonical_windows2 and its routes.  Working set: as above + a256(16 * windows) for the canonical words. */
+int kmx_count_read_paths2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, uint64_t n, const uint64_t *d_place,
+                          const uint64_t *d_offsets, uint64_t n_unitigs, uint64_t *d_path_offsets, uint64_t *d_segments,
+                          uint64_t max_segments, uint64_t *h_n_segments);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

@@ -32,6 +32,10 @@ RS_N_VALID, RS_N_PRESENT, RS_N_SOLID, RS_MIN, RS_MAX, RS_SUM, RS_MEDIAN, RS_SPAN
 RS_WORDS = 8
 # kmx_count_adjacency(2): the word of d_nbr where an edge is absent (KMX_NO_ENTRY; -1 in the int64 tensors of kmers_amd.api)
 NO_ENTRY = 2**64 - 1
+# kmx_count_unitig_index / kmx_count_read_paths(2): an entry in no unitig, and the words of a segment's record
+PLACE_NONE = 0
+PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_POS = range(4)
+PATH_WORDS = 4
 
 
 class KmxError(RuntimeError):
@@ -129,6 +133,9 @@ SIGNATURES = {
     "kmx_count_unitigs2": (_int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_count_unitig_sequences": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_unitig_sequences2": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
+    "kmx_count_unitig_index": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "kmx_count_read_paths": (_int, [_vp, _RP, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_read_paths2": (_int, [_vp, _RP, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -181,6 +181,54 @@ class Unitigs:
         lo, hi = (int(v) for v in self.offsets[u:u + 2].cpu())
         at = lo + u * (self.k - 1)
         return bytes(self.sequences()[at:at + (hi - lo) + self.k - 1].cpu().numpy())
+
+
+@dataclasses.dataclass
+class ReadPaths:
+    """What kmx_count_read_paths(2) returns: the segments of every read over the unitigs, ordered by read, then by start.
+    offsets int64[n_reads + 1]: read r owns segments[offsets[r]:offsets[r + 1]]; segments int64[S, 4] (u64 words, columns
+    _lib.PATH_*).  A segment is a maximal run of consecutive windows of one read that walk one unitig in one direction: window
+    start + t of the read sits at node pos + t of the unitig, or at pos - t when `reverse` is set."""
+    offsets: "torch.Tensor"
+    segments: "torch.Tensor"
+    k: int
+
+    @property
+    def n_segments(self) -> int:
+        return int(self.segments.shape[0])
+
+    @property
+    def read(self):
+        return self.segments[:, PATH_READ]
+
+    @property
+    def start(self):
+        """position of the segment's first window in its read (its bases: start .. start + length + k - 1)"""
+        return self.segments[:, PATH_SPAN] & 0xFFFFFFFF
+
+    @property
+    def length(self):
+        """windows in the segment"""
+        return (self.segments[:, PATH_SPAN] >> 32) & 0xFFFFFFFF
+
+    @property
+    def unitig(self):
+        return self.segments[:, PATH_UNITIG]
+
+    @property
+    def pos(self):
+        """node of the unitig, counted from its written start, where the segment's first window sits"""
+        return (self.segments[:, PATH_POS] >> 1) & 0x7FFFFFFFFFFFFFFF
+
+    @property
+    def reverse(self):
+        """bool: the read walks the unitig's mirror (positions descend along the read)"""
+        return (self.segments[:, PATH_POS] & 1) != 0
+
+    def unitig_coverage(self, n_unitigs: int):
+        """int64[n_unitigs]: how many windows of the batch lie on each unitig"""
+        cov = torch.zeros(int(n_unitigs), dtype=torch.int64, device=self.segments.device)
+        return cov.scatter_add_(0, self.unitig, self.length)
 
 
 def _on_ctx_stream(fn):
@@ -650,6 +698,51 @@ class Context:
         if u.n_unitigs:
             self._ck(fn(self._h, _ptr(u.kmers), n, u.k, _ptr(u.nodes), _ptr(u.offsets), u.n_unitigs, _ptr(seq)))
         return seq
+
+    # ------------------------------------------------------------ reads threaded through the unitigs
+    @_on_ctx_stream
+    def count_unitig_index(self, unitigs: Unitigs, n: int):
+        """kmx_count_unitig_index -> int64[n] (u64 words): where each of the table's n entries sits in `unitigs` --
+        ((p + 1) << 3) | (last << 2) | (first << 1) | o for the entry nodes[p] names, 0 (PLACE_NONE) for an entry in no unitig.  It
+        goes into count_lookup(2) / count_lookup_reads(2) as the counts array: 0 = absent or in no unitig."""
+        n = int(n)
+        place = self.empty(n, torch.int64)
+        self._ck(self.lib.kmx_count_unitig_index(self._h, _ptr(unitigs.nodes) if unitigs.n_nodes else None, _ptr(unitigs.offsets), unitigs.n_unitigs, n,
+                                                 _ptr(place) if n else None))
+        return place
+
+    def _read_paths(self, words, bases, n_reads, read_len, k, kmers, unitigs, place, offsets, max_segments):
+        n = int(kmers.numel()) // words if kmers is not None else 0
+        if n:
+            kmers = kmers.contiguous()
+        if place is None:
+            place = self.count_unitig_index(unitigs, n)
+        fn = self.lib.kmx_count_read_paths if words == 1 else self.lib.kmx_count_read_paths2
+        r = self._reads(bases, n_reads, read_len, offsets)
+        args = (self._h, C.byref(r), k, _ptr(kmers) if n else None, n, _ptr(place) if n else None, _ptr(unitigs.offsets), unitigs.n_unitigs)
+        s = C.c_uint64(0)
+        if max_segments is None:   # count, then allocate
+            self._ck(fn(*args, None, None, 0, C.byref(s)))
+            max_segments = int(s.value)
+        po = self.empty(int(n_reads) + 1, torch.int64)
+        segs = self.empty(PATH_WORDS * max(int(max_segments), 1), torch.int64)
+        self._ck(fn(*args, _ptr(po), _ptr(segs), int(max_segments), C.byref(s)))
+        if int(n_reads) == 0:
+            po.zero_()
+        return ReadPaths(po, segs[:PATH_WORDS * int(s.value)].view(-1, PATH_WORDS), int(k))
+
+    @_on_ctx_stream
+    def count_read_paths(self, bases, n_reads, read_len, k, kmers, unitigs: Unitigs, place=None, offsets=None, max_segments=None) -> ReadPaths:
+        """kmx_count_read_paths -> ReadPaths: where every read of the batch lies on the unitigs of the table `kmers` -- a 32-byte record
+        per maximal run of consecutive windows that walk one unitig in one direction (include/kmx.h has the rule).  `place` is
+        count_unitig_index(unitigs, n), made here when not given; `offsets` makes the reads ragged (no window offsets are needed);
+        max_segments=None counts first and then allocates, a number gives room for that many (KmxError E_NOMEM above it).  k 2..31."""
+        return self._read_paths(1, bases, n_reads, read_len, k, kmers, unitigs, place, offsets, max_segments)
+
+    @_on_ctx_stream
+    def count_read_paths2(self, bases, n_reads, read_len, k, kmers, unitigs: Unitigs, place=None, offsets=None, max_segments=None) -> ReadPaths:
+        """kmx_count_read_paths2 (k 33..64): kmers int64[n, 2] = (low, high) words."""
+        return self._read_paths(2, bases, n_reads, read_len, k, kmers, unitigs, place, offsets, max_segments)
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

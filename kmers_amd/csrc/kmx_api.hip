@@ -1183,6 +1183,92 @@ int kmx_count_unitig_sequences2(kmx_ctx* ctx, const uint64_t* d_kmers2, uint64_t
     return unitig_sequences_impl(ctx, kQuery2, d_kmers2, n, k, d_nodes, d_offsets, n_unitigs, d_seq);
 }
 
+// ---- reads threaded through the unitigs (kmx_count_paths.hip) ----
+int kmx_count_unitig_index(kmx_ctx* ctx, const uint64_t* d_nodes, const uint64_t* d_offsets, uint64_t n_unitigs, uint64_t n, uint64_t* d_place) {
+    if (!ctx || n > (1ull << 40) || n_unitigs > (1ull << 40)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    if (!d_place || (n_unitigs && (!d_nodes || !d_offsets))) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_unitig_index(d_nodes, d_offsets, n_unitigs, n, d_place, ctx->stream));
+    return KMX_OK;
+}
+
+// kmx_count_read_paths(2) = read_stats_impl's front half -- the windows call and the lookup kernel, with the places as the counts --
+// and the segment kernels of kmx_count_paths.hip over its answers.  The work buffer, laid out up front: [segment plan of long
+// reads][ragged reads: window offsets][two-word keys: canon 16 B/window][places 8 B/window][flags 1 B/window][the ballots, counts and
+// partials of the segment kernels][directory, when it pays and fits].  One-word keys: the windows call writes its canonical words
+// into the places array and they are looked up in place.
+static int read_paths_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers, uint64_t n,
+                           const uint64_t* d_place, const uint64_t* d_offsets, uint64_t n_unitigs, uint64_t* d_path_offsets, uint64_t* d_segments,
+                           uint64_t max_segments, uint64_t* h_n_segments) {
+    if (!ctx || !reads_ok(reads) || !h_n_segments || n > (1ull << 40) || n_unitigs > (1ull << 40)) return KMX_E_ARG;
+    if ((n && (!d_kmers || !d_place)) || (n_unitigs && !d_offsets) || ((d_path_offsets == nullptr) != (d_segments == nullptr))) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < (kind.words == 1u ? 2u : kind.k_min) || k > kind.k_max) return KMX_E_K_RANGE;
+    *h_n_segments = 0;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    const char* who = kind.words == 2u ? "kmx_count_read_paths2" : "kmx_count_read_paths";
+    const size_t offsets_bytes = 8u * (reads->n_reads + 1u);
+    uint64_t n_bound = 0, n_bases = 0;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
+    if (n_bound == 0 || n == 0 || n_unitigs == 0) {   // no window, or nothing to lie on: no segment, every offset 0
+        if (d_path_offsets) KMX_HIP(ctx, hipMemsetAsync(d_path_offsets, 0, offsets_bytes, ctx->stream));
+        return KMX_OK;
+    }
+    const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
+    const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
+    const size_t canon_at = plan + wo_bytes, places_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u);
+    const size_t flags_at = places_at + align256(8u * n_bound), area_at = flags_at + align256(n_bound);
+    const size_t reserved = area_at + kmx::count_paths_bytes(n_bound);
+    char* base = nullptr;
+    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &base)) return st;
+    const unsigned long long allocs = ctx->big_allocs;
+    uint64_t n_win = n_bound;
+    uint64_t* wo = nullptr;
+    if (reads->d_offsets) {
+        KMX_HIP(ctx, kmx::launch_count_win_offsets(reads->d_offsets, reads->n_reads, k, base + plan, &wo, ctx->h_pinned, &n_win, ctx->stream));
+        if (n_win > n_bound) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "%s: window count above its bound", who);
+            return fail_hip(ctx, hipErrorUnknown, msg);
+        }
+        if (n_win == 0) {
+            if (d_path_offsets) KMX_HIP(ctx, hipMemsetAsync(d_path_offsets, 0, offsets_bytes, ctx->stream));
+            return KMX_OK;
+        }
+    }
+    uint64_t* places = reinterpret_cast<uint64_t*>(base + places_at);
+    uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : places;
+    uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
+    if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
+    if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
+    if (int st = lookup_run(ctx, kind, d_kmers, d_place, n, k, canon, flags, n_win, places, reserved)) return st;
+    const uint32_t w = reads->read_len >= k ? reads->read_len - k + 1u : 0u;   // (uniform reads: the windows of a read)
+    uint64_t n_segments = 0;
+    KMX_HIP(ctx, kmx::launch_count_paths_mark(places, flags, wo, reads->n_reads, w, n_win, d_offsets, n_unitigs, base + area_at, ctx->h_pinned,
+                                              &n_segments, ctx->stream));
+    *h_n_segments = n_segments;
+    if (!d_path_offsets) return KMX_OK;
+    const int room = room_for(ctx, who, n_segments, "segments", max_segments);   // (the offsets are written all the same: they say how to batch)
+    KMX_HIP(ctx, kmx::launch_count_paths_emit(places, flags, wo, reads->n_reads, w, n_win, d_offsets, n_unitigs, base + area_at, d_path_offsets,
+                                              room == KMX_OK ? d_segments : nullptr, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return room;
+}
+
+int kmx_count_read_paths(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers, uint64_t n, const uint64_t* d_place,
+                         const uint64_t* d_offsets, uint64_t n_unitigs, uint64_t* d_path_offsets, uint64_t* d_segments, uint64_t max_segments,
+                         uint64_t* h_n_segments) {
+    return read_paths_impl(ctx, kQuery1, reads, k, d_kmers, n, d_place, d_offsets, n_unitigs, d_path_offsets, d_segments, max_segments, h_n_segments);
+}
+
+int kmx_count_read_paths2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers2, uint64_t n, const uint64_t* d_place,
+                          const uint64_t* d_offsets, uint64_t n_unitigs, uint64_t* d_path_offsets, uint64_t* d_segments, uint64_t max_segments,
+                          uint64_t* h_n_segments) {
+    return read_paths_impl(ctx, kQuery2, reads, k, d_kmers2, n, d_place, d_offsets, n_unitigs, d_path_offsets, d_segments, max_segments, h_n_segments);
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

@@ -166,6 +166,15 @@ hipError_t launch_count_unitigs(u32 words, const u64* keys, const u64* counts, u
                                 u64* n_unitigs, u64* n_nodes, u32* rounds, bool* bad, hipStream_t st);
 hipError_t launch_count_unitig_sequences(u32 words, const u64* keys, u64 n, u32 k, const u64* nodes, const u64* offsets, u64 n_unitigs, uint8_t* seq,
                                          hipStream_t st);
+// kmx_count_paths.hip: where each entry sits in the unitigs (place), and the segments of reads over them -- mark counts them (one host
+// round trip), emit writes the reads' offsets and, unless segments == nullptr, the records (win_offsets == nullptr: uniform reads of
+// W windows)
+hipError_t launch_count_unitig_index(const u64* nodes, const u64* offsets, u64 n_unitigs, u64 n, u64* place, hipStream_t st);
+size_t count_paths_bytes(u64 n_win);
+hipError_t launch_count_paths_mark(const u64* places, uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u64 n_win, const u64* unitig_offsets,
+                                   u64 n_unitigs, void* area, unsigned long long* h_pinned, u64* h_segments, hipStream_t st);
+hipError_t launch_count_paths_emit(const u64* places, const uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u64 n_win,
+                                   const u64* unitig_offsets, u64 n_unitigs, const void* area, u64* path_offsets, u64* segments, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
