@@ -700,6 +700,75 @@ pub fn count_read_paths2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64
     Ok(n_segments)
 }
 
+/// The device arrays `count_unitig_links` fills: `d_link_offsets` (2 * n_unitigs + 1 u64) and `d_links` (room for `max_links` u64).
+pub struct LinkOutputs<'a> {
+    pub d_link_offsets: &'a DeviceBuf<'a>,
+    pub d_links: &'a DeviceBuf<'a>,
+    pub max_links: u64,
+}
+
+/// The links between the oriented unitigs `t = 2 * u + s` of a table's de Bruijn graph (`kmx_count_unitig_links`): t owns
+/// `d_links[d_link_offsets[t] .. d_link_offsets[t + 1]]`, at most four targets `t'`, each an overlap of k - 1 bases (include/kmx.h
+/// has the rule).  `d_edges` / `d_flips` / `d_nbr` are `count_adjacency`'s outputs for the table's `n` entries, `d_nodes` /
+/// `d_offsets` `count_unitigs`' and `d_place` `count_unitig_index`'s.  One call for both key widths.  `out = None` counts only.
+/// Returns the number of links; Err(KMX_E_NOMEM) if there are more than `max_links` (the offsets are written all the same).
+/// Synchronous.
+pub fn count_unitig_links(ctx: &HipContext, d_edges: &DeviceBuf<'_>, d_flips: &DeviceBuf<'_>, d_nbr: &DeviceBuf<'_>, n: u64, d_nodes: &DeviceBuf<'_>,
+                          d_offsets: &DeviceBuf<'_>, n_unitigs: u64, n_nodes: u64, d_place: &DeviceBuf<'_>, out: Option<&LinkOutputs<'_>>)
+                          -> Result<u64, KmxError> {
+    unitig_inputs(n, d_edges, d_flips, d_nbr);
+    assert!(n_nodes as u128 * 8 <= d_nodes.len() as u128, "unitig nodes shorter than the node count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!(n as u128 * 8 <= d_place.len() as u128, "places shorter than the entry count");
+    let (link_offsets, links, max_links) = out.map_or((ptr::null_mut(), ptr::null_mut(), 0), |o| {
+        assert!((2 * n_unitigs as u128 + 1) * 8 <= o.d_link_offsets.len() as u128, "link offsets shorter than twice the unitig count + 1");
+        assert!(o.max_links as u128 * 8 <= o.d_links.len() as u128, "links shorter than max_links");
+        (o.d_link_offsets.as_mut_ptr::<u64>(), o.d_links.as_mut_ptr::<u64>(), o.max_links)
+    });
+    let mut n_links = 0u64;
+    ctx.ck(unsafe { kmx_count_unitig_links(ctx.0, d_edges.as_ptr::<u8>(), d_flips.as_ptr::<u8>(), d_nbr.as_ptr::<u64>(), n, d_nodes.as_ptr::<u64>(),
+                                           d_offsets.as_ptr::<u64>(), n_unitigs, d_place.as_ptr::<u64>(), link_offsets, links, max_links,
+                                           &mut n_links) })?;
+    Ok(n_links)
+}
+
+fn select_arrays(table: &CountTable<'_>, d_place: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64, d_keep: &DeviceBuf<'_>) {
+    assert!(table.n as u128 * 8 <= d_place.len() as u128, "places shorter than the entry count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!(n_unitigs as u128 <= d_keep.len() as u128, "keep bytes shorter than the unitig count");
+}
+
+/// The entries of a table that lie in a unitig `u` with `d_keep[u] != 0` (one byte per unitig), order kept
+/// (`kmx_count_unitig_select`): a table again.  `d_place` is what `count_unitig_index` wrote for `d_offsets` / `n_unitigs`; an
+/// entry in no unitig is dropped.  The outputs hold at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there
+/// are more than `max_out`.
+pub fn count_unitig_select(ctx: &HipContext, table: CountTable<'_>, d_place: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64,
+                           d_keep: &DeviceBuf<'_>, d_kmers_out: &DeviceBuf<'_>, d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    table.check(1);
+    let counts = table.counts.expect("count_unitig_select needs the table's counts");
+    select_arrays(&table, d_place, d_offsets, n_unitigs, d_keep);
+    assert!(max_out as u128 * 8 <= d_kmers_out.len().min(d_counts_out.len()) as u128, "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_unitig_select(ctx.0, table.keys.as_ptr::<u64>(), counts.as_ptr::<u64>(), table.n, d_place.as_ptr::<u64>(),
+                                            d_offsets.as_ptr::<u64>(), n_unitigs, d_keep.as_ptr::<u8>(), d_kmers_out.as_mut_ptr::<u64>(),
+                                            d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
+/// The same for two-word keys (`kmx_count_unitig_select2`): `d_kmers2_out` holds at least `2 * max_out` u64.
+pub fn count_unitig_select2(ctx: &HipContext, table: CountTable<'_>, d_place: &DeviceBuf<'_>, d_offsets: &DeviceBuf<'_>, n_unitigs: u64,
+                            d_keep: &DeviceBuf<'_>, d_kmers2_out: &DeviceBuf<'_>, d_counts_out: &DeviceBuf<'_>, max_out: u64) -> Result<u64, KmxError> {
+    table.check(2);
+    let counts = table.counts.expect("count_unitig_select2 needs the table's counts");
+    select_arrays(&table, d_place, d_offsets, n_unitigs, d_keep);
+    assert!(max_out as u128 * 16 <= d_kmers2_out.len() as u128 && max_out as u128 * 8 <= d_counts_out.len() as u128, "outputs shorter than max_out");
+    let mut n_out = 0u64;
+    ctx.ck(unsafe { kmx_count_unitig_select2(ctx.0, table.keys.as_ptr::<u64>(), counts.as_ptr::<u64>(), table.n, d_place.as_ptr::<u64>(),
+                                             d_offsets.as_ptr::<u64>(), n_unitigs, d_keep.as_ptr::<u8>(), d_kmers2_out.as_mut_ptr::<u64>(),
+                                             d_counts_out.as_mut_ptr::<u64>(), max_out, &mut n_out) })?;
+    Ok(n_out)
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

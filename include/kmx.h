@@ -511,6 +511,69 @@ int kmx_count_read_paths2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, cons
                           const uint64_t *d_offsets, uint64_t n_unitigs, uint64_t *d_path_offsets, uint64_t *d_segments,
                           uint64_t max_segments, uint64_t *h_n_segments);
 
+/* ---------------------------------------------------------------- the unitigs as a graph ----
+ * BUILD-DEFINED.  Which unitig follows which, and in which orientation: the compacted de Bruijn graph.
+ * The ORIENTED UNITIG t = 2 u + s is unitig u as written (s = 0: its ENTRY node is d_nodes[d_offsets[u]], its EXIT node is
+ * d_nodes[d_offsets[u + 1] - 1]) or its mirror (s = 1: ENTRY = mirror(last node), EXIT = mirror(first node)); mirror(t) = t ^ 1.
+ * The LINKS of t.  Let v = 2 i + o be the EXIT node of t.  For c = 0 .. 3 in ascending order let e = 4 o + c (an oriented node with
+ * o = 1 is left through the predecessor side, edge slots 4 .. 7).  If bit e of d_edges[i] is set: j = d_nbr[8 i + e], f = bit e of
+ * d_flips[i], w = 2 j + (o ^ f).  j >= n or d_place[j] == 0 gives no link.  Otherwise p, first, last and o_j come from d_place[j],
+ * and u' is the unitig that holds position p -- the largest u' with d_offsets[u'] <= p, one upper-bound search of d_offsets; a p at
+ * or beyond d_offsets[n_unitigs] gives no link.  Then
+ *     t -> 2 u' + 0   if (w & 1) == o_j and first is set        (w is the entry node of u' as written)
+ *     t -> 2 u' + 1   if (w & 1) != o_j and last is set         (w is the entry node of the mirror of u')
+ * and anything else gives no link (this cannot happen for the adjacency of the table: an edge that leaves a unitig's exit enters
+ * another's entry).  EVERY set edge bit on the exit side counts, whether or not that side is an END by the rule of
+ * kmx_count_unitig_ends: a circular unitig links to itself across its written start (2 u -> 2 u, and 2 u + 1 -> 2 u + 1), a chain
+ * cut by the palindrome rule links to the palindromic one-node unitig, and a hairpin links t -> mirror(t).  Consecutive nodes
+ * overlap by k - 1 bases, so every link is an overlap of k - 1 bases between the sequences of t and t' (the sequence of 2 u + 1 is
+ * the reverse complement of that of u).
+ * MIRROR SYMMETRY.  For inputs that are the adjacency, unitigs and index of one table, and unitigs none of which is a palindromic
+ * k-mer (every table at odd k): t -> t' is a link iff mirror(t') -> mirror(t) is, and no link occurs twice.  A palindromic entry
+ * (even k) is a one-node unitig P whose two orientations spell the same bases, and the rule does not pretend otherwise: 2 P and
+ * 2 P + 1 have the same neighbours (in opposite order of c), while a link INTO P names one orientation only -- 2 P + o, o the
+ * orientation of the exit node it comes from (a palindromic neighbour is never flipped).  What holds instead: with the orientation
+ * bit of every palindromic unitig cleared on both ends, the set of links is closed under (t, t') -> (mirror(t'), mirror(t)).
+ * d_link_offsets (2 U + 1 u64, U = n_unitigs): t owns d_links[d_link_offsets[t] .. d_link_offsets[t + 1]), at most four, in
+ * ascending c; d_links[x] = the target t'.  *h_n_links (host) is always set.  Both output arrays NULL = count only; one NULL =
+ * KMX_E_ARG.  More links than max_links: KMX_E_NOMEM with d_links untouched and d_link_offsets STILL WRITTEN in full -- the
+ * conventions of kmx_count_read_paths.  Exact and deterministic: repeated calls give identical bytes.
+ * d_edges / d_flips / d_nbr as kmx_count_adjacency(2) wrote them for the table's n entries, d_nodes / d_offsets / n_unitigs as
+ * kmx_count_unitigs(2) wrote them, d_place as kmx_count_unitig_index wrote it.  It reads indices only: one call for both key
+ * widths.  ANY bytes in the inputs give a result and never an access outside the arrays: an exit node naming an entry >= n, a
+ * unitig with d_offsets[u] >= d_offsets[u + 1] or d_offsets[u + 1] > d_offsets[n_unitigs] has no links; offsets that do not ascend
+ * give meaningless targets; every target is < 2 U.
+ * n_unitigs == 0 writes the single offset 0 (*h_n_links = 0); n == 0 with n_unitigs == 0 is a no-op with *h_n_links = 0.  NULL ctx /
+ * h_n_links, n or n_unitigs above 2^40, an input array missing with n_unitigs > 0 (d_nodes, d_offsets; with n > 0 also d_edges,
+ * d_flips, d_nbr, d_place): KMX_E_ARG.
+ * Working set in the context's work buffer, laid out before any kernel runs, with r = ceil((2 U + 1) / 4096) and each array rounded
+ * up to 256 bytes (a256):
+ *     a256(4096 * r) + a256(8 * (r + 1))                    a degree byte per oriented unitig, a scan partial per 4096 of them
+ * Above the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM BEFORE any kernel runs, nothing written.  The call uses the work buffer
+ * (a following kmx_fastx_parse cannot reuse its chunk prefixes).  Synchronous (the count comes back to the host: one round trip). */
+int kmx_count_unitig_links(kmx_ctx *ctx, const uint8_t *d_edges, const uint8_t *d_flips, const uint64_t *d_nbr, uint64_t n,
+                           const uint64_t *d_nodes, const uint64_t *d_offsets, uint64_t n_unitigs, const uint64_t *d_place,
+                           uint64_t *d_link_offsets, uint64_t *d_links, uint64_t max_links, uint64_t *h_n_links);
+
+/* The entries of a table that lie in kept unitigs, order kept: a table again (it feeds every other table call, the adjacency
+ * included: cut, then compact again).  Entry i is kept iff d_place[i] != 0, its position p (d_place as kmx_count_unitig_index wrote
+ * it) lies below d_offsets[n_unitigs], and d_keep[u] != 0 for the unitig u that holds p (the search of kmx_count_unitig_links);
+ * d_keep holds one byte per unitig.  An entry in no unitig -- one that was not present when the unitigs were made -- is dropped; a p
+ * outside the offsets reads as not kept.
+ * *h_n_out (host) = how many entries are kept; max_out / KMX_E_NOMEM with nothing written and *h_n_out set, both outputs NULL =
+ * count only, one NULL = KMX_E_ARG, outputs must not alias inputs: the conventions of kmx_count_filter.  n == 0 or n_unitigs == 0
+ * keeps nothing (*h_n_out = 0, nothing read).  NULL ctx / h_n_out, n above 2^38, n_unitigs above 2^40, d_kmers / d_counts / d_place
+ * NULL with n > 0, d_offsets / d_keep NULL with n_unitigs > 0: KMX_E_ARG.
+ * Working set in the work buffer, kmx_count_filter's: a256(16384 * ceil(n / 16384)) + a256(8 * (ceil(n / 16384) + 2)) -- a mark byte
+ * per entry and a partial per 16384 entries; above the cap KMX_E_NOMEM before any kernel runs.  Synchronous (one round trip). */
+int kmx_count_unitig_select(kmx_ctx *ctx, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n, const uint64_t *d_place,
+                            const uint64_t *d_offsets, uint64_t n_unitigs, const uint8_t *d_keep, uint64_t *d_kmers_out,
+                            uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
+/* The same for two-word keys (16-byte aligned key arrays, KMX_E_ARG otherwise). */
+int kmx_count_unitig_select2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n, const uint64_t *d_place,
+                             const uint64_t *d_offsets, uint64_t n_unitigs, const uint8_t *d_keep, uint64_t *d_kmers2_out,
+                             uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

@@ -136,6 +136,9 @@ SIGNATURES = {
     "kmx_count_unitig_index": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "kmx_count_read_paths": (_int, [_vp, _RP, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_read_paths2": (_int, [_vp, _RP, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_unitig_links": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_unitig_select": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_unitig_select2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

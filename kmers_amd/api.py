@@ -182,6 +182,57 @@ class Unitigs:
         at = lo + u * (self.k - 1)
         return bytes(self.sequences()[at:at + (hi - lo) + self.k - 1].cpu().numpy())
 
+    def tips(self, links: "UnitigLinks", max_nodes: int, islands: bool = False):
+        """bool[n_unitigs], in torch: the unitigs to clip as dead ends -- not circular, at most max_nodes nodes, and exactly one of
+        the two sides (2 u, 2 u + 1) without a link.  islands=True: a unitig without a link on either side qualifies too."""
+        open_sides = (links.degrees == 0).sum(1)
+        loose = (open_sides == 1) | (open_sides == 2) if islands else open_sides == 1
+        return (self.circular == 0) & (self.lengths <= int(max_nodes)) & loose
+
+    def write_gfa(self, file, links: "UnitigLinks | None" = None):
+        """The compacted graph as GFA 1, written on the host -- for graphs one would look at, not for 1e9 nodes.  `file` is a path
+        or a text file object.  H VN:Z:1.0; one S line per unitig u, named u, with LN:i (bases) and KC:i (the sum of its entries'
+        counts); with `links`, one L line per link, + / - from the orientation bit and an overlap of (k - 1)M.  A link and its mirror
+        image say the same thing and are one line, written from the smaller of (t, t') and (t' ^ 1, t ^ 1); lines are sorted."""
+        if isinstance(file, (str, bytes)) or hasattr(file, "__fspath__"):
+            with open(file, "w") as f:
+                return self.write_gfa(f, links)
+        k = self.k
+        seq = self.sequences().cpu().numpy().tobytes().decode("ascii")
+        offs = self.offsets.cpu().tolist()
+        sums = u64_numpy(self.count_sums).tolist()
+        file.write("H\tVN:Z:1.0\n")
+        for u in range(self.n_unitigs):
+            s = seq[offs[u] + u * (k - 1):offs[u + 1] + (u + 1) * (k - 1)]
+            file.write(f"S\t{u}\t{s}\tLN:i:{len(s)}\tKC:i:{sums[u]}\n")
+        if links is not None:
+            pairs = {min((t, t2), (t2 ^ 1, t ^ 1)) for t, t2 in zip(links.sources().cpu().tolist(), links.targets.cpu().tolist())}
+            for t, t2 in sorted(pairs):
+                file.write(f"L\t{t >> 1}\t{'+-'[t & 1]}\t{t2 >> 1}\t{'+-'[t2 & 1]}\t{k - 1}M\n")
+
+
+@dataclasses.dataclass
+class UnitigLinks:
+    """What kmx_count_unitig_links returns: which oriented unitig follows which.  The oriented unitig t = 2 * u + s is unitig u as
+    written (s = 0) or its reverse complement (s = 1); offsets int64[2 * n_unitigs + 1]: t owns targets[offsets[t]:offsets[t + 1]], at
+    most four; targets int64[n_links]: the oriented unitigs t' that follow, each overlapping t by k - 1 bases."""
+    offsets: "torch.Tensor"
+    targets: "torch.Tensor"
+
+    @property
+    def n_links(self) -> int:
+        return int(self.targets.numel())
+
+    @property
+    def degrees(self):
+        """int64[n_unitigs, 2]: the links leaving unitig u as written (column 0) and leaving its mirror (column 1)"""
+        return (self.offsets[1:] - self.offsets[:-1]).view(-1, 2)
+
+    def sources(self):
+        """int64[n_links]: the t of every link, in the order of `targets`"""
+        deg = self.offsets[1:] - self.offsets[:-1]
+        return torch.repeat_interleave(torch.arange(deg.numel(), device=deg.device), deg)
+
 
 @dataclasses.dataclass
 class ReadPaths:
@@ -743,6 +794,92 @@ class Context:
     def count_read_paths2(self, bases, n_reads, read_len, k, kmers, unitigs: Unitigs, place=None, offsets=None, max_segments=None) -> ReadPaths:
         """kmx_count_read_paths2 (k 33..64): kmers int64[n, 2] = (low, high) words."""
         return self._read_paths(2, bases, n_reads, read_len, k, kmers, unitigs, place, offsets, max_segments)
+
+    # ------------------------------------------------------------ the unitigs as a graph
+    @_on_ctx_stream
+    def count_unitig_links(self, unitigs: Unitigs, adjacency, n: int, place=None, max_links=None) -> UnitigLinks:
+        """kmx_count_unitig_links -> UnitigLinks: the links between the oriented unitigs (include/kmx.h has the rule).  adjacency =
+        (edges, flips, nbr) as count_adjacency(2)(..., flips=True, neighbors=True) returned them for the table the unitigs were made
+        of, n its entry count; `place` is count_unitig_index(unitigs, n), made here when not given.  max_links=None counts first and
+        then allocates, a number gives room for that many (KmxError E_NOMEM above it).  One call for both key widths."""
+        n = int(n)
+        edges, flips, nbr = adjacency
+        nbr = nbr.contiguous()
+        if place is None:
+            place = self.count_unitig_index(unitigs, n)
+        u = unitigs.n_unitigs
+        args = (self._h, _ptr(edges) if n else None, _ptr(flips) if n else None, _ptr(nbr) if n else None, n,
+                _ptr(unitigs.nodes) if unitigs.n_nodes else None, _ptr(unitigs.offsets), u, _ptr(place) if n else None)
+        m = C.c_uint64(0)
+        if max_links is None:   # count, then allocate
+            self._ck(self.lib.kmx_count_unitig_links(*args, None, None, 0, C.byref(m)))
+            max_links = int(m.value)
+        lo = torch.zeros(2 * u + 1, dtype=torch.int64, device=self.device)
+        targets = self.empty(max(int(max_links), 1), torch.int64)
+        self._ck(self.lib.kmx_count_unitig_links(*args, _ptr(lo), _ptr(targets), int(max_links), C.byref(m)))
+        return UnitigLinks(lo, targets[:int(m.value)])
+
+    def _unitig_select(self, words, kmers, counts, unitigs, keep, place):
+        n = int(counts.numel())
+        kmers = kmers.contiguous()
+        if place is None:
+            place = self.count_unitig_index(unitigs, n)
+        keep = (keep if keep.dtype == torch.uint8 else keep.to(torch.uint8)).contiguous()
+        if keep.numel() != unitigs.n_unitigs:
+            raise ValueError("keep holds one byte per unitig")
+        ok = self.empty(words * max(n, 1), torch.int64)
+        oc = self.empty(max(n, 1), torch.int64)
+        m = C.c_uint64(0)
+        fn = self.lib.kmx_count_unitig_select if words == 1 else self.lib.kmx_count_unitig_select2
+        self._ck(fn(self._h, _ptr(kmers) if n else None, _ptr(counts) if n else None, n, _ptr(place) if n else None, _ptr(unitigs.offsets),
+                    unitigs.n_unitigs, _ptr(keep) if unitigs.n_unitigs else None, _ptr(ok), _ptr(oc), n, C.byref(m)))
+        ok = ok[:words * m.value]
+        return (ok.view(-1, 2) if words == 2 else ok), oc[:m.value]
+
+    @_on_ctx_stream
+    def count_unitig_select(self, kmers, counts, unitigs: Unitigs, keep, place=None):
+        """kmx_count_unitig_select -> (kmers, counts): the entries of the table that lie in a unitig u with keep[u] set (bool or uint8
+        per unitig), order kept -- a table again.  Entries in no unitig are dropped.  `place` as for count_unitig_links."""
+        return self._unitig_select(1, kmers, counts, unitigs, keep, place)
+
+    @_on_ctx_stream
+    def count_unitig_select2(self, kmers, counts, unitigs: Unitigs, keep, place=None):
+        """kmx_count_unitig_select2 -> (kmers int64[n, 2], counts) for the tables of count_canonical2."""
+        return self._unitig_select(2, kmers, counts, unitigs, keep, place)
+
+    def _clip_tips(self, words, kmers, counts, k, min_count, max_nodes, rounds, islands):
+        one = words == 1
+        max_nodes = int(k) if max_nodes is None else int(max_nodes)
+        removed = []
+        for _ in range(int(rounds)):
+            n = int(counts.numel())
+            if n == 0:
+                break
+            adj = (self.count_adjacency if one else self.count_adjacency2)(kmers, counts, k, min_count, flips=True, neighbors=True)
+            un = (self.count_unitigs if one else self.count_unitigs2)(kmers, counts, k, min_count, adjacency=adj)
+            place = self.count_unitig_index(un, n)
+            links = self.count_unitig_links(un, adj, n, place=place)
+            keep = ~un.tips(links, max_nodes, islands)
+            kmers, counts = (self.count_unitig_select if one else self.count_unitig_select2)(kmers, counts, un, keep, place=place)
+            removed.append(n - int(counts.numel()))
+            if removed[-1] == 0:
+                break
+        return kmers, counts, removed
+
+    @_on_ctx_stream
+    def count_clip_tips(self, kmers, counts, k, min_count=1, max_nodes=None, rounds=1, islands=False):
+        """Tip clipping -> (kmers, counts, removed): the table without the entries of its short dead-end unitigs, and the number of
+        entries each round removed.  A round is adjacency -> unitigs -> index -> links -> Unitigs.tips -> select, all on the device;
+        it is run `rounds` times, or until a round removes nothing.  max_nodes (default k) is the longest unitig that counts as a
+        tip; islands=True also removes short unitigs with no link at all.  Entries below min_count lie in no unitig and leave in the
+        first round.  The rule is topological and blunt: it looks at no counts, and a fork whose two branches are BOTH short dead
+        ends loses both.  k 2..31."""
+        return self._clip_tips(1, kmers, counts, k, min_count, max_nodes, rounds, islands)
+
+    @_on_ctx_stream
+    def count_clip_tips2(self, kmers, counts, k, min_count=1, max_nodes=None, rounds=1, islands=False):
+        """count_clip_tips for the tables of count_canonical2 (k 33..64)."""
+        return self._clip_tips(2, kmers, counts, k, min_count, max_nodes, rounds, islands)
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

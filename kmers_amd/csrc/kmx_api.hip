@@ -1269,6 +1269,73 @@ int kmx_count_read_paths2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, cons
     return read_paths_impl(ctx, kQuery2, reads, k, d_kmers2, n, d_place, d_offsets, n_unitigs, d_path_offsets, d_segments, max_segments, h_n_segments);
 }
 
+// ---- the unitigs as a graph, and a table cut down by unitig (kmx_count_links.hip) ----
+int kmx_count_unitig_links(kmx_ctx* ctx, const uint8_t* d_edges, const uint8_t* d_flips, const uint64_t* d_nbr, uint64_t n, const uint64_t* d_nodes,
+                           const uint64_t* d_offsets, uint64_t n_unitigs, const uint64_t* d_place, uint64_t* d_link_offsets, uint64_t* d_links,
+                           uint64_t max_links, uint64_t* h_n_links) {
+    if (!ctx || !h_n_links || n > (1ull << 40) || n_unitigs > (1ull << 40)) return KMX_E_ARG;
+    if ((d_link_offsets == nullptr) != (d_links == nullptr)) return KMX_E_ARG;
+    if (n_unitigs && (!d_nodes || !d_offsets || (n && (!d_edges || !d_flips || !d_nbr || !d_place)))) return KMX_E_ARG;
+    *h_n_links = 0;
+    if (n_unitigs == 0 && (n == 0 || !d_link_offsets)) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    if (n_unitigs == 0) {   // the single offset 0
+        KMX_HIP(ctx, hipMemsetAsync(d_link_offsets, 0, 8u, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return KMX_OK;
+    }
+    const char* who = "kmx_count_unitig_links";
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::count_links_bytes(n_unitigs), &area)) return st;
+    uint64_t n_links = 0;
+    KMX_HIP(ctx, kmx::launch_count_links_count(d_edges, d_flips, d_nbr, n, d_nodes, d_offsets, n_unitigs, d_place, area, ctx->h_pinned, &n_links,
+                                               ctx->stream));
+    *h_n_links = n_links;
+    if (!d_link_offsets) return KMX_OK;
+    const int room = room_for(ctx, who, n_links, "links", max_links);   // (the offsets are written all the same, as the read paths' are)
+    KMX_HIP(ctx, kmx::launch_count_links_emit(d_edges, d_flips, d_nbr, n, d_nodes, d_offsets, n_unitigs, d_place, area, n_links, d_link_offsets,
+                                              room == KMX_OK ? d_links : nullptr, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return room;
+}
+
+// One body for both key widths: the filter's -- its area, its emit -- behind another mark.
+static int unitig_select_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n,
+                              const uint64_t* d_place, const uint64_t* d_offsets, uint64_t n_unitigs, const uint8_t* d_keep, uint64_t* d_kmers_out,
+                              uint64_t* d_counts_out, uint64_t max_out, uint64_t* h_n_out) {
+    if (!ctx || !h_n_out || ((d_kmers_out == nullptr) != (d_counts_out == nullptr))) return KMX_E_ARG;
+    if ((n && (!d_kmers || !d_counts || !d_place)) || n > (1ull << 38)) return KMX_E_ARG;   // (the mark pass is one grid of a thread per entry)
+    if ((n_unitigs && (!d_offsets || !d_keep)) || n_unitigs > (1ull << 40)) return KMX_E_ARG;
+    if (words == 2u && (!aligned16(d_kmers) || !aligned16(d_kmers_out))) return KMX_E_ARG;
+    *h_n_out = 0;
+    if (n == 0 || n_unitigs == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::count_filter_bytes(n), &area)) return st;
+    uint64_t n_out = 0;
+    KMX_HIP(ctx, kmx::launch_count_select_mark(d_place, n, d_offsets, n_unitigs, d_keep, area, ctx->h_pinned, &n_out, ctx->stream));
+    *h_n_out = n_out;
+    if (!d_kmers_out || n_out == 0) return KMX_OK;
+    if (int st = room_for(ctx, who, n_out, "entries kept", max_out)) return st;
+    KMX_HIP(ctx, kmx::launch_count_filter_emit(words, d_kmers, d_counts, n, area, d_kmers_out, d_counts_out, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_unitig_select(kmx_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, const uint64_t* d_place,
+                            const uint64_t* d_offsets, uint64_t n_unitigs, const uint8_t* d_keep, uint64_t* d_kmers_out, uint64_t* d_counts_out,
+                            uint64_t max_out, uint64_t* h_n_out) {
+    return unitig_select_impl(ctx, "kmx_count_unitig_select", 1u, d_kmers, d_counts, n, d_place, d_offsets, n_unitigs, d_keep, d_kmers_out, d_counts_out,
+                              max_out, h_n_out);
+}
+
+int kmx_count_unitig_select2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n, const uint64_t* d_place,
+                             const uint64_t* d_offsets, uint64_t n_unitigs, const uint8_t* d_keep, uint64_t* d_kmers2_out, uint64_t* d_counts_out,
+                             uint64_t max_out, uint64_t* h_n_out) {
+    return unitig_select_impl(ctx, "kmx_count_unitig_select2", 2u, d_kmers2, d_counts, n, d_place, d_offsets, n_unitigs, d_keep, d_kmers2_out,
+                              d_counts_out, max_out, h_n_out);
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

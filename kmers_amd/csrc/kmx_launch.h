@@ -175,6 +175,16 @@ hipError_t launch_count_paths_mark(const u64* places, uint8_t* flags, const u64*
                                    u64 n_unitigs, void* area, unsigned long long* h_pinned, u64* h_segments, hipStream_t st);
 hipError_t launch_count_paths_emit(const u64* places, const uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u64 n_win,
                                    const u64* unitig_offsets, u64 n_unitigs, const void* area, u64* path_offsets, u64* segments, hipStream_t st);
+// kmx_count_links.hip: the links between the unitigs -- count counts them (one host round trip), emit writes the 2 U + 1 offsets and,
+// unless links == nullptr, the targets (n_unitigs >= 1) -- and the mark of the entries of kept unitigs, in the filter's area
+// (count_filter_bytes(n)) and for the filter's emit
+size_t count_links_bytes(u64 n_unitigs);
+hipError_t launch_count_links_count(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, const u64* nodes, const u64* offsets, u64 n_unitigs,
+                                    const u64* place, void* area, unsigned long long* h_pinned, u64* h_links, hipStream_t st);
+hipError_t launch_count_links_emit(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, const u64* nodes, const u64* offsets, u64 n_unitigs,
+                                   const u64* place, const void* area, u64 n_links, u64* link_offsets, u64* links, hipStream_t st);
+hipError_t launch_count_select_mark(const u64* place, u64 n, const u64* offsets, u64 n_unitigs, const uint8_t* keep_u, void* area,
+                                    unsigned long long* h_pinned, u64* h_out, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
