@@ -769,6 +769,48 @@ pub fn count_unitig_select2(ctx: &HipContext, table: CountTable<'_>, d_place: &D
     Ok(n_out)
 }
 
+/// The parameters of `count_unitig_clean` (include/kmx.h has the rule): a limit of 0 turns its rule off; `tip_num == 0` makes the tip
+/// rule topological, otherwise a dead end goes if its mean count per node is below `tip_num / tip_den` of a sibling's.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct CleanRule {
+    pub tip_max_nodes: u64,
+    pub tip_num: u32,
+    pub tip_den: u32,
+    pub bubble_max_nodes: u64,
+    pub bubble_max_diff: u64,
+    pub island_max_nodes: u64,
+}
+
+impl CleanRule {
+    /// The choices of the Python layer for k-mers of k bases: tips of at most k nodes at ratio 1/1, bubbles whose branches have at most
+    /// 2 k nodes and differ by at most 4, islands kept.  Choices, not measurements.
+    pub fn for_k(k: u8) -> CleanRule {
+        CleanRule { tip_max_nodes: k as u64, tip_num: 1, tip_den: 1, bubble_max_nodes: 2 * k as u64, bubble_max_diff: 4, island_max_nodes: 0 }
+    }
+}
+
+/// Which unitigs to drop to clean the compacted graph (`kmx_count_unitig_clean`): one keep byte per unitig into `d_keep`, what
+/// `count_unitig_select(2)` takes, and the reason (`KMX_CLEAN_KEEP`, `KMX_CLEAN_TIP`, `KMX_CLEAN_BUBBLE`, `KMX_CLEAN_ISLAND`) into
+/// `d_reason` if given.  `d_offsets` / `d_circular` / `d_count_sums` are `count_unitigs`' outputs (the latter two may be None: no
+/// unitig circular, every mean count 1), `d_link_offsets` / `d_links` / `n_links` `count_unitig_links`'.  One call for both key widths.
+/// Asynchronous.
+pub fn count_unitig_clean(ctx: &HipContext, d_offsets: &DeviceBuf<'_>, d_circular: Option<&DeviceBuf<'_>>, d_count_sums: Option<&DeviceBuf<'_>>,
+                          n_unitigs: u64, d_link_offsets: &DeviceBuf<'_>, d_links: &DeviceBuf<'_>, n_links: u64, rule: CleanRule,
+                          d_keep: &DeviceBuf<'_>, d_reason: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!(d_circular.map_or(true, |b| n_unitigs as u128 <= b.len() as u128), "circular flags shorter than the unitig count");
+    assert!(d_count_sums.map_or(true, |b| n_unitigs as u128 * 8 <= b.len() as u128), "count sums shorter than the unitig count");
+    assert!((2 * n_unitigs as u128 + 1) * 8 <= d_link_offsets.len() as u128, "link offsets shorter than twice the unitig count + 1");
+    assert!(n_links as u128 * 8 <= d_links.len() as u128, "links shorter than the link count");
+    assert!(n_unitigs as u128 <= d_keep.len() as u128, "keep bytes shorter than the unitig count");
+    assert!(d_reason.map_or(true, |b| n_unitigs as u128 <= b.len() as u128), "reason bytes shorter than the unitig count");
+    ctx.ck(unsafe { kmx_count_unitig_clean(ctx.0, d_offsets.as_ptr::<u64>(), d_circular.map_or(ptr::null(), |b| b.as_ptr::<u8>()),
+                                           d_count_sums.map_or(ptr::null(), |b| b.as_ptr::<u64>()), n_unitigs, d_link_offsets.as_ptr::<u64>(),
+                                           d_links.as_ptr::<u64>(), n_links, rule.tip_max_nodes, rule.tip_num, rule.tip_den, rule.bubble_max_nodes,
+                                           rule.bubble_max_diff, rule.island_max_nodes, d_keep.as_mut_ptr::<u8>(),
+                                           d_reason.map_or(ptr::null_mut(), |b| b.as_mut_ptr::<u8>())) })
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -574,6 +574,56 @@ int kmx_count_unitig_select2(kmx_ctx *ctx, const uint64_t *d_kmers2, const uint6
                              const uint64_t *d_offsets, uint64_t n_unitigs, const uint8_t *d_keep, uint64_t *d_kmers2_out,
                              uint64_t *d_counts_out, uint64_t max_out, uint64_t *h_n_out);
 
+/* Which unitigs to drop to clean the compacted graph: one keep byte per unitig, exactly what kmx_count_unitig_select(2) takes, and
+ * optionally the reason.  Three rules, exclusive by degree: a short DEAD END (tip) that loses to a sibling by mean count, the weaker
+ * branch of a SIMPLE BUBBLE, a short ISLAND with no link at all.  The rule is defined on the arrays alone: any bytes give the answer
+ * stated here and never an access outside the arrays.
+ * NOTATION.  U = n_unitigs.  m(u) = d_offsets[u + 1] - d_offsets[u], read as 0 if d_offsets[u + 1] < d_offsets[u].  S(u) =
+ * d_count_sums[u] as a u64 (d_count_sums == NULL: S(u) = m(u), a mean of 1).  t = 2 u + s is an oriented unitig, mirror(t) = t ^ 1.
+ * L(t) is the list d_links[lo .. hi) with lo = d_link_offsets[t], hi = d_link_offsets[t + 1] -- but only if lo <= hi <= n_links,
+ * hi - lo <= 4 and every listed target is < 2 U; otherwise L(t) is empty.  deg(t) = |L(t)|.
+ * THE ORDER.  u LOSES to y at (a, b) iff S(u) m(y) b < S(y) m(u) a, or the two sides are equal and u > y: the mean count per node
+ * of u is below a / b of y's, ties going to the smaller index.  The comparison is exact, in integers (the products are formed in
+ * full, for any S and m; no floating point).  With a = b it is a strict total order on distinct unitigs; with 1 <= a <= b no two
+ * unitigs lose to each other.
+ * PARAMETERS.  tip_max_nodes (0 turns the tip rule off), tip_num / tip_den (the ratio a / b of the tip rule; tip_num == 0: the tip
+ * rule is topological), bubble_max_nodes (0 turns the bubble rule off), bubble_max_diff, island_max_nodes (0 turns the island rule
+ * off).  tip_num > tip_den, tip_den == 0 with tip_max_nodes > 0, tip_num or tip_den above 65535: KMX_E_ARG.
+ * THE REASON of unitig u.  A circular unitig (d_circular[u] != 0; d_circular == NULL: none is) has reason KMX_CLEAN_KEEP.  For
+ * the rest let d0 = deg(2 u), d1 = deg(2 u + 1):
+ *   KMX_CLEAN_ISLAND  d0 = d1 = 0, island_max_nodes > 0 and m(u) <= island_max_nodes.
+ *   KMX_CLEAN_TIP     exactly one of d0, d1 is 0, tip_max_nodes > 0 and m(u) <= tip_max_nodes; let t be the side that has links.
+ *                     tip_num == 0: dropped (all of this is then "not circular, short, one side open").  Otherwise dropped iff some
+ *                     x in L(t) and some z in L(x ^ 1) with z >> 1 != u have u LOSES to z >> 1 at (tip_num, tip_den): z ^ 1 is a
+ *                     SIBLING of t at x, another oriented unitig that enters x.  A tip without a sibling stays.
+ *   KMX_CLEAN_BUBBLE  d0 = d1 = 1, bubble_max_nodes > 0 and m(u) <= bubble_max_nodes; let x = L(2 u)[0], s = L(2 u + 1)[0] ^ 1.
+ *                     All of: L(s) has exactly two elements, distinct, one of them 2 u -- the other is y, yu = y >> 1; L(x ^ 1) has
+ *                     exactly two elements and they are 2 u + 1 and y ^ 1 in either order; L(y) = [x] and L(y ^ 1) = [s ^ 1];
+ *                     u != yu, and neither u nor yu equals s >> 1 or x >> 1; yu is not circular; m(yu) <= bubble_max_nodes;
+ *                     |m(u) - m(yu)| <= bubble_max_diff; u LOSES to yu at (1, 1).
+ *   KMX_CLEAN_KEEP    everything else.
+ * The bubble condition is symmetric under u <-> yu and under mirroring, and (1, 1) is a total order: for any input exactly one
+ * branch of each simple bubble is dropped.  d_keep[u] = 1 iff the reason is KMX_CLEAN_KEEP, else 0; d_reason[u] = the reason.
+ * PALINDROMIC UNITIGS (even k).  Where a palindromic one-node unitig sits at a junction the links lack mirror symmetry (above), so
+ * L(x ^ 1) can miss an oriented unitig that enters x.  The rule is not bent for it: such a tip finds no sibling, such a bubble does
+ * not close, and the unitig stays.
+ * One round drops tips, branches and islands that the SAME graph shows; dropping them makes new unitigs (the two stems around a
+ * popped bubble join), so cleaning is run in rounds: clean, select, adjacency, unitigs, index, links, clean.
+ * d_offsets / d_circular / d_count_sums / n_unitigs as kmx_count_unitigs(2) wrote them, d_link_offsets (2 U + 1 u64) / d_links /
+ * n_links as kmx_count_unitig_links wrote them.  Indices only: one call for both key widths.  d_keep and d_reason hold U bytes each
+ * and nothing beyond them is written; d_reason may be NULL.  Outputs must not alias inputs.  Deterministic: repeated calls give
+ * identical bytes.  n_unitigs == 0 is a no-op (nothing read, nothing written).  NULL ctx, n_unitigs above 2^40, n_links above 2^43
+ * (four links per oriented unitig), the parameter errors above; with n_unitigs > 0 also d_keep, d_offsets or d_link_offsets NULL, or
+ * d_links NULL with n_links > 0: KMX_E_ARG.  Working set: none.  Asynchronous. */
+#define KMX_CLEAN_KEEP 0
+#define KMX_CLEAN_TIP 1
+#define KMX_CLEAN_BUBBLE 2
+#define KMX_CLEAN_ISLAND 3
+int kmx_count_unitig_clean(kmx_ctx *ctx, const uint64_t *d_offsets, const uint8_t *d_circular, const uint64_t *d_count_sums,
+                           uint64_t n_unitigs, const uint64_t *d_link_offsets, const uint64_t *d_links, uint64_t n_links,
+                           uint64_t tip_max_nodes, uint32_t tip_num, uint32_t tip_den, uint64_t bubble_max_nodes,
+                           uint64_t bubble_max_diff, uint64_t island_max_nodes, uint8_t *d_keep, uint8_t *d_reason);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

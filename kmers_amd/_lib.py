@@ -36,6 +36,8 @@ NO_ENTRY = 2**64 - 1
 PLACE_NONE = 0
 PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_POS = range(4)
 PATH_WORDS = 4
+# kmx_count_unitig_clean: why a unitig is dropped (KMX_CLEAN_*; 0 = kept)
+CLEAN_KEEP, CLEAN_TIP, CLEAN_BUBBLE, CLEAN_ISLAND = range(4)
 
 
 class KmxError(RuntimeError):
@@ -139,6 +141,7 @@ SIGNATURES = {
     "kmx_count_unitig_links": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_unitig_select": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_unitig_select2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_unitig_clean": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _u32, _u32, _u64, _u64, _u64, _vp, _vp]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

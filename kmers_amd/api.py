@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -166,6 +166,17 @@ class Unitigs:
     def lengths(self):
         """int64[n_unitigs]: nodes per unitig (its sequence has k - 1 bases more)"""
         return self.offsets[1:] - self.offsets[:-1]
+
+    @property
+    def mean_counts(self):
+        """float64[n_unitigs]: the mean count per node, count_sums (as u64) / lengths -- for looking at a graph.  Without count_sums
+        every mean is 1, as the cleaning rule reads it.  The rule itself (count_unitig_clean) never uses this: it compares integer
+        products."""
+        if self.count_sums is None:
+            return torch.ones(self.n_unitigs, dtype=torch.float64, device=self.offsets.device)
+        s = self.count_sums.to(torch.float64)
+        s = torch.where(self.count_sums < 0, s + 2.0**64, s)
+        return s / self.lengths.to(torch.float64)
 
     def sequences(self):
         """kmx_count_unitig_sequences(2) -> uint8[n_nodes + n_unitigs * (k - 1)], ASCII ACGT: unitig u starts at byte
@@ -873,13 +884,73 @@ class Context:
         it is run `rounds` times, or until a round removes nothing.  max_nodes (default k) is the longest unitig that counts as a
         tip; islands=True also removes short unitigs with no link at all.  Entries below min_count lie in no unitig and leave in the
         first round.  The rule is topological and blunt: it looks at no counts, and a fork whose two branches are BOTH short dead
-        ends loses both.  k 2..31."""
+        ends loses both; count_simplify(2) compares mean counts and pops bubbles as well (count_unitig_clean).  k 2..31."""
         return self._clip_tips(1, kmers, counts, k, min_count, max_nodes, rounds, islands)
 
     @_on_ctx_stream
     def count_clip_tips2(self, kmers, counts, k, min_count=1, max_nodes=None, rounds=1, islands=False):
         """count_clip_tips for the tables of count_canonical2 (k 33..64)."""
         return self._clip_tips(2, kmers, counts, k, min_count, max_nodes, rounds, islands)
+
+    # ------------------------------------------------------------ cleaning the compacted graph
+    @_on_ctx_stream
+    def count_unitig_clean(self, unitigs: Unitigs, links: UnitigLinks, tip_max_nodes=None, tip_ratio=(1, 1), bubble_max_nodes=None, bubble_max_diff=4,
+                           island_max_nodes=0):
+        """kmx_count_unitig_clean -> (keep uint8[U], reason uint8[U]): which unitigs to drop, one kernel over the unitigs and their
+        links (include/kmx.h has the rule); `keep` goes into count_unitig_select(2) as it is, reason is CLEAN_KEEP (0), CLEAN_TIP,
+        CLEAN_BUBBLE or CLEAN_ISLAND.  A dead end of at most tip_max_nodes nodes (default k) is dropped if its mean count per node
+        is below tip_ratio = (num, den) of a sibling's, ties to the smaller index -- (1, 1): the weaker of two; None: every short
+        dead end, exactly Unitigs.tips.  Of a simple bubble whose branches have at most bubble_max_nodes nodes (default 2 k: a
+        substitution makes branches of k nodes, a short indel somewhat more or fewer) and differ by at most bubble_max_diff nodes
+        (default 4), the branch with the lower mean count is dropped.  island_max_nodes > 0 also drops unitigs of at most that many
+        nodes with no link at all.  The defaults are choices, not measurements.  One call for both key widths."""
+        k = int(unitigs.k)
+        num, den = (0, 1) if tip_ratio is None else (int(tip_ratio[0]), int(tip_ratio[1]))
+        u = unitigs.n_unitigs
+        if links.offsets.numel() != 2 * u + 1:
+            raise ValueError("links holds 2 * n_unitigs + 1 offsets")
+        keep, reason = self.empty(u, torch.uint8), self.empty(u, torch.uint8)
+        self._ck(self.lib.kmx_count_unitig_clean(
+            self._h, _ptr(unitigs.offsets), _ptr(unitigs.circular) if unitigs.circular is not None and u else None,
+            _ptr(unitigs.count_sums) if unitigs.count_sums is not None and u else None, u, _ptr(links.offsets),
+            _ptr(links.targets) if links.n_links else None, links.n_links, k if tip_max_nodes is None else int(tip_max_nodes), num, den,
+            2 * k if bubble_max_nodes is None else int(bubble_max_nodes), int(bubble_max_diff), int(island_max_nodes),
+            _ptr(keep) if u else None, _ptr(reason) if u else None))
+        return keep, reason
+
+    def _simplify(self, words, kmers, counts, k, min_count, rounds, rule):
+        one = words == 1
+        log = []
+        for _ in range(int(rounds)):
+            n = int(counts.numel())
+            if n == 0:
+                break
+            adj = (self.count_adjacency if one else self.count_adjacency2)(kmers, counts, k, min_count, flips=True, neighbors=True)
+            un = (self.count_unitigs if one else self.count_unitigs2)(kmers, counts, k, min_count, adjacency=adj)
+            place = self.count_unitig_index(un, n)
+            links = self.count_unitig_links(un, adj, n, place=place)
+            keep, reason = self.count_unitig_clean(un, links, **rule)
+            kmers, counts = (self.count_unitig_select if one else self.count_unitig_select2)(kmers, counts, un, keep, place=place)
+            c = torch.bincount(reason, minlength=4).cpu().tolist()
+            log.append({"tips": c[CLEAN_TIP], "bubbles": c[CLEAN_BUBBLE], "islands": c[CLEAN_ISLAND], "removed": n - int(counts.numel())})
+            if log[-1]["removed"] == 0:
+                break
+        return kmers, counts, log
+
+    @_on_ctx_stream
+    def count_simplify(self, kmers, counts, k, min_count=1, rounds=4, **rule):
+        """Graph simplification -> (kmers, counts, log): the table without the entries of the unitigs count_unitig_clean drops --
+        low-coverage dead ends, the weaker branch of every simple bubble and, if asked for, short islands.  A round is adjacency ->
+        unitigs -> index -> links -> clean -> select, all on the device; dropping a branch joins the unitigs around it, so rounds
+        are run until one removes nothing, `rounds` (default 4, a choice) at the most.  `rule` are count_unitig_clean's keyword
+        arguments.  log holds a dict per round: the unitigs dropped as "tips", "bubbles" and "islands", and the entries "removed".
+        Entries below min_count lie in no unitig and leave in the first round, as with count_clip_tips.  k 2..31."""
+        return self._simplify(1, kmers, counts, k, min_count, rounds, rule)
+
+    @_on_ctx_stream
+    def count_simplify2(self, kmers, counts, k, min_count=1, rounds=4, **rule):
+        """count_simplify for the tables of count_canonical2 (k 33..64)."""
+        return self._simplify(2, kmers, counts, k, min_count, rounds, rule)
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

@@ -1336,6 +1336,21 @@ int kmx_count_unitig_select2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint6
                               d_counts_out, max_out, h_n_out);
 }
 
+// ---- which unitigs to drop: tips, bubble branches, islands (kmx_count_clean.hip) ----
+int kmx_count_unitig_clean(kmx_ctx* ctx, const uint64_t* d_offsets, const uint8_t* d_circular, const uint64_t* d_count_sums, uint64_t n_unitigs,
+                           const uint64_t* d_link_offsets, const uint64_t* d_links, uint64_t n_links, uint64_t tip_max_nodes, uint32_t tip_num,
+                           uint32_t tip_den, uint64_t bubble_max_nodes, uint64_t bubble_max_diff, uint64_t island_max_nodes, uint8_t* d_keep,
+                           uint8_t* d_reason) {
+    if (!ctx || n_unitigs > (1ull << 40) || n_links > (1ull << 43)) return KMX_E_ARG;   // (four links per oriented unitig)
+    if (tip_num > tip_den || tip_num > 65535u || tip_den > 65535u || (tip_den == 0u && tip_max_nodes > 0u)) return KMX_E_ARG;
+    if (n_unitigs == 0) return KMX_OK;
+    if (!d_keep || !d_offsets || !d_link_offsets || (n_links && !d_links)) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_unitig_clean(d_offsets, d_circular, d_count_sums, n_unitigs, d_link_offsets, d_links, n_links, tip_max_nodes, tip_num,
+                                                tip_den, bubble_max_nodes, bubble_max_diff, island_max_nodes, d_keep, d_reason, ctx->stream));
+    return KMX_OK;
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

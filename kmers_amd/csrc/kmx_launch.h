@@ -185,6 +185,11 @@ hipError_t launch_count_links_emit(const uint8_t* edges, const uint8_t* flips, c
                                    const u64* place, const void* area, u64 n_links, u64* link_offsets, u64* links, hipStream_t st);
 hipError_t launch_count_select_mark(const u64* place, u64 n, const u64* offsets, u64 n_unitigs, const uint8_t* keep_u, void* area,
                                     unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+// kmx_count_clean.hip: which unitigs to drop -- a keep byte and, unless reason == nullptr, a reason byte per unitig (n_unitigs >= 1;
+// circular and sums may be nullptr); no working set, asynchronous
+hipError_t launch_count_unitig_clean(const u64* offsets, const uint8_t* circular, const u64* sums, u64 n_unitigs, const u64* link_offsets,
+                                     const u64* links, u64 n_links, u64 tip_max, u32 tip_num, u32 tip_den, u64 bubble_max, u64 bubble_diff,
+                                     u64 island_max, uint8_t* keep, uint8_t* reason, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
