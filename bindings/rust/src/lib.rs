@@ -508,6 +508,43 @@ pub fn count_read_stats2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64
                                           d_stats.as_mut_ptr::<u64>()) })
 }
 
+/// Substitution errors of a uniform batch repaired against a table (`kmx_count_correct_reads`): `d_out` receives the reads -- every
+/// byte of the batch is written -- with the bases replaced that no window of count >= `solid_min` covers, at least `min_cover`
+/// (1 ..= k) valid windows do, and exactly one other base makes all of those windows solid.  `d_fixes`, when given, receives
+/// `KMX_CR_WORDS` u64 per read (`KMX_CR_N_WEAK` .. `KMX_CR_N_AMBIGUOUS`).  Decisions are taken against the original bytes: `d_out`
+/// must not overlap `d_reads` (`KMX_E_ARG`).
+pub fn count_correct_reads(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>, solid_min: u64,
+                           min_cover: u32, d_out: &DeviceBuf<'_>, d_fixes: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    table.check(1);
+    let fixes = correct_outputs(d_reads, n_reads, read_len, d_out, d_fixes);
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_correct_reads(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, solid_min, min_cover,
+                                            d_out.as_mut_ptr::<u8>(), fixes) })
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_correct_reads2`).
+pub fn count_correct_reads2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>, solid_min: u64,
+                            min_cover: u32, d_out: &DeviceBuf<'_>, d_fixes: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    table.check(2);
+    let fixes = correct_outputs(d_reads, n_reads, read_len, d_out, d_fixes);
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_correct_reads2(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, solid_min, min_cover,
+                                             d_out.as_mut_ptr::<u8>(), fixes) })
+}
+
+// the sizes count_correct_reads(2) ask of their buffers; the rows' pointer, null when they are not wanted
+fn correct_outputs(d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_out: &DeviceBuf<'_>, d_fixes: Option<&DeviceBuf<'_>>) -> *mut u64 {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(n_reads as u128 * read_len as u128 <= d_out.len() as u128, "output shorter than the batch's reads");
+    match d_fixes {
+        Some(f) => {
+            assert!(n_reads as u128 * 8 * KMX_CR_WORDS as u128 <= f.len() as u128, "rows shorter than the batch's reads");
+            f.as_mut_ptr::<u64>()
+        }
+        None => ptr::null_mut(),
+    }
+}
+
 /// The abundance spectrum of a table's counts (`kmx_count_spectrum`): `n_bins` bins, bin c = how many entries have count c, the last
 /// bin everything at or above it.
 pub fn count_spectrum(ctx: &HipContext, d_counts: &DeviceBuf<'_>, n: u64, n_bins: usize) -> Result<Vec<u64>, KmxError> {

@@ -353,6 +353,61 @@ int kmx_count_read_stats(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const
 int kmx_count_read_stats2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n,
                           uint64_t solid_min, uint64_t *d_stats);
 
+/* ---- substitution errors corrected against a table ----
+ * BUILD-DEFINED (the crate corrects nothing).  Conservative two-sided spectral correction: a base is replaced only where every
+ * window that covers it says so.  The rule is defined on the arrays alone, so any bytes give one answer.
+ * For one read of L bytes b[0..L), k, a table and solid_min, with windows w = 0 .. L - k:
+ *     valid(w)  what the iterator says (no byte outside ACGTacgt in the window);
+ *     count(w)  what kmx_count_lookup_reads answers for it: an absent key counts 0, an entry whose count is 0 reads as absent,
+ *               d_counts == NULL gives membership 1 / 0;
+ *     solid(w)  valid(w) and count(w) >= solid_min;     weak(w)  valid(w) and not solid(w);
+ *     C(p)      the windows max(0, p - k + 1) .. min(p, L - k) that cover base p;     V(p)  the valid windows of C(p).
+ * Position p is a CANDIDATE iff b[p] is one of ACGTacgt, |V(p)| >= min_cover, and every window of V(p) is weak (no solid window
+ * covers p).  A base a of {A, C, G, T}, other than b[p] read case-insensitively, FIXES p iff every window of V(p), spelled with a at
+ * p and the read's ORIGINAL bytes everywhere else, has a canonical k-mer whose count is >= solid_min (validity of a window cannot
+ * change through such a substitution).  A candidate is CORRECTED iff exactly one base fixes it -- the output byte is that base in
+ * the case of the byte it replaces (lowercase stays lowercase) --, AMBIGUOUS if two or three bases fix it (the byte is left as it
+ * is), and left unchanged otherwise.
+ * Every decision is taken against the original read: decisions do not see each other, and all corrected positions are written.
+ * Two errors less than k apart therefore leave each other's windows weak and stay uncorrected (k or more apart: both are
+ * restored); run the call again on its output to reach them.  Out of scope: bytes outside ACGTacgt (an N is never replaced, and
+ * the windows around it are not in V(p)), insertions and deletions, and any cap on the corrections per read.
+ * What follows from the rule:
+ *   - solid_min == 0: every valid window is solid, so there is no candidate and the output equals the input;
+ *   - n == 0 (an empty table) with solid_min >= 1: every valid window is weak, nothing fixes, the output equals the input; the
+ *     candidates are still counted;
+ *   - a read with no window (shorter than k, empty, uniform read_len < k, a ragged read of 2^31 bases or more, which the scans skip)
+ *     is copied through and its row is four zeros;
+ *   - deterministic: repeated calls give identical bytes.
+ * One row of KMX_CR_WORDS u64 per read, row r at d_fixes + KMX_CR_WORDS * r: */
+#define KMX_CR_WORDS 4u
+#define KMX_CR_N_WEAK 0u       /* weak windows of the read: KMX_RS_N_VALID - KMX_RS_N_SOLID of kmx_count_read_stats for the same arguments */
+#define KMX_CR_N_CANDIDATES 1u /* candidate positions */
+#define KMX_CR_N_CORRECTED 2u  /* candidates with exactly one fixing base: the bytes that differ from the input */
+#define KMX_CR_N_AMBIGUOUS 3u  /* candidates with two or three fixing bases */
+/* d_out_bases is addressed exactly as reads->d_bases: byte i of the one corresponds to byte i of the other.  Uniform reads:
+ * n_reads * read_len bytes are written; ragged reads: the bytes [offsets[0], offsets[n_reads]) and nothing outside them.  Every byte
+ * of that range is written on every successful call that has reads (a device-to-device copy, then the corrected bytes).  It must
+ * not overlap d_bases over that range (KMX_E_ARG): decisions are against the original bytes, so there is no in-place form.  Every
+ * row of d_fixes is written; d_fixes == NULL skips the rows.  Only n_reads == 0 is a no-op.
+ * min_cover in 1 .. k (KMX_E_ARG otherwise): 1 lets the bases at a read's two ends, which a single window covers, be corrected;
+ * k restricts the call to bases that all k windows cover and that are all valid.  k in [1,31], KMX_E_K_RANGE otherwise (checked
+ * first); NULL ctx / reads / d_out_bases with n_reads > 0, n > 2^40: KMX_E_ARG.
+ * Every input kmx_count_read_stats accepts is accepted, through its routes and with its synchronisation (ragged reads: window
+ * offsets are made on the device, and the first and last read offset come back to the host).
+ * Working set in the context's work buffer: that of kmx_count_read_stats for the same reads -- a256(8 * windows) + a256(windows),
+ * ragged reads the window offsets, long reads the segment plan -- laid out before any kernel runs, and, behind it, the directory of
+ * kmx_count_lookup when it pays for one query per window and fits (left out, never refused); the decision's own searches use that
+ * directory when it is there and need nothing else.  150 bp reads at k = 31: 1080 bytes per read here, 150 + 32 bytes per read out.
+ * Above the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM BEFORE any kernel runs or any byte is written.  The call uses the work
+ * buffer (a following kmx_fastx_parse cannot reuse its chunk prefixes). */
+int kmx_count_correct_reads(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers, const uint64_t *d_counts, uint64_t n,
+                            uint64_t solid_min, uint32_t min_cover, uint8_t *d_out_bases, uint64_t *d_fixes);
+/* The same for two-word keys, k in [33,64] (d_kmers2 16-byte aligned, KMX_E_ARG otherwise): the routes and the working set of
+ * kmx_count_read_stats2 (+ a256(16 * windows) for the canonical words). */
+int kmx_count_correct_reads2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n,
+                             uint64_t solid_min, uint32_t min_cover, uint8_t *d_out_bases, uint64_t *d_fixes);
+
 /* ---------------------------------------------------------------- a count table as the node set of a de Bruijn graph ----
  * BUILD-DEFINED (the crate has no graph).  A TABLE as above.  With x the key of entry i read as the forward strand and
  * mask = 2^(2k) - 1, its eight possible neighbours are, for a base c in 0..3,

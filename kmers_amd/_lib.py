@@ -30,6 +30,9 @@ SETOP_TILE = 2048
 # kmx_count_read_stats(2): the words of a read's row
 RS_N_VALID, RS_N_PRESENT, RS_N_SOLID, RS_MIN, RS_MAX, RS_SUM, RS_MEDIAN, RS_SPAN = range(8)
 RS_WORDS = 8
+# kmx_count_correct_reads(2): the words of a read's row
+CR_N_WEAK, CR_N_CANDIDATES, CR_N_CORRECTED, CR_N_AMBIGUOUS = range(4)
+CR_WORDS = 4
 # kmx_count_adjacency(2): the word of d_nbr where an edge is absent (KMX_NO_ENTRY; -1 in the int64 tensors of kmers_amd.api)
 NO_ENTRY = 2**64 - 1
 # kmx_count_unitig_index / kmx_count_read_paths(2): an entry in no unitig, and the words of a segment's record
@@ -124,6 +127,8 @@ SIGNATURES = {
     "kmx_count_lookup_reads2": (_int, [_vp, _RP, _vp, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_read_stats": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _vp]),
     "kmx_count_read_stats2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _vp]),
+    "kmx_count_correct_reads": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "kmx_count_correct_reads2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
     "kmx_count_spectrum": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "kmx_count_filter": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_filter2": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -640,6 +640,33 @@ class Context:
     def count_read_stats2(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, offsets=None, out=None):
         """kmx_count_read_stats2 (k 33..64; kmers int64[n, 2]) -> int64[n_reads, 8]."""
         return self._read_stats(self.lib.kmx_count_read_stats2, 2, bases, n_reads, read_len, k, kmers, counts, solid_min, offsets, out)
+
+    def _correct_reads(self, fn, words, bases, n_reads, read_len, k, kmers, counts, solid_min, min_cover, offsets, out):
+        n = int(kmers.numel()) // words if kmers is not None else 0
+        if n:
+            kmers = kmers.contiguous()
+        if out is None:
+            out = bases.clone()   # (the call writes the bytes of the reads only: what lies around them in `bases` is kept)
+        fixes = self.empty(CR_WORDS * int(n_reads), torch.int64)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), k, _ptr(kmers) if n else None, _ptr(counts) if counts is not None and n else None, n,
+                    int(solid_min), int(min_cover), _ptr(out) if out.numel() else None, _ptr(fixes) if fixes.numel() else None))
+        return out, fixes.view(-1, CR_WORDS)
+
+    @_on_ctx_stream
+    def count_correct_reads(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, min_cover=1, offsets=None, out=None):
+        """kmx_count_correct_reads -> (corrected uint8 tensor shaped like `bases`, int64[n_reads, 4] (u64 words, columns _lib.CR_*)):
+        substitution errors repaired against the table (kmers, counts).  A base that no solid window (count >= solid_min) covers, but
+        at least `min_cover` valid ones do, is replaced when exactly one other base makes all of those windows solid; two or three such
+        bases leave it as it is (counted in CR_N_AMBIGUOUS).  Decisions are taken against the original bytes, so `out` (uint8, addressed
+        as `bases`) must not overlap `bases`; the bytes of the reads are all written -- ragged reads (`offsets`): the bytes
+        [offsets[0], offsets[n_reads]) and nothing else; without `out` the result starts as a copy of `bases`.  counts=None: membership."""
+        return self._correct_reads(self.lib.kmx_count_correct_reads, 1, bases, n_reads, read_len, k, kmers, counts, solid_min, min_cover, offsets, out)
+
+    @_on_ctx_stream
+    def count_correct_reads2(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, min_cover=1, offsets=None, out=None):
+        """kmx_count_correct_reads2 (k 33..64; kmers int64[n, 2]) -> (corrected bases, int64[n_reads, 4])."""
+        return self._correct_reads(self.lib.kmx_count_correct_reads2, 2, bases, n_reads, read_len, k, kmers, counts, solid_min, min_cover, offsets, out)
 
     @_on_ctx_stream
     def count_spectrum(self, counts, n_bins, out=None):

@@ -819,9 +819,13 @@ static const QueryKind kQuery2{"kmx_count_lookup2", 2u, 33u, 64u, kmx_canonical_
 
 // The lookup behind its argument checks.  `reserved` bytes at the start of the work buffer belong to the caller (the reads form keeps
 // its flags / canonical words there); the directory goes behind them when the byte counts say it pays (count_lookup_wants_dir) and it
-// fits under the cap -- otherwise the plain search, which needs no work buffer: never KMX_E_NOMEM from here.
+// fits under the cap -- otherwise the plain search, which needs no work buffer: never KMX_E_NOMEM from here.  *dir_out / *p_out,
+// where asked for: the directory that was built and its prefix bits, nullptr = the plain search ran.
 static int lookup_run(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k,
-                      const uint64_t* d_query, const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out, size_t reserved) {
+                      const uint64_t* d_query, const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out, size_t reserved,
+                      const void** dir_out = nullptr, uint32_t* p_out = nullptr) {
+    if (dir_out) *dir_out = nullptr;
+    if (p_out) *p_out = 0;
     if (n_query == 0) return KMX_OK;
     if (n == 0) {
         KMX_HIP(ctx, hipMemsetAsync(d_out, 0, 8u * n_query, ctx->stream));
@@ -842,6 +846,8 @@ static int lookup_run(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kme
         }
     }
     KMX_HIP(ctx, kmx::launch_count_lookup(kind.words, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out, dir, p, ctx->stream));
+    if (dir_out) *dir_out = dir;   // (it stays what it is until the work buffer is used again)
+    if (p_out) *p_out = p;
     return KMX_OK;
 }
 
@@ -867,11 +873,12 @@ int kmx_count_lookup2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_
 // ---- the reads forms of the queries: kmx_count_lookup_reads(2) and kmx_count_read_stats(2) ----
 // The windows their arrays are sized for, as kmx_count_canonical counts them: exact for uniform reads (*n_bound = 0: no window), the
 // number of bases -- a bound, also in *n_bases -- for ragged ones.
-static int query_window_bound(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t* n_bound, uint64_t* n_bases) {
+static int query_window_bound(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t* n_bound, uint64_t* n_bases, uint64_t* first = nullptr) {
     *n_bound = *n_bases = 0;
     if (reads->d_offsets) {
         uint64_t o_first = 0, o_last = 0;
         if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
+        if (first) *first = o_first;   // (ragged reads: where the batch's bases start)
         if (o_last < o_first) return KMX_E_ARG;
         if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
         *n_bases = *n_bound = o_last - o_first;
@@ -969,30 +976,29 @@ int kmx_count_lookup_reads2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t
     return lookup_reads_impl(ctx, kQuery2, reads, d_win_offsets, k, d_kmers2, d_counts, n, d_out);
 }
 
-// kmx_count_read_stats(2) = kmx_canonical_windows(2), the lookup kernel and the per-read reduction of kmx_count_read_stats.hip over its
-// answers.  The work buffer, laid out up front: [segment plan of long reads][ragged reads: window offsets][two-word keys: canon
-// 16 B/window][counts 8 B/window][flags 1 B/window][directory, when it pays and fits].  One-word keys: the windows call writes its
-// canonical words into the counts array and they are looked up in place.
-static int read_stats_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers,
-                           const uint64_t* d_counts, uint64_t n, uint64_t solid_min, uint64_t* d_stats) {
-    if (!ctx || !reads_ok(reads) || (n && !d_kmers) || n > (1ull << 40)) return KMX_E_ARG;
-    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
-    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
-    if (reads->n_reads == 0) return KMX_OK;
-    if (!d_stats) return KMX_E_ARG;
-    DeviceGuard g(ctx->device);
-    const char* who = kind.words == 2u ? "kmx_count_read_stats2" : "kmx_count_read_stats";
-    const size_t stats_bytes = 8u * KMX_RS_WORDS * reads->n_reads;
-    uint64_t n_bound = 0, n_bases = 0;
-    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
-    if (n_bound == 0) {   // no window in the batch: every row is eight zeros
-        KMX_HIP(ctx, hipMemsetAsync(d_stats, 0, stats_bytes, ctx->stream));
-        return KMX_OK;
-    }
+// The front half the per-read calls share (kmx_count_read_stats(2), kmx_count_read_paths(2), kmx_count_correct_reads(2)):
+// kmx_canonical_windows(2) and the lookup kernel, which leave one u64 answer (the count, or whatever `d_values` holds per entry) and one
+// flag byte per window.  The work buffer, laid out up front: [segment plan of long reads][ragged reads: window offsets][two-word keys:
+// canon 16 B/window][answers 8 B/window][flags 1 B/window][`extra` bytes of the caller's][directory, when it pays and fits].  One-word
+// keys: the windows call writes its canonical words into the answers array and they are looked up in place.
+struct ReadsFront {
+    char* base = nullptr;          // the work buffer
+    uint64_t n_win = 0;            // the windows there are; 0 = none, and nothing ran
+    uint64_t* wo = nullptr;        // ragged reads: the window offsets, made on the device
+    uint64_t* answers = nullptr;   // one u64 per window
+    uint8_t* flags = nullptr;      // one byte per window
+    size_t area_at = 0;            // where the caller's `extra` bytes start
+    const void* dir = nullptr;     // the directory the lookup built (prefix bits p), nullptr = it searched plainly
+    uint32_t p = 0;
+};
+// n_bound / n_bases: query_window_bound's, n_bound != 0.  KMX_E_NOMEM above the cap before any kernel runs.
+static int reads_front(kmx_ctx* ctx, const QueryKind& kind, const char* who, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers,
+                       const uint64_t* d_values, uint64_t n, uint64_t n_bound, uint64_t n_bases, size_t extra, ReadsFront* f) {
     const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
     const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
-    const size_t canon_at = plan + wo_bytes, counts_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u);
-    const size_t flags_at = counts_at + align256(8u * n_bound), reserved = flags_at + align256(n_bound);
+    const size_t canon_at = plan + wo_bytes, answers_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u);
+    const size_t flags_at = answers_at + align256(8u * n_bound), area_at = flags_at + align256(n_bound);
+    const size_t reserved = area_at + extra;
     char* base = nullptr;
     if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &base)) return st;
     const unsigned long long allocs = ctx->big_allocs;
@@ -1005,20 +1011,46 @@ static int read_stats_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads*
             std::snprintf(msg, sizeof msg, "%s: window count above its bound", who);
             return fail_hip(ctx, hipErrorUnknown, msg);
         }
-        if (n_win == 0) {
-            KMX_HIP(ctx, hipMemsetAsync(d_stats, 0, stats_bytes, ctx->stream));
-            return KMX_OK;
-        }
+        if (n_win == 0) return KMX_OK;
     }
-    uint64_t* counts = reinterpret_cast<uint64_t*>(base + counts_at);
-    uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : counts;
+    uint64_t* answers = reinterpret_cast<uint64_t*>(base + answers_at);
+    uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : answers;
     uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
     if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
     if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
-    if (int st = lookup_run(ctx, kind, d_kmers, d_counts, n, k, canon, flags, n_win, counts, reserved)) return st;
+    if (int st = lookup_run(ctx, kind, d_kmers, d_values, n, k, canon, flags, n_win, answers, reserved, &f->dir, &f->p)) return st;
+    f->base = base;
+    f->wo = wo;
+    f->answers = answers;
+    f->flags = flags;
+    f->area_at = area_at;
+    f->n_win = n_win;
+    return KMX_OK;
+}
+
+// kmx_count_read_stats(2) = reads_front and the per-read reduction of kmx_count_read_stats.hip over its answers.
+static int read_stats_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers,
+                           const uint64_t* d_counts, uint64_t n, uint64_t solid_min, uint64_t* d_stats) {
+    if (!ctx || !reads_ok(reads) || (n && !d_kmers) || n > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    if (reads->n_reads == 0) return KMX_OK;
+    if (!d_stats) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    const char* who = kind.words == 2u ? "kmx_count_read_stats2" : "kmx_count_read_stats";
+    const size_t stats_bytes = 8u * KMX_RS_WORDS * reads->n_reads;
+    uint64_t n_bound = 0, n_bases = 0;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
+    ReadsFront f;
+    if (n_bound != 0)
+        if (int st = reads_front(ctx, kind, who, reads, k, d_kmers, d_counts, n, n_bound, n_bases, 0, &f)) return st;
+    if (f.n_win == 0) {   // no window in the batch: every row is eight zeros
+        KMX_HIP(ctx, hipMemsetAsync(d_stats, 0, stats_bytes, ctx->stream));
+        return KMX_OK;
+    }
     // uniform reads: the windows of a read; ragged reads: the most a read within the bound has (0 = no bound given)
     const uint32_t w = reads->read_len >= k ? reads->read_len - k + 1u : 0u;
-    KMX_HIP(ctx, kmx::launch_count_read_stats(counts, flags, wo, reads->n_reads, w, solid_min, d_stats, ctx->n_cu, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_count_read_stats(f.answers, f.flags, f.wo, reads->n_reads, w, solid_min, d_stats, ctx->n_cu, ctx->stream));
     return KMX_OK;
 }
 
@@ -1030,6 +1062,52 @@ int kmx_count_read_stats(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const
 int kmx_count_read_stats2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n,
                           uint64_t solid_min, uint64_t* d_stats) {
     return read_stats_impl(ctx, kQuery2, reads, k, d_kmers2, d_counts, n, solid_min, d_stats);
+}
+
+// kmx_count_correct_reads(2) = reads_front, a copy of the reads into the output, and the decision kernel of kmx_count_correct.hip, which
+// stores the corrected bytes over the copy and a row per read.  Nothing is written before the work buffer is granted.
+static int correct_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers,
+                              const uint64_t* d_counts, uint64_t n, uint64_t solid_min, uint32_t min_cover, uint8_t* d_out_bases,
+                              uint64_t* d_fixes) {
+    if (!ctx || !reads_ok(reads) || (n && !d_kmers) || n > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    if (min_cover < 1u || min_cover > k) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    if (!d_out_bases) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    const char* who = kind.words == 2u ? "kmx_count_correct_reads2" : "kmx_count_correct_reads";
+    uint64_t n_bound = 0, n_bases = 0, first = 0;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases, &first)) return st;
+    // the bytes that are written: as many, and as far into the output, as the reads take of d_bases
+    uint64_t n_bytes = n_bases;
+    if (!reads->d_offsets) {
+        if (reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+        n_bytes = reads->n_reads * reads->read_len;
+    }
+    const uintptr_t in_at = reinterpret_cast<uintptr_t>(reads->d_bases) + first, out_at = reinterpret_cast<uintptr_t>(d_out_bases) + first;
+    if (n_bytes && in_at < out_at + n_bytes && out_at < in_at + n_bytes) return KMX_E_ARG;   // (decisions are against the original bytes)
+    ReadsFront f;
+    if (n_bound != 0)
+        if (int st = reads_front(ctx, kind, who, reads, k, d_kmers, d_counts, n, n_bound, n_bases, 0, &f)) return st;
+    if (n_bytes) KMX_HIP(ctx, hipMemcpyAsync(d_out_bases + first, reads->d_bases + first, n_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (f.n_win == 0) {   // no window in the batch: the copy, and every row is four zeros
+        if (d_fixes) KMX_HIP(ctx, hipMemsetAsync(d_fixes, 0, 8u * KMX_CR_WORDS * reads->n_reads, ctx->stream));
+        return KMX_OK;
+    }
+    KMX_HIP(ctx, kmx::launch_count_correct(kind.words, reads->d_bases, d_out_bases, reads->d_offsets, f.wo, reads->n_reads, reads->read_len, f.answers,
+                                           f.flags, d_kmers, d_counts, n, k, f.dir, f.p, solid_min, min_cover, d_fixes, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_correct_reads(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n,
+                            uint64_t solid_min, uint32_t min_cover, uint8_t* d_out_bases, uint64_t* d_fixes) {
+    return correct_reads_impl(ctx, kQuery1, reads, k, d_kmers, d_counts, n, solid_min, min_cover, d_out_bases, d_fixes);
+}
+
+int kmx_count_correct_reads2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n,
+                             uint64_t solid_min, uint32_t min_cover, uint8_t* d_out_bases, uint64_t* d_fixes) {
+    return correct_reads_impl(ctx, kQuery2, reads, k, d_kmers2, d_counts, n, solid_min, min_cover, d_out_bases, d_fixes);
 }
 
 int kmx_count_spectrum(kmx_ctx* ctx, const uint64_t* d_counts, uint64_t n, uint64_t n_bins, uint64_t* d_spectrum) {
@@ -1193,11 +1271,8 @@ int kmx_count_unitig_index(kmx_ctx* ctx, const uint64_t* d_nodes, const uint64_t
     return KMX_OK;
 }
 
-// kmx_count_read_paths(2) = read_stats_impl's front half -- the windows call and the lookup kernel, with the places as the counts --
-// and the segment kernels of kmx_count_paths.hip over its answers.  The work buffer, laid out up front: [segment plan of long
-// reads][ragged reads: window offsets][two-word keys: canon 16 B/window][places 8 B/window][flags 1 B/window][the ballots, counts and
-// partials of the segment kernels][directory, when it pays and fits].  One-word keys: the windows call writes its canonical words
-// into the places array and they are looked up in place.
+// kmx_count_read_paths(2) = reads_front -- the windows call and the lookup kernel, with the places as the counts -- and the segment
+// kernels of kmx_count_paths.hip over its answers; the ballots, counts and partials of the segment kernels are its `extra` bytes.
 static int read_paths_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers, uint64_t n,
                            const uint64_t* d_place, const uint64_t* d_offsets, uint64_t n_unitigs, uint64_t* d_path_offsets, uint64_t* d_segments,
                            uint64_t max_segments, uint64_t* h_n_segments) {
@@ -1216,34 +1291,17 @@ static int read_paths_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads*
         if (d_path_offsets) KMX_HIP(ctx, hipMemsetAsync(d_path_offsets, 0, offsets_bytes, ctx->stream));
         return KMX_OK;
     }
-    const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
-    const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
-    const size_t canon_at = plan + wo_bytes, places_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u);
-    const size_t flags_at = places_at + align256(8u * n_bound), area_at = flags_at + align256(n_bound);
-    const size_t reserved = area_at + kmx::count_paths_bytes(n_bound);
-    char* base = nullptr;
-    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &base)) return st;
-    const unsigned long long allocs = ctx->big_allocs;
-    uint64_t n_win = n_bound;
-    uint64_t* wo = nullptr;
-    if (reads->d_offsets) {
-        KMX_HIP(ctx, kmx::launch_count_win_offsets(reads->d_offsets, reads->n_reads, k, base + plan, &wo, ctx->h_pinned, &n_win, ctx->stream));
-        if (n_win > n_bound) {
-            char msg[96];
-            std::snprintf(msg, sizeof msg, "%s: window count above its bound", who);
-            return fail_hip(ctx, hipErrorUnknown, msg);
-        }
-        if (n_win == 0) {
-            if (d_path_offsets) KMX_HIP(ctx, hipMemsetAsync(d_path_offsets, 0, offsets_bytes, ctx->stream));
-            return KMX_OK;
-        }
+    ReadsFront f;
+    if (int st = reads_front(ctx, kind, who, reads, k, d_kmers, d_place, n, n_bound, n_bases, kmx::count_paths_bytes(n_bound), &f)) return st;
+    if (f.n_win == 0) {
+        if (d_path_offsets) KMX_HIP(ctx, hipMemsetAsync(d_path_offsets, 0, offsets_bytes, ctx->stream));
+        return KMX_OK;
     }
-    uint64_t* places = reinterpret_cast<uint64_t*>(base + places_at);
-    uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : places;
-    uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
-    if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
-    if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
-    if (int st = lookup_run(ctx, kind, d_kmers, d_place, n, k, canon, flags, n_win, places, reserved)) return st;
+    const uint64_t n_win = f.n_win;
+    const uint64_t *places = f.answers, *wo = f.wo;
+    uint8_t* flags = f.flags;
+    char* base = f.base;
+    const size_t area_at = f.area_at;
     const uint32_t w = reads->read_len >= k ? reads->read_len - k + 1u : 0u;   // (uniform reads: the windows of a read)
     uint64_t n_segments = 0;
     KMX_HIP(ctx, kmx::launch_count_paths_mark(places, flags, wo, reads->n_reads, w, n_win, d_offsets, n_unitigs, base + area_at, ctx->h_pinned,

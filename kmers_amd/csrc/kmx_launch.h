@@ -152,6 +152,12 @@ hipError_t launch_count_filter_emit(u32 words, const u64* keys, const u64* count
 // W windows; ragged reads: W = the most windows a read is expected to have, 0 = unknown)
 hipError_t launch_count_read_stats(const u64* counts, const uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u64 solid_min, u64* stats,
                                    int n_cu, hipStream_t st);
+// kmx_count_correct.hip: the corrected bytes of the reads into `out` (a copy of the reads already) and KMX_CR_WORDS u64 per read (fixes may
+// be nullptr) out of the counts / flags of its windows and searches of the table (offsets == nullptr: uniform reads of L >= k bases;
+// dir_area: the directory launch_count_lookup built for the table, prefix bits p, or nullptr = the plain search)
+hipError_t launch_count_correct(u32 words, const uint8_t* bases, uint8_t* out, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L,
+                                const u64* wcounts, const uint8_t* wflags, const u64* keys, const u64* tcounts, u64 n, u32 k, const void* dir_area,
+                                u32 p, u64 solid_min, u32 min_cover, u64* fixes, int n_cu, hipStream_t st);
 // kmx_count_graph.hip: a count table as the node set of a de Bruijn graph (dir_area: room for count_lookup_dir_bytes(n, k, &p), or
 // nullptr = the plain search; flips and nbr may be nullptr)
 hipError_t launch_count_adjacency(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, u64 min_count, uint8_t* edges, uint8_t* flips,
