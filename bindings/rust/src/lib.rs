@@ -545,6 +545,58 @@ fn correct_outputs(d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_out: 
     }
 }
 
+/// The pairwise matrix and the spectrum of a coloured table (`kmx_count_color_matrix`): a table whose u64 per key -- `d_colors`,
+/// in the place of the counts -- is a bit mask of the samples (colours `0 .. n_colors`, at most 64) that hold the key.  `d_matrix`
+/// receives `n_colors * n_colors` u64, row-major: the entries that hold colours i and j (the diagonal = the samples' sizes);
+/// `d_spectrum`, when given, `n_colors + 1` u64: the entries with exactly j colours.  Only the low `n_colors` bits of a mask count.
+/// Both outputs are overwritten.
+pub fn count_color_matrix(ctx: &HipContext, d_colors: &DeviceBuf<'_>, n: u64, n_colors: u32, d_matrix: &DeviceBuf<'_>,
+                          d_spectrum: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    assert!(n as u128 * 8 <= d_colors.len() as u128, "masks shorter than the entry count");
+    assert!(n_colors as u128 * n_colors as u128 * 8 <= d_matrix.len() as u128, "matrix shorter than n_colors * n_colors");
+    assert!(d_spectrum.map_or(true, |s| (n_colors as u128 + 1) * 8 <= s.len() as u128), "spectrum shorter than n_colors + 1");
+    let spectrum = d_spectrum.map_or(ptr::null_mut(), |s| s.as_mut_ptr::<u64>());
+    ctx.ck(unsafe { kmx_count_color_matrix(ctx.0, d_colors.as_ptr::<u64>(), n, n_colors, d_matrix.as_mut_ptr::<u64>(), spectrum) })
+}
+
+/// Which samples each read of a uniform batch is compatible with (`kmx_count_read_colors`): `table.counts` holds the colour masks
+/// of a coloured table (required unless the table is empty).  `d_rows` receives `KMX_RC_WORDS` u64 per read (`KMX_RC_N_VALID` ..
+/// `KMX_RC_N_SWITCH`): the valid, hit and single-colour windows, the AND and the OR of the hit windows' masks, the colours that at
+/// least `thr_num / thr_den` of the valid windows carry, the best colour with its hit count, and the mask changes between
+/// neighbouring hit windows.  `d_hits`, when given, receives `n_colors` u32 per read: the hit windows per colour.  Every row is written.
+pub fn count_read_colors(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>, n_colors: u32,
+                         thr_num: u32, thr_den: u32, d_rows: &DeviceBuf<'_>, d_hits: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    table.check(1);
+    let hits = read_colors_outputs(d_reads, n_reads, read_len, n_colors, d_rows, d_hits);
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_read_colors(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, n_colors, thr_num, thr_den,
+                                          d_rows.as_mut_ptr::<u64>(), hits) })
+}
+
+/// The same for two-word keys, k in 33..=64 (`kmx_count_read_colors2`).
+pub fn count_read_colors2(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8, table: CountTable<'_>, n_colors: u32,
+                          thr_num: u32, thr_den: u32, d_rows: &DeviceBuf<'_>, d_hits: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    table.check(2);
+    let hits = read_colors_outputs(d_reads, n_reads, read_len, n_colors, d_rows, d_hits);
+    let r = kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() };
+    ctx.ck(unsafe { kmx_count_read_colors2(ctx.0, &r, k as u32, table.keys.as_ptr::<u64>(), table.counts_ptr(), table.n, n_colors, thr_num, thr_den,
+                                           d_rows.as_mut_ptr::<u64>(), hits) })
+}
+
+// the sizes count_read_colors(2) ask of their buffers; the hit counts' pointer, null when they are not wanted
+fn read_colors_outputs(d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, n_colors: u32, d_rows: &DeviceBuf<'_>,
+                       d_hits: Option<&DeviceBuf<'_>>) -> *mut u32 {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    assert!(n_reads as u128 * 8 * KMX_RC_WORDS as u128 <= d_rows.len() as u128, "rows shorter than the batch's reads");
+    match d_hits {
+        Some(h) => {
+            assert!(n_reads as u128 * 4 * n_colors as u128 <= h.len() as u128, "hit counts shorter than the batch's reads");
+            h.as_mut_ptr::<u32>()
+        }
+        None => ptr::null_mut(),
+    }
+}
+
 /// The abundance spectrum of a table's counts (`kmx_count_spectrum`): `n_bins` bins, bin c = how many entries have count c, the last
 /// bin everything at or above it.
 pub fn count_spectrum(ctx: &HipContext, d_counts: &DeviceBuf<'_>, n: u64, n_bins: usize) -> Result<Vec<u64>, KmxError> {

@@ -408,6 +408,63 @@ int kmx_count_correct_reads(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, co
 int kmx_count_correct_reads2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, const uint64_t *d_counts, uint64_t n,
                              uint64_t solid_min, uint32_t min_cover, uint8_t *d_out_bases, uint64_t *d_fixes);
 
+/* ---------------------------------------------------------------- coloured tables: more than two samples at once ----
+ * BUILD-DEFINED (the crate has no colours).  A COLOURED TABLE is a TABLE as above whose u64 per key is not a count but a bit mask of
+ * the samples -- COLOURS, at most 64, colour c = bit c -- that hold the key: d_colors in the place of d_counts.  It is built from
+ * what exists: kmx_count_setop(2) with KMX_SETOP_UNION and KMX_RULE_SUM of the coloured table and a sample's keys carrying
+ * 1 << c, which is OR as long as bit c is clear in the table.  EVERY call that takes a table takes a coloured one unchanged, because
+ * none of them reads the u64 beyond "0 = absent": kmx_count_lookup(2) and kmx_count_lookup_reads(2) answer the mask of a key,
+ * kmx_count_filter(2) selects by the mask read as a number, the graph calls with d_counts == NULL see every key.  The two calls below
+ * are the reductions that make the masks useful.
+ * n_colors in 1 .. 64 (KMX_E_ARG otherwise) says how many colours are in use.  Only the low n_colors bits of a mask count, everywhere
+ * in these calls: the MASKED mask.  Bits at or above n_colors are ignored, also where that leaves a mask empty.
+ *
+ * The pairwise matrix and the spectrum of a coloured table, from the masks alone (no keys: one call for both key widths):
+ *     d_matrix[i * n_colors + j]   entries whose masked mask has bits i and j set: n_colors * n_colors u64, row-major, symmetric; the
+ *                                  diagonal is the size of each sample, and Jaccard / containment of every pair follow from it;
+ *     d_spectrum[j]                entries whose masked mask has exactly j bits set: n_colors + 1 u64, bin 0 = entries with none;
+ *                                  may be NULL (core = bin n_colors, private = bin 1, accessory = what lies between).
+ * Both outputs are OVERWRITTEN, not accumulated into (unlike kmx_count_spectrum); n == 0 gives all zeros.  Exact, and bit-identical
+ * between calls.  NULL ctx / d_matrix, d_colors == NULL with n > 0, n > 2^40: KMX_E_ARG.
+ * Working set in the context's work buffer: one partial result per block of the grid, (B * B + 65) * 8 bytes each with B = n_colors
+ * rounded up to 8 / 16 / 32 / 64, for min(ceil(n / 256), max(4 * CUs, 512)) blocks -- 32.5 MiB at most on 256 compute units; above the
+ * cap KMX_E_NOMEM before any kernel runs.  Asynchronous: it only enqueues work on the context's stream. */
+int kmx_count_color_matrix(kmx_ctx *ctx, const uint64_t *d_colors, uint64_t n, uint32_t n_colors, uint64_t *d_matrix, uint64_t *d_spectrum);
+
+/* Which samples a read is compatible with (pseudoalignment against a coloured table): one row of KMX_RC_WORDS u64 per read, row r at
+ * d_rows + KMX_RC_WORDS * r, from the masked masks of its windows.  The mask of a window is what kmx_count_lookup_reads answers for
+ * it with d_colors as the counts: 0 for an absent key and for an invalid window.  A HIT window is a valid window whose masked mask is
+ * not 0; hits_c is the number of hit windows of the read whose masked mask has bit c. */
+#define KMX_RC_WORDS 8u
+#define KMX_RC_N_VALID 0u  /* as KMX_RS_N_VALID */
+#define KMX_RC_N_HIT 1u    /* valid windows whose masked mask is not 0 */
+#define KMX_RC_N_UNIQUE 2u /* hit windows whose masked mask has exactly one bit */
+#define KMX_RC_ALL 3u      /* AND of the masked masks of the hit windows; 0 when there is none */
+#define KMX_RC_ANY 4u      /* OR of them */
+#define KMX_RC_THRESH 5u   /* colours c with hits_c > 0 and hits_c * thr_den >= thr_num * n_valid */
+#define KMX_RC_BEST 6u     /* (largest hits_c << 32) | c, the smallest such c; 0 when n_hit == 0 */
+#define KMX_RC_N_SWITCH 7u /* window positions p such that p and p + 1 are both hit windows of the read and their masked masks differ */
+/* d_hits may be NULL; otherwise n_reads * n_colors u32, row r at d_hits + n_colors * r, element c = hits_c: every element is written.
+ * thr_den >= 1 and thr_num <= thr_den, KMX_E_ARG otherwise; thr_num == 0 makes THRESH equal ANY, thr_num == thr_den asks for every
+ * valid window.  The products are taken in 64 bits: exact.  d_colors == NULL with n > 0 is KMX_E_ARG (membership has no colours);
+ * n == 0 is a valid empty table (N_VALID is counted, everything else is 0).  A pair of N_SWITCH never spans two reads, and an invalid
+ * or absent window between two hit windows separates them: they are no pair.
+ * Inputs, routes, synchronisation, alignment rules and the working set are exactly those of kmx_count_read_stats: uniform and ragged
+ * reads of any length, ragged ones without window offsets from the caller; a256(8 * windows) + a256(windows), ragged reads the window
+ * offsets, long reads the segment plan, the lookup's directory behind that when it pays and fits; above the cap KMX_E_NOMEM BEFORE
+ * any kernel runs, nothing written.  150 bp reads at k = 31: 1080 bytes per read here, 64 (+ 4 * n_colors) bytes per read out --
+ * against 8 bytes per window and sample through kmx_count_lookup_reads.
+ * EVERY row (and every element of d_hits) is written: a read without a window gets zeros, as does a batch without any; only
+ * n_reads == 0 is a no-op.  Every row has one writer: repeated calls give identical bytes.
+ * k in [1,31], KMX_E_K_RANGE otherwise; NULL ctx / reads, n > 2^40, n_colors outside 1 .. 64, d_rows == NULL with n_reads > 0:
+ * KMX_E_ARG. */
+int kmx_count_read_colors(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers, const uint64_t *d_colors, uint64_t n,
+                          uint32_t n_colors, uint32_t thr_num, uint32_t thr_den, uint64_t *d_rows, uint32_t *d_hits);
+/* The same for two-word keys, k in [33,64] (d_kmers2 16-byte aligned, KMX_E_ARG otherwise): the routes and the working set of
+ * kmx_count_read_stats2 (+ a256(16 * windows) for the canonical words). */
+int kmx_count_read_colors2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint64_t *d_kmers2, const uint64_t *d_colors, uint64_t n,
+                           uint32_t n_colors, uint32_t thr_num, uint32_t thr_den, uint64_t *d_rows, uint32_t *d_hits);
+
 /* ---------------------------------------------------------------- a count table as the node set of a de Bruijn graph ----
  * BUILD-DEFINED (the crate has no graph).  A TABLE as above.  With x the key of entry i read as the forward strand and
  * mask = 2^(2k) - 1, its eight possible neighbours are, for a base c in 0..3,

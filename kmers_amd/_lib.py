@@ -33,6 +33,9 @@ RS_WORDS = 8
 # kmx_count_correct_reads(2): the words of a read's row
 CR_N_WEAK, CR_N_CANDIDATES, CR_N_CORRECTED, CR_N_AMBIGUOUS = range(4)
 CR_WORDS = 4
+# kmx_count_read_colors(2): the words of a read's row
+RC_N_VALID, RC_N_HIT, RC_N_UNIQUE, RC_ALL, RC_ANY, RC_THRESH, RC_BEST, RC_N_SWITCH = range(8)
+RC_WORDS = 8
 # kmx_count_adjacency(2): the word of d_nbr where an edge is absent (KMX_NO_ENTRY; -1 in the int64 tensors of kmers_amd.api)
 NO_ENTRY = 2**64 - 1
 # kmx_count_unitig_index / kmx_count_read_paths(2): an entry in no unitig, and the words of a segment's record
@@ -129,6 +132,9 @@ SIGNATURES = {
     "kmx_count_read_stats2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _vp]),
     "kmx_count_correct_reads": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
     "kmx_count_correct_reads2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "kmx_count_color_matrix": (_int, [_vp, _vp, _u64, _u32, _vp, _vp]),
+    "kmx_count_read_colors": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "kmx_count_read_colors2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
     "kmx_count_spectrum": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "kmx_count_filter": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_filter2": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, RC_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -90,6 +90,44 @@ class TableComparison:
     def bray_curtis(self) -> float:
         """the Bray-Curtis dissimilarity 1 - 2 sum_min / (sum_a + sum_b)"""
         return 1.0 - 2.0 * self.sum_min / (self.sum_a + self.sum_b) if self.sum_a + self.sum_b else 0.0
+
+
+@dataclasses.dataclass(frozen=True)
+class ColorTable:
+    """A coloured table: the sorted distinct keys of a table (int64[n]; k 33..64: int64[n, 2] = (low, high) words) and, in the place
+    of the counts, one u64 bit mask per key (int64[n]) of the samples -- colours 0 .. n_colors - 1, at most 64 -- that hold it.  Every
+    call that takes a table (kmers, counts) takes (kmers, colors).  `k` is carried along for the caller (None = not said)."""
+    kmers: torch.Tensor
+    colors: torch.Tensor
+    n_colors: int
+    k: int | None = None
+
+
+@dataclasses.dataclass(frozen=True)
+class ColorMatrix:
+    """What kmx_count_color_matrix fills -- shared int64[n_colors, n_colors]: the entries that hold colours i and j (symmetric, the
+    diagonal = the samples' sizes); spectrum int64[n_colors + 1] or None: the entries with exactly j colours -- and the similarity
+    measures that follow, for all pairs at once.  Host or device tensors."""
+    shared: torch.Tensor
+    spectrum: torch.Tensor | None = None
+
+    @property
+    def sizes(self) -> torch.Tensor:
+        """int64[n_colors]: the number of entries of each colour"""
+        return torch.diagonal(self.shared)
+
+    def _over(self, den: torch.Tensor) -> torch.Tensor:
+        num, den = self.shared.to(torch.float64), den.to(torch.float64)
+        return torch.where(den > 0, num / den.clamp(min=1.0), torch.zeros_like(num))   # (an empty pair gives 0, as _ratio does)
+
+    def jaccard(self) -> torch.Tensor:
+        """float64[n_colors, n_colors]: shared / (size_i + size_j - shared)"""
+        sz = self.sizes
+        return self._over(sz[:, None] + sz[None, :] - self.shared)
+
+    def containment(self) -> torch.Tensor:
+        """float64[n_colors, n_colors]: element [i, j] = the share of sample i's keys that sample j holds"""
+        return self._over(self.sizes[:, None].expand_as(self.shared))
 
 
 _POPCOUNT4 = [bin(v).count("1") for v in range(16)]
@@ -667,6 +705,93 @@ class Context:
     def count_correct_reads2(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, min_cover=1, offsets=None, out=None):
         """kmx_count_correct_reads2 (k 33..64; kmers int64[n, 2]) -> (corrected bases, int64[n_reads, 4])."""
         return self._correct_reads(self.lib.kmx_count_correct_reads2, 2, bases, n_reads, read_len, k, kmers, counts, solid_min, min_cover, offsets, out)
+
+    # ------------------------------------------------------------ coloured tables: more than two samples at once
+    def _color_add(self, words, table, kmers_b, color, k):
+        taken = table.n_colors if table is not None else 0
+        if color is None:
+            color = taken
+        color = int(color)
+        if color >= 64:
+            raise ValueError(f"colour {color}: a coloured table holds at most 64 colours (0 .. 63)")
+        if color < taken:
+            raise ValueError(f"colour {color} may already be set in a table of {taken} colours")
+        if k is None and table is not None:
+            k = table.k
+        kmers_b = kmers_b.contiguous()
+        nb = int(kmers_b.numel()) // words
+        # (colour 63 is the sign bit of the int64 that holds the u64 mask)
+        cb = torch.full((nb,), (1 << color) - (1 << 64 if color == 63 else 0), dtype=torch.int64, device=self.device)
+        if table is None:
+            return ColorTable(kmers_b.clone(), cb, color + 1, k)
+        # (RULE_SUM is OR here: the bit is clear in every mask of the table)
+        kmers, colors = self._setop(self.lib.kmx_count_setop2 if words == 2 else self.lib.kmx_count_setop, words, SETOP_UNION, table.kmers,
+                                    table.colors, kmers_b, cb, RULE_SUM, None)
+        return ColorTable(kmers, colors, color + 1, k)
+
+    @_on_ctx_stream
+    def count_color_add(self, table, kmers_b, color=None, k=None):
+        """-> ColorTable: the union of the coloured `table` (None: an empty one) with sample b's key set (the sorted distinct keys of a
+        table), b's entries getting bit `color` (default: the next free one, table.n_colors).  Built from kmx_count_setop (UNION,
+        RULE_SUM) on a filled tensor of 1 << color.  ValueError for a colour at or above 64, or below table.n_colors (that bit may
+        already be set).  The result has n_colors = color + 1."""
+        return self._color_add(1, table, kmers_b, color, k)
+
+    @_on_ctx_stream
+    def count_color_add2(self, table, kmers_b, color=None, k=None):
+        """count_color_add for two-word keys (k 33..64): kmers_b int64[n, 2]."""
+        return self._color_add(2, table, kmers_b, color, k)
+
+    def count_color_build(self, tables, k=None):
+        """-> ColorTable of a list of (kmers, counts) tables, colour i = the list index (the counts are not read: filter each table with
+        count_filter first for a presence threshold).  At most 64 tables."""
+        table = None
+        for kmers, _ in tables:
+            table = self.count_color_add(table, kmers, k=k)
+        return table
+
+    def count_color_build2(self, tables, k=None):
+        table = None
+        for kmers, _ in tables:
+            table = self.count_color_add2(table, kmers, k=k)
+        return table
+
+    @_on_ctx_stream
+    def count_color_matrix(self, colors, n_colors, spectrum=True):
+        """kmx_count_color_matrix -> ColorMatrix: for all pairs of the n_colors samples, how many entries of the coloured table hold
+        both (shared int64[n_colors, n_colors]), and, unless spectrum=False, how many entries hold exactly j colours.  Only the low
+        n_colors bits of a mask count.  One call for both key widths (it reads the masks only)."""
+        n, nc = int(colors.numel()), int(n_colors)
+        shared = self.empty(max(nc, 0) ** 2, torch.int64)
+        spec = self.empty(max(nc, 0) + 1, torch.int64) if spectrum else None
+        self._ck(self.lib.kmx_count_color_matrix(self._h, _ptr(colors) if n else None, n, nc, _ptr(shared) if shared.numel() else None, _ptr(spec)))
+        return ColorMatrix(shared.view(nc, nc), spec)
+
+    def _read_colors(self, fn, words, bases, n_reads, read_len, k, kmers, colors, n_colors, threshold, offsets, hits, out):
+        n = int(kmers.numel()) // words if kmers is not None else 0
+        if n:
+            kmers = kmers.contiguous()
+        if out is None:
+            out = self.empty(RC_WORDS * int(n_reads), torch.int64)
+        h = self.empty(max(int(n_colors), 0) * int(n_reads), torch.int32) if hits else None
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), k, _ptr(kmers) if n else None, _ptr(colors) if colors is not None and n else None, n, int(n_colors),
+                    int(threshold[0]), int(threshold[1]), _ptr(out) if out.numel() else None, _ptr(h) if h is not None and h.numel() else None))
+        return out.view(-1, RC_WORDS), (h.view(int(n_reads), -1) if h is not None else None)
+
+    @_on_ctx_stream
+    def count_read_colors(self, bases, n_reads, read_len, k, kmers, colors, n_colors, threshold=(1, 2), offsets=None, hits=False, out=None):
+        """kmx_count_read_colors -> (int64[n_reads, 8] (u64 words, columns _lib.RC_*), int32[n_reads, n_colors] or None): per read,
+        which samples of the coloured table (kmers, colors) it is compatible with -- valid / hit / single-colour windows, the AND and the
+        OR of its hit windows' masks, the colours that at least threshold = (num, den) of its valid windows carry, the best colour with
+        its hit count, and how often the mask changes between neighbouring hit windows; with hits=True also the hit windows per
+        colour.  Ragged reads (`offsets`) need no window offsets.  `out` (int64, 8 * n_reads elements) is overwritten."""
+        return self._read_colors(self.lib.kmx_count_read_colors, 1, bases, n_reads, read_len, k, kmers, colors, n_colors, threshold, offsets, hits, out)
+
+    @_on_ctx_stream
+    def count_read_colors2(self, bases, n_reads, read_len, k, kmers, colors, n_colors, threshold=(1, 2), offsets=None, hits=False, out=None):
+        """kmx_count_read_colors2 (k 33..64; kmers int64[n, 2]) -> (int64[n_reads, 8], int32[n_reads, n_colors] or None)."""
+        return self._read_colors(self.lib.kmx_count_read_colors2, 2, bases, n_reads, read_len, k, kmers, colors, n_colors, threshold, offsets, hits, out)
 
     @_on_ctx_stream
     def count_spectrum(self, counts, n_bins, out=None):

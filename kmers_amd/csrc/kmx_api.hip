@@ -976,7 +976,7 @@ int kmx_count_lookup_reads2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t
     return lookup_reads_impl(ctx, kQuery2, reads, d_win_offsets, k, d_kmers2, d_counts, n, d_out);
 }
 
-// The front half the per-read calls share (kmx_count_read_stats(2), kmx_count_read_paths(2), kmx_count_correct_reads(2)):
+// The front half the per-read calls share (kmx_count_read_stats(2), kmx_count_read_paths(2), kmx_count_correct_reads(2), kmx_count_read_colors(2)):
 // kmx_canonical_windows(2) and the lookup kernel, which leave one u64 answer (the count, or whatever `d_values` holds per entry) and one
 // flag byte per window.  The work buffer, laid out up front: [segment plan of long reads][ragged reads: window offsets][two-word keys:
 // canon 16 B/window][answers 8 B/window][flags 1 B/window][`extra` bytes of the caller's][directory, when it pays and fits].  One-word
@@ -1108,6 +1108,54 @@ int kmx_count_correct_reads(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, co
 int kmx_count_correct_reads2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers2, const uint64_t* d_counts, uint64_t n,
                              uint64_t solid_min, uint32_t min_cover, uint8_t* d_out_bases, uint64_t* d_fixes) {
     return correct_reads_impl(ctx, kQuery2, reads, k, d_kmers2, d_counts, n, solid_min, min_cover, d_out_bases, d_fixes);
+}
+
+// kmx_count_read_colors(2) = reads_front -- with the masks as the values -- and the per-read reduction of kmx_count_color.hip.
+static int read_colors_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers,
+                            const uint64_t* d_colors, uint64_t n, uint32_t n_colors, uint32_t thr_num, uint32_t thr_den, uint64_t* d_rows,
+                            uint32_t* d_hits) {
+    if (!ctx || !reads_ok(reads) || (n && (!d_kmers || !d_colors)) || n > (1ull << 40)) return KMX_E_ARG;
+    if (kind.words == 2u && !aligned16(d_kmers)) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    if (n_colors < 1u || n_colors > 64u || thr_den < 1u || thr_num > thr_den) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    if (!d_rows) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    const char* who = kind.words == 2u ? "kmx_count_read_colors2" : "kmx_count_read_colors";
+    uint64_t n_bound = 0, n_bases = 0;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
+    ReadsFront f;
+    if (n_bound != 0)
+        if (int st = reads_front(ctx, kind, who, reads, k, d_kmers, d_colors, n, n_bound, n_bases, 0, &f)) return st;
+    if (f.n_win == 0) {   // no window in the batch: every row and every hit count is zero
+        KMX_HIP(ctx, hipMemsetAsync(d_rows, 0, 8u * KMX_RC_WORDS * reads->n_reads, ctx->stream));
+        if (d_hits) KMX_HIP(ctx, hipMemsetAsync(d_hits, 0, 4u * n_colors * reads->n_reads, ctx->stream));
+        return KMX_OK;
+    }
+    const uint32_t w = reads->read_len >= k ? reads->read_len - k + 1u : 0u;   // (uniform reads: the windows of a read)
+    KMX_HIP(ctx, kmx::launch_count_read_colors(f.answers, f.flags, f.wo, reads->n_reads, w, n_colors, thr_num, thr_den, d_rows, d_hits, ctx->n_cu,
+                                               ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_read_colors(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers, const uint64_t* d_colors, uint64_t n,
+                          uint32_t n_colors, uint32_t thr_num, uint32_t thr_den, uint64_t* d_rows, uint32_t* d_hits) {
+    return read_colors_impl(ctx, kQuery1, reads, k, d_kmers, d_colors, n, n_colors, thr_num, thr_den, d_rows, d_hits);
+}
+
+int kmx_count_read_colors2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint64_t* d_kmers2, const uint64_t* d_colors, uint64_t n,
+                           uint32_t n_colors, uint32_t thr_num, uint32_t thr_den, uint64_t* d_rows, uint32_t* d_hits) {
+    return read_colors_impl(ctx, kQuery2, reads, k, d_kmers2, d_colors, n, n_colors, thr_num, thr_den, d_rows, d_hits);
+}
+
+int kmx_count_color_matrix(kmx_ctx* ctx, const uint64_t* d_colors, uint64_t n, uint32_t n_colors, uint64_t* d_matrix, uint64_t* d_spectrum) {
+    if (!ctx || !d_matrix || n_colors < 1u || n_colors > 64u || (n && !d_colors) || n > (1ull << 40)) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;   // the blocks' partial results (n == 0: none, the summing kernel writes the zeros)
+    if (n != 0)
+        if (int st = work_area(ctx, "kmx_count_color_matrix", kmx::count_color_matrix_bytes(n, n_colors, ctx->n_cu), &area)) return st;
+    KMX_HIP(ctx, kmx::launch_count_color_matrix(d_colors, n, n_colors, area, d_matrix, d_spectrum, ctx->n_cu, ctx->stream));
+    return KMX_OK;
 }
 
 int kmx_count_spectrum(kmx_ctx* ctx, const uint64_t* d_counts, uint64_t n, uint64_t n_bins, uint64_t* d_spectrum) {

@@ -158,6 +158,14 @@ hipError_t launch_count_read_stats(const u64* counts, const uint8_t* flags, cons
 hipError_t launch_count_correct(u32 words, const uint8_t* bases, uint8_t* out, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L,
                                 const u64* wcounts, const uint8_t* wflags, const u64* keys, const u64* tcounts, u64 n, u32 k, const void* dir_area,
                                 u32 p, u64 solid_min, u32 min_cover, u64* fixes, int n_cu, hipStream_t st);
+// kmx_count_color.hip: a coloured table's pairwise matrix and spectrum (area: count_color_matrix_bytes(n, n_colors, n_cu) bytes of
+// per-block partials, none for n == 0; spectrum may be nullptr; both outputs are overwritten), and KMX_RC_WORDS u64 per read plus,
+// unless hits == nullptr, n_colors u32 per read out of the masks / flags of its windows (win_offsets == nullptr: uniform reads of W
+// windows)
+size_t count_color_matrix_bytes(u64 n, u32 n_colors, int n_cu);
+hipError_t launch_count_color_matrix(const u64* colors, u64 n, u32 n_colors, void* area, u64* matrix, u64* spectrum, int n_cu, hipStream_t st);
+hipError_t launch_count_read_colors(const u64* answers, const uint8_t* flags, const u64* win_offsets, u64 n_reads, u32 W, u32 n_colors, u32 thr_num,
+                                    u32 thr_den, u64* rows, u32* hits, int n_cu, hipStream_t st);
 // kmx_count_graph.hip: a count table as the node set of a de Bruijn graph (dir_area: room for count_lookup_dir_bytes(n, k, &p), or
 // nullptr = the plain search; flips and nbr may be nullptr)
 hipError_t launch_count_adjacency(u32 words, const u64* keys, const u64* counts, u64 n, u32 k, u64 min_count, uint8_t* edges, uint8_t* flips,
