@@ -900,6 +900,45 @@ pub fn count_unitig_clean(ctx: &HipContext, d_offsets: &DeviceBuf<'_>, d_circula
                                            d_reason.map_or(ptr::null_mut(), |b| b.as_mut_ptr::<u8>())) })
 }
 
+/// The label and id of a unitig that the mask of `count_unitig_components` leaves out (`KMX_COMPONENT_NONE`).
+pub const COMPONENT_NONE: u64 = !0u64;
+
+/// What `count_unitig_components` brings back to the host: the number of components, and the hook / jump rounds the call ran.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ComponentCount {
+    pub n_components: u64,
+    pub rounds: u32,
+}
+
+/// The connected components of the compacted graph (`kmx_count_unitig_components`; include/kmx.h has the rule): into `d_labels`
+/// the smallest unitig index of every unitig's component, into `d_ids` (if given) the component's number in ascending order of the
+/// labels, into `d_components` (if given, room for `max_components` records of 4 u64) root, unitigs, nodes and count sum of every
+/// component.  `d_mask` (if given, a byte per unitig) leaves unitigs out: their label and id are `COMPONENT_NONE`.  `d_offsets` /
+/// `d_count_sums` are `count_unitigs`' outputs (either may be None: every unitig one node, every mean count 1), `d_link_offsets` /
+/// `d_links` / `n_links` `count_unitig_links`'.  More components than `max_components`: Err(KMX_E_NOMEM) with `d_components`
+/// untouched and labels and ids written all the same.  One call for both key widths.  Synchronous.
+pub fn count_unitig_components(ctx: &HipContext, d_offsets: Option<&DeviceBuf<'_>>, d_count_sums: Option<&DeviceBuf<'_>>, n_unitigs: u64,
+                               d_link_offsets: &DeviceBuf<'_>, d_links: &DeviceBuf<'_>, n_links: u64, d_mask: Option<&DeviceBuf<'_>>,
+                               d_labels: &DeviceBuf<'_>, d_ids: Option<&DeviceBuf<'_>>, d_components: Option<&DeviceBuf<'_>>,
+                               max_components: u64) -> Result<ComponentCount, KmxError> {
+    assert!(d_offsets.map_or(true, |b| (n_unitigs as u128 + 1) * 8 <= b.len() as u128), "unitig offsets shorter than the unitig count + 1");
+    assert!(d_count_sums.map_or(true, |b| n_unitigs as u128 * 8 <= b.len() as u128), "count sums shorter than the unitig count");
+    assert!((2 * n_unitigs as u128 + 1) * 8 <= d_link_offsets.len() as u128, "link offsets shorter than twice the unitig count + 1");
+    assert!(n_links as u128 * 8 <= d_links.len() as u128, "links shorter than the link count");
+    assert!(d_mask.map_or(true, |b| n_unitigs as u128 <= b.len() as u128), "mask shorter than the unitig count");
+    assert!(n_unitigs as u128 * 8 <= d_labels.len() as u128, "labels shorter than the unitig count");
+    assert!(d_ids.map_or(true, |b| n_unitigs as u128 * 8 <= b.len() as u128), "ids shorter than the unitig count");
+    assert!(d_components.map_or(true, |b| max_components as u128 * 32 <= b.len() as u128), "records shorter than max_components");
+    let mut out = ComponentCount { n_components: 0, rounds: 0 };
+    ctx.ck(unsafe { kmx_count_unitig_components(ctx.0, d_offsets.map_or(ptr::null(), |b| b.as_ptr::<u64>()),
+                                                d_count_sums.map_or(ptr::null(), |b| b.as_ptr::<u64>()), n_unitigs, d_link_offsets.as_ptr::<u64>(),
+                                                d_links.as_ptr::<u64>(), n_links, d_mask.map_or(ptr::null(), |b| b.as_ptr::<u8>()),
+                                                d_labels.as_mut_ptr::<u64>(), d_ids.map_or(ptr::null_mut(), |b| b.as_mut_ptr::<u64>()),
+                                                d_components.map_or(ptr::null_mut(), |b| b.as_mut_ptr::<u64>()), max_components,
+                                                &mut out.n_components, &mut out.rounds) })?;
+    Ok(out)
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

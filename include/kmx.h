@@ -736,6 +736,45 @@ int kmx_count_unitig_clean(kmx_ctx *ctx, const uint64_t *d_offsets, const uint8_
                            uint64_t tip_max_nodes, uint32_t tip_num, uint32_t tip_den, uint64_t bubble_max_nodes,
                            uint64_t bubble_max_diff, uint64_t island_max_nodes, uint8_t *d_keep, uint8_t *d_reason);
 
+/* Which unitigs hang together: the connected components of the compacted graph -- a label and an id per unitig, a record per
+ * component.  The cleaning rules above look at one unitig and its neighbours; this is the global question: how many pieces, how big
+ * is each, and which piece is a unitig (and, through kmx_count_read_paths, a read) in.  The rule is defined on the arrays alone: any
+ * bytes give the answer stated here and never an access outside the arrays.
+ * NOTATION.  U, m(u), S(u), t = 2 u + s and L(t) exactly as for kmx_count_unitig_clean: L(t) is empty unless lo <= hi <= n_links,
+ * hi - lo <= 4 and every listed target is < 2 U; m(u) reads as 0 where the offsets descend; d_count_sums == NULL: S(u) = m(u).
+ * In addition d_offsets == NULL: m(u) = 1.
+ * ALIVE.  u is alive iff d_mask == NULL or d_mask[u] != 0 (d_mask: U bytes, for instance the keep bytes of kmx_count_unitig_clean).
+ * A unitig that is not alive takes no part: its links, and links into it, do not exist.
+ * ADJACENCY.  Alive unitigs u and v are adjacent iff some target t' in L(2 u) or L(2 u + 1) has t' >> 1 == v, or the same with u and
+ * v swapped.  A link listed in one direction only still joins the two (palindromic junctions make such links at even k, see
+ * kmx_count_unitig_links); self-links and hairpins join nothing new.  Orientation plays no part.
+ * COMPONENTS are the classes of the reflexive-transitive closure of adjacency over the alive unitigs; C is their number.
+ * OUTPUTS.  d_labels[u] (U u64, required) = the smallest unitig index in u's component, KMX_COMPONENT_NONE for a unitig that is not
+ * alive.  d_ids[u] (U u64, may be NULL) = the rank of u's label among all distinct labels in ascending order, 0 .. C - 1, and
+ * KMX_COMPONENT_NONE where the label is.  d_components (max_components records of 4 u64, may be NULL): for component c its root
+ * (the label), its number of unitigs, the sum of m(u) and the wrapping u64 sum of S(u) over its unitigs.  *h_n_components (host) = C,
+ * always set.  *h_rounds (host, may be NULL) = the hook / jump rounds the call ran (at least 1 for U > 0: the round that finds
+ * nothing left to do).
+ * C > max_components with d_components != NULL: KMX_E_NOMEM with d_components untouched and d_labels and d_ids STILL WRITTEN in
+ * full -- the convention of kmx_count_unitig_links.
+ * Exact and deterministic: only integer minima and wrapping integer sums, so repeated calls give identical bytes.  Nothing beyond
+ * U, U and 4 * min(C, max_components) words is written.  Outputs must not alias inputs.  d_offsets (U + 1 u64) / d_count_sums as
+ * kmx_count_unitigs(2) wrote them, d_link_offsets (2 U + 1 u64) / d_links / n_links as kmx_count_unitig_links wrote them.  Indices
+ * only: one call for both key widths.  n_unitigs == 0 is a no-op with *h_n_components = 0 and *h_rounds = 0.  NULL ctx /
+ * h_n_components, n_unitigs above 2^40, n_links above 2^43, d_labels or d_link_offsets NULL with n_unitigs > 0, d_links NULL with
+ * n_links > 0: KMX_E_ARG.
+ * Working set in the context's work buffer, laid out before any kernel runs, each array rounded up to 256 bytes (a256):
+ *     a256(8 * (ceil(U / 4096) + 1)) + 256                   a scan partial per 4096 unitigs (+ the total), the change counter
+ *   + d_components != NULL and d_ids == NULL:  a256(8 * U)   the roots' ids, which d_ids holds otherwise
+ * The labels are their own parent array: no second array of U words.  Above the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM
+ * BEFORE any kernel runs, nothing written.  The call uses the work buffer (a following kmx_fastx_parse cannot reuse its chunk
+ * prefixes).  Synchronous: one small read-back per round, one for C. */
+#define KMX_COMPONENT_NONE 0xFFFFFFFFFFFFFFFFu /* a label or id of a unitig that is not alive (a u64, ~0) */
+int kmx_count_unitig_components(kmx_ctx *ctx, const uint64_t *d_offsets, const uint64_t *d_count_sums, uint64_t n_unitigs,
+                                const uint64_t *d_link_offsets, const uint64_t *d_links, uint64_t n_links, const uint8_t *d_mask,
+                                uint64_t *d_labels, uint64_t *d_ids, uint64_t *d_components, uint64_t max_components,
+                                uint64_t *h_n_components, uint32_t *h_rounds);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

@@ -44,6 +44,11 @@ PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_POS = range(4)
 PATH_WORDS = 4
 # kmx_count_unitig_clean: why a unitig is dropped (KMX_CLEAN_*; 0 = kept)
 CLEAN_KEEP, CLEAN_TIP, CLEAN_BUBBLE, CLEAN_ISLAND = range(4)
+# kmx_count_unitig_components: the label and id of a unitig the mask leaves out (KMX_COMPONENT_NONE; -1 in the int64 tensors of
+# kmers_amd.api), and the words of a component's record
+COMPONENT_NONE = 2**64 - 1
+COMP_ROOT, COMP_N_UNITIGS, COMP_N_NODES, COMP_COUNT_SUM = range(4)
+COMP_WORDS = 4
 
 
 class KmxError(RuntimeError):
@@ -153,6 +158,7 @@ SIGNATURES = {
     "kmx_count_unitig_select": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_unitig_select2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_unitig_clean": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _u32, _u32, _u64, _u64, _u64, _vp, _vp]),
+    "kmx_count_unitig_components": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, RC_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, COMP_COUNT_SUM, COMP_N_NODES, COMP_N_UNITIGS, COMP_ROOT, COMP_WORDS, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, RC_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -284,6 +284,66 @@ class UnitigLinks:
 
 
 @dataclasses.dataclass
+class UnitigComponents:
+    """What kmx_count_unitig_components returns: the connected components of the compacted graph.  labels int64[U]: the smallest
+    unitig index of the unitig's component; ids int64[U]: the component's number, 0 .. n_components - 1 in ascending order of the
+    labels (both -1, COMPONENT_NONE, for a unitig the mask left out); records int64[C, 4] (u64 words, columns _lib.COMP_*), None
+    with stats=False; rounds: the hook / jump rounds the call ran."""
+    labels: "torch.Tensor"
+    ids: "torch.Tensor"
+    records: "torch.Tensor"
+    n_components: int
+    rounds: int
+
+    @property
+    def roots(self):
+        """int64[C]: the label of each component"""
+        return self.records[:, COMP_ROOT]
+
+    @property
+    def n_unitigs(self):
+        """int64[C]: unitigs per component"""
+        return self.records[:, COMP_N_UNITIGS]
+
+    @property
+    def n_nodes(self):
+        """int64[C]: nodes (entries of the table) per component"""
+        return self.records[:, COMP_N_NODES]
+
+    @property
+    def count_sums(self):
+        """int64[C]: the u64 wrapping sum of the count sums of the component's unitigs"""
+        return self.records[:, COMP_COUNT_SUM]
+
+    @property
+    def mean_counts(self):
+        """float64[C]: the mean count per node, count_sums (as u64) / n_nodes, as Unitigs.mean_counts -- for looking at a graph"""
+        s = self.count_sums.to(torch.float64)
+        s = torch.where(self.count_sums < 0, s + 2.0**64, s)
+        return s / self.n_nodes.to(torch.float64)
+
+    def keep(self, min_nodes=0, min_unitigs=0, min_count_sum=0, largest=None):
+        """uint8[U] for count_unitig_select(2): 1 iff the unitig's component has at least min_nodes nodes, min_unitigs unitigs and a
+        count sum (as u64) of min_count_sum, all of them; largest=n keeps, of those, only the n components with the most nodes,
+        ties going to the smaller id.  A unitig the mask left out is 0.  In torch."""
+        if self.records is None:
+            raise ValueError("keep needs the records: count_unitig_components(..., stats=True)")
+        cs = self.count_sums
+        big = int(min_count_sum) >= 2**63   # (u64 order on int64 words: a negative word is a sum of 2^63 or more)
+        enough = (cs < 0) & (cs >= int(min_count_sum) - 2**64) if big else (cs < 0) | (cs >= int(min_count_sum))
+        ok = (self.n_nodes >= int(min_nodes)) & (self.n_unitigs >= int(min_unitigs)) & enough
+        if largest is not None:
+            order = torch.sort(self.n_nodes, descending=True, stable=True).indices   # (stable: equal sizes stay in order of id)
+            top = torch.zeros_like(ok)
+            top[order[:max(int(largest), 0)]] = True
+            ok = ok & top
+        alive = self.ids >= 0
+        out = torch.zeros(self.ids.numel(), dtype=torch.uint8, device=self.ids.device)
+        out[alive] = ok[self.ids[alive]].to(torch.uint8)
+        return out
+
+
+@dataclasses.dataclass
 class ReadPaths:
     """What kmx_count_read_paths(2) returns: the segments of every read over the unitigs, ordered by read, then by start.
     offsets int64[n_reads + 1]: read r owns segments[offsets[r]:offsets[r + 1]]; segments int64[S, 4] (u64 words, columns
@@ -329,6 +389,11 @@ class ReadPaths:
         """int64[n_unitigs]: how many windows of the batch lie on each unitig"""
         cov = torch.zeros(int(n_unitigs), dtype=torch.int64, device=self.segments.device)
         return cov.scatter_add_(0, self.unitig, self.length)
+
+    def components(self, comp: "UnitigComponents"):
+        """int64[S]: the component id of every segment's unitig (-1 where the mask of count_unitig_components left the unitig
+        out) -- a gather in torch.  Reads in different components share no unitig: the batch splits into independent jobs."""
+        return comp.ids[self.unitig]
 
 
 def _on_ctx_stream(fn):
@@ -1103,6 +1168,58 @@ class Context:
     def count_simplify2(self, kmers, counts, k, min_count=1, rounds=4, **rule):
         """count_simplify for the tables of count_canonical2 (k 33..64)."""
         return self._simplify(2, kmers, counts, k, min_count, rounds, rule)
+
+    # ------------------------------------------------------------ which unitigs hang together
+    @_on_ctx_stream
+    def count_unitig_components(self, unitigs: Unitigs, links: UnitigLinks, mask=None, stats=True) -> UnitigComponents:
+        """kmx_count_unitig_components -> UnitigComponents: the connected components of the compacted graph (include/kmx.h has the
+        rule) -- a label (the smallest unitig index of its component) and an id per unitig, and with stats=True a record per
+        component: root, unitigs, nodes, count sum.  `mask` (bool or uint8 per unitig, for instance the keep of count_unitig_clean)
+        leaves unitigs out, with their links.  One call for both key widths."""
+        u = unitigs.n_unitigs
+        if links.offsets.numel() != 2 * u + 1:
+            raise ValueError("links holds 2 * n_unitigs + 1 offsets")
+        if mask is not None:
+            mask = (mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)).contiguous()
+            if mask.numel() != u:
+                raise ValueError("mask holds one byte per unitig")
+        labels, ids = self.empty(u, torch.int64), self.empty(u, torch.int64)
+        c, r = C.c_uint64(0), C.c_uint32(0)
+        args = (self._h, _ptr(unitigs.offsets), _ptr(unitigs.count_sums) if unitigs.count_sums is not None and u else None, u, _ptr(links.offsets),
+                _ptr(links.targets) if links.n_links else None, links.n_links, _ptr(mask) if mask is not None and u else None,
+                _ptr(labels) if u else None, _ptr(ids) if u else None)
+        self._ck(self.lib.kmx_count_unitig_components(*args, None, 0, C.byref(c), C.byref(r)))
+        if not stats:
+            return UnitigComponents(labels, ids, None, int(c.value), int(r.value))
+        # (the records need C: count, then allocate, as count_unitig_links does)
+        rec = self.empty(COMP_WORDS * max(int(c.value), 1), torch.int64)
+        self._ck(self.lib.kmx_count_unitig_components(*args, _ptr(rec), int(c.value), C.byref(c), C.byref(r)))
+        return UnitigComponents(labels, ids, rec[:COMP_WORDS * int(c.value)].view(-1, COMP_WORDS), int(c.value), int(r.value))
+
+    def _drop_small_components(self, words, kmers, counts, k, min_nodes, min_count):
+        one = words == 1
+        n = int(counts.numel())
+        adj = (self.count_adjacency if one else self.count_adjacency2)(kmers, counts, k, min_count, flips=True, neighbors=True)
+        un = (self.count_unitigs if one else self.count_unitigs2)(kmers, counts, k, min_count, adjacency=adj)
+        place = self.count_unitig_index(un, n)
+        links = self.count_unitig_links(un, adj, n, place=place)
+        comp = self.count_unitig_components(un, links)
+        kmers, counts = (self.count_unitig_select if one else self.count_unitig_select2)(kmers, counts, un, comp.keep(min_nodes=min_nodes), place=place)
+        return kmers, counts, comp
+
+    @_on_ctx_stream
+    def count_drop_small_components(self, kmers, counts, k, min_nodes, min_count=1):
+        """Component filter -> (kmers, counts, components): the table without the entries of every connected component of fewer than
+        min_nodes nodes -- a contaminant, a cluster of errors that forms a graph of its own: what count_simplify(2), whose rules see
+        one unitig and its neighbours, keeps -- and the UnitigComponents of the graph BEFORE the cut.  adjacency -> unitigs -> index
+        -> links -> components -> keep(min_nodes) -> select, all on the device.  Entries below min_count lie in no unitig and
+        leave, as with count_clip_tips.  k 2..31."""
+        return self._drop_small_components(1, kmers, counts, k, min_nodes, min_count)
+
+    @_on_ctx_stream
+    def count_drop_small_components2(self, kmers, counts, k, min_nodes, min_count=1):
+        """count_drop_small_components for the tables of count_canonical2 (k 33..64)."""
+        return self._drop_small_components(2, kmers, counts, k, min_nodes, min_count)
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

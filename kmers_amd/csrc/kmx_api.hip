@@ -1457,6 +1457,43 @@ int kmx_count_unitig_clean(kmx_ctx* ctx, const uint64_t* d_offsets, const uint8_
     return KMX_OK;
 }
 
+// ---- which unitigs hang together (kmx_count_components.hip) ----
+int kmx_count_unitig_components(kmx_ctx* ctx, const uint64_t* d_offsets, const uint64_t* d_count_sums, uint64_t n_unitigs,
+                                const uint64_t* d_link_offsets, const uint64_t* d_links, uint64_t n_links, const uint8_t* d_mask, uint64_t* d_labels,
+                                uint64_t* d_ids, uint64_t* d_components, uint64_t max_components, uint64_t* h_n_components, uint32_t* h_rounds) {
+    if (!ctx || !h_n_components || n_unitigs > (1ull << 40) || n_links > (1ull << 43)) return KMX_E_ARG;   // (four links per oriented unitig)
+    if (n_unitigs && (!d_labels || !d_link_offsets)) return KMX_E_ARG;
+    if (n_links && !d_links) return KMX_E_ARG;
+    *h_n_components = 0;
+    if (h_rounds) *h_rounds = 0;
+    if (n_unitigs == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    const char* who = "kmx_count_unitig_components";
+    const bool own_rank = d_components && !d_ids;
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::count_components_bytes(n_unitigs, own_rank), &area)) return st;
+    uint64_t n_components = 0;
+    uint32_t rounds = 0;
+    bool bad = false;
+    KMX_HIP(ctx, kmx::launch_count_components_label(d_link_offsets, d_links, n_links, d_mask, n_unitigs, d_labels, area, own_rank, ctx->h_pinned,
+                                                    &n_components, &rounds, &bad, ctx->stream));
+    if (bad) {
+        char msg[96];
+        std::snprintf(msg, sizeof msg, "%s: the rounds did not end", who);
+        return fail_hip(ctx, hipErrorUnknown, msg);
+    }
+    *h_n_components = n_components;
+    if (h_rounds) *h_rounds = rounds;
+    const int room = d_components ? room_for(ctx, who, n_components, "components", max_components) : KMX_OK;   // (labels and ids all the same)
+    uint64_t* records = room == KMX_OK ? d_components : nullptr;
+    if (d_ids || records) {
+        KMX_HIP(ctx, kmx::launch_count_components_emit(d_labels, n_unitigs, d_offsets, d_count_sums, area, own_rank, d_ids, records, n_components,
+                                                       ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return room;
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

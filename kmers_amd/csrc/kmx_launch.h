@@ -204,6 +204,16 @@ hipError_t launch_count_select_mark(const u64* place, u64 n, const u64* offsets,
 hipError_t launch_count_unitig_clean(const u64* offsets, const uint8_t* circular, const u64* sums, u64 n_unitigs, const u64* link_offsets,
                                      const u64* links, u64 n_links, u64 tip_max, u32 tip_num, u32 tip_den, u64 bubble_max, u64 bubble_diff,
                                      u64 island_max, uint8_t* keep, uint8_t* reason, hipStream_t st);
+// kmx_count_components.hip: the connected components of the unitig graph -- label writes the labels and counts the components (one
+// host round trip per round and one for the count; mask may be nullptr; *bad: the rounds ran out), emit writes, unless nullptr, the
+// ids and the records (offsets and sums may be nullptr).  own_rank: the area holds a word per unitig for the roots' ids (records
+// without ids)
+size_t count_components_bytes(u64 n_unitigs, bool own_rank);
+hipError_t launch_count_components_label(const u64* link_offsets, const u64* links, u64 n_links, const uint8_t* mask, u64 n_unitigs, u64* labels,
+                                         void* area, bool own_rank, unsigned long long* h_pinned, u64* h_components, u32* h_rounds, bool* bad,
+                                         hipStream_t st);
+hipError_t launch_count_components_emit(const u64* labels, u64 n_unitigs, const u64* offsets, const u64* sums, const void* area, bool own_rank, u64* ids,
+                                        u64* records, u64 n_components, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
