@@ -939,6 +939,45 @@ pub fn count_unitig_components(ctx: &HipContext, d_offsets: Option<&DeviceBuf<'_
     Ok(out)
 }
 
+/// How many reads walk each link (`kmx_count_link_support`; include/kmx.h has the rule): for every pair of consecutive segments of one
+/// read, the second beginning one base after the first ends, that leaves the exit node of one oriented unitig and enters the entry
+/// node of the next, `d_support` (one u64 per link slot) gains 1 at the link's slot and at its mirror's; `d_summary` (`KMX_LS_WORDS`
+/// u64) gains the junctions, those that crossed a link and those that did not (0 for paths over the links' own graph).  Both are
+/// accumulated into: the caller zeroes them.  `d_segments` / `n_segments` are `count_read_paths(2)`' output, `d_offsets` is
+/// `count_unitigs`', `d_link_offsets` / `d_links` / `n_links` `count_unitig_links`'.  One call for both key widths.  Asynchronous.
+pub fn count_link_support(ctx: &HipContext, d_segments: &DeviceBuf<'_>, n_segments: u64, d_offsets: &DeviceBuf<'_>, n_unitigs: u64,
+                          d_link_offsets: &DeviceBuf<'_>, d_links: &DeviceBuf<'_>, n_links: u64, d_support: &DeviceBuf<'_>,
+                          d_summary: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    assert!(n_segments as u128 * 32 <= d_segments.len() as u128, "segments shorter than the segment count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!((2 * n_unitigs as u128 + 1) * 8 <= d_link_offsets.len() as u128, "link offsets shorter than twice the unitig count + 1");
+    assert!(n_links as u128 * 8 <= d_links.len() as u128, "links shorter than the link count");
+    assert!(n_links as u128 * 8 <= d_support.len() as u128, "support shorter than the link count");
+    assert!(KMX_LS_WORDS as usize * 8 <= d_summary.len(), "summary shorter than KMX_LS_WORDS words");
+    ctx.ck(unsafe { kmx_count_link_support(ctx.0, d_segments.as_ptr::<u64>(), n_segments, d_offsets.as_ptr::<u64>(), n_unitigs,
+                                           d_link_offsets.as_ptr::<u64>(), d_links.as_ptr::<u64>(), n_links, d_support.as_mut_ptr::<u64>(),
+                                           d_summary.as_mut_ptr::<u64>()) })
+}
+
+/// The adjacency without chosen links (`kmx_count_adjacency_cut`): `d_edges_out` (n bytes, not overlapping `d_edges`) = `d_edges` with
+/// the edge bit cleared from which link slot l was derived, for every l with `d_cut[l] != 0` (one byte per link slot).  The arrays
+/// are those `count_unitig_links` made `d_link_offsets` from; `d_flips` and `d_nbr` go on unchanged with the new edges into
+/// `count_unitigs(2)` and `count_unitig_links`.  One call for both key widths.  Asynchronous.
+pub fn count_cut_links(ctx: &HipContext, d_edges: &DeviceBuf<'_>, d_flips: &DeviceBuf<'_>, d_nbr: &DeviceBuf<'_>, n: u64, d_nodes: &DeviceBuf<'_>,
+                       d_offsets: &DeviceBuf<'_>, n_unitigs: u64, d_place: &DeviceBuf<'_>, d_link_offsets: &DeviceBuf<'_>, n_links: u64,
+                       d_cut: &DeviceBuf<'_>, d_edges_out: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    assert!(n as u128 <= d_edges.len() as u128 && n as u128 <= d_flips.len() as u128 && n as u128 * 64 <= d_nbr.len() as u128,
+            "adjacency shorter than the entry count");
+    assert!(n as u128 * 8 <= d_place.len() as u128, "places shorter than the entry count");
+    assert!((n_unitigs as u128 + 1) * 8 <= d_offsets.len() as u128, "unitig offsets shorter than the unitig count + 1");
+    assert!((2 * n_unitigs as u128 + 1) * 8 <= d_link_offsets.len() as u128, "link offsets shorter than twice the unitig count + 1");
+    assert!(n_links as u128 <= d_cut.len() as u128, "cut bytes shorter than the link count");
+    assert!(n as u128 <= d_edges_out.len() as u128, "output edges shorter than the entry count");
+    ctx.ck(unsafe { kmx_count_adjacency_cut(ctx.0, d_edges.as_ptr::<u8>(), d_flips.as_ptr::<u8>(), d_nbr.as_ptr::<u64>(), n, d_nodes.as_ptr::<u64>(),
+                                            d_offsets.as_ptr::<u64>(), n_unitigs, d_place.as_ptr::<u64>(), d_link_offsets.as_ptr::<u64>(), n_links,
+                                            d_cut.as_ptr::<u8>(), d_edges_out.as_mut_ptr::<u8>()) })
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -775,6 +775,72 @@ int kmx_count_unitig_components(kmx_ctx *ctx, const uint64_t *d_offsets, const u
                                 uint64_t *d_labels, uint64_t *d_ids, uint64_t *d_components, uint64_t max_components,
                                 uint64_t *h_n_components, uint32_t *h_rounds);
 
+/* How many reads walk each link: the evidence that an edge of the graph is real.  A link exists because two present k-mers overlap by
+ * k - 1 bases, whether or not any read ever passed from one to the other; the segments of kmx_count_read_paths(2) say where reads
+ * did.  The rule is defined on the arrays alone: any bytes give the answer stated here and never an access outside the arrays.
+ * NOTATION.  U = n_unitigs; m(u) = d_offsets[u + 1] - d_offsets[u], read as 0 where the offsets descend; segment s is the record
+ * d_segments + KMX_PATH_WORDS * s with read(s), start(s) and length(s) (the low and high 32 bits of KMX_PATH_SPAN), u(s), and q(s), d(s)
+ * (KMX_PATH_POS = (q << 1) | d); t(s) = 2 u(s) + d(s), the oriented unitig the segment walks.  L(t), for t < 2 U, is the list
+ * d_links[lo .. hi), lo = d_link_offsets[t], hi = d_link_offsets[t + 1]; it is empty unless lo <= hi <= n_links and hi - lo <= 4.
+ * JUNCTION.  Segments s and s + 1 (s + 1 < n_segments) form a junction iff read(s + 1) == read(s) and start(s + 1) == start(s) +
+ * length(s): the next run of windows begins one base after the last window of this one.  A gap -- an N, a window that is not
+ * mapped -- is no junction, nor is the step from one read to the next.
+ * CROSSING.  A junction crosses link slot l iff u(s) < U, u(s + 1) < U, and with t = t(s), t' = t(s + 1), as integers without wrap:
+ *     s ends on the exit node of t:            d(s) = 0:  q(s) + length(s) == m(u(s))      d(s) = 1:  q(s) + 1 == length(s)
+ *     s + 1 starts on the entry node of t':    d(s + 1) = 0:  q(s + 1) == 0                d(s + 1) = 1:  q(s + 1) + 1 == m(u(s + 1))
+ *     l is the first slot of L(t) with d_links[l] == t'.
+ * Then d_support[l] += 1, and if the MIRROR link mirror(t') -> mirror(t) has a slot m -- the first slot of L(t' ^ 1) whose target is
+ * t ^ 1 -- and m != l, also d_support[m] += 1.  A hairpin t -> t ^ 1 is its own mirror and counts once.  Every other junction is
+ * UNLINKED: a unitig index at or above U, an end condition that fails, or no slot l.
+ * d_support (n_links u64) and d_summary (KMX_LS_WORDS u64: junctions, crossed, unlinked; junctions == crossed + unlinked) are
+ * ACCUMULATED into, as kmx_count_spectrum accumulates (the caller zeroes): batches of reads stream against one graph.
+ * WHAT IT COUNTS.  For segments made over the unitigs the links were made of (same table, adjacency, unitigs, index), at odd k:
+ * d_support[l] = the number of occurrences in the reads, on either strand, of the (k + 1)-mer link l spells -- the last k bases of t
+ * followed by base k - 1 of t' -- a (k + 1)-mer that is its own reverse complement counted once; a link and its mirror carry the same
+ * number; and unlinked is 0: two consecutive mapped windows of a read are an edge of the adjacency, and where they lie in different
+ * runs that edge is a link.  unlinked != 0 says the paths and the links belong to different graphs.  The support is a property of
+ * the pair of NODES the link joins, not of the compaction.
+ * EVEN k.  A link into a palindromic one-node unitig names one orientation only and may have no mirror slot (see
+ * kmx_count_unitig_links): the rule above then adds to one slot, and the two directions of such an edge need not carry the same
+ * number.  And a palindromic window always reads d = 1 (kmx_count_read_paths) while a link into the palindrome names the orientation
+ * of the node it comes from: where the two differ the junction finds no slot and is UNLINKED.  At even k unlinked counts such
+ * junctions, and only such, for paths and links of one graph.
+ * d_segments / n_segments as kmx_count_read_paths(2) wrote them, d_offsets (U + 1 u64) as kmx_count_unitigs(2), d_link_offsets
+ * (2 U + 1 u64) / d_links / n_links as kmx_count_unitig_links.  Indices only: one call for both key widths.  Exact and
+ * deterministic: integer sums only, so repeated calls give identical bytes.  n_segments < 2 is a no-op.  NULL ctx / d_summary,
+ * n_segments or n_unitigs above 2^40, n_links above 2^43, d_segments NULL with n_segments > 0, d_offsets or d_link_offsets NULL with
+ * n_unitigs > 0, d_links or d_support NULL with n_links > 0: KMX_E_ARG.  Working set: none.  Asynchronous. */
+#define KMX_LS_WORDS 3u
+#define KMX_LS_JUNCTIONS 0u /* pairs of consecutive segments of one read without a gap between them */
+#define KMX_LS_CROSSED 1u   /* ... that cross a link slot */
+#define KMX_LS_UNLINKED 2u  /* ... that do not: 0 for paths over the graph the links were made of */
+int kmx_count_link_support(kmx_ctx *ctx, const uint64_t *d_segments, uint64_t n_segments, const uint64_t *d_offsets, uint64_t n_unitigs,
+                           const uint64_t *d_link_offsets, const uint64_t *d_links, uint64_t n_links, uint64_t *d_support,
+                           uint64_t *d_summary);
+
+/* The adjacency without chosen links: d_edges_out (n bytes) = d_edges with one bit cleared per cut link slot.  Slot
+ * l = d_link_offsets[t] + d is the d-th link of oriented unitig t as kmx_count_unitig_links derives it from these same arrays: it
+ * comes from bit 4 o + c of d_edges[i], v = 2 i + o the exit node of t and c the d-th base, in ascending order, that gives a link.
+ * If l < n_links and d_cut[l] != 0 (d_cut: one byte per link slot), that bit is 0 in d_edges_out[i]; every other bit is copied.  The
+ * call re-derives the links, it does not read them: d_link_offsets must be the offsets kmx_count_unitig_links wrote for these
+ * arrays, or the slots mean something else (any bytes still give a result and no access outside the arrays).
+ * d_flips and d_nbr go on unchanged with d_edges_out: a neighbour word behind a cleared bit is stale and harmless --
+ * kmx_count_unitig_ends, kmx_count_unitigs(2) and kmx_count_unitig_links read d_nbr only under a set edge bit.  The result feeds
+ * kmx_count_unitigs(2) and kmx_count_unitig_links: cut, then compact again.
+ * ONE-SIDED CUTS are legal: a bit cleared at one end of an edge only leaves the other end pointing at a node that no longer points
+ * back, which the unitigs' mutual-link rule and the END rule already handle.  To remove an edge in both directions pass a mask that
+ * is closed under the mirror, (t -> t') with (t' ^ 1 -> t ^ 1); d_support[l] < min_support is one wherever mirrors exist.
+ * What a cut does not see: a false join INSIDE a unitig is not a link.
+ * d_edges_out must not overlap d_edges (the bits are re-derived from the input while the output is cut): KMX_E_ARG.  The bits are
+ * cleared by atomic ANDs on the aligned 32-bit word that holds the byte -- neighbouring entries share it -- so up to three bytes
+ * before and after an output array that is not 4-byte aligned are ANDed with ones: rewritten with the value they hold.
+ * n == 0 is a no-op; n_unitigs == 0 or n_links == 0 copies the edges.  NULL ctx, n or n_unitigs above 2^40, n_links above 2^43,
+ * d_edges or d_edges_out NULL with n > 0, any other array NULL with n, n_unitigs and n_links > 0: KMX_E_ARG.  One call for both key
+ * widths.  Deterministic.  Working set: none.  Asynchronous. */
+int kmx_count_adjacency_cut(kmx_ctx *ctx, const uint8_t *d_edges, const uint8_t *d_flips, const uint64_t *d_nbr, uint64_t n,
+                            const uint64_t *d_nodes, const uint64_t *d_offsets, uint64_t n_unitigs, const uint64_t *d_place,
+                            const uint64_t *d_link_offsets, uint64_t n_links, const uint8_t *d_cut, uint8_t *d_edges_out);
+
 /* ---------------------------------------------------------------- set algebra and comparison of two count tables ----
  * BUILD-DEFINED.  Two TABLES (as above: keys ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs in
  * 16-byte aligned arrays, KMX_E_ARG otherwise) go in, a table comes out -- it feeds every other table call -- or a record of sums.

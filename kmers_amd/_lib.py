@@ -49,6 +49,9 @@ CLEAN_KEEP, CLEAN_TIP, CLEAN_BUBBLE, CLEAN_ISLAND = range(4)
 COMPONENT_NONE = 2**64 - 1
 COMP_ROOT, COMP_N_UNITIGS, COMP_N_NODES, COMP_COUNT_SUM = range(4)
 COMP_WORDS = 4
+# kmx_count_link_support: the words of the summary (KMX_LS_*)
+LS_JUNCTIONS, LS_CROSSED, LS_UNLINKED = range(3)
+LS_WORDS = 3
 
 
 class KmxError(RuntimeError):
@@ -159,6 +162,8 @@ SIGNATURES = {
     "kmx_count_unitig_select2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_unitig_clean": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _u32, _u32, _u64, _u64, _u64, _vp, _vp]),
     "kmx_count_unitig_components": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "kmx_count_link_support": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "kmx_count_adjacency_cut": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

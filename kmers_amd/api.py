@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, COMP_COUNT_SUM, COMP_N_NODES, COMP_N_UNITIGS, COMP_ROOT, COMP_WORDS, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, RC_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
+from ._lib import (CLEAN_BUBBLE, CLEAN_ISLAND, CLEAN_TIP, COMP_COUNT_SUM, COMP_N_NODES, COMP_N_UNITIGS, COMP_ROOT, COMP_WORDS, CR_WORDS, HASH_IDENTITY, HASH_LEX, HASH_NONE, LS_CROSSED, LS_JUNCTIONS, LS_UNLINKED, LS_WORDS, NO_ENTRY, PATH_POS, PATH_READ, PATH_SPAN, PATH_UNITIG, PATH_WORDS, RC_WORDS, REDUCE_SUM_FW, RS_SPAN, RS_WORDS, RULE_LEFT, RULE_MAX, RULE_MIN, RULE_RIGHT, RULE_SUM,
                    SETOP_COUNTER_SUBTRACT, SETOP_INTERSECT, SETOP_SUBTRACT, SETOP_SYMDIFF, SETOP_UNION, KmxError, Reads, Summary, Summary2,
                    TableCompare)
 
@@ -238,14 +238,16 @@ class Unitigs:
         loose = (open_sides == 1) | (open_sides == 2) if islands else open_sides == 1
         return (self.circular == 0) & (self.lengths <= int(max_nodes)) & loose
 
-    def write_gfa(self, file, links: "UnitigLinks | None" = None):
+    def write_gfa(self, file, links: "UnitigLinks | None" = None, support: "LinkSupport | None" = None):
         """The compacted graph as GFA 1, written on the host -- for graphs one would look at, not for 1e9 nodes.  `file` is a path
         or a text file object.  H VN:Z:1.0; one S line per unitig u, named u, with LN:i (bases) and KC:i (the sum of its entries'
         counts); with `links`, one L line per link, + / - from the orientation bit and an overlap of (k - 1)M.  A link and its mirror
-        image say the same thing and are one line, written from the smaller of (t, t') and (t' ^ 1, t ^ 1); lines are sorted."""
+        image say the same thing and are one line, written from the smaller of (t, t') and (t' ^ 1, t ^ 1); lines are sorted.
+        With `support` (count_link_support over these links) every L line ends in RC:i:<n>, the reads that cross the link -- the
+        larger of the two numbers where a link and its mirror differ (even k, around a palindromic k-mer)."""
         if isinstance(file, (str, bytes)) or hasattr(file, "__fspath__"):
             with open(file, "w") as f:
-                return self.write_gfa(f, links)
+                return self.write_gfa(f, links, support)
         k = self.k
         seq = self.sequences().cpu().numpy().tobytes().decode("ascii")
         offs = self.offsets.cpu().tolist()
@@ -256,8 +258,14 @@ class Unitigs:
             file.write(f"S\t{u}\t{s}\tLN:i:{len(s)}\tKC:i:{sums[u]}\n")
         if links is not None:
             pairs = {min((t, t2), (t2 ^ 1, t ^ 1)) for t, t2 in zip(links.sources().cpu().tolist(), links.targets.cpu().tolist())}
+            rc = {}
+            if support is not None:
+                for t, t2, c in zip(links.sources().cpu().tolist(), links.targets.cpu().tolist(), u64_numpy(support.support).tolist()):
+                    key = min((t, t2), (t2 ^ 1, t ^ 1))
+                    rc[key] = max(rc.get(key, 0), c)
             for t, t2 in sorted(pairs):
-                file.write(f"L\t{t >> 1}\t{'+-'[t & 1]}\t{t2 >> 1}\t{'+-'[t2 & 1]}\t{k - 1}M\n")
+                tag = f"\tRC:i:{rc[(t, t2)]}" if support is not None else ""
+                file.write(f"L\t{t >> 1}\t{'+-'[t & 1]}\t{t2 >> 1}\t{'+-'[t2 & 1]}\t{k - 1}M{tag}\n")
 
 
 @dataclasses.dataclass
@@ -281,6 +289,39 @@ class UnitigLinks:
         """int64[n_links]: the t of every link, in the order of `targets`"""
         deg = self.offsets[1:] - self.offsets[:-1]
         return torch.repeat_interleave(torch.arange(deg.numel(), device=deg.device), deg)
+
+
+@dataclasses.dataclass
+class LinkSupport:
+    """What kmx_count_link_support accumulates: support int64[n_links] (u64 words), the junctions of the reads that cross each link
+    slot or its mirror -- for paths over the links' own graph, the occurrences in the reads, on either strand, of the (k + 1)-mer
+    the link spells -- and summary int64[3] (columns _lib.LS_*): junctions = crossed + unlinked.  Both live on the device; hand the
+    object back as `out` to add another batch of reads."""
+    support: "torch.Tensor"
+    summary: "torch.Tensor"
+
+    @property
+    def junctions(self) -> int:
+        """pairs of consecutive segments of one read with no gap between them"""
+        return int(u64_numpy(self.summary)[LS_JUNCTIONS])
+
+    @property
+    def crossed(self) -> int:
+        """... that cross a link"""
+        return int(u64_numpy(self.summary)[LS_CROSSED])
+
+    @property
+    def unlinked(self) -> int:
+        """... that cross none: 0 when the paths were made over the graph the links were made of -- a self-check"""
+        return int(u64_numpy(self.summary)[LS_UNLINKED])
+
+    def unsupported(self, min_support: int = 1):
+        """uint8[n_links] for count_cut_links: 1 where fewer than min_support reads cross the link (as u64).  A link and its mirror
+        carry the same support wherever the mirror exists, so the mask removes an edge in both directions."""
+        m = int(min_support)
+        s = self.support
+        below = (s >= 0) & (s < m) if m < 2**63 else (s >= 0) | (s < m - 2**64)
+        return below.to(torch.uint8)
 
 
 @dataclasses.dataclass
@@ -1220,6 +1261,87 @@ class Context:
     def count_drop_small_components2(self, kmers, counts, k, min_nodes, min_count=1):
         """count_drop_small_components for the tables of count_canonical2 (k 33..64)."""
         return self._drop_small_components(2, kmers, counts, k, min_nodes, min_count)
+
+    # ------------------------------------------------------------ which links the reads walk
+    @_on_ctx_stream
+    def count_link_support(self, paths: ReadPaths, unitigs: Unitigs, links: UnitigLinks, out: "LinkSupport | None" = None) -> LinkSupport:
+        """kmx_count_link_support -> LinkSupport: per link slot, how many reads of the batch cross it (include/kmx.h has the rule) --
+        a pair of consecutive segments of one read, the second beginning one base after the first ends, that leaves the exit node of
+        one oriented unitig and enters the entry node of the next; the link and its mirror are both credited.  `paths` as
+        count_read_paths(2) returned them for `unitigs`, `links` as count_unitig_links.  `out` (a LinkSupport of the same links) is
+        accumulated into: batches of reads stream against one graph.  One call for both key widths; asynchronous."""
+        u = unitigs.n_unitigs
+        if links.offsets.numel() != 2 * u + 1:
+            raise ValueError("links holds 2 * n_unitigs + 1 offsets")
+        if out is None:
+            out = LinkSupport(torch.zeros(links.n_links, dtype=torch.int64, device=self.device),
+                              torch.zeros(LS_WORDS, dtype=torch.int64, device=self.device))
+        elif out.support.numel() != links.n_links or out.summary.numel() != LS_WORDS:
+            raise ValueError("out holds one word per link and three summary words")
+        segs = paths.segments.contiguous()
+        s = int(segs.shape[0])
+        self._ck(self.lib.kmx_count_link_support(self._h, _ptr(segs) if s else None, s, _ptr(unitigs.offsets), u, _ptr(links.offsets),
+                                                 _ptr(links.targets) if links.n_links else None, links.n_links,
+                                                 _ptr(out.support) if links.n_links else None, _ptr(out.summary)))
+        return out
+
+    @_on_ctx_stream
+    def count_cut_links(self, unitigs: Unitigs, links: UnitigLinks, adjacency, n: int, cut, place=None):
+        """kmx_count_adjacency_cut -> (edges, flips, nbr): the adjacency with the edge bit of every link slot whose `cut` byte (bool
+        or uint8 per link slot, for instance LinkSupport.unsupported()) is set cleared in a copy of the edges; flips and nbr are the
+        tensors handed in (a neighbour word behind a cleared bit is never read).  adjacency, n and place as for count_unitig_links,
+        which must have made `links` from them.  The result goes into count_unitigs(2)(..., adjacency=) and count_unitig_links: cut,
+        then compact again.  A mask that is not closed under the mirror cuts one direction of an edge only, which is legal."""
+        n = int(n)
+        edges, flips, nbr = adjacency
+        nbr = nbr.contiguous()
+        u = unitigs.n_unitigs
+        if links.offsets.numel() != 2 * u + 1:
+            raise ValueError("links holds 2 * n_unitigs + 1 offsets")
+        cut = (cut if cut.dtype == torch.uint8 else cut.to(torch.uint8)).contiguous()
+        if cut.numel() != links.n_links:
+            raise ValueError("cut holds one byte per link slot")
+        if place is None:
+            place = self.count_unitig_index(unitigs, n)
+        out = self.empty(n, torch.uint8)
+        self._ck(self.lib.kmx_count_adjacency_cut(self._h, _ptr(edges) if n else None, _ptr(flips) if n else None, _ptr(nbr) if n else None, n,
+                                                  _ptr(unitigs.nodes) if unitigs.n_nodes else None, _ptr(unitigs.offsets), u,
+                                                  _ptr(place) if n else None, _ptr(links.offsets), links.n_links,
+                                                  _ptr(cut) if links.n_links else None, _ptr(out) if n else None))
+        return out, flips, nbr
+
+    def _prune_links(self, words, bases, n_reads, read_len, k, kmers, counts, min_support, min_count, offsets):
+        one = words == 1
+        n = int(counts.numel())
+        adj = (self.count_adjacency if one else self.count_adjacency2)(kmers, counts, k, min_count, flips=True, neighbors=True)
+        unitigs = self.count_unitigs if one else self.count_unitigs2
+        un = unitigs(kmers, counts, k, min_count, adjacency=adj)
+        place = self.count_unitig_index(un, n)
+        links = self.count_unitig_links(un, adj, n, place=place)
+        paths = (self.count_read_paths if one else self.count_read_paths2)(bases, n_reads, read_len, k, kmers, un, place=place, offsets=offsets)
+        support = self.count_link_support(paths, un, links)
+        cut = support.unsupported(min_support)
+        adj = self.count_cut_links(un, links, adj, n, cut, place=place)
+        un = unitigs(kmers, counts, k, min_count, adjacency=adj)
+        return adj, un, self.count_unitig_links(un, adj, n), support, int(cut.sum())
+
+    @_on_ctx_stream
+    def count_prune_links(self, bases, n_reads, read_len, k, kmers, counts, min_support=1, min_count=1, offsets=None):
+        """Edge filter -> (adjacency, unitigs, links, support, n_cut): the graph of the table without the links that fewer than
+        min_support reads of the batch cross -- two k-mers that overlap by chance, at a repeat boundary or next to an error, with
+        no read passing from one to the other.  adjacency -> unitigs -> index -> links -> read paths -> support -> cut, then
+        unitigs and links again over the cut adjacency, all on the device.  Returns the cut adjacency (edges, flips, nbr), the
+        Unitigs and UnitigLinks made of it, the LinkSupport of the FIRST pass (over the links before the cut) and the number of link
+        slots cut.  One pass suffices: support belongs to the pair of nodes a link joins, not to the compaction, so the links that
+        remain are links that were counted.  The table is not changed: the cuts live in the adjacency returned here, and
+        count_simplify(2), which rebuilds the adjacency from the table, does not see them.  A false join inside a unitig is not a
+        link and stays.  k 2..31."""
+        return self._prune_links(1, bases, n_reads, read_len, k, kmers, counts, min_support, min_count, offsets)
+
+    @_on_ctx_stream
+    def count_prune_links2(self, bases, n_reads, read_len, k, kmers, counts, min_support=1, min_count=1, offsets=None):
+        """count_prune_links for the tables of count_canonical2 (k 33..64)."""
+        return self._prune_links(2, bases, n_reads, read_len, k, kmers, counts, min_support, min_count, offsets)
 
     @_on_ctx_stream
     def canonical_reduce2(self, bases, n_reads, read_len, k, with_hash=False, offsets=None) -> Summary2:

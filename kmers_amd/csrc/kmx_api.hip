@@ -1494,6 +1494,33 @@ int kmx_count_unitig_components(kmx_ctx* ctx, const uint64_t* d_offsets, const u
     return room;
 }
 
+// ---- which links the reads walk, and an adjacency without chosen links (kmx_count_link_support.hip) ----
+int kmx_count_link_support(kmx_ctx* ctx, const uint64_t* d_segments, uint64_t n_segments, const uint64_t* d_offsets, uint64_t n_unitigs,
+                           const uint64_t* d_link_offsets, const uint64_t* d_links, uint64_t n_links, uint64_t* d_support, uint64_t* d_summary) {
+    if (!ctx || !d_summary || n_segments > (1ull << 40) || n_unitigs > (1ull << 40) || n_links > (1ull << 43)) return KMX_E_ARG;
+    if ((n_segments && !d_segments) || (n_links && (!d_links || !d_support)) || (n_unitigs && (!d_offsets || !d_link_offsets))) return KMX_E_ARG;
+    if (n_segments < 2) return KMX_OK;   // (no pair of segments)
+    DeviceGuard g(ctx->device);
+    // (n_unitigs == 0: every junction names a unitig at or above U and is unlinked; neither offsets array is read)
+    KMX_HIP(ctx, kmx::launch_count_link_support(d_segments, n_segments, d_offsets, n_unitigs, d_link_offsets, d_links, n_links, d_support, d_summary,
+                                                ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_count_adjacency_cut(kmx_ctx* ctx, const uint8_t* d_edges, const uint8_t* d_flips, const uint64_t* d_nbr, uint64_t n, const uint64_t* d_nodes,
+                            const uint64_t* d_offsets, uint64_t n_unitigs, const uint64_t* d_place, const uint64_t* d_link_offsets, uint64_t n_links,
+                            const uint8_t* d_cut, uint8_t* d_edges_out) {
+    if (!ctx || n > (1ull << 40) || n_unitigs > (1ull << 40) || n_links > (1ull << 43)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    if (!d_edges || !d_edges_out) return KMX_E_ARG;
+    if (d_edges_out < d_edges + n && d_edges < d_edges_out + n) return KMX_E_ARG;   // (the bits are re-derived from the input while the output is cut)
+    if (n_unitigs && n_links && (!d_flips || !d_nbr || !d_nodes || !d_offsets || !d_place || !d_link_offsets || !d_cut)) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_count_adjacency_cut(d_edges, d_flips, d_nbr, n, d_nodes, d_offsets, n_unitigs, d_place, d_link_offsets, n_links, d_cut,
+                                                 d_edges_out, ctx->stream));
+    return KMX_OK;
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

@@ -20,6 +20,7 @@
 // Behind that mark byte the compaction is the filter's: keep_count_kernel and scan_single_kernel of kmx_count_common.h here, over
 // the filter's layout of the work buffer, and the filter's own emit (launch_count_filter_emit, compact_write_kernel<W, 1>).
 #include "kmx_count_common.h"
+#include "kmx_count_links.h"
 
 namespace kmx {
 
@@ -27,55 +28,12 @@ namespace {
 
 constexpr u32 LINK_RANGE = CT * 16u;   // oriented unitigs per block of the partial / offsets kernels, and per scanned partial
 
-// the largest i in [0, n) with a[i] <= x (0 if there is none); n >= 1; reads a[1 .. n) only (kmx_count_paths.hip has its twin)
-__device__ __forceinline__ u64 last_at_or_below(const u64* __restrict__ a, u64 n, u64 x) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1u) {
-        const u64 mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // ---------------------------------------------------------------- the links
-struct LinkIn {
-    const uint8_t *edges, *flips;
-    const u64 *nbr, *nodes, *offsets, *place;
-    u64 n, n_unitigs;
-};
-
-// emit(d, target) for the d-th link of oriented unitig t (t < 2 n_unitigs), in ascending c; returns how many there are
-template <typename F>
-__device__ __forceinline__ u32 for_links(u64 t, const LinkIn& in, F&& emit) {
-    const u64 n_nodes = in.offsets[in.n_unitigs];
-    const u64 a = in.offsets[t >> 1], b = in.offsets[(t >> 1) + 1u];
-    if (a >= b || b > n_nodes) return 0u;   // (an empty unitig, or offsets that do not ascend)
-    const u64 v = (t & 1u) == 0u ? in.nodes[b - 1u] : in.nodes[a] ^ 1u;
-    const u64 i = v >> 1;
-    if (i >= in.n) return 0u;
-    const u32 o = (u32)(v & 1u);
-    const u32 eb = ((u32)in.edges[i] >> (4u * o)) & 15u, fb = ((u32)in.flips[i] >> (4u * o)) & 15u;
-    u32 d = 0;
-#pragma unroll
-    for (u32 c = 0; c < 4u; ++c) {
-        if ((eb >> c & 1u) == 0u) continue;
-        const u64 j = in.nbr[8u * i + 4u * o + c];
-        if (j >= in.n) continue;
-        const u64 x = in.place[j], p1 = x >> 3;
-        if (p1 == 0u || p1 > n_nodes) continue;   // in no unitig, or a position p = p1 - 1 outside the offsets
-        const bool same = ((o ^ (fb >> c)) & 1u) == (u32)(x & 1u);   // w enters j as j is written in its unitig
-        if ((x & (same ? 2u : 4u)) == 0u) continue;                    // ... then it must be the first node, else the last
-        emit(d, 2u * last_at_or_below(in.offsets, in.n_unitigs, p1 - 1u) + (same ? 0u : 1u));
-        ++d;
-    }
-    return d;
-}
-
+// (LinkIn and for_links: kmx_count_links.h, shared with the cut of kmx_count_link_support.hip)
 __global__ void __launch_bounds__(CT) link_count_kernel(LinkIn in, u64 n_pad, uint8_t* __restrict__ deg) {
     const u64 n_t = 2u * in.n_unitigs;
     for (u64 t = (u64)blockIdx.x * CT + threadIdx.x; t < n_pad; t += (u64)gridDim.x * CT)
-        deg[t] = t < n_t ? (uint8_t)for_links(t, in, [](u32, u64) {}) : (uint8_t)0u;
+        deg[t] = t < n_t ? (uint8_t)for_links(t, in, [](u32, u64, u64, u32, u32) {}) : (uint8_t)0u;
 }
 
 // the sum of four degree bytes (each at most 4)
@@ -109,7 +67,7 @@ __global__ void __launch_bounds__(CT) link_emit_kernel(LinkIn in, const u64* __r
     const u64 n_t = 2u * in.n_unitigs;
     for (u64 t = (u64)blockIdx.x * CT + threadIdx.x; t < n_t; t += (u64)gridDim.x * CT) {
         const u64 at = link_offsets[t];
-        (void)for_links(t, in, [&](u32 d, u64 target) {
+        (void)for_links(t, in, [&](u32 d, u64 target, u64, u32, u32) {
             if (at + d < n_links) links[at + d] = target;   // (always, for offsets this call scanned from the same inputs)
         });
     }

@@ -214,6 +214,15 @@ hipError_t launch_count_components_label(const u64* link_offsets, const u64* lin
                                          hipStream_t st);
 hipError_t launch_count_components_emit(const u64* labels, u64 n_unitigs, const u64* offsets, const u64* sums, const void* area, bool own_rank, u64* ids,
                                         u64* records, u64 n_components, hipStream_t st);
+// kmx_count_link_support.hip: support[l] += the junctions of the segments that cross link slot l or its mirror, summary[0 .. 3) +=
+// junctions, crossed, unlinked (n_segments >= 2; n_unitigs == 0 reads no offsets: every junction is unlinked); and the edges with
+// the bit of every cut link slot cleared (n >= 1; the slots are those of launch_count_links_emit over the same arrays).  Both
+// asynchronous, no work buffer
+hipError_t launch_count_link_support(const u64* segments, u64 n_segments, const u64* offsets, u64 n_unitigs, const u64* link_offsets, const u64* links,
+                                     u64 n_links, u64* support, u64* summary, hipStream_t st);
+hipError_t launch_count_adjacency_cut(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, const u64* nodes, const u64* offsets,
+                                      u64 n_unitigs, const u64* place, const u64* link_offsets, u64 n_links, const uint8_t* cut, uint8_t* edges_out,
+                                      hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
