@@ -978,6 +978,107 @@ pub fn count_cut_links(ctx: &HipContext, d_edges: &DeviceBuf<'_>, d_flips: &Devi
                                             d_cut.as_ptr::<u8>(), d_edges_out.as_mut_ptr::<u8>()) })
 }
 
+/// The span of every source read for `reads_select` / `reads_gather` (include/kmx.h, "THE SPAN OF A READ"): the span word of read r is
+/// word `first_word + r * stride` of `words`, start in its low 32 bits and length in its high 32; `k == 0`: the length counts bases,
+/// `k > 0`: windows of k bases.  `ReadSpans { words: &d_stats, first_word: KMX_RS_SPAN as u64, stride: KMX_RS_WORDS as u64, k }` trims
+/// every read to its longest run of solid windows straight from the rows of `count_read_stats`.
+#[derive(Clone, Copy)]
+pub struct ReadSpans<'a> {
+    pub words: &'a DeviceBuf<'a>,
+    pub first_word: u64,
+    pub stride: u64,
+    pub k: u32,
+}
+
+fn span_args(spans: Option<ReadSpans<'_>>, n_reads: u64) -> (*const u64, u64, u32) {
+    match spans {
+        None => (ptr::null(), 0, 0),
+        Some(s) => {
+            assert!(s.stride >= 1, "span stride of 0");
+            assert!(n_reads == 0 || (s.first_word as u128 + (n_reads as u128 - 1) * s.stride as u128 + 1) * 8 <= s.words.len() as u128,
+                    "span words shorter than the batch's reads");
+            (unsafe { s.words.as_ptr::<u64>().add(s.first_word as usize) }, s.stride, s.k)
+        }
+    }
+}
+
+/// The outputs of `reads_select` / `reads_gather`: `bases` (at least `max_bases` bytes), `offsets` (at least `max_reads + 1` u64) and,
+/// for `reads_select`, optionally `index` (at least `max_reads` u64: the source read of every output read).
+pub struct ReadOutputs<'a> {
+    pub bases: &'a DeviceBuf<'a>,
+    pub offsets: &'a DeviceBuf<'a>,
+    pub index: Option<&'a DeviceBuf<'a>>,
+    pub max_reads: u64,
+    pub max_bases: u64,
+}
+
+fn reads_of(d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>) -> kmx_reads {
+    match d_read_offsets {
+        Some(o) => {
+            assert!((n_reads as u128 + 1) * 8 <= o.len() as u128, "read offsets shorter than the read count + 1");
+            kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: o.as_ptr::<u64>() }
+        }
+        None => {
+            assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+            kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() }
+        }
+    }
+}
+
+/// Keep, drop and clip the reads of a batch (`kmx_reads_select`; include/kmx.h has the rule): read r is kept iff `d_keep` is None or
+/// its byte r is not 0, and its clip -- the whole read, or its span -- has at least `min_len` bases; the clips are written back to back
+/// in source order, a ragged batch again.  Uniform reads (`d_read_offsets` None) or ragged ones.  `out = None` counts only.  Returns
+/// (reads kept, bases kept); Err(KMX_E_NOMEM) if they exceed `max_reads` / `max_bases`, with nothing written.  Synchronous.
+pub fn reads_select(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>,
+                    d_keep: Option<&DeviceBuf<'_>>, spans: Option<ReadSpans<'_>>, min_len: u64, out: Option<&ReadOutputs<'_>>)
+                    -> Result<(u64, u64), KmxError> {
+    let r = reads_of(d_reads, n_reads, read_len, d_read_offsets);
+    if let Some(kp) = d_keep {
+        assert!(n_reads as u128 <= kp.len() as u128, "keep bytes shorter than the batch's reads");
+    }
+    let (d_span, stride, span_k) = span_args(spans, n_reads);
+    let (mut n_out, mut n_bases) = (0u64, 0u64);
+    let (ob, oo, oi, max_reads, max_bases) = match out {
+        None => (ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), 0, 0),
+        Some(o) => {
+            assert!(o.max_bases as u128 <= o.bases.len() as u128 && (o.max_reads as u128 + 1) * 8 <= o.offsets.len() as u128,
+                    "outputs shorter than max_reads / max_bases");
+            if let Some(ix) = o.index {
+                assert!(o.max_reads as u128 * 8 <= ix.len() as u128, "index shorter than max_reads");
+            }
+            (o.bases.as_mut_ptr::<u8>(), o.offsets.as_mut_ptr::<u64>(), o.index.map_or(ptr::null_mut(), |ix| ix.as_mut_ptr::<u64>()), o.max_reads,
+             o.max_bases)
+        }
+    };
+    ctx.ck(unsafe { kmx_reads_select(ctx.0, &r, d_keep.map_or(ptr::null(), |kp| kp.as_ptr::<u8>()), d_span, stride, span_k, min_len, ob, oo, oi,
+                                     max_reads, max_bases, &mut n_out, &mut n_bases) })?;
+    Ok((n_out, n_bases))
+}
+
+/// Reorder, repeat and clip the reads of a batch (`kmx_reads_gather`): output read j is the clip of source read `d_index[j]` (u64; an
+/// index at or above `n_reads` gives an empty read), the span looked up by the source index.  Exactly `n_index` reads and
+/// `n_index + 1` offsets are written (`out.max_reads >= n_index`; `out.index` is not used).  `out = None` counts only.  Returns the
+/// bases written; Err(KMX_E_NOMEM) above `max_bases`, with nothing written.  A stable sort of labels gives the index that partitions
+/// a batch.  Synchronous.
+pub fn reads_gather(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>,
+                    d_index: &DeviceBuf<'_>, n_index: u64, spans: Option<ReadSpans<'_>>, out: Option<&ReadOutputs<'_>>) -> Result<u64, KmxError> {
+    let r = reads_of(d_reads, n_reads, read_len, d_read_offsets);
+    assert!(n_index as u128 * 8 <= d_index.len() as u128, "index shorter than n_index");
+    let (d_span, stride, span_k) = span_args(spans, n_reads);
+    let mut n_bases = 0u64;
+    let (ob, oo, max_bases) = match out {
+        None => (ptr::null_mut(), ptr::null_mut(), 0),
+        Some(o) => {
+            assert!(o.max_reads >= n_index, "room for fewer reads than the index holds");
+            assert!(o.max_bases as u128 <= o.bases.len() as u128 && (n_index as u128 + 1) * 8 <= o.offsets.len() as u128,
+                    "outputs shorter than n_index / max_bases");
+            (o.bases.as_mut_ptr::<u8>(), o.offsets.as_mut_ptr::<u64>(), o.max_bases)
+        }
+    };
+    ctx.ck(unsafe { kmx_reads_gather(ctx.0, &r, d_index.as_ptr::<u64>(), n_index, d_span, stride, span_k, ob, oo, max_bases, &mut n_bases) })?;
+    Ok(n_bases)
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -1099,6 +1099,51 @@ int kmx_fastx_parse(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint3
  * UINT32_MAX.  BUILD-DEFINED helper; synchronises the context's stream (the two values come back to the host). */
 int kmx_reads_length_range(kmx_ctx *ctx, const uint64_t *d_offsets, uint64_t n_reads, uint32_t *h_min_len, uint32_t *h_max_len);
 
+/* ---------------------------------------------------------------- a new batch of reads from an old one: select, trim, gather ----
+ * BUILD-DEFINED.  The per-read answers of the count family -- a median, a longest solid run, a colour, a component -- acted on: reads
+ * are kept or dropped, clipped to a span, reordered or repeated, and the result is a ragged batch again (bytes back to back, n + 1
+ * offsets starting at 0) that every call taking kmx_reads accepts.  Both calls take every layout of kmx_reads: uniform reads
+ * (d_offsets == NULL), ragged reads with d_offsets[0] > 0, any d_bases alignment, empty reads.
+ * THE SPAN OF A READ.  d_span == NULL: the whole read.  Otherwise the span word of SOURCE read r is w = d_span[r * span_stride]
+ * (span_stride: the u64 words between the span words of consecutive reads, >= 1; 0 with a non-NULL d_span is KMX_E_ARG), with
+ * start = w & 0xFFFFFFFF, len = w >> 32, and L the read's length:
+ *     span_k == 0:  len counts bases:                 keep [start, start + len) within [0, L)
+ *     span_k  > 0:  len counts windows of span_k bases, the packing of KMX_RS_SPAN and KMX_PATH_SPAN: len == 0 keeps nothing,
+ *                   otherwise keep [start, start + len + span_k - 1) within [0, L)
+ * All arithmetic is in 64 bits; start >= L keeps nothing: any bytes give one defined answer.  A source read of 2^31 bases or more
+ * counts as empty (L = 0), in line with the scans, which skip it; an offsets pair that descends likewise.
+ * With d_stats the rows of kmx_count_read_stats(2) for the same reads, (d_stats + KMX_RS_SPAN, KMX_RS_WORDS, k) trims every read to
+ * its longest run of solid windows without an array in between.
+ *
+ * kmx_reads_select.  Source read r is KEPT iff (d_keep == NULL or d_keep[r] != 0) and its clipped length is >= min_len; with
+ * min_len == 0 a kept read whose clip is empty stays in the batch as an empty read.  The clips of the kept reads are written back to
+ * back in source order to d_out_bases; d_out_offsets gets n_out + 1 words, the first 0, the last n_bases; d_out_index (optional) gets
+ * n_out words, the source index of every output read.  *h_n_reads / *h_n_bases (host) = n_out / n_bases, always.  Both of d_out_bases
+ * and d_out_offsets NULL = count only; exactly one of them NULL = KMX_E_ARG.  n_out > max_reads or n_bases > max_bases:
+ * KMX_E_NOMEM with nothing written and the counts set (d_out_offsets holds max_reads + 1 words, d_out_bases max_bases bytes,
+ * d_out_index max_reads words).  Not one byte of d_out_bases at or past n_bases is written, nor a word of the other two past
+ * what is stated here.  d_out_bases must not overlap the source reads: KMX_E_ARG where the host can tell (the bytes the batch spans
+ * against the n_bases bytes written).  n_reads == 0 is a no-op with both counts 0 (nothing is written).  n_reads up to 2^40.
+ *
+ * kmx_reads_gather.  Output read j, j < n_index, is the clip of source read d_index[j]; the span is looked up by the SOURCE index.
+ * Repeats are allowed; an index >= n_reads gives an empty read.  Exactly n_index output reads and n_index + 1 offsets are written,
+ * n_bases bytes of d_out_bases, *h_n_bases = n_bases; count only and KMX_E_NOMEM (n_bases > max_bases) as above.  n_index == 0 is a
+ * no-op with a count of 0.  n_index up to 2^32 (the sum of 2^32 clips of less than 2^31 bases fits 64 bits).  The primitive for
+ * reordering and partitioning: a stable sort of labels gives the index.
+ *
+ * Working set in the work buffer, laid out before any kernel runs, with m = n_reads (select) or n_index (gather):
+ * a256(8 * m) + a256(8 * (2 * ceil(m / 2048) + 4)) -- the source start of every output read (its length is the difference of its
+ * output offsets), and two partial sums per 2048 reads with the four words that come back to the host.  Above the cap
+ * (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM before any kernel runs, nothing written.  Deterministic: repeated calls give
+ * identical bytes.  NULL ctx / reads / host pointers, d_index NULL with n_index > 0: KMX_E_ARG.  Both calls are synchronous (the
+ * counts come back to the host; they return after the copy has finished). */
+int kmx_reads_select(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *d_keep, const uint64_t *d_span, uint64_t span_stride,
+                     uint32_t span_k, uint64_t min_len, uint8_t *d_out_bases, uint64_t *d_out_offsets, uint64_t *d_out_index,
+                     uint64_t max_reads, uint64_t max_bases, uint64_t *h_n_reads, uint64_t *h_n_bases);
+int kmx_reads_gather(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_index, uint64_t n_index, const uint64_t *d_span,
+                     uint64_t span_stride, uint32_t span_k, uint8_t *d_out_bases, uint64_t *d_out_offsets, uint64_t max_bases,
+                     uint64_t *h_n_bases);
+
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,
  * canonical_kmer_iterator.rs:72-83), so the scans need no collective.  What is exchanged is the optional bucket

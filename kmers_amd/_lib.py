@@ -164,6 +164,8 @@ SIGNATURES = {
     "kmx_count_unitig_components": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "kmx_count_link_support": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "kmx_count_adjacency_cut": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "kmx_reads_select": (_int, [_vp, _RP, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _u64, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_reads_gather": (_int, [_vp, _RP, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_setop2": (_int, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_compare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),

@@ -51,6 +51,21 @@ def read_stats_span(stats: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Te
     return start, torch.where(length > 0, start + length + (int(k) - 1), torch.zeros_like(start))
 
 
+def _u64_key(v: int) -> int:
+    """the int64 that orders like the u64 v (0 <= v < 2^64) once the sign bit is flipped"""
+    v = int(v) ^ (1 << 63)
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _u64_ge(t: torch.Tensor, v: int) -> torch.Tensor:
+    """t >= v with the int64 words of t read as u64"""
+    return (t ^ (-2**63)) >= _u64_key(v)
+
+
+def _u64_le(t: torch.Tensor, v: int) -> torch.Tensor:
+    return (t ^ (-2**63)) <= _u64_key(v)
+
+
 def _ratio(num: int, den: int) -> float:
     return num / den if den else 0.0
 
@@ -435,6 +450,53 @@ class ReadPaths:
         """int64[S]: the component id of every segment's unitig (-1 where the mask of count_unitig_components left the unitig
         out) -- a gather in torch.  Reads in different components share no unitig: the batch splits into independent jobs."""
         return comp.ids[self.unitig]
+
+    def read_components(self, comp: "UnitigComponents", n_reads: int):
+        """int64[n_reads]: per read the smallest component id over its segments, -1 for a read without a segment in a component
+        (no mapped window, or only unitigs the mask left out) -- a scatter_reduce(amin) in torch.  What Context.reads_partition
+        wants as labels: a read whose segments lie in one component goes to that component's group."""
+        big = torch.iinfo(torch.int64).max
+        ids = self.components(comp)
+        out = torch.full((int(n_reads),), big, dtype=torch.int64, device=self.segments.device)
+        out.scatter_reduce_(0, self.read, torch.where(ids >= 0, ids, torch.full_like(ids, big)), "amin", include_self=True)
+        return torch.where(out == big, torch.full_like(out, -1), out)
+
+
+@dataclasses.dataclass
+class ReadBatch:
+    """A ragged batch of reads on the device, what reads_select / reads_gather write: bases uint8[n_bases], offsets
+    int64[n_reads + 1] starting at 0, and -- where asked for -- index int64[n_reads], the source read of every read.  It goes
+    straight into any call as (b.bases, b.n_reads, b.max_len(), offsets=b.offsets).  `ctx` is the context that made it (for
+    max_len)."""
+    bases: "torch.Tensor"
+    offsets: "torch.Tensor"
+    n_reads: int
+    index: "torch.Tensor | None" = None
+    ctx: "Context | None" = dataclasses.field(default=None, repr=False, compare=False)
+
+    @property
+    def n_bases(self) -> int:
+        return int(self.bases.numel())
+
+    def max_len(self) -> int:
+        """the longest read (kmx_reads_length_range: one host round trip), the bound kmx_reads.read_len wants; 0 for no reads"""
+        if self.n_reads == 0:
+            return 0
+        return self.ctx.reads_length_range(self.offsets)[1]
+
+
+@dataclasses.dataclass
+class ReadGroups:
+    """What reads_partition returns: `batch` holds the reads of every non-negative label, grouped by label ascending and in source
+    order within a group (batch.index: the source reads); labels int64[G], the distinct labels; group_offsets int64[G + 1]: group g
+    is reads [group_offsets[g], group_offsets[g + 1]) of `batch`."""
+    batch: ReadBatch
+    labels: "torch.Tensor"
+    group_offsets: "torch.Tensor"
+
+    @property
+    def n_groups(self) -> int:
+        return int(self.labels.numel())
 
 
 def _on_ctx_stream(fn):
@@ -1624,6 +1686,115 @@ class Context:
         if n > 0 and mn == mx:
             return bases, n, mx, None
         return bases, n, mx, offsets
+
+    # ------------------------------------------------------------ a new batch of reads from an old one
+    @staticmethod
+    def _span_arg(span):
+        """span -> (tensor to keep alive, pointer, stride in words).  ONE form: a 1-D int64 tensor of span words, one per source
+        read, with any positive element stride -- so a column view such as stats[:, RS_SPAN] of the [n_reads, 8] stats tensor is
+        passed as it is, without a copy."""
+        if span is None:
+            return None, None, 0
+        if span.dtype != torch.int64 or span.dim() != 1 or not span.is_cuda:
+            raise ValueError("span: a 1-D int64 CUDA tensor of span words (a strided column view is fine)")
+        if span.numel() == 0:
+            return None, None, 0
+        stride = int(span.stride(0)) if span.numel() > 1 else 1
+        if stride < 1:
+            raise ValueError("span: the element stride must be positive")
+        return span, C.c_void_p(span.data_ptr()), stride
+
+    @_on_ctx_stream
+    def reads_select(self, bases, n_reads, read_len, keep=None, span=None, span_k=0, min_len=0, offsets=None, index=False) -> ReadBatch:
+        """kmx_reads_select -> ReadBatch: the reads with keep[r] != 0 (keep: uint8 or bool per read; None = all), each clipped to its
+        span, those whose clip is shorter than min_len dropped, back to back in source order.  `span`: a 1-D int64 tensor of span
+        words (start in the low 32 bits, length in the high 32), one per source read; it may be a strided view, so
+        stats[:, RS_SPAN] of count_read_stats is handed over without a copy.  span_k = 0: the length counts bases; span_k = k: it
+        counts windows of k bases (the packing of RS_SPAN and PATH_SPAN).  index=True also returns the source index of every output
+        read.  Sizing: one count-only call first, then the write into buffers of exactly that size (two host round trips, no
+        over-allocation)."""
+        n_reads = int(n_reads)
+        if keep is not None:
+            keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+            if keep.dtype != torch.uint8 or keep.numel() < n_reads:
+                raise ValueError("keep: one uint8 / bool per read")
+        span_t, span_p, stride = self._span_arg(span)
+        if span_t is not None and span_t.numel() < n_reads:
+            raise ValueError("span: one word per read")
+        r = self._reads(bases, n_reads, read_len, offsets)
+        nr, nb = C.c_uint64(0), C.c_uint64(0)
+        args = (self._h, C.byref(r), _ptr(keep) if keep is not None and n_reads else None, span_p, stride, int(span_k), int(min_len))
+        self._ck(self.lib.kmx_reads_select(*args, None, None, None, 0, 0, C.byref(nr), C.byref(nb)))
+        out = self.empty(max(nb.value, 1), torch.uint8)   # (a pointer also for a batch of empty reads)
+        off = torch.zeros(nr.value + 1, dtype=torch.int64, device=self.device)
+        idx = self.empty(nr.value, torch.int64) if index else None
+        if n_reads:
+            self._ck(self.lib.kmx_reads_select(*args, _ptr(out), _ptr(off),
+                                               _ptr(idx) if index and nr.value else None, nr.value, nb.value, C.byref(nr), C.byref(nb)))
+        return ReadBatch(out[:nb.value], off, int(nr.value), idx, self)
+
+    @_on_ctx_stream
+    def reads_gather(self, bases, n_reads, read_len, index, span=None, span_k=0, offsets=None) -> ReadBatch:
+        """kmx_reads_gather -> ReadBatch: output read j is the clip of source read index[j] (int64; repeats allowed, an index
+        outside [0, n_reads) gives an empty read); `span` / span_k as in reads_select, looked up by the source index.  Sizing: a
+        count-only call first, then the write into buffers of exactly that size."""
+        index = index.contiguous()
+        if index.dtype != torch.int64:
+            raise ValueError("index: int64")
+        n_index = int(index.numel())
+        span_t, span_p, stride = self._span_arg(span)
+        if span_t is not None and span_t.numel() < int(n_reads):
+            raise ValueError("span: one word per source read")
+        r = self._reads(bases, n_reads, read_len, offsets)
+        nb = C.c_uint64(0)
+        args = (self._h, C.byref(r), _ptr(index) if n_index else None, n_index, span_p, stride, int(span_k))
+        self._ck(self.lib.kmx_reads_gather(*args, None, None, 0, C.byref(nb)))
+        out = self.empty(max(nb.value, 1), torch.uint8)
+        off = torch.zeros(n_index + 1, dtype=torch.int64, device=self.device)
+        if n_index:
+            self._ck(self.lib.kmx_reads_gather(*args, _ptr(out), _ptr(off), nb.value, C.byref(nb)))
+        return ReadBatch(out[:nb.value], off, n_index, index, self)
+
+    @_on_ctx_stream
+    def reads_partition(self, bases, n_reads, read_len, labels, offsets=None) -> ReadGroups:
+        """The batch split by a label per read (int64[n_reads]; a negative label drops the read) -> ReadGroups: the reads grouped
+        by label ascending, source order within a group.  The stable sort of the labels and the group boundaries are torch; the
+        copy is ONE kmx_reads_gather over the sorted index.  What ReadPaths.read_components or a colour per read feed."""
+        labels = labels.reshape(-1)[:int(n_reads)].to(torch.int64)
+        order = torch.sort(labels, stable=True).indices
+        order = order[labels[order] >= 0]
+        distinct, counts = torch.unique_consecutive(labels[order], return_counts=True)
+        group_offsets = torch.zeros(distinct.numel() + 1, dtype=torch.int64, device=labels.device)
+        group_offsets[1:] = torch.cumsum(counts, 0)
+        batch = self.reads_gather(bases, n_reads, read_len, order, offsets=offsets)
+        return ReadGroups(batch, distinct, group_offsets)
+
+    def _select_reads(self, stats_fn, bases, n_reads, read_len, k, kmers, counts, solid_min, min_median, max_median, trim, min_len, offsets):
+        stats = stats_fn(bases, n_reads, read_len, k, kmers, counts, solid_min=solid_min, offsets=offsets)
+        med = stats[:, _lib.RS_MEDIAN]
+        keep = _u64_ge(med, int(min_median)) & _u64_le(med, int(max_median))
+        batch = self.reads_select(bases, n_reads, read_len, keep=keep, span=stats[:, RS_SPAN] if trim else None, span_k=int(k) if trim else 0,
+                                  min_len=int(k) if min_len is None else int(min_len), offsets=offsets, index=True)
+        return batch, stats
+
+    @_on_ctx_stream
+    def count_select_reads(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, min_median=0, max_median=2**64 - 1, trim=True,
+                           min_len=None, offsets=None):
+        """count_read_stats, then reads_select on its rows -> (ReadBatch with index, stats int64[n_reads, 8]): a read is kept iff
+        min_median <= its median abundance (RS_MEDIAN, as u64) <= max_median; with `trim` it is clipped to its longest run of
+        solid windows (RS_SPAN, windows of k bases); clips shorter than min_len (default k: one window) are dropped.  The abundance
+        cut is the ONE-SHOT, order-independent form of digital normalisation -- every read is judged against the table of the whole
+        batch -- not the streaming one, whose table grows with the reads it has kept.  The stats are those of the SOURCE reads.
+        Sizing as reads_select: count first, then exactly sized buffers."""
+        return self._select_reads(self.count_read_stats, bases, n_reads, read_len, k, kmers, counts, solid_min, min_median, max_median, trim, min_len,
+                                  offsets)
+
+    @_on_ctx_stream
+    def count_select_reads2(self, bases, n_reads, read_len, k, kmers, counts, solid_min=2, min_median=0, max_median=2**64 - 1, trim=True,
+                            min_len=None, offsets=None):
+        """count_select_reads for two-word keys (k 33..64; kmers int64[n, 2])."""
+        return self._select_reads(self.count_read_stats2, bases, n_reads, read_len, k, kmers, counts, solid_min, min_median, max_median, trim, min_len,
+                                  offsets)
 
     @_on_ctx_stream
     def reads_length_range(self, offsets: torch.Tensor) -> tuple[int, int]:

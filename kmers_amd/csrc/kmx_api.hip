@@ -1521,6 +1521,63 @@ int kmx_count_adjacency_cut(kmx_ctx* ctx, const uint8_t* d_edges, const uint8_t*
     return KMX_OK;
 }
 
+// ---- a new batch of reads from an old one (kmx_reads_edit.hip) ----
+// What kmx_reads_select and kmx_reads_gather share behind their argument checks (e.n_rows > 0): the work buffer, the plan's count,
+// the room and overlap checks, the emit.  n_out may be nullptr (gather: every row is an output read).
+static int reads_edit_impl(kmx_ctx* ctx, const char* who, const kmx::ReadsEdit& e, uint8_t* d_out_bases, uint64_t* d_out_offsets,
+                           uint64_t* d_out_index, uint64_t max_reads, uint64_t max_bases, uint64_t* h_n_reads, uint64_t* h_n_bases) {
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::reads_edit_bytes(e.n_rows), &area)) return st;
+    uint64_t h[4] = {0, 0, 0, 0};   // output reads, output bases, the batch's first and last offset
+    KMX_HIP(ctx, kmx::launch_reads_edit_count(e, area, ctx->h_pinned, h, ctx->stream));
+    if (h_n_reads) *h_n_reads = h[0];
+    *h_n_bases = h[1];
+    if (!d_out_bases) return KMX_OK;
+    if (int st = room_for(ctx, who, h[0], "reads kept", max_reads)) return st;
+    if (int st = room_for(ctx, who, h[1], "bases kept", max_bases)) return st;
+    if (h[1] >= (1ull << 44)) {   // (the copy is one grid of a block per 16 KiB)
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu bases in one batch", who, (unsigned long long)h[1]);
+        return KMX_E_NOMEM;
+    }
+    // the bytes the source batch spans against the bytes that are written
+    uintptr_t in_at = reinterpret_cast<uintptr_t>(e.bases);
+    uint64_t in_bytes = e.n_reads * (uint64_t)e.read_len;
+    if (e.offsets) {
+        in_at += h[2];
+        in_bytes = h[3] >= h[2] ? h[3] - h[2] : 0;
+    }
+    const uintptr_t out_at = reinterpret_cast<uintptr_t>(d_out_bases);
+    if (h[1] && in_bytes && in_at < out_at + h[1] && out_at < in_at + in_bytes) return KMX_E_ARG;
+    KMX_HIP(ctx, kmx::launch_reads_edit_emit(e, area, h[0], h[1], d_out_bases, d_out_offsets, d_out_index, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_reads_select(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_keep, const uint64_t* d_span, uint64_t span_stride, uint32_t span_k,
+                     uint64_t min_len, uint8_t* d_out_bases, uint64_t* d_out_offsets, uint64_t* d_out_index, uint64_t max_reads, uint64_t max_bases,
+                     uint64_t* h_n_reads, uint64_t* h_n_bases) {
+    if (!ctx || !reads_ok(reads) || !h_n_reads || !h_n_bases || ((d_out_bases == nullptr) != (d_out_offsets == nullptr))) return KMX_E_ARG;
+    if ((d_span && span_stride == 0) || reads->n_reads > (1ull << 40)) return KMX_E_ARG;
+    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+    *h_n_reads = *h_n_bases = 0;
+    if (reads->n_reads == 0) return KMX_OK;
+    const kmx::ReadsEdit e{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, d_keep, d_span, span_stride, span_k, min_len, nullptr,
+                           reads->n_reads};
+    return reads_edit_impl(ctx, "kmx_reads_select", e, d_out_bases, d_out_offsets, d_out_index, max_reads, max_bases, h_n_reads, h_n_bases);
+}
+
+int kmx_reads_gather(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_index, uint64_t n_index, const uint64_t* d_span, uint64_t span_stride,
+                     uint32_t span_k, uint8_t* d_out_bases, uint64_t* d_out_offsets, uint64_t max_bases, uint64_t* h_n_bases) {
+    if (!ctx || !reads_ok(reads) || !h_n_bases || ((d_out_bases == nullptr) != (d_out_offsets == nullptr))) return KMX_E_ARG;
+    if ((d_span && span_stride == 0) || reads->n_reads > (1ull << 40) || n_index > (1ull << 32) || (n_index && !d_index)) return KMX_E_ARG;
+    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+    *h_n_bases = 0;
+    if (n_index == 0) return KMX_OK;
+    const kmx::ReadsEdit e{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, nullptr, d_span, span_stride, span_k, 0u, d_index, n_index};
+    return reads_edit_impl(ctx, "kmx_reads_gather", e, d_out_bases, d_out_offsets, nullptr, n_index, max_bases, nullptr, h_n_bases);
+}
+
 // ---- set algebra and comparison of two count tables (kmx_count_setop.hip) ----
 // The checks the six calls share, and the work buffer for n_a + n_b > 0 entries (*area).
 static int setop_area(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, uint64_t n_a, const uint64_t* d_kmers_b, uint64_t n_b,

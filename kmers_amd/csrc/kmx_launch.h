@@ -223,6 +223,28 @@ hipError_t launch_count_link_support(const u64* segments, u64 n_segments, const 
 hipError_t launch_count_adjacency_cut(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, const u64* nodes, const u64* offsets,
                                       u64 n_unitigs, const u64* place, const u64* link_offsets, u64 n_links, const uint8_t* cut, uint8_t* edges_out,
                                       hipStream_t st);
+// kmx_reads_edit.hip: a new ragged batch from an old one (kmx_reads_select / kmx_reads_gather).  A ROW is a source read (select:
+// index == nullptr, n_rows == n_reads) or an entry of the index (gather).  The count plans every row in an area of
+// reads_edit_bytes(n_rows) and brings back h_out[0 .. 4) = output reads, output bases, the batch's first and last offset (0, 0 for
+// uniform reads): synchronous, one round trip.  The emit writes offsets, index (optional) and bytes from the same area (n_out,
+// n_bases: what the count returned); asynchronous.
+struct ReadsEdit {
+    const uint8_t* bases;
+    const u64* offsets;   // nullptr: uniform reads of read_len bases
+    u64 n_reads;
+    u32 read_len;
+    const uint8_t* keep;  // nullptr: every read
+    const u64* span;      // nullptr: the whole read
+    u64 span_stride;
+    u32 span_k;
+    u64 min_len;
+    const u64* index;     // gather: the source read of every row
+    u64 n_rows;
+};
+size_t reads_edit_bytes(u64 n_rows);
+hipError_t launch_reads_edit_count(const ReadsEdit& e, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+hipError_t launch_reads_edit_emit(const ReadsEdit& e, void* area, u64 n_out, u64 n_bases, uint8_t* out_bases, u64* out_offsets, u64* out_index,
+                                  hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
