@@ -1079,6 +1079,47 @@ pub fn reads_gather(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, rea
     Ok(n_bases)
 }
 
+/// The quality lines of a FASTQ image (`kmx_fastx_parse_quals`): `kmx_fastx_parse` with line 3 of every record in place of line 1.
+/// `d_text`: the image (16-byte aligned, `n_bytes` of it).  `out = None` counts only; otherwise `out.0` gets the quality bytes (room
+/// for `n_bytes` always suffices) and `out.1` `max_reads + 1` offsets.  `d_read_offsets` (what `kmx_fastx_parse` wrote for the same
+/// image) turns on the length check.  Returns (quality lines, bytes, first read whose two lines differ in length or `u64::MAX`);
+/// Err(KMX_E_NOMEM) above `max_reads`, Err(KMX_E_ARG) for a text that is not FASTQ.  Synchronous.
+pub fn fastx_parse_quals(ctx: &HipContext, d_text: &DeviceBuf<'_>, n_bytes: u64, format: u32, out: Option<(&DeviceBuf<'_>, &DeviceBuf<'_>)>,
+                         max_reads: u64, d_read_offsets: Option<&DeviceBuf<'_>>) -> Result<(u64, u64, u64), KmxError> {
+    assert!(n_bytes as u128 <= d_text.len() as u128, "text shorter than n_bytes");
+    let (dq, dqo) = match out {
+        None => (ptr::null_mut(), ptr::null_mut()),
+        Some((q, o)) => {
+            assert!((max_reads as u128 + 1) * 8 <= o.len() as u128, "offsets shorter than max_reads + 1");
+            (q.as_mut_ptr::<u8>(), o.as_mut_ptr::<u64>())
+        }
+    };
+    let (mut n_reads, mut n_out, mut bad) = (0u64, 0u64, u64::MAX);
+    let dro = d_read_offsets.map_or(ptr::null(), |o| o.as_ptr::<u64>());
+    ctx.ck(unsafe { kmx_fastx_parse_quals(ctx.0, d_text.as_ptr::<u8>(), n_bytes, format, dq, dqo, max_reads, dro, &mut n_reads, &mut n_out, &mut bad) })?;
+    Ok((n_reads, n_out, bad))
+}
+
+/// One pass over the bases and quality bytes of a batch (`kmx_reads_quality`; include/kmx.h has the words of a row and the trim
+/// span): `d_quals` is laid out as the reads are.  `d_masked` (may be `d_reads` itself: in place) gets the bases with every base of
+/// q < `min_q` turned into 'N'; `d_rows` gets `KMX_RQ_WORDS` u64 per read.  At least one of the two.  `d_weights`: 256 u64 indexed by
+/// the raw quality byte.  `ReadSpans { words: &d_rows, first_word: KMX_RQ_TRIM as u64, stride: KMX_RQ_WORDS as u64, k: 0 }` trims
+/// with `reads_select`.  Asynchronous on the context's stream.
+pub fn reads_quality(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>,
+                     d_quals: &DeviceBuf<'_>, phred_base: u32, min_q: u32, trim_q: u32, k: u32, d_weights: Option<&DeviceBuf<'_>>,
+                     d_masked: Option<&DeviceBuf<'_>>, d_rows: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    let r = reads_of(d_reads, n_reads, read_len, d_read_offsets);
+    if let Some(w) = d_weights {
+        assert!(w.len() >= 256 * 8, "weight table shorter than 256 words");
+    }
+    if let Some(rows) = d_rows {
+        assert!(n_reads as u128 * KMX_RQ_WORDS as u128 * 8 <= rows.len() as u128, "rows shorter than the batch's reads");
+    }
+    ctx.ck(unsafe { kmx_reads_quality(ctx.0, &r, d_quals.as_ptr::<u8>(), phred_base, min_q, trim_q, k,
+                                      d_weights.map_or(ptr::null(), |w| w.as_ptr::<u64>()), d_masked.map_or(ptr::null_mut(), |m| m.as_mut_ptr::<u8>()),
+                                      d_rows.map_or(ptr::null_mut(), |x| x.as_mut_ptr::<u64>())) })
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -1144,6 +1144,59 @@ int kmx_reads_gather(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_ind
                      uint64_t span_stride, uint32_t span_k, uint8_t *d_out_bases, uint64_t *d_out_offsets, uint64_t max_bases,
                      uint64_t *h_n_bases);
 
+/* ---------------------------------------------------------------- FASTQ qualities: parse, mask, trim, per-read rows ----
+ * BUILD-DEFINED.  kmx_fastx_parse keeps line 1 of every FASTQ record; the two calls here bring line 3 to the device and act on it.
+ *
+ * kmx_fastx_parse_quals.  The contract of kmx_fastx_parse(KMX_FASTX_FASTQ) with line i % 4 == 3 in place of line i % 4 == 1:
+ * d_quals = the quality lines back to back, d_qoffsets[r] = first byte of quality line r, d_qoffsets[n_reads] = n_bytes out.  Lines
+ * end at '\n'; every '\r' is dropped; the last line may lack its '\n'; a quality line may hold any other byte ('@' and '>' included:
+ * the records are four lines, whatever the lines hold).  A quality line exists as soon as it has a byte or its '\n': a text cut off
+ * before its last quality line has one quality line fewer than reads.  format: KMX_FASTX_AUTO or KMX_FASTX_FASTQ; KMX_FASTX_FASTA, or a
+ * text that does not begin with '@', gives KMX_E_ARG.  d_text 16-byte aligned; d_quals: room for the bytes (n_bytes always suffices);
+ * d_qoffsets: max_reads + 1 words.  d_quals == d_qoffsets == NULL: only the counts; n_reads > max_reads: KMX_E_NOMEM with nothing
+ * written and the counts set.  *h_n_reads / *h_n_bytes (host, optional) = quality lines / bytes kept.
+ * With d_read_offsets (what kmx_fastx_parse wrote for the same image: at least n_reads + 1 words) and h_first_mismatch both given, the
+ * lengths of the two offsets arrays are compared on the device: *h_first_mismatch = the smallest r whose quality line and sequence
+ * line differ in length, ~0 if there is none.  The status stays KMX_OK: what a mismatch means is the caller's business.
+ * KMX_FASTX_SAME_TEXT may be OR-ed into `format` under the contract stated at kmx_fastx_parse, where "the previous call" is either of
+ * the two parse calls: the chunk summaries of pass 1 serve both, so reads and qualities of one image cost one summarising pass less,
+ * and a count-then-emit pair of this call reuses the count whole.  Synchronous. */
+int kmx_fastx_parse_quals(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t format, uint8_t *d_quals,
+                          uint64_t *d_qoffsets, uint64_t max_reads, const uint64_t *d_read_offsets, uint64_t *h_n_reads,
+                          uint64_t *h_n_bytes, uint64_t *h_first_mismatch);
+
+/* kmx_reads_quality.  One pass over the bases and the quality bytes of a batch.  d_quals is laid out as the reads are: the quality
+ * byte of base i of read r is d_quals[d_offsets[r] + i] (uniform reads: d_quals[r * read_len + i]).  Every layout kmx_reads_select
+ * takes is taken: uniform and ragged reads, d_offsets[0] > 0, empty reads, any alignment of d_bases, and any alignment of d_quals
+ * independently.  A read of 2^31 bases or more, or an offsets pair that descends, counts as empty.
+ *     q = byte >= phred_base ? byte - phred_base : 0          a base is GOOD iff it is one of ACGTacgt and q >= min_q
+ * d_masked (optional): same layout, same offsets; a base with q < min_q becomes 'N', every other byte is copied as it is -- so every
+ * k-mer call skips the windows over a low base.  d_masked == d_bases (in place) is allowed; any other overlap of d_masked with the
+ * bases, and any with the quality bytes, is KMX_E_ARG where the host can tell (the bytes the batch spans; ragged reads: one round
+ * trip for its first and last offset).  Not one byte outside the bytes of the reads is written, and no load touches an aligned dword
+ * that holds no byte of the batch.
+ * d_rows (optional): KMX_RQ_WORDS u64 per read, the words below.  At least one of d_masked and d_rows must be given.
+ * THE TRIM SPAN (Mott / BWA).  s_i = q_i - trim_q (signed), P_0 = 0, P_{i+1} = P_i + s_i, V = max over 0 <= a <= b <= L of P_b - P_a.
+ * V == 0: the word is 0.  Otherwise b* = the smallest b with max_{a <= b}(P_b - P_a) = V, a* = the largest a < b* with
+ * P_b* - P_a = V, and the word is a* | (b* - a*) << 32: the first and the last base of the span both have q > trim_q.  All sums are
+ * 64-bit.  KMX_RQ_TRIM and KMX_RQ_RUN are span words in bases: kmx_reads_select takes (d_rows + KMX_RQ_TRIM, KMX_RQ_WORDS, 0).
+ * d_weights (optional): 256 device words, indexed by the RAW quality byte; with a table of round(2^32 * 10^(-q / 10)) KMX_RQ_WEIGHT is
+ * the read's expected errors in exact integer arithmetic.
+ * phred_base, min_q or trim_q above 255, d_quals NULL with bases present, both outputs NULL, NULL ctx / reads: KMX_E_ARG.  n_reads
+ * up to 2^40; n_reads == 0 is a no-op.  Deterministic (no atomics: a row is written by the one wave that owns its read).
+ * Asynchronous on the context's stream (ragged reads with d_masked: after the one round trip above). */
+#define KMX_RQ_WORDS 8u
+#define KMX_RQ_BASES 0u   /* L */
+#define KMX_RQ_LOW 1u     /* bases with q < min_q */
+#define KMX_RQ_QSUM 2u    /* sum of q */
+#define KMX_RQ_WEIGHT 3u  /* sum of d_weights[byte] over the raw quality bytes, wrapping mod 2^64; 0 when d_weights == NULL */
+#define KMX_RQ_MINMAX 4u  /* min q | max q << 32; 0 for an empty read */
+#define KMX_RQ_TRIM 5u    /* the trim span: start | len << 32, in bases; 0 when V == 0 */
+#define KMX_RQ_RUN 6u     /* the longest run of GOOD bases: start | len << 32, of equal runs the leftmost; 0 when there is none */
+#define KMX_RQ_WINDOWS 7u /* windows of k bases that are all GOOD (what a k-mer call yields on the masked read); 0 for k == 0 */
+int kmx_reads_quality(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *d_quals, uint32_t phred_base, uint32_t min_q,
+                      uint32_t trim_q, uint32_t k, const uint64_t *d_weights, uint8_t *d_masked, uint64_t *d_rows);
+
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,
  * canonical_kmer_iterator.rs:72-83), so the scans need no collective.  What is exchanged is the optional bucket

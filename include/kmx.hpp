@@ -433,6 +433,48 @@ class FastxReads {
     uint32_t min_len_ = 0, max_len_ = 0;
 };
 
+// FASTQ with its quality lines (kmx.h, "FASTQ qualities"): the reads as FastxReads holds them and the quality bytes in the same
+// layout (the read offsets serve both; a record whose two lines differ in length throws).  quality() is kmx_reads_quality: the eight
+// KMX_RQ_* words of every read on the host and, with mask = true, every base of q < min_q turned into 'N' in place -- what the
+// k-mer calls then skip.
+class FastqReads {
+  public:
+    explicit FastqReads(const std::string& text, Context& ctx = Context::instance()) : ctx_(&ctx), reads_(text, ctx, KMX_FASTX_FASTQ) {
+        DeviceBuffer<uint8_t> d(ctx, text.size() ? text.size() : 1);
+        if (!text.empty()) d.upload(reinterpret_cast<const uint8_t*>(text.data()), text.size());
+        uint64_t nr = 0, nb = 0, bad = ~0ull;
+        ctx.check(kmx_fastx_parse_quals(ctx.get(), d.data(), text.size(), KMX_FASTX_FASTQ, nullptr, nullptr, 0, nullptr, &nr, &nb, nullptr),
+                  "fastx_parse_quals (count)");
+        if (nr != reads_.len()) throw std::runtime_error("FastqReads: the text ends inside a record");
+        quals_.reset(new DeviceBuffer<uint8_t>(ctx, nb ? nb : 1));
+        DeviceBuffer<uint64_t> qoff(ctx, nr + 1);
+        ctx.check(kmx_fastx_parse_quals(ctx.get(), d.data(), text.size(), KMX_FASTX_FASTQ | KMX_FASTX_SAME_TEXT, quals_->data(), qoff.data(), nr,
+                                        reads_.reads().d_offsets, &nr, &nb, &bad),
+                  "fastx_parse_quals");
+        if (bad != ~0ull) throw std::runtime_error("FastqReads: read " + std::to_string(bad) + ": quality and sequence lines differ in length");
+    }
+    const FastxReads& reads() const { return reads_; }
+    const uint8_t* d_quals() const { return quals_->data(); }
+    std::vector<uint8_t> quals() const { return quals_->download(); }
+    // KMX_RQ_WORDS u64 per read; d_weights: 256 device words by the raw quality byte, or nullptr
+    std::vector<uint64_t> quality(uint32_t min_q, uint32_t trim_q, uint32_t k, bool mask = false, uint32_t phred_base = 33,
+                                  const uint64_t* d_weights = nullptr) {
+        DeviceBuffer<uint64_t> rows(*ctx_, reads_.len() * KMX_RQ_WORDS + 1);
+        const kmx_reads r = reads_.reads(reads_.max_len());
+        ctx_->check(kmx_reads_quality(ctx_->get(), &r, quals_->data(), phred_base, min_q, trim_q, k, d_weights,
+                                      mask ? const_cast<uint8_t*>(r.d_bases) : nullptr, rows.data()),
+                    "reads_quality");
+        auto out = rows.download();   // (synchronises)
+        out.resize(reads_.len() * KMX_RQ_WORDS);
+        return out;
+    }
+
+  private:
+    Context* ctx_;
+    FastxReads reads_;
+    std::unique_ptr<DeviceBuffer<uint8_t>> quals_;
+};
+
 // src/naive_impl/seq_vector.rs: the 2-bit packed sequence container, resident on the device.
 class SeqVector {
   public:

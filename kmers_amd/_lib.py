@@ -52,6 +52,9 @@ COMP_WORDS = 4
 # kmx_count_link_support: the words of the summary (KMX_LS_*)
 LS_JUNCTIONS, LS_CROSSED, LS_UNLINKED = range(3)
 LS_WORDS = 3
+# kmx_reads_quality: the words of a read's row (KMX_RQ_*)
+RQ_BASES, RQ_LOW, RQ_QSUM, RQ_WEIGHT, RQ_MINMAX, RQ_TRIM, RQ_RUN, RQ_WINDOWS = range(8)
+RQ_WORDS = 8
 
 
 class KmxError(RuntimeError):
@@ -174,6 +177,8 @@ SIGNATURES = {
     "kmx_seqvec_minimizers_sip13": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _u64, _u64, _vp, _vp]),
     "kmx_minimizers_sip13": (_int, [_vp, _RP, _vp, _u32, _u32, _u64, _u64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "kmx_fastx_parse": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_fastx_parse_quals": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_reads_quality": (_int, [_vp, _RP, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "kmx_sub_kmer_words": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp]),
     "kmx_kmers_to_strings": (_int, [_vp, _vp, _u64, _u32, _vp]),
     "kmx_bitmers_to_bytes": (_int, [_vp, _vp, _u64, _u32, _vp]),

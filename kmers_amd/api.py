@@ -462,6 +462,20 @@ class ReadPaths:
         return torch.where(out == big, torch.full_like(out, -1), out)
 
 
+def ee_weights(phred: int = 33) -> np.ndarray:
+    """The default weight table of reads_quality: 256 words by the RAW quality byte, round(2^32 * 10^(-q / 10)) with
+    q = max(byte - phred, 0) -- expected errors as exact integer sums."""
+    q = np.maximum(np.arange(256, dtype=np.int64) - int(phred), 0)
+    return np.round(2.0**32 * 10.0 ** (-q / 10.0)).astype(np.uint64)
+
+
+def expected_errors(rows):
+    """float64[n_reads]: RQ_WEIGHT of reads_quality's rows (weights "ee") as expected errors; the word is a u64, so the top bit
+    is added back"""
+    w = rows[:, _lib.RQ_WEIGHT]
+    return (w & 0x7FFFFFFFFFFFFFFF).to(torch.float64) / 2.0**32 + (w < 0).to(torch.float64) * 2.0**31
+
+
 @dataclasses.dataclass
 class ReadBatch:
     """A ragged batch of reads on the device, what reads_select / reads_gather write: bases uint8[n_bases], offsets
@@ -1686,6 +1700,95 @@ class Context:
         if n > 0 and mn == mx:
             return bases, n, mx, None
         return bases, n, mx, offsets
+
+    @_on_ctx_stream
+    def fastx_quals(self, text: torch.Tensor, read_offsets: torch.Tensor | None = None, same_text: bool = False):
+        """kmx_fastx_parse_quals: FASTQ file image -> (quals uint8[n_bytes], qoffsets int64[n + 1]), the quality lines as fastx_parse
+        gives the reads.  Two calls: the counts, then the emit into exactly sized buffers.  same_text=True: the caller vouches that
+        the last parse call on this context was on this very image, unchanged (KMX_FASTX_SAME_TEXT: the text is not summarised
+        again; fastq_reads does this).  With `read_offsets` (what fastx_parse returned for the image) the lengths
+        are compared on the device: ValueError naming the first read whose quality line and sequence line differ in length, or
+        the counts where the image ends inside a record."""
+        n = int(text.numel())
+        nr, nb, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(2**64 - 1)
+        tp = _ptr(text) if n else None
+        fmt = _lib.FASTX_FASTQ | _lib.FASTX_SAME_TEXT
+        self._ck(self.lib.kmx_fastx_parse_quals(self._h, tp, n, fmt if same_text else _lib.FASTX_FASTQ, None, None, 0, None, C.byref(nr),
+                                                C.byref(nb), None))
+        if read_offsets is not None and int(read_offsets.numel()) - 1 != nr.value:
+            raise ValueError(f"fastx_quals: {nr.value} quality lines for {int(read_offsets.numel()) - 1} reads (the image ends inside a record)")
+        quals = self.empty(max(nb.value, 1), torch.uint8)
+        qoffsets = self.empty(nr.value + 1, torch.int64)
+        self._ck(self.lib.kmx_fastx_parse_quals(self._h, tp, n, fmt, _ptr(quals), _ptr(qoffsets), nr.value,
+                                                _ptr(read_offsets) if read_offsets is not None else None, C.byref(nr), C.byref(nb),
+                                                C.byref(bad) if read_offsets is not None else None))
+        if bad.value != 2**64 - 1:
+            raise ValueError(f"fastx_quals: read {bad.value}: its quality line and its sequence line differ in length")
+        return quals[:nb.value], qoffsets
+
+    def fastq_reads(self, text: torch.Tensor):
+        """FASTQ file image -> (bases, quals, n_reads, read_len, offsets): fastx_reads with the quality bytes, laid out as the bases
+        are (the same offsets serve both; ValueError where a record's two lines differ in length)"""
+        bases, offsets = self.fastx_parse(text, _lib.FASTX_FASTQ)
+        quals, _ = self.fastx_quals(text, offsets, same_text=True)
+        n = int(offsets.numel()) - 1
+        mn, mx = self.reads_length_range(offsets)
+        if n > 0 and mn == mx:
+            return bases, quals, n, mx, None
+        return bases, quals, n, mx, offsets
+
+    # ------------------------------------------------------------ quality bytes acted on
+    def _weights_arg(self, weights, phred):
+        if weights is None:
+            return None
+        if isinstance(weights, str):
+            if weights != "ee":
+                raise ValueError('weights: None, "ee" or an int64 tensor of 256 words')
+            return self.to_device(ee_weights(phred))
+        if weights.dtype != torch.int64 or weights.numel() != 256 or not weights.is_cuda:
+            raise ValueError("weights: an int64 CUDA tensor of 256 words, indexed by the raw quality byte")
+        return weights.contiguous()
+
+    @_on_ctx_stream
+    def reads_quality(self, bases, quals, n_reads, read_len, min_q=0, trim_q=0, k=0, phred=33, weights=None, offsets=None, mask=True, out=None):
+        """kmx_reads_quality -> (masked, rows): masked = the bases with every base of q < min_q turned into 'N' (same layout, same
+        offsets; None with mask=False; out=bases masks in place), rows int64[n_reads, RQ_WORDS] (viewable as u64; include/kmx.h has
+        the words).  weights: None, "ee" (round(2^32 * 10^(-q / 10)): RQ_WEIGHT / 2^32 is the read's expected errors, see
+        expected_errors) or an int64 tensor of 256 words indexed by the raw quality byte."""
+        n_reads = int(n_reads)
+        w = self._weights_arg(weights, int(phred))
+        masked = None
+        if mask:
+            masked = out if out is not None else torch.empty_like(bases)
+            if masked.dtype != torch.uint8 or masked.numel() < bases.numel():
+                raise ValueError("out: a uint8 tensor as large as bases")
+        rows = self.empty(_lib.RQ_WORDS * n_reads, torch.int64)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_reads_quality(self._h, C.byref(r), _ptr(quals) if quals is not None and quals.numel() else None, int(phred), int(min_q),
+                                            int(trim_q), int(k), _ptr(w) if w is not None else None,
+                                            _ptr(masked) if masked is not None and masked.numel() else None, _ptr(rows) if n_reads else None))
+        return masked, rows.view(-1, _lib.RQ_WORDS)
+
+    @_on_ctx_stream
+    def reads_quality_filter(self, bases, quals, n_reads, read_len, min_q=0, trim_q=0, k=0, phred=33, weights=None, offsets=None, max_ee=None,
+                             min_len=0, trim="mott"):
+        """reads_quality, then reads_select on its rows -> (ReadBatch of the bases, ReadBatch of the quality bytes, rows of the SOURCE
+        reads).  trim = "mott" clips every read to its RQ_TRIM span, "run" to its longest run of good bases (RQ_RUN), None keeps it
+        whole; max_ee drops the reads whose expected errors (weights "ee" unless a table is given) exceed it; clips shorter than
+        min_len are dropped.  The bases that are kept are the MASKED ones.  One keep tensor and one span column (a strided view of
+        the rows) go into two reads_select calls, so the two batches have identical offsets."""
+        if trim not in ("mott", "run", None):
+            raise ValueError('trim: "mott", "run" or None')
+        if max_ee is not None and weights is None:
+            weights = "ee"
+        masked, rows = self.reads_quality(bases, quals, n_reads, read_len, min_q, trim_q, k, phred, weights, offsets)
+        keep = None
+        if max_ee is not None:
+            keep = expected_errors(rows) <= float(max_ee)
+        span = None if trim is None else rows[:, _lib.RQ_TRIM if trim == "mott" else _lib.RQ_RUN]
+        b = self.reads_select(masked, n_reads, read_len, keep=keep, span=span, span_k=0, min_len=min_len, offsets=offsets, index=True)
+        q = self.reads_select(quals, n_reads, read_len, keep=keep, span=span, span_k=0, min_len=min_len, offsets=offsets)
+        return b, q, rows
 
     # ------------------------------------------------------------ a new batch of reads from an old one
     @staticmethod

@@ -2285,7 +2285,7 @@ int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint3
         return KMX_OK;
     }
     // (the emit call of a counts-then-emit pair: the counting call looked at the first byte and settled the format)
-    const bool reuse = same_text && ctx->fx_valid && ctx->fx_text == d_text && ctx->fx_bytes == n_bytes &&
+    const bool reuse = same_text && ctx->fx_valid && ctx->fx_entry == 0u && ctx->fx_text == d_text && ctx->fx_bytes == n_bytes &&
                        (format == KMX_FASTX_AUTO || ctx->fx_fasta == (format == KMX_FASTX_FASTA ? 1u : 0u));
     if (reuse) {
         format = ctx->fx_fasta ? KMX_FASTX_FASTA : KMX_FASTX_FASTQ;
@@ -2316,6 +2316,7 @@ int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint3
         ctx->fx_text = d_text;
         ctx->fx_bytes = n_bytes;
         ctx->fx_fasta = fasta ? 1u : 0u;
+        ctx->fx_entry = 0u;
         ctx->fx_totals[0] = totals[0];
         ctx->fx_totals[1] = totals[1];
         ctx->fx_valid = true;
@@ -2330,6 +2331,110 @@ int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint3
     }
     KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, fasta, scratch, d_totals, d_bases, d_offsets, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+// kmx_fastx_parse with the FASTQ machine entered on line 2: passes 2 and 3 select line 3 of every record (kmx_fastx.hip).  What the
+// context remembers of a count (fx_*) is shared with kmx_fastx_parse: the chunk summaries of pass 1 do not depend on the entry line,
+// the chunk prefixes and totals of pass 2 do (fx_entry).
+int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_quals, uint64_t* d_qoffsets,
+                          uint64_t max_reads, const uint64_t* d_read_offsets, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_first_mismatch) {
+    const bool same_text = (format & KMX_FASTX_SAME_TEXT) != 0u;
+    format &= ~KMX_FASTX_SAME_TEXT;
+    if (!ctx || format > KMX_FASTX_FASTQ || (n_bytes && !d_text) || (!d_quals != !d_qoffsets)) return KMX_E_ARG;
+    if (!aligned16(d_text)) return KMX_E_ARG;
+    if (h_n_reads) *h_n_reads = 0;
+    if (h_n_bytes) *h_n_bytes = 0;
+    if (h_first_mismatch) *h_first_mismatch = ~0ull;
+    DeviceGuard g(ctx->device);
+    if (n_bytes == 0) {
+        if (d_qoffsets) {
+            KMX_HIP(ctx, hipMemsetAsync(d_qoffsets, 0, 8, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return KMX_OK;
+    }
+    const bool known = same_text && ctx->fx_valid && ctx->fx_text == d_text && ctx->fx_bytes == n_bytes && ctx->fx_fasta == 0u;
+    if (!known) {
+        uint8_t first = 0;
+        KMX_HIP(ctx, hipMemcpyAsync(&first, d_text, 1, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (first != '@') {
+            std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_fastx_parse_quals: the text starts with byte 0x%02x, not with '@' (FASTQ)", first);
+            return KMX_E_ARG;
+        }
+    }
+    void* scratch = big_scratch(ctx, kmx::fastx_scratch_bytes(n_bytes));
+    if (!scratch) return KMX_E_NOMEM;
+    unsigned long long* d_totals = ctx->d_scratch + KMX_S_FASTX_TOTALS;
+    unsigned long long totals[2] = {0, 0};
+    const bool summaries = known && scratch == ctx->d_big;   // pass 1 of an earlier count of this text is still in the work buffer
+    if (summaries && ctx->fx_entry == 2u) {
+        totals[0] = ctx->fx_totals[0];
+        totals[1] = ctx->fx_totals[1];
+    } else {
+        ctx->fx_valid = false;
+        KMX_HIP(ctx, kmx::launch_fastx_count(d_text, n_bytes, false, scratch, d_totals, ctx->stream, 2u, !summaries));
+        KMX_HIP(ctx, hipMemcpyAsync(totals, d_totals, 16, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->fx_text = d_text;
+        ctx->fx_bytes = n_bytes;
+        ctx->fx_fasta = 0u;
+        ctx->fx_entry = 2u;
+        ctx->fx_totals[0] = totals[0];
+        ctx->fx_totals[1] = totals[1];
+        ctx->fx_valid = true;
+    }
+    if (h_n_reads) *h_n_reads = totals[0];
+    if (h_n_bytes) *h_n_bytes = totals[1];
+    if (!d_quals) return KMX_OK;
+    if (totals[0] > max_reads) {
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_fastx_parse_quals: %llu quality lines, room for %llu", totals[0],
+                      (unsigned long long)max_reads);
+        return KMX_E_NOMEM;
+    }
+    KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, false, scratch, d_totals, d_quals, d_qoffsets, ctx->stream));
+    if (d_read_offsets && h_first_mismatch && totals[0]) {
+        KMX_HIP(ctx, first_bad_reset(ctx));
+        KMX_HIP(ctx, kmx::launch_fastx_length_mismatch(d_qoffsets, d_read_offsets, totals[0], first_bad_of(ctx), ctx->n_cu, ctx->stream));
+        if (int st = first_bad_read(ctx, ctx->h_pinned + KMX_PIN_READ)) return st;
+        *h_first_mismatch = ctx->h_pinned[KMX_PIN_READ];
+        return KMX_OK;
+    }
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+// ---- the quality bytes of a batch acted on (kmx_reads_quality.hip) ----
+int kmx_reads_quality(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_quals, uint32_t phred_base, uint32_t min_q, uint32_t trim_q, uint32_t k,
+                      const uint64_t* d_weights, uint8_t* d_masked, uint64_t* d_rows) {
+    if (!ctx || !reads_ok(reads) || phred_base > 255u || min_q > 255u || trim_q > 255u || (!d_masked && !d_rows)) return KMX_E_ARG;
+    if (reads->n_reads > (1ull << 40)) return KMX_E_ARG;
+    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    const bool bytes = reads->d_offsets || reads->read_len;   // (uniform reads of no bases: rows of zeros, nothing is read)
+    if (bytes && !d_quals) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    if (bytes && d_masked) {
+        // the bytes the batch spans (ragged: its first and last offset, one round trip) against the bytes that are written; the
+        // quality bytes are read on another dword grid than the bases, so they must not be written over either
+        uint64_t lo = 0, hi = reads->n_reads * (uint64_t)reads->read_len;
+        if (reads->d_offsets) {
+            unsigned long long* h = ctx->h_pinned;
+            KMX_HIP(ctx, hipMemcpyAsync(h, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipMemcpyAsync(h + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            lo = h[0];
+            hi = h[1] >= h[0] ? h[1] : h[0];
+        }
+        const uintptr_t m0 = reinterpret_cast<uintptr_t>(d_masked) + lo, m1 = reinterpret_cast<uintptr_t>(d_masked) + hi;
+        const uintptr_t b0 = reinterpret_cast<uintptr_t>(reads->d_bases) + lo, b1 = reinterpret_cast<uintptr_t>(reads->d_bases) + hi;
+        const uintptr_t q0 = reinterpret_cast<uintptr_t>(d_quals) + lo, q1 = reinterpret_cast<uintptr_t>(d_quals) + hi;
+        if (d_masked != reads->d_bases && m0 < b1 && b0 < m1) return KMX_E_ARG;
+        if (m0 < q1 && q0 < m1) return KMX_E_ARG;
+    }
+    KMX_HIP(ctx, kmx::launch_reads_quality(reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, d_quals, phred_base, min_q, trim_q, k,
+                                           d_weights, d_masked, d_rows, ctx->n_cu, ctx->stream));
     return KMX_OK;
 }
 

@@ -478,14 +478,15 @@ fastx_scan_blocks_kernel(const u32* __restrict__ summ, u64 n_chunks, u32* __rest
 template <bool FASTA>
 __global__ void __launch_bounds__(FX_SCAN_THREADS)
 fastx_scan_chunks_kernel(const u32* __restrict__ summ, u64 n_chunks, const u32* __restrict__ block_agg, u64* __restrict__ prefix,
-                         unsigned long long* __restrict__ totals) {
+                         unsigned long long* __restrict__ totals, u32 entry) {
     __shared__ u32 tmp32[FX_SCAN_THREADS / 64];
     __shared__ u32 wave_last[FX_SCAN_THREADS / 64];
     __shared__ u32 ags[FX_SCAN_THREADS][9];
     __shared__ u64 sh_entry[3];
     // ---- where the block begins: the aggregates of the blocks before it, composed in order (the text starts with a header line
-    // ('>' checked by the host) / on line 0; FASTA: record 0 opens at byte 0, no newline announces it)
-    u64 state = FASTA ? T_HDR : 0, out_pos = 0, rec = FASTA ? 1 : 0;
+    // ('>' checked by the host) / on line `entry`: 0 for the reads; 2 makes line 3 of every record "the read" and the newline that
+    // ends the '+' line "a record opens" -- the quality lines; FASTA: record 0 opens at byte 0, no newline announces it)
+    u64 state = FASTA ? T_HDR : entry, out_pos = 0, rec = FASTA ? 1 : 0;
     for (u64 base = 0; base < blockIdx.x; base += FX_SCAN_THREADS) {
         const u64 bb = base + threadIdx.x;
         __syncthreads();
@@ -657,27 +658,44 @@ __global__ void fastx_last_offset_kernel(const unsigned long long* __restrict__ 
     offsets[totals[0]] = totals[1];
 }
 
+// first_bad (~0 before) = the smallest read whose length differs between the two offsets arrays
+__global__ void __launch_bounds__(FX_THREADS) fastx_length_mismatch_kernel(const u64* __restrict__ a, const u64* __restrict__ b, u64 n_reads,
+                                                                           unsigned long long* __restrict__ first_bad) {
+    const u64 stride = (u64)gridDim.x * FX_THREADS;
+    for (u64 r = (u64)blockIdx.x * FX_THREADS + threadIdx.x; r < n_reads; r += stride)
+        if (a[r + 1u] - a[r] != b[r + 1u] - b[r]) atomicMin(first_bad, (unsigned long long)r);
+}
+
+hipError_t launch_fastx_length_mismatch(const u64* a, const u64* b, u64 n_reads, unsigned long long* first_bad, int n_cu, hipStream_t st) {
+    const u64 want = (n_reads + FX_THREADS - 1u) / FX_THREADS, cap = (u64)(n_cu > 0 ? n_cu : 256) * 8u;
+    hipLaunchKernelGGL(fastx_length_mismatch_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(FX_THREADS), 0, st, a, b, n_reads, first_bad);
+    return hipGetLastError();
+}
+
 size_t fastx_scratch_bytes(u64 n_bytes) {
     const u64 n_chunks = (n_bytes + FX_CHUNK - 1u) / FX_CHUNK;
     const u64 n_blocks = (n_chunks + FX_SCAN_THREADS - 1u) / FX_SCAN_THREADS;
     return (size_t)(n_chunks * (FX_SUM_WORDS * 4u + FX_PFX_WORDS * 8u) + n_blocks * FX_AGG_WORDS * 4u + 64u);
 }
 
-// counts: passes 1 and 2; totals (device) receives {n_reads, n_bases}
-hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st) {
+// counts: passes 1 and 2; totals (device) receives {n_reads, n_bases}.  entry (FASTQ): the line number the text is taken to begin on,
+// 0 = the reads, 2 = the quality lines; summarise == false: the chunk summaries of an earlier count of the same text are still in
+// `scratch`, only pass 2 runs
+hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st, u32 entry,
+                              bool summarise) {
     const u64 n_chunks = (n + FX_CHUNK - 1u) / FX_CHUNK;
     const u64 n_blocks = (n_chunks + FX_SCAN_THREADS - 1u) / FX_SCAN_THREADS;
     u64* prefix = static_cast<u64*>(scratch);
     u32* summ = reinterpret_cast<u32*>(prefix + n_chunks * FX_PFX_WORDS);
     u32* agg = summ + n_chunks * FX_SUM_WORDS;
     if (fasta) {
-        hipLaunchKernelGGL(fastx_summarise_kernel<true>, dim3((unsigned)n_chunks), dim3(FX_THREADS), 0, st, text, n, summ);
+        if (summarise) hipLaunchKernelGGL(fastx_summarise_kernel<true>, dim3((unsigned)n_chunks), dim3(FX_THREADS), 0, st, text, n, summ);
         hipLaunchKernelGGL(fastx_scan_blocks_kernel<true>, dim3((unsigned)n_blocks), dim3(FX_SCAN_THREADS), 0, st, summ, n_chunks, agg);
-        hipLaunchKernelGGL(fastx_scan_chunks_kernel<true>, dim3((unsigned)n_blocks), dim3(FX_SCAN_THREADS), 0, st, summ, n_chunks, agg, prefix, totals);
+        hipLaunchKernelGGL(fastx_scan_chunks_kernel<true>, dim3((unsigned)n_blocks), dim3(FX_SCAN_THREADS), 0, st, summ, n_chunks, agg, prefix, totals, entry);
     } else {
-        hipLaunchKernelGGL(fastx_summarise_kernel<false>, dim3((unsigned)n_chunks), dim3(FX_THREADS), 0, st, text, n, summ);
+        if (summarise) hipLaunchKernelGGL(fastx_summarise_kernel<false>, dim3((unsigned)n_chunks), dim3(FX_THREADS), 0, st, text, n, summ);
         hipLaunchKernelGGL(fastx_scan_blocks_kernel<false>, dim3((unsigned)n_blocks), dim3(FX_SCAN_THREADS), 0, st, summ, n_chunks, agg);
-        hipLaunchKernelGGL(fastx_scan_chunks_kernel<false>, dim3((unsigned)n_blocks), dim3(FX_SCAN_THREADS), 0, st, summ, n_chunks, agg, prefix, totals);
+        hipLaunchKernelGGL(fastx_scan_chunks_kernel<false>, dim3((unsigned)n_blocks), dim3(FX_SCAN_THREADS), 0, st, summ, n_chunks, agg, prefix, totals, entry);
     }
     return hipGetLastError();
 }

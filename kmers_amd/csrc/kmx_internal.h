@@ -31,6 +31,7 @@ struct kmx_ctx {
     const uint8_t* fx_text;
     uint64_t fx_bytes;
     uint32_t fx_fasta;
+    uint32_t fx_entry;              // the line the chunk prefixes and totals were placed for: 0 = the reads, 2 = the quality lines (kmx_fastx_parse_quals)
     bool fx_valid;
     unsigned long long fx_totals[2];
     char last_error[256];

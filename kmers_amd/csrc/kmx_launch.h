@@ -59,7 +59,9 @@ hipError_t launch_segments_build(const u64* offsets, u64 n_reads, u32 k, u32 t_m
                                  hipStream_t stream, const u64* win_offsets = nullptr, const u64** wins_out = nullptr);
 // kmx_fastx.hip
 size_t fastx_scratch_bytes(u64 n_bytes);
-hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st);
+hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st, u32 entry = 0u,
+                              bool summarise = true);
+hipError_t launch_fastx_length_mismatch(const u64* a, const u64* b, u64 n_reads, unsigned long long* first_bad, int n_cu, hipStream_t st);
 hipError_t launch_fastx_emit(const uint8_t* text, u64 n, bool fasta, const void* scratch, const unsigned long long* totals,
                              uint8_t* bases, u64* offsets, hipStream_t st);
 // kmx_seqvec.hip
@@ -245,6 +247,10 @@ size_t reads_edit_bytes(u64 n_rows);
 hipError_t launch_reads_edit_count(const ReadsEdit& e, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
 hipError_t launch_reads_edit_emit(const ReadsEdit& e, void* area, u64 n_out, u64 n_bases, uint8_t* out_bases, u64* out_offsets, u64* out_index,
                                   hipStream_t st);
+// kmx_reads_quality.hip: the masked copy and / or KMX_RQ_WORDS u64 per read out of the bases and the quality bytes (kmx_reads_quality;
+// a wave per read, asynchronous)
+hipError_t launch_reads_quality(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 read_len, const uint8_t* quals, u32 phred, u32 min_q,
+                                u32 trim_q, u32 k, const u64* weights, uint8_t* masked, u64* rows, int n_cu, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
