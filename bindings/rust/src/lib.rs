@@ -1120,6 +1120,34 @@ pub fn reads_quality(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, re
                                       d_rows.map_or(ptr::null_mut(), |x| x.as_mut_ptr::<u64>())) })
 }
 
+/// The leftmost 3' adapter hit of every read (`kmx_reads_adapter`; include/kmx.h has the definition of a hit and the words of a row).
+/// `adapters`: 1 to `KMX_RA_MAX_ADAPTERS` host byte strings of 1 to `KMX_RA_MAX_ADAPTER_LEN` of ACGTacgt, N / n a wildcard; they travel in
+/// the kernel arguments.  `d_rows` gets `KMX_RA_WORDS` u64 per read;
+/// `ReadSpans { words: &d_rows, first_word: KMX_RA_KEEP as u64, stride: KMX_RA_WORDS as u64, k: 0 }` cuts the adapters off with
+/// `reads_select`.  Asynchronous on the context's stream.
+pub fn reads_adapter(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>,
+                     adapters: &[&[u8]], min_overlap: u32, err_num: u32, err_den: u32, d_rows: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    let r = reads_of(d_reads, n_reads, read_len, d_read_offsets);
+    assert!(n_reads as u128 * KMX_RA_WORDS as u128 * 8 <= d_rows.len() as u128, "rows shorter than the batch's reads");
+    let blob: Vec<u8> = adapters.iter().flat_map(|a| a.iter().copied()).collect();
+    let lens: Vec<u32> = adapters.iter().map(|a| a.len() as u32).collect();
+    ctx.ck(unsafe { kmx_reads_adapter(ctx.0, &r, blob.as_ptr(), lens.as_ptr(), lens.len() as u32, min_overlap, err_num, err_den,
+                                      d_rows.as_mut_ptr::<u64>()) })
+}
+
+/// The insert size of every mate pair from the overlap of mate 1 with the reverse complement of mate 2 (`kmx_reads_pair_overlap`;
+/// include/kmx.h has the definition and the words of a row).  The two batches have `n_reads` reads each and layouts of their own.
+/// `d_rows` gets `KMX_RP_WORDS` u64 per pair; `KMX_RP_KEEP1` / `KMX_RP_KEEP2` are the span words that cut the read-through off mate 1 /
+/// mate 2 with `reads_select`.  Asynchronous on the context's stream.
+pub fn reads_pair_overlap(ctx: &HipContext, d_reads1: &DeviceBuf<'_>, read_len1: u32, d_read_offsets1: Option<&DeviceBuf<'_>>,
+                          d_reads2: &DeviceBuf<'_>, read_len2: u32, d_read_offsets2: Option<&DeviceBuf<'_>>, n_reads: u64, min_overlap: u32,
+                          max_mism: u32, err_num: u32, err_den: u32, d_rows: &DeviceBuf<'_>) -> Result<(), KmxError> {
+    let r1 = reads_of(d_reads1, n_reads, read_len1, d_read_offsets1);
+    let r2 = reads_of(d_reads2, n_reads, read_len2, d_read_offsets2);
+    assert!(n_reads as u128 * KMX_RP_WORDS as u128 * 8 <= d_rows.len() as u128, "rows shorter than the batch's pairs");
+    ctx.ck(unsafe { kmx_reads_pair_overlap(ctx.0, &r1, &r2, min_overlap, max_mism, err_num, err_den, d_rows.as_mut_ptr::<u64>()) })
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -1197,6 +1197,55 @@ int kmx_fastx_parse_quals(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes,
 int kmx_reads_quality(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *d_quals, uint32_t phred_base, uint32_t min_q,
                       uint32_t trim_q, uint32_t k, const uint64_t *d_weights, uint8_t *d_masked, uint64_t *d_rows);
 
+/* ---------------------------------------------------------------- adapter read-through: 3' adapters, the overlap of two mates ----
+ * BUILD-DEFINED (the reference has nothing like it): what cutadapt, fastp and Trimmomatic do between the parse and the count.  Both
+ * calls produce rows only; kmx_reads_select clips the reads by a word of a row.  Both take every layout kmx_reads_select takes:
+ * uniform and ragged reads, d_offsets[0] > 0, empty reads, any alignment of d_bases; a read of 2^31 bases or more, or an offsets pair
+ * that descends, counts as empty (L = 0).  No load touches an aligned dword that holds no byte of the batch.  Both are asynchronous
+ * on the context's stream, use no work buffer and no atomics (a row is written by the one wave that owns its read: repeated calls
+ * give identical bytes), and n_reads == 0 is a no-op (its arguments are still checked).  n_reads up to 2^40.
+ *
+ * kmx_reads_adapter.  The leftmost 3' adapter hit of every read.  h_adapters (HOST): the adapters back to back, h_adapter_lens[a]
+ * (HOST) bytes each; 1 <= n_adapters <= KMX_RA_MAX_ADAPTERS, 1 <= length <= KMX_RA_MAX_ADAPTER_LEN.  An adapter byte is one of
+ * ACGTacgt, or N / n: a wildcard.  They travel as bit planes in the kernel arguments: no upload, no host round trip.
+ * With L the read's length and A the length of adapter a, for a position p in [0, L):
+ *     n(p) = min(A, L - p)                                        the overlap
+ *     read base p + j MATCHES adapter base j  iff  the adapter base is a wildcard, or both are one of ACGTacgt and the same letter
+ *                                                  whatever the case (a read byte that is not ACGTacgt matches only a wildcard)
+ *     m(p) = the number of j < n(p) that do not match
+ *     p is a HIT of a  iff  n(p) >= min_overlap  and  m(p) * err_den <= err_num * n(p)                       (64-bit arithmetic)
+ * The read's hit is the smallest p that is a hit of any adapter; of the adapters that hit there, the smallest index.
+ * (d_rows + KMX_RA_KEEP, KMX_RA_WORDS, 0) is what kmx_reads_select takes; a hit at p = 0 keeps nothing (an adapter dimer).
+ * NULL ctx / reads / d_rows / h_adapters / h_adapter_lens, n_adapters or a length out of range, any other adapter byte,
+ * min_overlap == 0, err_den == 0, err_num > err_den: KMX_E_ARG. */
+#define KMX_RA_MAX_ADAPTERS 8u
+#define KMX_RA_MAX_ADAPTER_LEN 64u
+#define KMX_RA_WORDS 4u
+#define KMX_RA_KEEP 0u  /* span word in bases, 0 | len << 32: len = p on a hit, otherwise L */
+#define KMX_RA_HIT 1u   /* 0 without a hit, otherwise (a + 1) | n(p) << 16 | m(p) << 32 */
+#define KMX_RA_BASES 2u /* L */
+#define KMX_RA_HITS 3u  /* bit a set iff adapter a hits anywhere in the read */
+int kmx_reads_adapter(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *h_adapters, const uint32_t *h_adapter_lens,
+                      uint32_t n_adapters, uint32_t min_overlap, uint32_t err_num, uint32_t err_den, uint64_t *d_rows);
+
+/* kmx_reads_pair_overlap.  The insert size of every mate pair from the overlap of the mates: read-through found without knowing
+ * the adapter.  Pair r is read r of reads1 and read r of reads2 (reads1->n_reads != reads2->n_reads: KMX_E_ARG); the two batches
+ * have layouts, offsets and alignments of their own.  X = mate 1 (L1 bases), Y = the reverse complement of mate 2 (L2 bases); a
+ * byte that is not ACGTacgt matches nothing, and there are no wildcards.  For an integer d with -L2 < d < L1:
+ *     X[i] is compared with Y[i - d] for i in [max(0, d), min(L1, d + L2));  n(d) = the length of that range, m(d) = the mismatches
+ *     d is a HIT  iff  n(d) >= min_overlap  and  m(d) <= max_mism  and  m(d) * err_den <= err_num * n(d)     (64-bit arithmetic)
+ * Of all hits the one with the largest n is taken, of equal n the largest d (the longer insert: less is trimmed).  The insert size
+ * is I = d + L2.  A pair of which either mate is longer than KMX_RP_MAX_LEN bases has no hit, by definition (paired reads do not
+ * get there, and it bounds the plane words a wave keeps).  The argument errors of kmx_reads_adapter. */
+#define KMX_RP_MAX_LEN 1024u
+#define KMX_RP_WORDS 4u
+#define KMX_RP_INSERT 0u  /* I on a hit, 0 without */
+#define KMX_RP_OVERLAP 1u /* n | m << 32, 0 without a hit */
+#define KMX_RP_KEEP1 2u   /* span word in bases for mate 1: 0 | min(L1, I) << 32; without a hit 0 | L1 << 32 */
+#define KMX_RP_KEEP2 3u   /* the same for mate 2 in its own orientation: 0 | min(L2, I) << 32; without a hit 0 | L2 << 32 */
+int kmx_reads_pair_overlap(kmx_ctx *ctx, const kmx_reads *reads1, const kmx_reads *reads2, uint32_t min_overlap, uint32_t max_mism,
+                           uint32_t err_num, uint32_t err_den, uint64_t *d_rows);
+
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,
  * canonical_kmer_iterator.rs:72-83), so the scans need no collective.  What is exchanged is the optional bucket

@@ -475,6 +475,35 @@ class FastqReads {
     std::unique_ptr<DeviceBuffer<uint8_t>> quals_;
 };
 
+// Adapter read-through (kmx.h, "adapter read-through").  reads_adapter: the KMX_RA_* words of every read on the host -- the leftmost
+// 3' hit of any of `adapters` (up to 8 of up to 64 of ACGTacgt, N a wildcard).  reads_pair_overlap: the KMX_RP_* words of every mate
+// pair -- the insert size from the overlap of mate 1 with the reverse complement of mate 2.  Both work on any kmx_reads (FastxReads::reads());
+// the KEEP words are what kmx_reads_select clips by.
+inline std::vector<uint64_t> reads_adapter(Context& ctx, const kmx_reads& reads, const std::vector<std::string>& adapters, uint32_t min_overlap = 3,
+                                           uint32_t err_num = 1, uint32_t err_den = 10) {
+    std::string blob;
+    std::vector<uint32_t> lens;
+    for (const auto& a : adapters) {
+        blob += a;
+        lens.push_back(static_cast<uint32_t>(a.size()));
+    }
+    DeviceBuffer<uint64_t> rows(ctx, reads.n_reads * KMX_RA_WORDS + 1);
+    ctx.check(kmx_reads_adapter(ctx.get(), &reads, reinterpret_cast<const uint8_t*>(blob.data()), lens.data(), static_cast<uint32_t>(lens.size()),
+                                min_overlap, err_num, err_den, rows.data()),
+              "reads_adapter");
+    auto out = rows.download();   // (synchronises)
+    out.resize(reads.n_reads * KMX_RA_WORDS);
+    return out;
+}
+inline std::vector<uint64_t> reads_pair_overlap(Context& ctx, const kmx_reads& reads1, const kmx_reads& reads2, uint32_t min_overlap = 30,
+                                                uint32_t max_mism = 5, uint32_t err_num = 1, uint32_t err_den = 5) {
+    DeviceBuffer<uint64_t> rows(ctx, reads1.n_reads * KMX_RP_WORDS + 1);
+    ctx.check(kmx_reads_pair_overlap(ctx.get(), &reads1, &reads2, min_overlap, max_mism, err_num, err_den, rows.data()), "reads_pair_overlap");
+    auto out = rows.download();   // (synchronises)
+    out.resize(reads1.n_reads * KMX_RP_WORDS);
+    return out;
+}
+
 // src/naive_impl/seq_vector.rs: the 2-bit packed sequence container, resident on the device.
 class SeqVector {
   public:

@@ -55,6 +55,13 @@ LS_WORDS = 3
 # kmx_reads_quality: the words of a read's row (KMX_RQ_*)
 RQ_BASES, RQ_LOW, RQ_QSUM, RQ_WEIGHT, RQ_MINMAX, RQ_TRIM, RQ_RUN, RQ_WINDOWS = range(8)
 RQ_WORDS = 8
+# kmx_reads_adapter / kmx_reads_pair_overlap: the words of a row (KMX_RA_* / KMX_RP_*), the limits
+RA_KEEP, RA_HIT, RA_BASES, RA_HITS = range(4)
+RA_WORDS = 4
+RA_MAX_ADAPTERS, RA_MAX_ADAPTER_LEN = 8, 64
+RP_INSERT, RP_OVERLAP, RP_KEEP1, RP_KEEP2 = range(4)
+RP_WORDS = 4
+RP_MAX_LEN = 1024
 
 
 class KmxError(RuntimeError):
@@ -179,6 +186,8 @@ SIGNATURES = {
     "kmx_fastx_parse": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_fastx_parse_quals": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_reads_quality": (_int, [_vp, _RP, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "kmx_reads_adapter": (_int, [_vp, _RP, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
+    "kmx_reads_pair_overlap": (_int, [_vp, _RP, _RP, _u32, _u32, _u32, _u32, _vp]),
     "kmx_sub_kmer_words": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp]),
     "kmx_kmers_to_strings": (_int, [_vp, _vp, _u64, _u32, _vp]),
     "kmx_bitmers_to_bytes": (_int, [_vp, _vp, _u64, _u32, _vp]),

@@ -476,6 +476,14 @@ def expected_errors(rows):
     return (w & 0x7FFFFFFFFFFFFFFF).to(torch.float64) / 2.0**32 + (w < 0).to(torch.float64) * 2.0**31
 
 
+# The public Illumina adapter sequences, as the 3' read-through shows them: what reads_adapter / reads_trim_adapters take.
+ADAPTERS = {
+    "truseq": "AGATCGGAAGAGC",
+    "nextera": "CTGTCTCTTATACACATCT",
+    "small_rna": "TGGAATTCTCGGGTGCCAAGG",
+}
+
+
 @dataclasses.dataclass
 class ReadBatch:
     """A ragged batch of reads on the device, what reads_select / reads_gather write: bases uint8[n_bases], offsets
@@ -1789,6 +1797,75 @@ class Context:
         b = self.reads_select(masked, n_reads, read_len, keep=keep, span=span, span_k=0, min_len=min_len, offsets=offsets, index=True)
         q = self.reads_select(quals, n_reads, read_len, keep=keep, span=span, span_k=0, min_len=min_len, offsets=offsets)
         return b, q, rows
+
+    # ------------------------------------------------------------ adapter read-through
+    @staticmethod
+    def _adapters_arg(adapters):
+        """adapters -> (the bytes back to back, uint32 lengths, count): one adapter as str / bytes, or a sequence of them"""
+        if isinstance(adapters, (str, bytes)):
+            adapters = [adapters]
+        seqs = [a.encode("ascii") if isinstance(a, str) else bytes(a) for a in adapters]
+        blob = b"".join(seqs)
+        return (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0"), (C.c_uint32 * max(len(seqs), 1))(*[len(s) for s in seqs]), len(seqs)
+
+    def _rows_arg(self, out, words):
+        rows = out if out is not None else self.empty(max(words, 1), torch.int64)
+        if rows.dtype != torch.int64 or rows.numel() < words or not rows.is_contiguous():
+            raise ValueError(f"out: a contiguous int64 tensor of at least {words} words")
+        return rows.view(-1)
+
+    @_on_ctx_stream
+    def reads_adapter(self, bases, n_reads, read_len, adapters, min_overlap=3, max_error=(1, 10), offsets=None, out=None):
+        """kmx_reads_adapter -> rows int64[n_reads, RA_WORDS] (viewable as u64; include/kmx.h has the words): per read the leftmost
+        3' hit of any of `adapters` (str / bytes or a sequence of up to 8, each up to 64 of ACGTacgt and N as a wildcard; see
+        ADAPTERS), with an overlap of at least min_overlap bases and at most max_error = (num, den) mismatches per overlapping
+        base.  rows[:, RA_KEEP] is the span reads_select takes."""
+        n_reads = int(n_reads)
+        blob, lens, n_ad = self._adapters_arg(adapters)
+        rows = self._rows_arg(out, _lib.RA_WORDS * n_reads)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_reads_adapter(self._h, C.byref(r), blob, lens, n_ad, int(min_overlap), int(max_error[0]), int(max_error[1]), _ptr(rows)))
+        return rows[:_lib.RA_WORDS * n_reads].view(-1, _lib.RA_WORDS)
+
+    @_on_ctx_stream
+    def reads_trim_adapters(self, bases, n_reads, read_len, adapters, min_overlap=3, max_error=(1, 10), offsets=None, quals=None, min_len=0):
+        """reads_adapter, then reads_select on RA_KEEP -> (ReadBatch of the bases with index, ReadBatch of the quality bytes or None,
+        rows of the SOURCE reads): every read cut at its adapter, clips shorter than min_len dropped.  With `quals` (the layout of
+        bases) the same span column goes into a second reads_select, so the two batches have identical offsets."""
+        rows = self.reads_adapter(bases, n_reads, read_len, adapters, min_overlap, max_error, offsets)
+        span = rows[:, _lib.RA_KEEP]
+        b = self.reads_select(bases, n_reads, read_len, span=span, span_k=0, min_len=min_len, offsets=offsets, index=True)
+        q = None
+        if quals is not None:
+            q = self.reads_select(quals, n_reads, read_len, span=span, span_k=0, min_len=min_len, offsets=offsets)
+        return b, q, rows
+
+    @_on_ctx_stream
+    def reads_pair_overlap(self, bases1, bases2, n_reads, read_len1, read_len2, offsets1=None, offsets2=None, min_overlap=30, max_mism=5,
+                           max_error=(1, 5), out=None):
+        """kmx_reads_pair_overlap -> rows int64[n_reads, RP_WORDS]: per mate pair the insert size from the overlap of mate 1 with the
+        reverse complement of mate 2 (at least min_overlap bases, at most max_mism mismatches and max_error = (num, den) per
+        overlapping base; the longest overlap, of equal ones the longer insert), and the spans that cut the read-through off both
+        mates (RP_KEEP1, RP_KEEP2)."""
+        n_reads = int(n_reads)
+        rows = self._rows_arg(out, _lib.RP_WORDS * n_reads)
+        r1 = self._reads(bases1, n_reads, read_len1, offsets1)
+        r2 = self._reads(bases2, n_reads, read_len2, offsets2)
+        self._ck(self.lib.kmx_reads_pair_overlap(self._h, C.byref(r1), C.byref(r2), int(min_overlap), int(max_mism), int(max_error[0]),
+                                                 int(max_error[1]), _ptr(rows)))
+        return rows[:_lib.RP_WORDS * n_reads].view(-1, _lib.RP_WORDS)
+
+    @_on_ctx_stream
+    def reads_trim_pairs(self, bases1, bases2, n_reads, read_len1, read_len2, offsets1=None, offsets2=None, min_overlap=30, max_mism=5,
+                         max_error=(1, 5), min_len=0):
+        """reads_pair_overlap, then reads_select on RP_KEEP1 / RP_KEEP2 -> (ReadBatch of mate 1, ReadBatch of mate 2, rows of the
+        SOURCE pairs).  A pair is dropped when either clip is shorter than min_len -- one keep tensor, computed from the two span
+        words, goes into both calls, so the two batches stay in step (both carry the index of the source pair)."""
+        rows = self.reads_pair_overlap(bases1, bases2, n_reads, read_len1, read_len2, offsets1, offsets2, min_overlap, max_mism, max_error)
+        keep = ((rows[:, _lib.RP_KEEP1] >> 32) >= int(min_len)) & ((rows[:, _lib.RP_KEEP2] >> 32) >= int(min_len))
+        b1 = self.reads_select(bases1, n_reads, read_len1, keep=keep, span=rows[:, _lib.RP_KEEP1], span_k=0, offsets=offsets1, index=True)
+        b2 = self.reads_select(bases2, n_reads, read_len2, keep=keep, span=rows[:, _lib.RP_KEEP2], span_k=0, offsets=offsets2, index=True)
+        return b1, b2, rows
 
     # ------------------------------------------------------------ a new batch of reads from an old one
     @staticmethod

@@ -2438,6 +2438,66 @@ int kmx_reads_quality(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_qua
     return KMX_OK;
 }
 
+// ---- adapter read-through (kmx_reads_adapter.hip) ----
+namespace {
+// what both calls refuse in a batch and in the thresholds
+bool adapter_args_ok(const kmx_reads* reads, uint32_t min_overlap, uint32_t err_num, uint32_t err_den) {
+    if (!reads_ok(reads) || min_overlap == 0u || err_den == 0u || err_num > err_den) return false;
+    if (reads->n_reads > (1ull << 40)) return false;
+    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return false;
+    return true;
+}
+}  // namespace
+
+int kmx_reads_adapter(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* h_adapters, const uint32_t* h_adapter_lens, uint32_t n_adapters,
+                      uint32_t min_overlap, uint32_t err_num, uint32_t err_den, uint64_t* d_rows) {
+    if (!ctx || !d_rows || !h_adapters || !h_adapter_lens || !adapter_args_ok(reads, min_overlap, err_num, err_den)) return KMX_E_ARG;
+    if (n_adapters < 1u || n_adapters > KMX_RA_MAX_ADAPTERS) return KMX_E_ARG;
+    kmx::ReadsAdapter a{};
+    a.bases = reads->d_bases;
+    a.offsets = reads->d_offsets;
+    a.n_reads = reads->n_reads;
+    a.read_len = reads->read_len;
+    a.n_adapters = n_adapters;
+    a.min_overlap = min_overlap;
+    a.err_num = err_num;
+    a.err_den = err_den;
+    a.rows = d_rows;
+    const uint8_t* s = h_adapters;
+    for (uint32_t i = 0; i < n_adapters; ++i) {
+        const uint32_t len = h_adapter_lens[i];
+        if (len < 1u || len > KMX_RA_MAX_ADAPTER_LEN) return KMX_E_ARG;
+        a.len[i] = len;
+        for (uint32_t j = 0; j < len; ++j) {
+            const uint32_t b = s[j], u = b & 0xDFu;
+            if (u == 'N') continue;   // a wildcard: no bit of care
+            if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return KMX_E_ARG;
+            const uint32_t c = (b >> 1) & 3u;   // the code of kmx_reads_adapter.hip
+            a.lo[i] |= (uint64_t)(c & 1u) << j;
+            a.hi[i] |= (uint64_t)(c >> 1) << j;
+            a.care[i] |= 1ull << j;
+        }
+        s += len;
+    }
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_reads_adapter(a, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_reads_pair_overlap(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_reads* reads2, uint32_t min_overlap, uint32_t max_mism, uint32_t err_num,
+                           uint32_t err_den, uint64_t* d_rows) {
+    if (!ctx || !d_rows || !adapter_args_ok(reads1, min_overlap, err_num, err_den) || !adapter_args_ok(reads2, min_overlap, err_num, err_den))
+        return KMX_E_ARG;
+    if (reads1->n_reads != reads2->n_reads) return KMX_E_ARG;
+    if (reads1->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    const kmx::ReadsPairOverlap a{reads1->d_bases, reads2->d_bases, reads1->d_offsets, reads2->d_offsets, reads1->n_reads, reads1->read_len,
+                                  reads2->read_len, min_overlap, max_mism, err_num, err_den, d_rows};
+    KMX_HIP(ctx, kmx::launch_reads_pair_overlap(a, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
 int kmx_reads_length_range(kmx_ctx* ctx, const uint64_t* d_offsets, uint64_t n_reads, uint32_t* h_min_len, uint32_t* h_max_len) {
     if (!ctx || (n_reads && !d_offsets)) return KMX_E_ARG;
     if (h_min_len) *h_min_len = 0;

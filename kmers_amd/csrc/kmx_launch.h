@@ -251,6 +251,30 @@ hipError_t launch_reads_edit_emit(const ReadsEdit& e, void* area, u64 n_out, u64
 // a wave per read, asynchronous)
 hipError_t launch_reads_quality(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 read_len, const uint8_t* quals, u32 phred, u32 min_q,
                                 u32 trim_q, u32 k, const u64* weights, uint8_t* masked, u64* rows, int n_cu, hipStream_t st);
+// kmx_reads_adapter.hip: KMX_RA_WORDS u64 per read (kmx_reads_adapter) and KMX_RP_WORDS u64 per mate pair (kmx_reads_pair_overlap); a
+// wave per read or pair, asynchronous, no work buffer.  The adapters travel in the kernel arguments as bit planes: bit j of lo / hi =
+// the low / high bit of the code (byte >> 1) & 3 of adapter base j, bit j of care = base j exists and is no wildcard.
+struct ReadsAdapter {
+    const uint8_t* bases;
+    const u64* offsets;   // nullptr: uniform reads of read_len bases
+    u64 n_reads;
+    u32 read_len;
+    u32 n_adapters;       // 1 .. KMX_RA_MAX_ADAPTERS
+    u64 lo[KMX_RA_MAX_ADAPTERS], hi[KMX_RA_MAX_ADAPTERS], care[KMX_RA_MAX_ADAPTERS];
+    u32 len[KMX_RA_MAX_ADAPTERS];
+    u32 min_overlap, err_num, err_den;
+    u64* rows;
+};
+struct ReadsPairOverlap {
+    const uint8_t *bases1, *bases2;
+    const u64 *offsets1, *offsets2;   // nullptr: uniform reads of read_len1 / read_len2 bases
+    u64 n_reads;
+    u32 read_len1, read_len2;
+    u32 min_overlap, max_mism, err_num, err_den;
+    u64* rows;
+};
+hipError_t launch_reads_adapter(const ReadsAdapter& a, int n_cu, hipStream_t st);
+hipError_t launch_reads_pair_overlap(const ReadsPairOverlap& a, int n_cu, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
