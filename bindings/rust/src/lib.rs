@@ -1148,6 +1148,61 @@ pub fn reads_pair_overlap(ctx: &HipContext, d_reads1: &DeviceBuf<'_>, read_len1:
     ctx.ck(unsafe { kmx_reads_pair_overlap(ctx.0, &r1, &r2, min_overlap, max_mism, err_num, err_den, d_rows.as_mut_ptr::<u64>()) })
 }
 
+/// One batch of mates for `reads_pair_merge`: the bases, their layout and, optionally, the quality bytes laid out as the bases are.
+pub struct Mates<'a> {
+    pub bases: &'a DeviceBuf<'a>,
+    pub read_len: u32,
+    pub offsets: Option<&'a DeviceBuf<'a>>,
+    pub quals: Option<&'a DeviceBuf<'a>>,
+}
+
+/// The outputs of `reads_pair_merge`: `bases` (at least `max_bases` bytes), `offsets` (at least `n_reads + 1` u64) and, where the mates
+/// have quality bytes, optionally `quals` (at least `max_bases` bytes).
+pub struct MergeOutputs<'a> {
+    pub bases: &'a DeviceBuf<'a>,
+    pub quals: Option<&'a DeviceBuf<'a>>,
+    pub offsets: &'a DeviceBuf<'a>,
+    pub max_bases: u64,
+}
+
+/// Overlapping mate pairs merged into consensus reads (`kmx_reads_pair_merge`; include/kmx.h has which pairs merge, the consensus rule
+/// and the words of a row).  `inserts`: one insert size per pair as strided words --
+/// `ReadSpans { words: &d_rows_of_pair_overlap, first_word: KMX_RP_INSERT as u64, stride: KMX_RP_WORDS as u64, k: 0 }` hands the overlap
+/// rows over as they are.  Output read r is the merged read of pair r, empty where the pair does not merge.  `out = None` counts only;
+/// `d_rows` (optional) gets `KMX_RM_WORDS` u64 per pair.  Returns (pairs merged, bases merged); Err(KMX_E_NOMEM) if the bases exceed
+/// `max_bases`, with nothing of the batch written.  Synchronous.
+pub fn reads_pair_merge(ctx: &HipContext, mates1: &Mates<'_>, mates2: &Mates<'_>, n_reads: u64, inserts: ReadSpans<'_>, phred_base: u32,
+                        q_cap: u32, out: Option<&MergeOutputs<'_>>, d_rows: Option<&DeviceBuf<'_>>) -> Result<(u64, u64), KmxError> {
+    let r1 = reads_of(mates1.bases, n_reads, mates1.read_len, mates1.offsets);
+    let r2 = reads_of(mates2.bases, n_reads, mates2.read_len, mates2.offsets);
+    assert!(mates1.quals.is_some() == mates2.quals.is_some(), "quality bytes for both mates or for neither");
+    for m in [mates1, mates2] {
+        if let Some(q) = m.quals {
+            assert!(q.len() >= m.bases.len(), "quality bytes shorter than the bases");
+        }
+    }
+    let (d_insert, stride, _) = span_args(Some(inserts), n_reads);
+    if let Some(rw) = d_rows {
+        assert!(n_reads as u128 * KMX_RM_WORDS as u128 * 8 <= rw.len() as u128, "rows shorter than the batch's pairs");
+    }
+    let (ob, oq, oo, max_bases) = match out {
+        None => (ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), 0),
+        Some(o) => {
+            assert!(o.max_bases as u128 <= o.bases.len() as u128 && (n_reads as u128 + 1) * 8 <= o.offsets.len() as u128,
+                    "outputs shorter than n_reads + 1 offsets / max_bases");
+            if let Some(q) = o.quals {
+                assert!(mates1.quals.is_some() && o.max_bases as u128 <= q.len() as u128, "quality output without quality bytes, or shorter than max_bases");
+            }
+            (o.bases.as_mut_ptr::<u8>(), o.quals.map_or(ptr::null_mut(), |q| q.as_mut_ptr::<u8>()), o.offsets.as_mut_ptr::<u64>(), o.max_bases)
+        }
+    };
+    let (mut n_merged, mut n_bases) = (0u64, 0u64);
+    ctx.ck(unsafe { kmx_reads_pair_merge(ctx.0, &r1, &r2, mates1.quals.map_or(ptr::null(), |q| q.as_ptr::<u8>()),
+                                         mates2.quals.map_or(ptr::null(), |q| q.as_ptr::<u8>()), d_insert, stride, phred_base, q_cap, ob, oq, oo,
+                                         d_rows.map_or(ptr::null_mut(), |x| x.as_mut_ptr::<u64>()), max_bases, &mut n_merged, &mut n_bases) })?;
+    Ok((n_merged, n_bases))
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

@@ -1246,6 +1246,57 @@ int kmx_reads_adapter(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *h_ada
 int kmx_reads_pair_overlap(kmx_ctx *ctx, const kmx_reads *reads1, const kmx_reads *reads2, uint32_t min_overlap, uint32_t max_mism,
                            uint32_t err_num, uint32_t err_den, uint64_t *d_rows);
 
+/* ---------------------------------------------------------------- overlapping mate pairs merged into consensus reads ----
+ * BUILD-DEFINED (the reference has nothing like it): what fastp --merge, PEAR, FLASH and vsearch --fastq_mergepairs do with the
+ * insert size kmx_reads_pair_overlap finds.  kmx_reads_pair_merge writes a new ragged batch -- bases, quality bytes, offsets -- out
+ * of two: output read r is the merged read of pair r, or EMPTY where the pair does not merge, so the output has exactly n_reads
+ * reads and stays in step with the pairs (a kmx_reads_select with min_len = 1 compacts it).
+ *
+ * Pair r is read r of reads1 and read r of reads2 (reads1->n_reads != reads2->n_reads: KMX_E_ARG).  Every layout
+ * kmx_reads_pair_overlap takes is taken: uniform or ragged, d_offsets[0] > 0, empty mates, alignments of their own; a mate of 2^31
+ * bases or more, or an offsets pair that descends, has length 0.  d_quals1 / d_quals2 are laid out as their bases are (the rule of
+ * kmx_reads_quality), each at any alignment of its own.  d_insert[r * insert_stride] is the insert size of pair r:
+ * (d_rows of kmx_reads_pair_overlap + KMX_RP_INSERT, KMX_RP_WORDS) is handed over with no array in between.
+ *
+ * WHICH PAIRS MERGE.  L1, L2 = the mates' lengths, I = the insert word, d = I - L2 (signed).  The pair merges iff
+ *     1 <= L1, L2 <= KMX_RP_MAX_LEN   and   0 < I < L1 + L2            (that is -L2 < d < L1: at least one position overlaps)
+ * Any other word (0 = no hit, garbage, too large) means not merged: any bytes give one defined answer.  The insert is trusted: no
+ * mismatch threshold is tested again, what is found goes into the row.
+ *
+ * THE MERGED READ M has I bases.  X[i] = byte i of mate 1; Y[j] = the complement of byte L2 - 1 - j of mate 2 (A<->T, C<->G,
+ * a<->t, c<->g: the case is kept; any other byte becomes 'N').  Position i of M, in [0, I), is covered by X iff i < L1 and by Y iff
+ * i >= max(d, 0), as Y[i - d]; X at or past I and Y before 0 are read-through and dropped.  q of a quality byte is
+ * byte >= phred_base ? byte - phred_base : 0.
+ *     X alone: the base and the quality byte of mate 1, raw.     Y alone: Y[i - d] and the raw quality byte L2 - 1 - (i - d) of mate 2.
+ *     both ("valid" = one of ACGTacgt); the quality byte written is phred_base + q:
+ *       AGREE  both valid, the same letter whatever the case    X's byte                                       q = min(qx + qy, q_cap)
+ *       DIS    both valid, the letters differ                   Y's byte iff qy > qx, else X's (a tie: mate 1)  q = min(|qx - qy|, q_cap)
+ *       ONE    exactly one valid                                that one's byte                                q = min(its q, q_cap)
+ *       NONE   neither valid                                    'N'                                            q = 0
+ * d_quals1 == d_quals2 == NULL: every q is 0 (mate 1 wins every DIS) and d_out_quals must be NULL; exactly one of the two NULL, or
+ * d_out_quals without them: KMX_E_ARG.  With them d_out_quals is optional.
+ *
+ * OUTPUTS.  d_out_offsets: n_reads + 1 words, the first 0, the last n_bases; d_out_bases and d_out_quals: the reads back to back by
+ * those offsets, each at any alignment.  d_rows (optional): KMX_RM_WORDS u64 per pair.  *h_n_merged, *h_n_bases: always set.
+ * d_out_bases == d_out_offsets == NULL (d_out_quals NULL as well): only the counts, and the rows where d_rows is given; exactly one
+ * of the two NULL: KMX_E_ARG.  n_bases > max_bases: KMX_E_NOMEM with the counts set and no byte of the three batch outputs written.
+ * No byte at or past n_bases is written, no word past n_reads + 1 offsets or KMX_RM_WORDS * n_reads row words; no load touches an
+ * aligned dword that holds no byte of its batch.  An output that overlaps an input (bases, quality bytes, offsets, insert words),
+ * where the host can tell: KMX_E_ARG.  phred_base + q_cap > 255, insert_stride == 0 or d_insert NULL with pairs present, NULL ctx /
+ * reads / h_n_merged / h_n_bases: KMX_E_ARG.  n_reads == 0 is a no-op with both counts 0, its arguments still checked; n_reads up
+ * to 2^40.  Working set: the partial sums of the plan, 16 bytes per 2048 pairs and six words, laid out in the work buffer before any
+ * kernel runs; above the work buffer's cap KMX_E_NOMEM with nothing written.  Synchronous (the counts come back to the host); no
+ * atomics: repeated calls give identical bytes. */
+#define KMX_RM_WORDS 4u
+#define KMX_RM_LEN 0u     /* I if merged, otherwise 0 (and the other words 0) */
+#define KMX_RM_OVERLAP 1u /* n | DIS << 32: n = min(L1, I) - max(d, 0) overlapping positions, DIS of them disagree */
+#define KMX_RM_TAKEN 2u   /* DIS positions taken from mate 2 | DIS positions with qx == qy << 32 */
+#define KMX_RM_INVALID 3u /* ONE | NONE << 32 */
+int kmx_reads_pair_merge(kmx_ctx *ctx, const kmx_reads *reads1, const kmx_reads *reads2, const uint8_t *d_quals1,
+                         const uint8_t *d_quals2, const uint64_t *d_insert, uint64_t insert_stride, uint32_t phred_base,
+                         uint32_t q_cap, uint8_t *d_out_bases, uint8_t *d_out_quals, uint64_t *d_out_offsets, uint64_t *d_rows,
+                         uint64_t max_bases, uint64_t *h_n_merged, uint64_t *h_n_bases);
+
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,
  * canonical_kmer_iterator.rs:72-83), so the scans need no collective.  What is exchanged is the optional bucket

@@ -504,6 +504,44 @@ inline std::vector<uint64_t> reads_pair_overlap(Context& ctx, const kmx_reads& r
     return out;
 }
 
+// Overlapping mate pairs merged into consensus reads (kmx.h, "overlapping mate pairs merged"): a ragged batch on the host with one read
+// per PAIR, empty where the pair does not merge -- bases, quality bytes (empty without d_quals1 / d_quals2), n_reads + 1 offsets and
+// the KMX_RM_* words of every pair.  d_insert / insert_stride: the insert size of every pair on the device, strided;
+// (rows of kmx_reads_pair_overlap + KMX_RP_INSERT, KMX_RP_WORDS) is handed over as it is.  A count-only call sizes the buffers.
+struct MergedReads {
+    std::vector<uint8_t> bases, quals;
+    std::vector<uint64_t> offsets, rows;
+    uint64_t n_merged = 0;
+};
+inline MergedReads reads_pair_merge(Context& ctx, const kmx_reads& reads1, const kmx_reads& reads2, const uint64_t* d_insert, uint64_t insert_stride,
+                                    const uint8_t* d_quals1 = nullptr, const uint8_t* d_quals2 = nullptr, uint32_t phred_base = 33,
+                                    uint32_t q_cap = 41) {
+    MergedReads m;
+    uint64_t n_bases = 0;
+    ctx.check(kmx_reads_pair_merge(ctx.get(), &reads1, &reads2, d_quals1, d_quals2, d_insert, insert_stride, phred_base, q_cap, nullptr, nullptr,
+                                   nullptr, nullptr, 0, &m.n_merged, &n_bases),
+              "reads_pair_merge");
+    DeviceBuffer<uint8_t> bases(ctx, n_bases + 1), quals(ctx, n_bases + 1);
+    DeviceBuffer<uint64_t> offsets(ctx, reads1.n_reads + 1), rows(ctx, reads1.n_reads * KMX_RM_WORDS + 1);
+    ctx.check(kmx_reads_pair_merge(ctx.get(), &reads1, &reads2, d_quals1, d_quals2, d_insert, insert_stride, phred_base, q_cap, bases.data(),
+                                   d_quals1 ? quals.data() : nullptr, offsets.data(), rows.data(), n_bases, &m.n_merged, &n_bases),
+              "reads_pair_merge");
+    m.bases = bases.download();
+    m.bases.resize(n_bases);
+    if (d_quals1) {
+        m.quals = quals.download();
+        m.quals.resize(n_bases);
+    }
+    if (reads1.n_reads) {
+        m.offsets = offsets.download();
+        m.rows = rows.download();
+        m.rows.resize(reads1.n_reads * KMX_RM_WORDS);
+    } else {
+        m.offsets.assign(1, 0);
+    }
+    return m;
+}
+
 // src/naive_impl/seq_vector.rs: the 2-bit packed sequence container, resident on the device.
 class SeqVector {
   public:

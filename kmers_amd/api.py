@@ -521,6 +521,22 @@ class ReadGroups:
         return int(self.labels.numel())
 
 
+@dataclasses.dataclass
+class MergedPairs:
+    """What reads_merge_pairs returns.  merged / merged_quals: the consensus reads of the pairs that merged and their quality bytes
+    (identical offsets; merged.index: the source pair).  unmerged1 / unmerged2: the mates of the pairs that did not, in step
+    (both carry the pair index), unmerged1_quals / unmerged2_quals their quality bytes.  The *_quals are None where no quality
+    bytes were given.  overlap_rows int64[n_reads, RP_WORDS] and merge_rows int64[n_reads, RM_WORDS] belong to the SOURCE pairs."""
+    merged: ReadBatch
+    merged_quals: "ReadBatch | None"
+    unmerged1: ReadBatch
+    unmerged2: ReadBatch
+    unmerged1_quals: "ReadBatch | None"
+    unmerged2_quals: "ReadBatch | None"
+    overlap_rows: "torch.Tensor"
+    merge_rows: "torch.Tensor"
+
+
 def _on_ctx_stream(fn):
     """Run a Context method with Context.stream as torch's current stream (see "Stream discipline" above)."""
     @functools.wraps(fn)
@@ -1866,6 +1882,59 @@ class Context:
         b1 = self.reads_select(bases1, n_reads, read_len1, keep=keep, span=rows[:, _lib.RP_KEEP1], span_k=0, offsets=offsets1, index=True)
         b2 = self.reads_select(bases2, n_reads, read_len2, keep=keep, span=rows[:, _lib.RP_KEEP2], span_k=0, offsets=offsets2, index=True)
         return b1, b2, rows
+
+    # ------------------------------------------------------------ overlapping mates merged into consensus reads
+    @_on_ctx_stream
+    def reads_pair_merge(self, bases1, bases2, n_reads, read_len1, read_len2, insert, quals1=None, quals2=None, offsets1=None, offsets2=None,
+                         phred_base=33, q_cap=41, rows=True):
+        """kmx_reads_pair_merge -> (ReadBatch of the merged bases, ReadBatch of their quality bytes or None, rows
+        int64[n_reads, RM_WORDS] or None).  Both batches have n_reads reads and identical offsets: read r is the consensus of pair
+        r, empty where the pair does not merge.  `insert`: a 1-D int64 tensor of insert sizes, one per pair, with any positive
+        element stride -- reads_pair_overlap(...)[:, RP_INSERT] is handed over as it is.  quals1 / quals2 (both or neither): the
+        quality bytes, laid out as the bases; without them mate 1 wins every disagreement.  include/kmx.h has the consensus rule
+        and the words of a row.  Sizing: a count-only call first, then the write into buffers of exactly that size."""
+        n_reads = int(n_reads)
+        if (quals1 is None) != (quals2 is None):
+            raise ValueError("quals1 and quals2: both or neither")
+        ins_t, ins_p, stride = self._span_arg(insert)
+        if n_reads and (ins_t is None or ins_t.numel() < n_reads):
+            raise ValueError("insert: one word per pair")
+        r1 = self._reads(bases1, n_reads, read_len1, offsets1)
+        r2 = self._reads(bases2, n_reads, read_len2, offsets2)
+        nm, nb = C.c_uint64(0), C.c_uint64(0)
+        args = (self._h, C.byref(r1), C.byref(r2), _ptr(quals1), _ptr(quals2), ins_p, max(stride, 1), int(phred_base), int(q_cap))
+        self._ck(self.lib.kmx_reads_pair_merge(*args, None, None, None, None, 0, C.byref(nm), C.byref(nb)))
+        out = self.empty(max(nb.value, 1), torch.uint8)   # (a pointer also where nothing merges)
+        outq = self.empty(max(nb.value, 1), torch.uint8) if quals1 is not None else None
+        off = torch.zeros(n_reads + 1, dtype=torch.int64, device=self.device)
+        rws = self.empty(_lib.RM_WORDS * n_reads, torch.int64) if rows else None
+        if n_reads:
+            self._ck(self.lib.kmx_reads_pair_merge(*args, _ptr(out), _ptr(outq), _ptr(off), _ptr(rws), nb.value, C.byref(nm), C.byref(nb)))
+        b = ReadBatch(out[:nb.value], off, n_reads, None, self)
+        q = ReadBatch(outq[:nb.value], off, n_reads, None, self) if outq is not None else None
+        return b, q, rws.view(-1, _lib.RM_WORDS) if rows else None
+
+    @_on_ctx_stream
+    def reads_merge_pairs(self, bases1, bases2, n_reads, read_len1, read_len2, quals1=None, quals2=None, offsets1=None, offsets2=None,
+                          min_overlap=30, max_mism=5, max_error=(1, 5), phred_base=33, q_cap=41):
+        """reads_pair_overlap, reads_pair_merge, then reads_select -> MergedPairs: the merged reads and their quality bytes,
+        compacted, with the index of the source pair; the pairs that did not merge as a mate-1 and a mate-2 batch that stay in
+        step (with their quality bytes where given, and the pair index); the rows of both calls for the SOURCE pairs.  ONE keep
+        tensor, rows[:, RM_LEN] != 0, goes into all the selects (negated for the unmerged mates)."""
+        n_reads = int(n_reads)
+        overlap_rows = self.reads_pair_overlap(bases1, bases2, n_reads, read_len1, read_len2, offsets1, offsets2, min_overlap, max_mism, max_error)
+        m, mq, merge_rows = self.reads_pair_merge(bases1, bases2, n_reads, read_len1, read_len2, overlap_rows[:, _lib.RP_INSERT], quals1, quals2,
+                                                  offsets1, offsets2, phred_base, q_cap)
+        keep = merge_rows[:, _lib.RM_LEN] != 0
+        drop = ~keep
+        some = lambda t: t if t.numel() else self.empty(1, torch.uint8)   # (a pointer also where nothing merges)
+        merged = self.reads_select(some(m.bases), n_reads, 0, keep=keep, offsets=m.offsets, index=True)
+        merged_q = self.reads_select(some(mq.bases), n_reads, 0, keep=keep, offsets=mq.offsets) if mq is not None else None
+        un1 = self.reads_select(bases1, n_reads, read_len1, keep=drop, offsets=offsets1, index=True)
+        un2 = self.reads_select(bases2, n_reads, read_len2, keep=drop, offsets=offsets2, index=True)
+        un1_q = self.reads_select(quals1, n_reads, read_len1, keep=drop, offsets=offsets1) if quals1 is not None else None
+        un2_q = self.reads_select(quals2, n_reads, read_len2, keep=drop, offsets=offsets2) if quals2 is not None else None
+        return MergedPairs(merged, merged_q, un1, un2, un1_q, un2_q, overlap_rows, merge_rows)
 
     # ------------------------------------------------------------ a new batch of reads from an old one
     @staticmethod

@@ -2498,6 +2498,60 @@ int kmx_reads_pair_overlap(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_read
     return KMX_OK;
 }
 
+// ---- overlapping mate pairs merged into consensus reads (kmx_reads_merge.hip) ----
+int kmx_reads_pair_merge(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_reads* reads2, const uint8_t* d_quals1, const uint8_t* d_quals2,
+                         const uint64_t* d_insert, uint64_t insert_stride, uint32_t phred_base, uint32_t q_cap, uint8_t* d_out_bases,
+                         uint8_t* d_out_quals, uint64_t* d_out_offsets, uint64_t* d_rows, uint64_t max_bases, uint64_t* h_n_merged,
+                         uint64_t* h_n_bases) {
+    const char* who = "kmx_reads_pair_merge";
+    if (!ctx || !reads_ok(reads1) || !reads_ok(reads2) || !h_n_merged || !h_n_bases) return KMX_E_ARG;
+    *h_n_merged = *h_n_bases = 0;
+    const uint64_t n = reads1->n_reads;
+    if (n != reads2->n_reads || n > (1ull << 40) || (uint64_t)phred_base + q_cap > 255u) return KMX_E_ARG;
+    for (const kmx_reads* r : {reads1, reads2})
+        if (!r->d_offsets && r->read_len && n > (1ull << 62) / r->read_len) return KMX_E_ARG;
+    if ((d_quals1 == nullptr) != (d_quals2 == nullptr) || (d_out_quals && !d_quals1)) return KMX_E_ARG;
+    if ((d_out_bases == nullptr) != (d_out_offsets == nullptr) || (d_out_quals && !d_out_bases)) return KMX_E_ARG;
+    if (n && (!d_insert || insert_stride == 0 || (n - 1u) > ((1ull << 60) - 1u) / insert_stride)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::reads_merge_bytes(n), &area)) return st;
+    const kmx::ReadsPairMerge a{reads1->d_bases, reads2->d_bases, reads1->d_offsets, reads2->d_offsets, d_quals1, d_quals2, d_insert, insert_stride, n,
+                                reads1->read_len, reads2->read_len, phred_base, q_cap, d_out_bases, d_out_quals, d_out_offsets, d_rows};
+    uint64_t h[6] = {0, 0, 0, 0, 0, 0};   // merged pairs, merged bases, the first and last offset of batch 1, of batch 2
+    KMX_HIP(ctx, kmx::launch_reads_merge_count(a, area, ctx->h_pinned, h, ctx->stream));
+    *h_n_merged = h[0];
+    *h_n_bases = h[1];
+    if (!d_out_bases && !d_rows) return KMX_OK;
+    if (d_out_bases)
+        if (int st = room_for(ctx, who, h[1], "bases merged", max_bases)) return st;
+    // the bytes the inputs span against the bytes that are written
+    struct Range {
+        uintptr_t at;
+        uint64_t bytes;
+    };
+    auto batch = [&](const void* base, const kmx_reads* r, uint64_t first, uint64_t last) {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(base);
+        if (!base) return Range{0, 0};
+        if (r->d_offsets) return Range{at + first, last >= first ? last - first : 0};
+        return Range{at, n * (uint64_t)r->read_len};
+    };
+    auto words = [](const void* base, uint64_t n_words) { return Range{reinterpret_cast<uintptr_t>(base), base ? 8u * n_words : 0u}; };
+    const Range in[] = {batch(reads1->d_bases, reads1, h[2], h[3]), batch(reads2->d_bases, reads2, h[4], h[5]), batch(d_quals1, reads1, h[2], h[3]),
+                        batch(d_quals2, reads2, h[4], h[5]), words(reads1->d_offsets, n + 1u), words(reads2->d_offsets, n + 1u),
+                        words(d_insert, (n - 1u) * insert_stride + 1u)};
+    const Range out[] = {Range{reinterpret_cast<uintptr_t>(d_out_bases), d_out_bases ? h[1] : 0u},
+                         Range{reinterpret_cast<uintptr_t>(d_out_quals), d_out_quals ? h[1] : 0u}, words(d_out_offsets, n + 1u),
+                         words(d_rows, KMX_RM_WORDS * n)};
+    for (const Range& o : out)
+        for (const Range& i : in)
+            if (o.bytes && i.bytes && i.at < o.at + o.bytes && o.at < i.at + i.bytes) return KMX_E_ARG;
+    KMX_HIP(ctx, kmx::launch_reads_merge_emit(a, area, ctx->n_cu, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
 int kmx_reads_length_range(kmx_ctx* ctx, const uint64_t* d_offsets, uint64_t n_reads, uint32_t* h_min_len, uint32_t* h_max_len) {
     if (!ctx || (n_reads && !d_offsets)) return KMX_E_ARG;
     if (h_min_len) *h_min_len = 0;

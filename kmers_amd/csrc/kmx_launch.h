@@ -275,6 +275,26 @@ struct ReadsPairOverlap {
 };
 hipError_t launch_reads_adapter(const ReadsAdapter& a, int n_cu, hipStream_t st);
 hipError_t launch_reads_pair_overlap(const ReadsPairOverlap& a, int n_cu, hipStream_t st);
+// kmx_reads_merge.hip: the consensus read of every mate pair (kmx_reads_pair_merge).  The count lays the plan's partial sums (merged
+// pairs, merged bases, per block of pairs) into `area` of reads_merge_bytes(n_reads) and brings back h_out[0 .. 6) = merged pairs,
+// merged bases, then the first and last offset of batch 1 and of batch 2 (0, 0 for uniform reads): synchronous, one round trip.
+// The emit writes the offsets from the same area (where out_offsets is given), then bases, quality bytes and rows, a wave per pair;
+// asynchronous.  out_bases == nullptr with rows: the rows alone.
+struct ReadsPairMerge {
+    const uint8_t *bases1, *bases2;
+    const u64 *offsets1, *offsets2;   // nullptr: uniform reads of read_len1 / read_len2 bases
+    const uint8_t *quals1, *quals2;   // both or neither
+    const u64* insert;                // insert[r * insert_stride]: the insert size of pair r
+    u64 insert_stride;
+    u64 n_reads;
+    u32 read_len1, read_len2;
+    u32 phred_base, q_cap;
+    uint8_t *out_bases, *out_quals;
+    u64 *out_offsets, *rows;
+};
+size_t reads_merge_bytes(u64 n_reads);
+hipError_t launch_reads_merge_count(const ReadsPairMerge& a, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+hipError_t launch_reads_merge_emit(const ReadsPairMerge& a, void* area, int n_cu, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
