@@ -1521,6 +1521,28 @@ int kmx_count_adjacency_cut(kmx_ctx* ctx, const uint8_t* d_edges, const uint8_t*
     return KMX_OK;
 }
 
+// ---- what the kmx_reads_* calls share on the host ----
+namespace {
+// the size of a batch the calls accept (behind reads_ok): at most 2^40 reads and, of uniform reads, at most 2^62 bases
+bool reads_batch_ok(const kmx_reads* reads) {
+    if (reads->n_reads > (1ull << 40)) return false;
+    return reads->d_offsets || !reads->read_len || reads->n_reads <= (1ull << 62) / reads->read_len;
+}
+struct Range {   // device bytes, for "the bytes a call reads against the bytes it writes"; an empty range overlaps nothing
+    uintptr_t at;
+    uint64_t bytes;
+    bool overlaps(const Range& o) const { return bytes && o.bytes && at < o.at + o.bytes && o.at < at + bytes; }
+    static Range of_bytes(const void* base, uint64_t n) { return Range{reinterpret_cast<uintptr_t>(base), base ? n : 0u}; }
+    static Range of_words(const void* base, uint64_t n_words) { return of_bytes(base, 8u * n_words); }
+    // the bytes at `base` that a batch spans: from its first to its last offset (both from the device), or n_reads uniform reads
+    static Range of_batch(const void* base, const uint64_t* d_offsets, uint64_t n_reads, uint32_t read_len, uint64_t first, uint64_t last) {
+        if (!base) return Range{0, 0};
+        if (d_offsets) return Range{reinterpret_cast<uintptr_t>(base) + first, last >= first ? last - first : 0};
+        return of_bytes(base, n_reads * (uint64_t)read_len);
+    }
+};
+}  // namespace
+
 // ---- a new batch of reads from an old one (kmx_reads_edit.hip) ----
 // What kmx_reads_select and kmx_reads_gather share behind their argument checks (e.n_rows > 0): the work buffer, the plan's count,
 // the room and overlap checks, the emit.  n_out may be nullptr (gather: every row is an output read).
@@ -1541,14 +1563,7 @@ static int reads_edit_impl(kmx_ctx* ctx, const char* who, const kmx::ReadsEdit& 
         return KMX_E_NOMEM;
     }
     // the bytes the source batch spans against the bytes that are written
-    uintptr_t in_at = reinterpret_cast<uintptr_t>(e.bases);
-    uint64_t in_bytes = e.n_reads * (uint64_t)e.read_len;
-    if (e.offsets) {
-        in_at += h[2];
-        in_bytes = h[3] >= h[2] ? h[3] - h[2] : 0;
-    }
-    const uintptr_t out_at = reinterpret_cast<uintptr_t>(d_out_bases);
-    if (h[1] && in_bytes && in_at < out_at + h[1] && out_at < in_at + in_bytes) return KMX_E_ARG;
+    if (Range::of_batch(e.bases, e.offsets, e.n_reads, e.read_len, h[2], h[3]).overlaps(Range::of_bytes(d_out_bases, h[1]))) return KMX_E_ARG;
     KMX_HIP(ctx, kmx::launch_reads_edit_emit(e, area, h[0], h[1], d_out_bases, d_out_offsets, d_out_index, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
@@ -1558,8 +1573,7 @@ int kmx_reads_select(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_keep
                      uint64_t min_len, uint8_t* d_out_bases, uint64_t* d_out_offsets, uint64_t* d_out_index, uint64_t max_reads, uint64_t max_bases,
                      uint64_t* h_n_reads, uint64_t* h_n_bases) {
     if (!ctx || !reads_ok(reads) || !h_n_reads || !h_n_bases || ((d_out_bases == nullptr) != (d_out_offsets == nullptr))) return KMX_E_ARG;
-    if ((d_span && span_stride == 0) || reads->n_reads > (1ull << 40)) return KMX_E_ARG;
-    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+    if ((d_span && span_stride == 0) || !reads_batch_ok(reads)) return KMX_E_ARG;
     *h_n_reads = *h_n_bases = 0;
     if (reads->n_reads == 0) return KMX_OK;
     const kmx::ReadsEdit e{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, d_keep, d_span, span_stride, span_k, min_len, nullptr,
@@ -1570,8 +1584,7 @@ int kmx_reads_select(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_keep
 int kmx_reads_gather(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_index, uint64_t n_index, const uint64_t* d_span, uint64_t span_stride,
                      uint32_t span_k, uint8_t* d_out_bases, uint64_t* d_out_offsets, uint64_t max_bases, uint64_t* h_n_bases) {
     if (!ctx || !reads_ok(reads) || !h_n_bases || ((d_out_bases == nullptr) != (d_out_offsets == nullptr))) return KMX_E_ARG;
-    if ((d_span && span_stride == 0) || reads->n_reads > (1ull << 40) || n_index > (1ull << 32) || (n_index && !d_index)) return KMX_E_ARG;
-    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+    if ((d_span && span_stride == 0) || !reads_batch_ok(reads) || n_index > (1ull << 32) || (n_index && !d_index)) return KMX_E_ARG;
     *h_n_bases = 0;
     if (n_index == 0) return KMX_OK;
     const kmx::ReadsEdit e{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, nullptr, d_span, span_stride, span_k, 0u, d_index, n_index};
@@ -2409,8 +2422,7 @@ int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes,
 int kmx_reads_quality(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_quals, uint32_t phred_base, uint32_t min_q, uint32_t trim_q, uint32_t k,
                       const uint64_t* d_weights, uint8_t* d_masked, uint64_t* d_rows) {
     if (!ctx || !reads_ok(reads) || phred_base > 255u || min_q > 255u || trim_q > 255u || (!d_masked && !d_rows)) return KMX_E_ARG;
-    if (reads->n_reads > (1ull << 40)) return KMX_E_ARG;
-    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return KMX_E_ARG;
+    if (!reads_batch_ok(reads)) return KMX_E_ARG;
     if (reads->n_reads == 0) return KMX_OK;
     const bool bytes = reads->d_offsets || reads->read_len;   // (uniform reads of no bases: rows of zeros, nothing is read)
     if (bytes && !d_quals) return KMX_E_ARG;
@@ -2418,23 +2430,23 @@ int kmx_reads_quality(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_qua
     if (bytes && d_masked) {
         // the bytes the batch spans (ragged: its first and last offset, one round trip) against the bytes that are written; the
         // quality bytes are read on another dword grid than the bases, so they must not be written over either
-        uint64_t lo = 0, hi = reads->n_reads * (uint64_t)reads->read_len;
+        uint64_t first = 0, last = 0;
         if (reads->d_offsets) {
             unsigned long long* h = ctx->h_pinned;
             KMX_HIP(ctx, hipMemcpyAsync(h, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
             KMX_HIP(ctx, hipMemcpyAsync(h + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
             KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            lo = h[0];
-            hi = h[1] >= h[0] ? h[1] : h[0];
+            first = h[0];
+            last = h[1];
         }
-        const uintptr_t m0 = reinterpret_cast<uintptr_t>(d_masked) + lo, m1 = reinterpret_cast<uintptr_t>(d_masked) + hi;
-        const uintptr_t b0 = reinterpret_cast<uintptr_t>(reads->d_bases) + lo, b1 = reinterpret_cast<uintptr_t>(reads->d_bases) + hi;
-        const uintptr_t q0 = reinterpret_cast<uintptr_t>(d_quals) + lo, q1 = reinterpret_cast<uintptr_t>(d_quals) + hi;
-        if (d_masked != reads->d_bases && m0 < b1 && b0 < m1) return KMX_E_ARG;
-        if (m0 < q1 && q0 < m1) return KMX_E_ARG;
+        auto spanned = [&](const void* base) { return Range::of_batch(base, reads->d_offsets, reads->n_reads, reads->read_len, first, last); };
+        const Range m = spanned(d_masked);
+        if (d_masked != reads->d_bases && m.overlaps(spanned(reads->d_bases))) return KMX_E_ARG;
+        if (m.overlaps(spanned(d_quals))) return KMX_E_ARG;
     }
-    KMX_HIP(ctx, kmx::launch_reads_quality(reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, d_quals, phred_base, min_q, trim_q, k,
-                                           d_weights, d_masked, d_rows, ctx->n_cu, ctx->stream));
+    const kmx::ReadsQuality a{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, d_quals, phred_base, min_q, trim_q, k, d_weights,
+                              d_masked, d_rows};
+    KMX_HIP(ctx, kmx::launch_reads_quality(a, ctx->n_cu, ctx->stream));
     return KMX_OK;
 }
 
@@ -2443,9 +2455,7 @@ namespace {
 // what both calls refuse in a batch and in the thresholds
 bool adapter_args_ok(const kmx_reads* reads, uint32_t min_overlap, uint32_t err_num, uint32_t err_den) {
     if (!reads_ok(reads) || min_overlap == 0u || err_den == 0u || err_num > err_den) return false;
-    if (reads->n_reads > (1ull << 40)) return false;
-    if (!reads->d_offsets && reads->read_len && reads->n_reads > (1ull << 62) / reads->read_len) return false;
-    return true;
+    return reads_batch_ok(reads);
 }
 }  // namespace
 
@@ -2507,9 +2517,7 @@ int kmx_reads_pair_merge(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_reads*
     if (!ctx || !reads_ok(reads1) || !reads_ok(reads2) || !h_n_merged || !h_n_bases) return KMX_E_ARG;
     *h_n_merged = *h_n_bases = 0;
     const uint64_t n = reads1->n_reads;
-    if (n != reads2->n_reads || n > (1ull << 40) || (uint64_t)phred_base + q_cap > 255u) return KMX_E_ARG;
-    for (const kmx_reads* r : {reads1, reads2})
-        if (!r->d_offsets && r->read_len && n > (1ull << 62) / r->read_len) return KMX_E_ARG;
+    if (n != reads2->n_reads || !reads_batch_ok(reads1) || !reads_batch_ok(reads2) || (uint64_t)phred_base + q_cap > 255u) return KMX_E_ARG;
     if ((d_quals1 == nullptr) != (d_quals2 == nullptr) || (d_out_quals && !d_quals1)) return KMX_E_ARG;
     if ((d_out_bases == nullptr) != (d_out_offsets == nullptr) || (d_out_quals && !d_out_bases)) return KMX_E_ARG;
     if (n && (!d_insert || insert_stride == 0 || (n - 1u) > ((1ull << 60) - 1u) / insert_stride)) return KMX_E_ARG;
@@ -2527,26 +2535,17 @@ int kmx_reads_pair_merge(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_reads*
     if (d_out_bases)
         if (int st = room_for(ctx, who, h[1], "bases merged", max_bases)) return st;
     // the bytes the inputs span against the bytes that are written
-    struct Range {
-        uintptr_t at;
-        uint64_t bytes;
-    };
     auto batch = [&](const void* base, const kmx_reads* r, uint64_t first, uint64_t last) {
-        const uintptr_t at = reinterpret_cast<uintptr_t>(base);
-        if (!base) return Range{0, 0};
-        if (r->d_offsets) return Range{at + first, last >= first ? last - first : 0};
-        return Range{at, n * (uint64_t)r->read_len};
+        return Range::of_batch(base, r->d_offsets, n, r->read_len, first, last);
     };
-    auto words = [](const void* base, uint64_t n_words) { return Range{reinterpret_cast<uintptr_t>(base), base ? 8u * n_words : 0u}; };
     const Range in[] = {batch(reads1->d_bases, reads1, h[2], h[3]), batch(reads2->d_bases, reads2, h[4], h[5]), batch(d_quals1, reads1, h[2], h[3]),
-                        batch(d_quals2, reads2, h[4], h[5]), words(reads1->d_offsets, n + 1u), words(reads2->d_offsets, n + 1u),
-                        words(d_insert, (n - 1u) * insert_stride + 1u)};
-    const Range out[] = {Range{reinterpret_cast<uintptr_t>(d_out_bases), d_out_bases ? h[1] : 0u},
-                         Range{reinterpret_cast<uintptr_t>(d_out_quals), d_out_quals ? h[1] : 0u}, words(d_out_offsets, n + 1u),
-                         words(d_rows, KMX_RM_WORDS * n)};
+                        batch(d_quals2, reads2, h[4], h[5]), Range::of_words(reads1->d_offsets, n + 1u), Range::of_words(reads2->d_offsets, n + 1u),
+                        Range::of_words(d_insert, (n - 1u) * insert_stride + 1u)};
+    const Range out[] = {Range::of_bytes(d_out_bases, h[1]), Range::of_bytes(d_out_quals, h[1]), Range::of_words(d_out_offsets, n + 1u),
+                         Range::of_words(d_rows, KMX_RM_WORDS * n)};
     for (const Range& o : out)
         for (const Range& i : in)
-            if (o.bytes && i.bytes && i.at < o.at + o.bytes && o.at < i.at + i.bytes) return KMX_E_ARG;
+            if (o.overlaps(i)) return KMX_E_ARG;
     KMX_HIP(ctx, kmx::launch_reads_merge_emit(a, area, ctx->n_cu, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;

@@ -205,12 +205,18 @@ __device__ __forceinline__ u32 wave_max_u32(u32 v) {
 #define KMX_DPP64(v, ctrl)                                                                                         \
     (((u64)(u32)__builtin_amdgcn_update_dpp(0, (int)(u32)((v) >> 32), (ctrl), 0xF, 0xF, true) << 32) |          \
      (u64)(u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(v), (ctrl), 0xF, 0xF, true))
+// Lane l's 64-bit value, wave-uniform (l is wave-uniform): two v_readlane_b32.  The form that takes the halves is for a caller that
+// reads several lanes of one value: splitting the value once, outside, is what keeps the scalar adds behind wave_sum as they are.
+__device__ __forceinline__ u64 readlane64(u32 lo, u32 hi, int l) {
+    return ((u64)(u32)__builtin_amdgcn_readlane((int)hi, l) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, l);
+}
+__device__ __forceinline__ u64 readlane64(u64 v, u32 l) { return readlane64((u32)v, (u32)(v >> 32), (int)l); }
 __device__ __forceinline__ u64 wave_lanes_0_16_32_48(u64 v, bool add) {
     const u32 lo = (u32)v, hi = (u32)(v >> 32);
     u64 r = 0;
 #pragma unroll
     for (int l = 0; l < 64; l += 16) {
-        const u64 x = ((u64)(u32)__builtin_amdgcn_readlane((int)hi, l) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, l);
+        const u64 x = readlane64(lo, hi, l);
         r = add ? r + x : r ^ x;
     }
     return r;
@@ -247,8 +253,7 @@ __device__ __forceinline__ u64 half_sum(u64 v) {
     v += KMX_DPP64(v, 0x124);
     v += KMX_DPP64(v, 0x128);
     const u32 lo = (u32)v, hi = (u32)(v >> 32);
-    auto at = [&](int l) { return ((u64)(u32)__builtin_amdgcn_readlane((int)hi, l) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, l); };
-    const u64 h0 = at(0) + at(16), h1 = at(32) + at(48);
+    const u64 h0 = readlane64(lo, hi, 0) + readlane64(lo, hi, 16), h1 = readlane64(lo, hi, 32) + readlane64(lo, hi, 48);
     return (threadIdx.x & 32u) ? h1 : h0;
 }
 

@@ -225,6 +225,9 @@ hipError_t launch_count_link_support(const u64* segments, u64 n_segments, const 
 hipError_t launch_count_adjacency_cut(const uint8_t* edges, const uint8_t* flips, const u64* nbr, u64 n, const u64* nodes, const u64* offsets,
                                       u64 n_unitigs, const u64* place, const u64* link_offsets, u64 n_links, const uint8_t* cut, uint8_t* edges_out,
                                       hipStream_t st);
+// The four kmx_reads_*.hip units share kmx_reads_common.h (the span of a read, "is one of ACGTacgt", the wave-per-read launch shape);
+// the two that produce a batch, edit and merge, share kmx_reads_plan.h on top of it (the plan's place in the work area, the body
+// of its count kernel, the scans and the read-back).
 // kmx_reads_edit.hip: a new ragged batch from an old one (kmx_reads_select / kmx_reads_gather).  A ROW is a source read (select:
 // index == nullptr, n_rows == n_reads) or an entry of the index (gather).  The count plans every row in an area of
 // reads_edit_bytes(n_rows) and brings back h_out[0 .. 4) = output reads, output bases, the batch's first and last offset (0, 0 for
@@ -249,8 +252,18 @@ hipError_t launch_reads_edit_emit(const ReadsEdit& e, void* area, u64 n_out, u64
                                   hipStream_t st);
 // kmx_reads_quality.hip: the masked copy and / or KMX_RQ_WORDS u64 per read out of the bases and the quality bytes (kmx_reads_quality;
 // a wave per read, asynchronous)
-hipError_t launch_reads_quality(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 read_len, const uint8_t* quals, u32 phred, u32 min_q,
-                                u32 trim_q, u32 k, const u64* weights, uint8_t* masked, u64* rows, int n_cu, hipStream_t st);
+struct ReadsQuality {
+    const uint8_t* bases;
+    const u64* offsets;   // nullptr: uniform reads of read_len bases
+    u64 n_reads;
+    u32 read_len;
+    const uint8_t* quals;
+    u32 phred, min_q, trim_q, k;
+    const u64* weights;   // 256 words or nullptr
+    uint8_t* masked;      // or nullptr
+    u64* rows;            // KMX_RQ_WORDS per read, or nullptr
+};
+hipError_t launch_reads_quality(const ReadsQuality& a, int n_cu, hipStream_t st);
 // kmx_reads_adapter.hip: KMX_RA_WORDS u64 per read (kmx_reads_adapter) and KMX_RP_WORDS u64 per mate pair (kmx_reads_pair_overlap); a
 // wave per read or pair, asynchronous, no work buffer.  The adapters travel in the kernel arguments as bit planes: bit j of lo / hi =
 // the low / high bit of the code (byte >> 1) & 3 of adapter base j, bit j of care = base j exists and is no wildcard.

@@ -24,26 +24,18 @@
 // it is loaded, no bit reversal -- go to LDS once (at most 1024 bases: 17 words and a zero word behind them, per plane), a lane
 // owns a shift d and walks the overlap word by word; it stops once it is past max_mism, which only a non-hit can be.
 // No atomics, no scratch, no work buffer; a row is written by the four low lanes of the one wave that owns the read.
-#include "kmx_device.h"
-#include "kmx_launch.h"
+// The bounds of a read, "is one of ACGTacgt" and the wave-per-read launch shape are the family's (kmx_reads_common.h).
+#include "kmx_reads_common.h"
 
 namespace kmx {
 
 namespace {
 
-constexpr u32 RA_THREADS = 256;
-constexpr u32 RA_WAVES = RA_THREADS / 64u;
-constexpr u32 RA_BLOCKS_PER_CU = 8;                       // 8 waves per SIMD
 constexpr u32 RP_WORDS_MAX = KMX_RP_MAX_LEN / 64u + 2u;   // the plane words of a mate on its grid (A + L <= 1027) and the zero word behind them
 
 struct Planes {
     u64 lo, hi, val;
 };
-
-__device__ __forceinline__ bool is_acgt(u32 b) {
-    const u32 u = b & 0xDFu;
-    return u == 'A' || u == 'C' || u == 'G' || u == 'T';
-}
 
 // A read on its dword grid (see above).  span = A + L, 0 for an empty read.
 struct Grid {
@@ -87,30 +79,16 @@ __device__ __forceinline__ Planes planes64(u32 dw, const Grid& G, u32 q0, u32 la
 __device__ __forceinline__ u64 funnel(u64 lo, u64 hi, u32 sh) { return sh ? (lo >> sh) | (hi << (64u - sh)) : lo; }
 __device__ __forceinline__ u64 low_bits(u32 n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }
 
-// the length of read r (a read of 2^31 bases or more, or an offsets pair that descends: 0) and its first byte's offset
-__device__ __forceinline__ u32 read_bounds(const u64* offsets, u32 read_len, u64 r, u64& off) {
-    u64 len;
-    if (offsets) {
-        off = offsets[r];
-        const u64 e = offsets[r + 1u];
-        len = e >= off ? e - off : 0u;
-    } else {
-        off = r * (u64)read_len;
-        len = read_len;
-    }
-    return len >= (1ull << 31) ? 0u : (u32)len;
-}
-
 }  // namespace
 
-__global__ void __launch_bounds__(RA_THREADS) reads_adapter_kernel(const ReadsAdapter a) {
+__global__ void __launch_bounds__(WPR_THREADS) reads_adapter_kernel(const ReadsAdapter a) {
     const u32 lane = threadIdx.x & 63u;
     const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const u64 stride = (u64)gridDim.x * RA_WAVES;
+    const u64 stride = (u64)gridDim.x * WPR_WAVES;
     const u32 all = (1u << a.n_adapters) - 1u;
-    for (u64 r = (u64)blockIdx.x * RA_WAVES + wv; r < a.n_reads; r += stride) {
+    for (u64 r = (u64)blockIdx.x * WPR_WAVES + wv; r < a.n_reads; r += stride) {
         u64 off;
-        const u32 L = read_bounds(a.offsets, a.read_len, r, off);
+        const u32 L = read_span(a.offsets, a.read_len, r, off);
         const uintptr_t src = reinterpret_cast<uintptr_t>(a.bases) + off;
         bool found = false;
         u32 keep = L, hits = 0;
@@ -168,11 +146,11 @@ __global__ void __launch_bounds__(RA_THREADS) reads_adapter_kernel(const ReadsAd
     }
 }
 
-__global__ void __launch_bounds__(RA_THREADS) reads_pair_overlap_kernel(const ReadsPairOverlap a) {
-    __shared__ u64 planes[RA_WAVES][2][3][RP_WORDS_MAX];
+__global__ void __launch_bounds__(WPR_THREADS) reads_pair_overlap_kernel(const ReadsPairOverlap a) {
+    __shared__ u64 planes[WPR_WAVES][2][3][RP_WORDS_MAX];
     const u32 lane = threadIdx.x & 63u;
     const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const u64 stride = (u64)gridDim.x * RA_WAVES;
+    const u64 stride = (u64)gridDim.x * WPR_WAVES;
     u64(*const X)[RP_WORDS_MAX] = planes[wv][0];
     u64(*const Y)[RP_WORDS_MAX] = planes[wv][1];
     // what one lane wrote the others read: the wave's own barrier (the waves of a block share nothing)
@@ -181,9 +159,9 @@ __global__ void __launch_bounds__(RA_THREADS) reads_pair_overlap_kernel(const Re
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
-    for (u64 r = (u64)blockIdx.x * RA_WAVES + wv; r < a.n_reads; r += stride) {
+    for (u64 r = (u64)blockIdx.x * WPR_WAVES + wv; r < a.n_reads; r += stride) {
         u64 off1, off2;
-        const u32 L1 = read_bounds(a.offsets1, a.read_len1, r, off1), L2 = read_bounds(a.offsets2, a.read_len2, r, off2);
+        const u32 L1 = read_span(a.offsets1, a.read_len1, r, off1), L2 = read_span(a.offsets2, a.read_len2, r, off2);
         const uintptr_t src1 = reinterpret_cast<uintptr_t>(a.bases1) + off1, src2 = reinterpret_cast<uintptr_t>(a.bases2) + off2;
         u32 best_n = 0, best_i = 0, best_m = 0;
         if (L1 && L2 && L1 <= KMX_RP_MAX_LEN && L2 <= KMX_RP_MAX_LEN) {
@@ -252,21 +230,13 @@ __global__ void __launch_bounds__(RA_THREADS) reads_pair_overlap_kernel(const Re
     }
 }
 
-namespace {
-unsigned grid_for(u64 n_reads, int n_cu) {
-    const u64 want = (n_reads + RA_WAVES - 1u) / RA_WAVES;
-    const u64 cap = (u64)(n_cu > 0 ? n_cu : 256) * RA_BLOCKS_PER_CU * 4u;
-    return (unsigned)(want < cap ? want : cap);
-}
-}  // namespace
-
 hipError_t launch_reads_adapter(const ReadsAdapter& a, int n_cu, hipStream_t st) {
-    hipLaunchKernelGGL(reads_adapter_kernel, dim3(grid_for(a.n_reads, n_cu)), dim3(RA_THREADS), 0, st, a);
+    hipLaunchKernelGGL(reads_adapter_kernel, dim3(wave_per_read_grid(a.n_reads, n_cu)), dim3(WPR_THREADS), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_reads_pair_overlap(const ReadsPairOverlap& a, int n_cu, hipStream_t st) {
-    hipLaunchKernelGGL(reads_pair_overlap_kernel, dim3(grid_for(a.n_reads, n_cu)), dim3(RA_THREADS), 0, st, a);
+    hipLaunchKernelGGL(reads_pair_overlap_kernel, dim3(wave_per_read_grid(a.n_reads, n_cu)), dim3(WPR_THREADS), 0, st, a);
     return hipGetLastError();
 }
 

@@ -4,12 +4,12 @@
 // A ROW is a source read (select) or an entry of the index (gather); a row has a CLIP -- where its bytes start in d_bases and how
 // many there are -- and is kept or not.  A thread plans eight consecutive rows, a block 2048.
 //
-// Plan.  The count kernel sums the kept rows and their bytes per block; one block scans the two arrays of partial sums (the count
-// family's scan_single_kernel) and the two totals come back to the host with the batch's first and last offset: one round trip,
-// which is all a count-only call costs.  The write kernel computes the clips again -- 16 bytes of offsets, a span word and a keep
-// byte per row, cheaper than an array that carries them -- scans kept rows and bytes over the block and writes, per OUTPUT read, its
-// output offset, its source index (optional) and into the work buffer its source start.  The length of an output read is the
-// difference of its output offsets.
+// Plan (its prologue is kmx_reads_plan.h's, the span of a read kmx_reads_common.h's).  The count kernel sums the kept rows and their
+// bytes per block; one block scans the two arrays of partial sums (the count family's scan_single_kernel) and the two totals come
+// back to the host with the batch's first and last offset: one round trip, all a count-only call costs.  The write kernel
+// computes the clips again -- 16 bytes of offsets, a span word and a keep byte per row, cheaper than an array that carries them --
+// scans kept rows and bytes over the block and writes, per OUTPUT read, its output offset, its source index (optional) and into
+// the work buffer its source start.  The length of an output read is the difference of its output offsets.
 //
 // Copy.  Built around the output: a lane owns aligned 16-byte pieces of d_out_bases, a block 4096 consecutive
 // pieces (64 KiB; a wave's 64 lanes store 1 KiB contiguous, sixteen times).  One search per block: the output read that holds the
@@ -25,14 +25,12 @@
 // where they are partial: those go out byte by byte, so no byte outside [0, n_bases) is written.  Everything is unrolled over
 // registers: no scratch, no atomics; 16 KiB of LDS per block, eight waves per SIMD.  (A variant that searched and loaded a lane's
 // four pieces together -- 122 VGPRs, four waves -- measured 40 % slower: what hides the latency here is the waves in flight.)
-#include "kmx_count_common.h"
+#include "kmx_reads_plan.h"
 
 namespace kmx {
 
 namespace {
 
-constexpr u32 RPT = 8;                 // rows per thread in the plan
-constexpr u32 ROWS = CT * RPT;         // rows per block
 constexpr u32 CP_ITER = 16;            // pieces per lane
 constexpr u32 CP_PIECES = CT * CP_ITER;   // pieces per block: 64 KiB of output
 constexpr u32 CP_NS = 1024;            // output reads staged in LDS per block
@@ -51,16 +49,8 @@ __host__ __device__ __forceinline__ Clip clip_of(const ReadsEdit& e, u64 row) {
         r = e.index[row];
         if (r >= e.n_reads) return Clip{0u, 0u, true};   // an empty read
     }
-    u64 a, L;
-    if (e.offsets) {
-        a = e.offsets[r];
-        const u64 b = e.offsets[r + 1u];
-        L = b >= a ? b - a : 0u;
-    } else {
-        a = r * (u64)e.read_len;
-        L = e.read_len;
-    }
-    if (L >= (1ull << 31)) L = 0u;   // (the scans skip such a read)
+    u64 a;
+    const u64 L = read_span(e.offsets, e.read_len, r, a);
     u64 start = 0u, len = L;
     if (e.span) {
         const u64 w = e.span[r * e.span_stride];
@@ -81,27 +71,16 @@ __host__ __device__ __forceinline__ Clip clip_of(const ReadsEdit& e, u64 row) {
 // partial[b] = kept rows of block b, partial[n_blocks + b] = their bytes; tail[2], tail[3] = the batch's first and last offset
 template <bool GATHER>
 __global__ void __launch_bounds__(CT) reads_plan_count_kernel(ReadsEdit e, u64* __restrict__ partial, u64 n_blocks, u64* __restrict__ tail) {
-    __shared__ u64 sh[CT / 64];
-    const u64 i0 = (u64)blockIdx.x * ROWS + (u64)threadIdx.x * RPT;
-    u64 n = 0, bytes = 0;
-#pragma unroll
-    for (u32 j = 0; j < RPT; ++j) {
-        if (i0 + j < e.n_rows) {
-            const Clip c = clip_of<GATHER>(e, i0 + j);
-            n += c.kept ? 1u : 0u;
-            bytes += c.len;
-        }
-    }
-    const u64 tn = block_sum(n, sh);
-    const u64 tb = block_sum(bytes, sh);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = tn;
-        partial[n_blocks + blockIdx.x] = tb;
-        if (blockIdx.x == 0) {
+    plan_count(
+        e.n_rows, partial, n_blocks,
+        [&e](u64 row) {
+            const Clip c = clip_of<GATHER>(e, row);
+            return PlanRow{c.kept, c.len};
+        },
+        [&e, tail] {
             tail[2] = e.offsets && e.n_reads ? e.offsets[0] : 0u;
             tail[3] = e.offsets && e.n_reads ? e.offsets[e.n_reads] : 0u;
-        }
-    }
+        });
 }
 
 // per output read o: out_offsets[o], src[o], out_index[o]; out_offsets[n_out] = n_bases (tail[0], tail[1]: the scanned totals)
@@ -291,32 +270,28 @@ __global__ void __launch_bounds__(CT) reads_copy_kernel(const uint8_t* __restric
     }
 }
 
-u64 plan_blocks(u64 n_rows) { return ceil_div(n_rows, (u64)ROWS); }
+// the work area: the source start of every output read, then the plan
+Plan plan_of(void* area, u64 n_rows) { return plan_at(static_cast<char*>(area) + align256(8u * n_rows), n_rows); }
 
 }  // namespace
 
 // the source start of every output read, then the partial sums (kept rows, bytes) of every block and four words for the host
-size_t reads_edit_bytes(u64 n_rows) { return align256(8u * n_rows) + align256(8u * (2u * plan_blocks(n_rows) + 4u)); }
+size_t reads_edit_bytes(u64 n_rows) { return align256(8u * n_rows) + plan_bytes(n_rows, 4u); }
 
 hipError_t launch_reads_edit_count(const ReadsEdit& e, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st) {
-    const u64 nb = plan_blocks(e.n_rows);
-    u64* partial = reinterpret_cast<u64*>(static_cast<char*>(area) + align256(8u * e.n_rows));
-    u64* tail = partial + 2u * nb;
-    if (e.index) hipLaunchKernelGGL(reads_plan_count_kernel<true>, dim3((unsigned)nb), dim3(CT), 0, st, e, partial, nb, tail);
-    else hipLaunchKernelGGL(reads_plan_count_kernel<false>, dim3((unsigned)nb), dim3(CT), 0, st, e, partial, nb, tail);
-    hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial, nb, tail);
-    hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial + nb, nb, tail + 1);
-    return read_back(h_pinned, tail, 4u, h_out, st);
+    const Plan p = plan_of(area, e.n_rows);
+    if (e.index) hipLaunchKernelGGL(reads_plan_count_kernel<true>, dim3((unsigned)p.n_blocks), dim3(CT), 0, st, e, p.partial, p.n_blocks, p.tail);
+    else hipLaunchKernelGGL(reads_plan_count_kernel<false>, dim3((unsigned)p.n_blocks), dim3(CT), 0, st, e, p.partial, p.n_blocks, p.tail);
+    return plan_totals(p, 4u, h_pinned, h_out, st);
 }
 
 hipError_t launch_reads_edit_emit(const ReadsEdit& e, void* area, u64 n_out, u64 n_bases, uint8_t* out_bases, u64* out_offsets, u64* out_index,
                                   hipStream_t st) {
-    const u64 nb = plan_blocks(e.n_rows);
+    const Plan p = plan_of(area, e.n_rows);
     u64* src = static_cast<u64*>(area);
-    const u64* partial = reinterpret_cast<const u64*>(static_cast<char*>(area) + align256(8u * e.n_rows));
-    const u64* tail = partial + 2u * nb;
-    if (e.index) hipLaunchKernelGGL(reads_plan_write_kernel<true>, dim3((unsigned)nb), dim3(CT), 0, st, e, partial, nb, tail, src, out_offsets, out_index);
-    else hipLaunchKernelGGL(reads_plan_write_kernel<false>, dim3((unsigned)nb), dim3(CT), 0, st, e, partial, nb, tail, src, out_offsets, out_index);
+    const dim3 grid((unsigned)p.n_blocks);
+    if (e.index) hipLaunchKernelGGL(reads_plan_write_kernel<true>, grid, dim3(CT), 0, st, e, p.partial, p.n_blocks, p.tail, src, out_offsets, out_index);
+    else hipLaunchKernelGGL(reads_plan_write_kernel<false>, grid, dim3(CT), 0, st, e, p.partial, p.n_blocks, p.tail, src, out_offsets, out_index);
     if (n_bases != 0) {
         const u64 pieces = (((u64)reinterpret_cast<uintptr_t>(out_bases) & 15u) + n_bases + 15u) >> 4;
         hipLaunchKernelGGL(reads_copy_kernel, dim3((unsigned)ceil_div(pieces, (u64)CP_PIECES)), dim3(CT), 0, st, e.bases, out_offsets, src, n_out, n_bases,

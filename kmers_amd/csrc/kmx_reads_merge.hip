@@ -1,11 +1,13 @@
 // kmx_reads_merge.hip -- overlapping mate pairs merged into consensus reads: kmx_reads_pair_merge.  kmx.h has the contract (which
 // pairs merge, the four classes of an overlap position, the words of a row); DESIGN 4.6.17 has the reasoning and the figures.
 //
-// Plan.  One length per pair -- the insert word where the pair merges, 0 otherwise -- out of two offset pairs and the insert word.
-// A thread plans eight consecutive pairs, a block 2048: the count kernel sums merged pairs and bases per block, one block scans
-// the two arrays of partial sums (the count family's scan_single_kernel) and the two totals come back to the host with the first
-// and last offset of both batches: one round trip, all a count-only call without rows costs.  The write kernel computes the lengths
-// again, scans them over the block and writes one output offset per PAIR: the output batch has as many reads as there are pairs.
+// Plan (its prologue is the family's, kmx_reads_plan.h; the length between two offsets and the wave-per-read launch shape are
+// kmx_reads_common.h's).  One length per pair -- the insert word where the pair merges, 0 otherwise -- out of two offset pairs and the insert
+// word.  A thread plans eight consecutive pairs, a block 2048: the count kernel sums merged pairs and bases per block, one block
+// scans the two arrays of partial sums (the count family's scan_single_kernel) and the two totals come back to the host with the
+// first and last offset of both batches: one round trip, all a count-only call without rows costs.  The write kernel computes the
+// lengths again, scans them over the block and writes one output offset per PAIR: the output batch has as many reads as there are
+// pairs.
 //
 // Merge.  A WAVE PER PAIR, built around the output: the merged read is laid on the grid of aligned dwords of d_out_bases that holds
 // it, a lane owns one dword -- four consecutive positions i of the merged read -- per step of 256 positions, and stores it with
@@ -19,17 +21,12 @@
 // of a row are popcounts of the masks, packed into two registers per lane and summed over the wave once per pair.  The six words of
 // a pair are one load of six lanes, requested a pair ahead.  No LDS, no atomics, no scratch; a row is written by the four low lanes
 // of the wave that owns the pair.
-#include "kmx_count_common.h"
+#include "kmx_reads_plan.h"
 
 namespace kmx {
 
 namespace {
 
-constexpr u32 RM_THREADS = 256;
-constexpr u32 RM_WAVES = RM_THREADS / 64u;
-constexpr u32 RM_BLOCKS_PER_CU = 8;    // 8 waves per SIMD
-constexpr u32 RPT = 8;                 // pairs per thread in the plan
-constexpr u32 ROWS = CT * RPT;         // pairs per block in the plan
 constexpr u32 ONES = 0x01010101u, HIGH = 0x80808080u;
 
 // The WORDS of pair r, six u64: where mate 1 begins and ends in d_bases, where mate 2 does, the insert word, the pair's output offset
@@ -45,18 +42,13 @@ __device__ __forceinline__ u64 pair_word(const ReadsPairMerge& a, u64 r, u32 w, 
     return out && w == W_OUT ? a.out_offsets[r] : 0u;
 }
 
-// the mates of a pair and the length of its merged read out of its words: the insert word if the pair merges (kmx.h), otherwise 0.
-// A mate of 2^31 bases or more, or an offsets pair that descends, has length 0.
+// the mates of a pair (their lengths: span_len) and the length of its merged read: the insert word if the pair merges (kmx.h), else 0
 struct Pair {
     u64 off1, off2;
     u32 L1, L2, I;
 };
 __device__ __forceinline__ Pair pair_from(u64 b1, u64 e1, u64 b2, u64 e2, u64 insert) {
-    auto len = [](u64 b, u64 e) {
-        const u64 n = e >= b ? e - b : 0u;
-        return n >= (1ull << 31) ? 0u : (u32)n;
-    };
-    Pair p{b1, b2, len(b1, e1), len(b2, e2), 0u};
+    Pair p{b1, b2, span_len(b1, e1), span_len(b2, e2), 0u};
     const bool ok = p.L1 >= 1u && p.L2 >= 1u && p.L1 <= KMX_RP_MAX_LEN && p.L2 <= KMX_RP_MAX_LEN && insert > 0u && insert < (u64)p.L1 + p.L2;
     p.I = ok ? (u32)insert : 0u;
     return p;
@@ -69,29 +61,18 @@ __device__ __forceinline__ Pair pair_of(const ReadsPairMerge& a, u64 r) {
 // partial[b] = merged pairs of block b, partial[n_blocks + b] = their bases; tail[2 .. 6) = first and last offset of batch 1, of batch 2
 __global__ void __launch_bounds__(CT) reads_merge_plan_count_kernel(const ReadsPairMerge a, u64* __restrict__ partial, u64 n_blocks,
                                                                     u64* __restrict__ tail) {
-    __shared__ u64 sh[CT / 64];
-    const u64 i0 = (u64)blockIdx.x * ROWS + (u64)threadIdx.x * RPT;
-    u64 n = 0, bytes = 0;
-#pragma unroll
-    for (u32 j = 0; j < RPT; ++j) {
-        if (i0 + j < a.n_reads) {
-            const u32 len = pair_of(a, i0 + j).I;
-            n += len ? 1u : 0u;
-            bytes += len;
-        }
-    }
-    const u64 tn = block_sum(n, sh);
-    const u64 tb = block_sum(bytes, sh);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = tn;
-        partial[n_blocks + blockIdx.x] = tb;
-        if (blockIdx.x == 0) {
+    plan_count(
+        a.n_reads, partial, n_blocks,
+        [&a](u64 r) {
+            const u32 len = pair_of(a, r).I;
+            return PlanRow{len != 0u, len};
+        },
+        [&a, tail] {
             tail[2] = a.offsets1 ? a.offsets1[0] : 0u;
             tail[3] = a.offsets1 ? a.offsets1[a.n_reads] : 0u;
             tail[4] = a.offsets2 ? a.offsets2[0] : 0u;
             tail[5] = a.offsets2 ? a.offsets2[a.n_reads] : 0u;
-        }
-    }
+        });
 }
 
 // out_offsets[r] for every pair r; out_offsets[n_reads] = n_bases (tail[1]: the scanned total)
@@ -165,23 +146,21 @@ __device__ __forceinline__ void store4(uint8_t* dst, int i0, u32 len, u32 w, boo
 
 // QUALS: the mates have quality bytes (without: every quality byte reads as 0, so every q is 0).  OUT: the batch is written (without: the rows alone).
 template <bool QUALS, bool OUT>
-__global__ void __launch_bounds__(RM_THREADS) reads_merge_kernel(const ReadsPairMerge a) {
+__global__ void __launch_bounds__(WPR_THREADS) reads_merge_kernel(const ReadsPairMerge a) {
     const u32 lane = threadIdx.x & 63u;
     const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const u64 stride = (u64)gridDim.x * RM_WAVES;
+    const u64 stride = (u64)gridDim.x * WPR_WAVES;
     // Lane w < 6 loads word w of a pair, so the six words of a pair are ONE load of the wave, and those of the NEXT pair are requested
     // before this pair's bytes: a wave then waits for memory once per pair, not three times in a row (words, output offset, bytes).
     auto lane_word = [&](u64 pair) { return lane < W_WORDS && pair < a.n_reads ? pair_word(a, pair, lane, OUT) : 0u; };
-    auto word = [](u64 v, u32 w) {   // lane w's word, wave-uniform
-        return ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)w) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)v, (int)w);
-    };
-    u64 r = (u64)blockIdx.x * RM_WAVES + wv;
+    u64 r = (u64)blockIdx.x * WPR_WAVES + wv;
     u64 next = lane_word(r);
     for (; r < a.n_reads; r += stride) {
         const u64 cur = next;
         next = lane_word(r + stride);
-        const Pair p = pair_from(word(cur, W_B1), word(cur, W_E1), word(cur, W_B2), word(cur, W_E2), word(cur, W_INSERT));
-        const u64 oo = word(cur, W_OUT);
+        const Pair p = pair_from(readlane64(cur, W_B1), readlane64(cur, W_E1), readlane64(cur, W_B2), readlane64(cur, W_E2),
+                                 readlane64(cur, W_INSERT));
+        const u64 oo = readlane64(cur, W_OUT);
         const u32 I = p.I;
         u32 n_ov = 0;
         u64 cnt = 0;   // 12-bit fields: DIS, DIS taken from mate 2, DIS with qx == qy, ONE, NONE (each at most 1024)
@@ -257,36 +236,25 @@ __global__ void __launch_bounds__(RM_THREADS) reads_merge_kernel(const ReadsPair
     }
 }
 
-namespace {
-u64 plan_blocks(u64 n_reads) { return ceil_div(n_reads, (u64)ROWS); }
-}  // namespace
-
-// the partial sums (merged pairs, merged bases) of every block of the plan and six words for the host
-size_t reads_merge_bytes(u64 n_reads) { return align256(8u * (2u * plan_blocks(n_reads) + 6u)); }
+// the plan: the partial sums (merged pairs, merged bases) of every block and six words for the host
+size_t reads_merge_bytes(u64 n_reads) { return plan_bytes(n_reads, 6u); }
 
 hipError_t launch_reads_merge_count(const ReadsPairMerge& a, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st) {
-    const u64 nb = plan_blocks(a.n_reads);
-    u64* partial = static_cast<u64*>(area);
-    u64* tail = partial + 2u * nb;
-    hipLaunchKernelGGL(reads_merge_plan_count_kernel, dim3((unsigned)nb), dim3(CT), 0, st, a, partial, nb, tail);
-    hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial, nb, tail);
-    hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(CT), 0, st, partial + nb, nb, tail + 1);
-    return read_back(h_pinned, tail, 6u, h_out, st);
+    const Plan p = plan_at(area, a.n_reads);
+    hipLaunchKernelGGL(reads_merge_plan_count_kernel, dim3((unsigned)p.n_blocks), dim3(CT), 0, st, a, p.partial, p.n_blocks, p.tail);
+    return plan_totals(p, 6u, h_pinned, h_out, st);
 }
 
 hipError_t launch_reads_merge_emit(const ReadsPairMerge& a, void* area, int n_cu, hipStream_t st) {
-    const u64 nb = plan_blocks(a.n_reads);
-    const u64* partial = static_cast<const u64*>(area);
-    if (a.out_offsets) hipLaunchKernelGGL(reads_merge_plan_write_kernel, dim3((unsigned)nb), dim3(CT), 0, st, a, partial, nb, partial + 2u * nb);
-    const u64 want = ceil_div(a.n_reads, (u64)RM_WAVES);
-    const u64 cap = (u64)(n_cu > 0 ? n_cu : 256) * RM_BLOCKS_PER_CU * 4u;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
+    const Plan p = plan_at(area, a.n_reads);
+    if (a.out_offsets) hipLaunchKernelGGL(reads_merge_plan_write_kernel, dim3((unsigned)p.n_blocks), dim3(CT), 0, st, a, p.partial, p.n_blocks, p.tail);
+    const dim3 grid(wave_per_read_grid(a.n_reads, n_cu));
     if (a.quals1) {
-        if (a.out_bases) hipLaunchKernelGGL((reads_merge_kernel<true, true>), grid, dim3(RM_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((reads_merge_kernel<true, false>), grid, dim3(RM_THREADS), 0, st, a);
+        if (a.out_bases) hipLaunchKernelGGL((reads_merge_kernel<true, true>), grid, dim3(WPR_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((reads_merge_kernel<true, false>), grid, dim3(WPR_THREADS), 0, st, a);
     } else {
-        if (a.out_bases) hipLaunchKernelGGL((reads_merge_kernel<false, true>), grid, dim3(RM_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((reads_merge_kernel<false, false>), grid, dim3(RM_THREADS), 0, st, a);
+        if (a.out_bases) hipLaunchKernelGGL((reads_merge_kernel<false, true>), grid, dim3(WPR_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((reads_merge_kernel<false, false>), grid, dim3(WPR_THREADS), 0, st, a);
     }
     return hipGetLastError();
 }

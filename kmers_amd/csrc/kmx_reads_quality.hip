@@ -21,17 +21,15 @@
 // the lanes that hold it, the lowest of them: the smallest b, the leftmost run) and the sums.
 // The weight table (256 u64) is staged in LDS once per block: a lane gathers four words of it per step.
 // No atomics, no scratch; a row is written by the eight low lanes of the one wave that owns the read.
-#include "kmx_device.h"
-#include "kmx_launch.h"
+// The bounds of a read, "is one of ACGTacgt" and the wave-per-read launch shape are the family's (kmx_reads_common.h).
+#include "kmx_reads_common.h"
 
 namespace kmx {
 
 namespace {
 
-constexpr u32 RQ_THREADS = 256;
 constexpr u32 RQ_LANE = 4;                 // bytes a lane owns per step
 constexpr u32 RQ_STEP = 64u * RQ_LANE;     // bytes a wave handles per step
-constexpr u32 RQ_BLOCKS_PER_CU = 8;        // 8 waves per SIMD
 
 // op(earlier, later) over the lanes before and at this one.  `ident`: what a lane without a source gets (update_dpp keeps `old`).
 #define KMX_RQ_DPP32(ident, v, ctrl, rows) ((u32)__builtin_amdgcn_update_dpp((int)(ident), (int)(v), (ctrl), (rows), 0xF, false))
@@ -69,10 +67,6 @@ __device__ __forceinline__ u64 lane_before(u64 v, u64 ident, u32 lane) {
     return lane ? o : ident;
 }
 
-__device__ __forceinline__ u64 read_lane64(u64 v, u32 l) {
-    return ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)l) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)v, (int)l);
-}
-
 // max over the wave of a 64-bit value, wave-uniform (the shape of wave_sum, kmx_device.h)
 __device__ __forceinline__ u64 wave_max_u64(u64 v) {
     auto mx = [](u64 a, u64 b) { return a > b ? a : b; };
@@ -80,7 +74,7 @@ __device__ __forceinline__ u64 wave_max_u64(u64 v) {
     v = mx(v, KMX_DPP64(v, 0x4E));
     v = mx(v, KMX_DPP64(v, 0x124));
     v = mx(v, KMX_DPP64(v, 0x128));
-    return mx(mx(read_lane64(v, 0), read_lane64(v, 16)), mx(read_lane64(v, 32), read_lane64(v, 48)));
+    return mx(mx(readlane64(v, 0), readlane64(v, 16)), mx(readlane64(v, 32), readlane64(v, 48)));
 }
 
 // the lowest lane whose flag is set (some lane's is)
@@ -97,44 +91,19 @@ __device__ __forceinline__ u32 load4(uintptr_t src, u32 L, int64_t p, u32 phase)
     return (u32)((((u64)x1 << 32) | x0) >> (8u * phase));
 }
 
-__device__ __forceinline__ bool is_acgt(u32 b) {
-    const u32 u = b & 0xDFu;
-    return u == 'A' || u == 'C' || u == 'G' || u == 'T';
-}
-
 }  // namespace
 
-struct ReadsQuality {
-    const uint8_t* bases;
-    const u64* offsets;   // nullptr: uniform reads of read_len bases
-    u64 n_reads;
-    u32 read_len;
-    const uint8_t* quals;
-    u32 phred, min_q, trim_q, k;
-    const u64* weights;   // 256 words or nullptr
-    uint8_t* masked;      // or nullptr
-    u64* rows;            // KMX_RQ_WORDS per read, or nullptr
-};
-
-__global__ void __launch_bounds__(RQ_THREADS) reads_quality_kernel(const ReadsQuality a) {
+__global__ void __launch_bounds__(WPR_THREADS) reads_quality_kernel(const ReadsQuality a) {
     __shared__ u64 wt[256];
     const bool weigh = a.weights != nullptr;
     if (weigh) wt[threadIdx.x] = a.weights[threadIdx.x];
     __syncthreads();
     const u32 lane = threadIdx.x & 63u;
     const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const u64 stride = (u64)gridDim.x * (RQ_THREADS / 64u);
-    for (u64 r = (u64)blockIdx.x * (RQ_THREADS / 64u) + wv; r < a.n_reads; r += stride) {
-        u64 off, len;
-        if (a.offsets) {
-            off = a.offsets[r];
-            const u64 e = a.offsets[r + 1u];
-            len = e >= off ? e - off : 0u;
-        } else {
-            off = r * (u64)a.read_len;
-            len = a.read_len;
-        }
-        const u32 L = len >= (1ull << 31) ? 0u : (u32)len;   // (the scans skip such a read)
+    const u64 stride = (u64)gridDim.x * WPR_WAVES;
+    for (u64 r = (u64)blockIdx.x * WPR_WAVES + wv; r < a.n_reads; r += stride) {
+        u64 off;
+        const u32 L = read_span(a.offsets, a.read_len, r, off);
         const uintptr_t bsrc = reinterpret_cast<uintptr_t>(a.bases) + off, qsrc = reinterpret_cast<uintptr_t>(a.quals) + off;
         const uintptr_t dst = a.masked ? reinterpret_cast<uintptr_t>(a.masked) + off : bsrc;
         const u32 A = (u32)(dst & 3u);
@@ -262,7 +231,7 @@ __global__ void __launch_bounds__(RQ_THREADS) reads_quality_kernel(const ReadsQu
                 run_start = (u32)__builtin_amdgcn_readlane((int)beststart, (int)sel);
             }
             Pc += (int64_t)(int32_t)__builtin_amdgcn_readlane((int)S_in, 63);
-            Mc = (int64_t)read_lane64((u64)M, 63);
+            Mc = (int64_t)readlane64((u64)M, 63);
             Ac = (u32)__builtin_amdgcn_readlane((int)Ai, 63);
             last_bad = (u32)__builtin_amdgcn_readlane((int)lbr, 63);
             // (these ride in vector registers between the steps: with them the kernel's uniform state is past what
@@ -288,12 +257,8 @@ __global__ void __launch_bounds__(RQ_THREADS) reads_quality_kernel(const ReadsQu
     }
 }
 
-hipError_t launch_reads_quality(const uint8_t* bases, const u64* offsets, u64 n_reads, u32 read_len, const uint8_t* quals, u32 phred, u32 min_q,
-                                u32 trim_q, u32 k, const u64* weights, uint8_t* masked, u64* rows, int n_cu, hipStream_t st) {
-    const ReadsQuality a{bases, offsets, n_reads, read_len, quals, phred, min_q, trim_q, k, weights, masked, rows};
-    const u64 want = (n_reads + RQ_THREADS / 64u - 1u) / (RQ_THREADS / 64u);
-    const u64 cap = (u64)(n_cu > 0 ? n_cu : 256) * RQ_BLOCKS_PER_CU * 4u;
-    hipLaunchKernelGGL(reads_quality_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(RQ_THREADS), 0, st, a);
+hipError_t launch_reads_quality(const ReadsQuality& a, int n_cu, hipStream_t st) {
+    hipLaunchKernelGGL(reads_quality_kernel, dim3(wave_per_read_grid(a.n_reads, n_cu)), dim3(WPR_THREADS), 0, st, a);
     return hipGetLastError();
 }
 

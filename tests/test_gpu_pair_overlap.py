@@ -13,34 +13,14 @@ from tests import adapter_np as A
 from tests import reads_np
 from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
 from tests.count_np import u64
+from tests.reads_dev import SENT_WORD, dev_bytes, dev_words, ptr, ragged
 
 pytestmark = pytest.mark.gpu
 
 OK, E_ARG = 0, 1
-SENT_WORD = -0x5A5A5A5A5A5A5A5B   # 0xA5A5... as int64
 GW = 8                            # sentinel words on either side of d_rows
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 JUNK = np.frombuffer(b"ACGTacgtN", np.uint8)
-
-
-def _dev_bytes(ctx, host, shift=0):
-    import torch
-
-    buf = torch.empty(len(host) + shift + 16, dtype=torch.uint8, device=ctx.device)
-    assert buf.data_ptr() % 256 == 0
-    view = buf[shift:shift + len(host)]
-    if len(host):
-        view.copy_(torch.from_numpy(np.array(host)))   # (a writable copy: the batches come from np.frombuffer)
-    return view
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def ragged(reads, first=0):
-    off = (np.concatenate([[0], np.cumsum([len(r) for r in reads])]) + first).astype(np.uint64)
-    return np.frombuffer(b"." * first + b"".join(reads), np.uint8), off
 
 
 def seq(rng, n, alpha=ACGT):
@@ -72,13 +52,13 @@ def run(ctx, b1, b2, n, len1=0, len2=0, off1=None, off2=None, min_overlap=30, ma
 
     if want is None:
         want = A.reads_pair_overlap_np(b1, b2, n, len1, len2, off1, off2, min_overlap, max_mism, err[0], err[1])
-    d1, d2 = _dev_bytes(ctx, b1, shift1), _dev_bytes(ctx, b2, shift2)
-    d_o1 = torch.from_numpy(np.ascontiguousarray(off1).view(np.int64)).to(ctx.device) if off1 is not None else None
-    d_o2 = torch.from_numpy(np.ascontiguousarray(off2).view(np.int64)).to(ctx.device) if off2 is not None else None
+    d1, d2 = dev_bytes(ctx, b1, shift1), dev_bytes(ctx, b2, shift2)
+    d_o1 = dev_words(ctx, off1)
+    d_o2 = dev_words(ctx, off2)
     rbuf = torch.full((2 * GW + A.RP_WORDS * n,), SENT_WORD, dtype=torch.int64, device=ctx.device)
     r1 = Reads(d1.data_ptr() if n else None, n, len1, d_o1.data_ptr() if off1 is not None else None)
     r2 = Reads(d2.data_ptr() if n else None, n, len2, d_o2.data_ptr() if off2 is not None else None)
-    st = ctx.lib.kmx_reads_pair_overlap(ctx._h, C.byref(r1), C.byref(r2), min_overlap, max_mism, err[0], err[1], _p(rbuf[GW:]))
+    st = ctx.lib.kmx_reads_pair_overlap(ctx._h, C.byref(r1), C.byref(r2), min_overlap, max_mism, err[0], err[1], ptr(rbuf[GW:]))
     assert st == OK, ctx.lib.kmx_last_error(ctx._h)
     ctx.synchronize()
     got = u64(rbuf)
@@ -213,7 +193,7 @@ def test_argument_errors(ctx):
     f = ctx.lib.kmx_reads_pair_overlap
 
     def call(a=r4, b=r4, min_overlap=5, max_mism=2, num=1, den=5, rw=rows, h=ctx._h):
-        return f(h, C.byref(a) if a is not None else None, C.byref(b) if b is not None else None, min_overlap, max_mism, num, den, _p(rw))
+        return f(h, C.byref(a) if a is not None else None, C.byref(b) if b is not None else None, min_overlap, max_mism, num, den, ptr(rw))
 
     assert call() == OK
     assert call(b=r3) == E_ARG and call(a=r3) == E_ARG and call(a=r3, b=r3) == OK      # the two batches differ in n_reads

@@ -13,11 +13,11 @@ from tests import adapter_np as A
 from tests import reads_np
 from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
 from tests.count_np import u64
+from tests.reads_dev import SENT_WORD, dev_bytes, dev_words, ptr, ragged
 
 pytestmark = pytest.mark.gpu
 
 OK, E_ARG = 0, 1
-SENT_WORD = -0x5A5A5A5A5A5A5A5B   # 0xA5A5... as int64
 GW = 8                            # sentinel words on either side of d_rows
 BASE_ALPHA = np.frombuffer(b"ACGTACGTACGTACGTacgtN", np.uint8)
 TRUSEQ = b"AGATCGGAAGAGC"
@@ -26,30 +26,9 @@ EIGHT = [b"AGATCGGAAGAGC", b"T", b"CTGTCTCTTATACACATCTNNgactgcATCGGAt", b"TGGAAT
          (b"GATTACA" * 10)[:64], b"CTGTCTCTTATACACATCT", b"nnGGT"]
 
 
-def _dev_bytes(ctx, host, shift=0):
-    import torch
-
-    buf = torch.empty(len(host) + shift + 16, dtype=torch.uint8, device=ctx.device)
-    assert buf.data_ptr() % 256 == 0
-    view = buf[shift:shift + len(host)]
-    if len(host):
-        view.copy_(torch.from_numpy(np.array(host)))   # (a writable copy: the batches come from np.frombuffer)
-    return view
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _adapters_c(adapters):
     blob = b"".join(adapters)
     return (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0"), (C.c_uint32 * max(len(adapters), 1))(*[len(a) for a in adapters])
-
-
-def ragged(reads, first=0):
-    """a list of byte strings -> (bases with `first` bytes of '.' before the batch, offsets)"""
-    off = (np.concatenate([[0], np.cumsum([len(r) for r in reads])]) + first).astype(np.uint64)
-    return np.frombuffer(b"." * first + b"".join(reads), np.uint8), off
 
 
 def random_reads(rng, lens, adapters, share=0.6):
@@ -77,12 +56,12 @@ def run(ctx, bases, n, read_len, off, adapters, min_overlap=3, err=(1, 10), bshi
 
     if want is None:
         want = A.reads_adapter_np(bases, n, read_len, adapters, min_overlap, err[0], err[1], off)
-    d_b = _dev_bytes(ctx, bases, bshift)
-    d_off = torch.from_numpy(np.ascontiguousarray(off).view(np.int64)).to(ctx.device) if off is not None else None
+    d_b = dev_bytes(ctx, bases, bshift)
+    d_off = dev_words(ctx, off)
     rbuf = torch.full((2 * GW + A.RA_WORDS * n,), SENT_WORD, dtype=torch.int64, device=ctx.device)
     reads = Reads(d_b.data_ptr() if n else None, n, read_len, d_off.data_ptr() if off is not None else None)
     blob, lens = _adapters_c(adapters)
-    st = ctx.lib.kmx_reads_adapter(ctx._h, C.byref(reads), blob, lens, len(adapters), min_overlap, err[0], err[1], _p(rbuf[GW:]))
+    st = ctx.lib.kmx_reads_adapter(ctx._h, C.byref(reads), blob, lens, len(adapters), min_overlap, err[0], err[1], ptr(rbuf[GW:]))
     assert st == OK, ctx.lib.kmx_last_error(ctx._h)
     ctx.synchronize()
     got = u64(rbuf)
@@ -248,7 +227,7 @@ def test_argument_errors(ctx):
         blob, ln = _adapters_c(list(ads))
         if lens is not None:
             ln = (C.c_uint32 * len(lens))(*lens)
-        return f(h, C.byref(r) if r is not None else None, blob, ln, len(ads) if n_ad is None else n_ad, min_overlap, num, den, _p(rw))
+        return f(h, C.byref(r) if r is not None else None, blob, ln, len(ads) if n_ad is None else n_ad, min_overlap, num, den, ptr(rw))
 
     assert call() == OK
     assert call(min_overlap=0) == E_ARG and call(den=0) == E_ARG and call(num=11) == E_ARG and call(num=10) == OK
@@ -257,8 +236,8 @@ def test_argument_errors(ctx):
     assert call(lens=[0]) == E_ARG and call(ads=[b"A" * 65]) == E_ARG and call(ads=[b"A" * 64]) == OK
     assert call(ads=[b"ACGU"]) == E_ARG and call(ads=[b"AC-T"]) == E_ARG and call(ads=[b"ACGT", b"AC.T"]) == E_ARG
     assert call(ads=[b"acgtNn"]) == OK
-    assert f(ctx._h, C.byref(reads), None, (C.c_uint32 * 1)(4), 1, 3, 1, 10, _p(rows)) == E_ARG
-    assert f(ctx._h, C.byref(reads), (C.c_uint8 * 4)(65, 67, 71, 84), None, 1, 3, 1, 10, _p(rows)) == E_ARG
+    assert f(ctx._h, C.byref(reads), None, (C.c_uint32 * 1)(4), 1, 3, 1, 10, ptr(rows)) == E_ARG
+    assert f(ctx._h, C.byref(reads), (C.c_uint8 * 4)(65, 67, 71, 84), None, 1, 3, 1, 10, ptr(rows)) == E_ARG
     assert call(r=Reads(None, 0, 16, None)) == OK                  # no reads: a no-op ...
     assert call(r=Reads(None, 0, 16, None), ads=[b"AC.T"]) == E_ARG  # ... whose arguments are still checked
     ctx.synchronize()

@@ -14,35 +14,12 @@ from tests import reads_np
 from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
 from tests.count_np import random_reads, u64
 from tests.reads_np import span_word
+from tests.reads_dev import SENT, SENT_WORD, dev_bytes, dev_words, ptr
 
 pytestmark = pytest.mark.gpu
 
 OK, E_ARG, E_NOMEM = 0, 1, 6
 GUARD = 64           # sentinel bytes behind d_out_bases
-SENT = 0xA5
-SENT_WORD = -0x5A5A5A5A5A5A5A5B   # 0xA5A5... as int64
-
-
-def _dev_bytes(ctx, host, shift=0):
-    """host bytes on the device at `shift` bytes from an aligned allocation (a view: the same storage, a pointer that is not aligned)"""
-    import torch
-
-    buf = torch.empty(len(host) + shift + 16, dtype=torch.uint8, device=ctx.device)
-    assert buf.data_ptr() % 256 == 0
-    view = buf[shift:shift + len(host)]
-    if len(host):
-        view.copy_(torch.from_numpy(np.ascontiguousarray(host)))
-    return view
-
-
-def _dev_words(ctx, a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(ctx.device)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class Batch:
@@ -52,8 +29,8 @@ class Batch:
         from kmers_amd._lib import Reads
 
         self.ctx, self.h_bases, self.n, self.read_len, self.h_off = ctx, np.asarray(bases, np.uint8), int(n_reads), int(read_len), offsets
-        self.d_bases = _dev_bytes(ctx, self.h_bases, shift)
-        self.d_off = _dev_words(ctx, offsets) if offsets is not None else None
+        self.d_bases = dev_bytes(ctx, self.h_bases, shift)
+        self.d_off = dev_words(ctx, offsets)
         self.reads = Reads(self.d_bases.data_ptr() if self.n else None, self.n, self.read_len, self.d_off.data_ptr() if offsets is not None else None)
 
     def args(self):
@@ -73,7 +50,7 @@ def _span_dev(ctx, span, stride):
         return None, 0
     a = np.full(max(len(span) * stride, 1), 0xDEADBEEFDEADBEEF, np.uint64)
     a[:len(span) * stride:stride] = span
-    return _dev_words(ctx, a), stride
+    return dev_words(ctx, a), stride
 
 
 def run_select(b, keep=None, span=None, span_k=0, min_len=0, stride=1, out_shift=0, want_index=True):
@@ -83,10 +60,10 @@ def run_select(b, keep=None, span=None, span_k=0, min_len=0, stride=1, out_shift
 
     ctx = b.ctx
     want_b, want_o, want_i = reads_np.select_np(b.h_bases, b.n, b.read_len, b.h_off, keep=keep, span=span, span_k=span_k, min_len=min_len)
-    d_keep = _dev_bytes(ctx, np.asarray(keep, np.uint8)) if keep is not None else None
+    d_keep = dev_bytes(ctx, np.asarray(keep, np.uint8)) if keep is not None else None
     d_span, stride = _span_dev(ctx, span, stride)
     nr, nb = C.c_uint64(99), C.c_uint64(99)
-    head = (ctx._h, C.byref(b.reads), _p(d_keep), _p(d_span), stride, span_k, min_len)
+    head = (ctx._h, C.byref(b.reads), ptr(d_keep), ptr(d_span), stride, span_k, min_len)
     st = ctx.lib.kmx_reads_select(*head, None, None, None, 0, 0, C.byref(nr), C.byref(nb))
     assert st == OK and (nr.value, nb.value) == (len(want_i), len(want_b)), (st, nr.value, nb.value, len(want_i), len(want_b))
     n_out, n_bases = nr.value, nb.value
@@ -95,7 +72,7 @@ def run_select(b, keep=None, span=None, span_k=0, min_len=0, stride=1, out_shift
     off = torch.full((n_out + 2,), SENT_WORD, dtype=torch.int64, device=ctx.device)
     idx = torch.full((n_out + 1,), SENT_WORD, dtype=torch.int64, device=ctx.device)
     nr, nb = C.c_uint64(99), C.c_uint64(99)
-    st = ctx.lib.kmx_reads_select(*head, _p(out), _p(off), _p(idx) if want_index else None, n_out, n_bases, C.byref(nr), C.byref(nb))
+    st = ctx.lib.kmx_reads_select(*head, ptr(out), ptr(off), ptr(idx) if want_index else None, n_out, n_bases, C.byref(nr), C.byref(nb))
     assert st == OK and (nr.value, nb.value) == (n_out, n_bases)
     h_raw, h_off, h_idx = raw.cpu().numpy(), u64(off), u64(idx)
     h_out = h_raw[out_shift:out_shift + n_bases]
@@ -120,10 +97,10 @@ def run_gather(b, index, span=None, span_k=0, stride=1, out_shift=0):
     ctx = b.ctx
     index = np.asarray(index, np.uint64)
     want_b, want_o = reads_np.gather_np(b.h_bases, b.n, b.read_len, index, b.h_off, span=span, span_k=span_k)
-    d_index = _dev_words(ctx, index) if len(index) else None
+    d_index = dev_words(ctx, index) if len(index) else None
     d_span, stride = _span_dev(ctx, span, stride)
     nb = C.c_uint64(99)
-    head = (ctx._h, C.byref(b.reads), _p(d_index), len(index), _p(d_span), stride, span_k)
+    head = (ctx._h, C.byref(b.reads), ptr(d_index), len(index), ptr(d_span), stride, span_k)
     st = ctx.lib.kmx_reads_gather(*head, None, None, 0, C.byref(nb))
     assert st == OK and nb.value == len(want_b), (st, nb.value, len(want_b))
     n_bases = nb.value
@@ -131,7 +108,7 @@ def run_gather(b, index, span=None, span_k=0, stride=1, out_shift=0):
     out = raw[out_shift:out_shift + n_bases + GUARD]
     off = torch.full((len(index) + 2,), SENT_WORD, dtype=torch.int64, device=ctx.device)
     nb = C.c_uint64(99)
-    st = ctx.lib.kmx_reads_gather(*head, _p(out), _p(off), n_bases, C.byref(nb))
+    st = ctx.lib.kmx_reads_gather(*head, ptr(out), ptr(off), n_bases, C.byref(nb))
     assert st == OK and nb.value == n_bases
     h_raw, h_off = raw.cpu().numpy(), u64(off)
     sent = np.uint64(SENT_WORD & (2**64 - 1))
@@ -303,22 +280,22 @@ def test_conventions(ctx):
     assert sel(None, None, None, 0, 0) == OK and (nr.value, nb.value) == (10, int(lens.sum()))
     # one byte, one read short: KMX_E_NOMEM, the counts set, nothing written
     nr.value = nb.value = 99
-    assert sel(_p(out), _p(off), _p(idx), 10, int(lens.sum()) - 1) == E_NOMEM and (nr.value, nb.value) == (10, int(lens.sum())) and untouched()
-    assert sel(_p(out), _p(off), _p(idx), 9, int(lens.sum())) == E_NOMEM and untouched()
+    assert sel(ptr(out), ptr(off), ptr(idx), 10, int(lens.sum()) - 1) == E_NOMEM and (nr.value, nb.value) == (10, int(lens.sum())) and untouched()
+    assert sel(ptr(out), ptr(off), ptr(idx), 9, int(lens.sum())) == E_NOMEM and untouched()
     # exactly one of the two outputs
-    assert sel(_p(out), None, None, 10, 200) == E_ARG and sel(None, _p(off), None, 10, 200) == E_ARG and untouched()
+    assert sel(ptr(out), None, None, 10, 200) == E_ARG and sel(None, ptr(off), None, 10, 200) == E_ARG and untouched()
     # a span array without a stride
-    d_span = _dev_words(ctx, np.zeros(10, np.uint64))
-    assert ctx.lib.kmx_reads_select(ctx._h, C.byref(b.reads), None, _p(d_span), 0, 0, 0, _p(out), _p(off), None, 10, 200, C.byref(nr), C.byref(nb)) == E_ARG
-    assert ctx.lib.kmx_reads_gather(ctx._h, C.byref(b.reads), _p(d_span), 3, _p(d_span), 0, 0, _p(out), _p(off), 200, C.byref(nb)) == E_ARG
-    assert ctx.lib.kmx_reads_gather(ctx._h, C.byref(b.reads), _p(d_span), 3, None, 0, 0, _p(out), None, 200, C.byref(nb)) == E_ARG
+    d_span = dev_words(ctx, np.zeros(10, np.uint64))
+    assert ctx.lib.kmx_reads_select(ctx._h, C.byref(b.reads), None, ptr(d_span), 0, 0, 0, ptr(out), ptr(off), None, 10, 200, C.byref(nr), C.byref(nb)) == E_ARG
+    assert ctx.lib.kmx_reads_gather(ctx._h, C.byref(b.reads), ptr(d_span), 3, ptr(d_span), 0, 0, ptr(out), ptr(off), 200, C.byref(nb)) == E_ARG
+    assert ctx.lib.kmx_reads_gather(ctx._h, C.byref(b.reads), ptr(d_span), 3, None, 0, 0, ptr(out), None, 200, C.byref(nb)) == E_ARG
     assert untouched()
     # the output over the source
-    assert ctx.lib.kmx_reads_select(ctx._h, C.byref(b.reads), None, None, 0, 0, 0, C.c_void_p(b.d_bases.data_ptr() + 8), _p(off), None, 10, 200,
+    assert ctx.lib.kmx_reads_select(ctx._h, C.byref(b.reads), None, None, 0, 0, 0, C.c_void_p(b.d_bases.data_ptr() + 8), ptr(off), None, 10, 200,
                                     C.byref(nr), C.byref(nb)) == E_ARG and untouched()
     # gather: a byte short
     nb.value = 99
-    assert ctx.lib.kmx_reads_gather(ctx._h, C.byref(b.reads), _p(_dev_words(ctx, np.array([6, 6], np.uint64))), 2, None, 0, 0, _p(out), _p(off), 49,
+    assert ctx.lib.kmx_reads_gather(ctx._h, C.byref(b.reads), ptr(dev_words(ctx, np.array([6, 6], np.uint64))), 2, None, 0, 0, ptr(out), ptr(off), 49,
                                     C.byref(nb)) == E_NOMEM and nb.value == 50 and untouched()
     # no reads: a no-op with zero counts
     e = Batch(ctx, np.zeros(0, np.uint8), 0, 0, np.zeros(1, np.uint64))
@@ -380,7 +357,7 @@ def test_python_layer_matches_raw(ctx):
     span = _random_spans(rng, lens)
     rows = np.full((len(lens), 8), 0xDEADBEEF, np.uint64)
     rows[:, 7] = span
-    d_rows = _dev_words(ctx, rows)
+    d_rows = dev_words(ctx, rows)
     got = ctx.reads_select(*b.args(), keep=torch.from_numpy(keep).to(ctx.device), span=d_rows[:, 7], min_len=2, offsets=b.d_off, index=True)
     assert d_rows[:, 7].data_ptr() == d_rows.data_ptr() + 56 and not d_rows[:, 7].is_contiguous()     # a view: no copy was made
     wb, wo, wi = reads_np.select_np(b.h_bases, b.n, 0, b.h_off, keep=keep, span=span, min_len=2)
@@ -513,7 +490,7 @@ def test_two_calls_give_identical_bytes(ctx):
     lens[1234] = 40_000
     b = ragged(ctx, lens, rng, first=5, shift=3)
     keep = torch.from_numpy((rng.random(len(lens)) < 0.7).astype(np.uint8)).to(ctx.device)
-    span = _dev_words(ctx, _random_spans(rng, lens))
+    span = dev_words(ctx, _random_spans(rng, lens))
     a1 = ctx.reads_select(*b.args(), keep=keep, span=span, offsets=b.d_off, index=True)
     a2 = ctx.reads_select(*b.args(), keep=keep, span=span, offsets=b.d_off, index=True)
     assert torch.equal(a1.bases, a2.bases) and torch.equal(a1.offsets, a2.offsets) and torch.equal(a1.index, a2.index)

@@ -16,40 +16,14 @@ from tests import merge_np as M
 from tests import reads_np
 from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
 from tests.count_np import u64
+from tests.reads_dev import SENT, SENT_WORD, dev_bytes, dev_words, ptr, ragged
 
 pytestmark = pytest.mark.gpu
 
 OK, E_ARG, E_NOMEM = 0, 1, 6
-SENT, SENT_WORD = 0xA5, -0x5A5A5A5A5A5A5A5B   # 0xA5A5... as int64
 GB, GW = 32, 8                                # sentinel bytes / words on either side of an output
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 JUNK = np.frombuffer(b"ACGTacgtN", np.uint8)
-
-
-def _dev_bytes(ctx, host, shift=0):
-    import torch
-
-    buf = torch.empty(len(host) + shift + 16, dtype=torch.uint8, device=ctx.device)
-    assert buf.data_ptr() % 256 == 0
-    view = buf[shift:shift + max(len(host), 1)]   # (an empty batch still gets a pointer: torch gives an empty view none)
-    if len(host):
-        view.copy_(torch.from_numpy(np.array(host)))   # (a writable copy: the batches come from np.frombuffer)
-    return view
-
-
-def _dev_words(ctx, host):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(host).view(np.int64).copy()).to(ctx.device) if host is not None else None
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def ragged(reads, first=0):
-    off = (np.concatenate([[0], np.cumsum([len(r) for r in reads])]) + first).astype(np.uint64)
-    return np.frombuffer(b"." * first + b"".join(reads), np.uint8), off
 
 
 def seq(rng, n, alpha=ACGT):
@@ -110,17 +84,17 @@ def run(ctx, b1, b2, n, len1, len2, insert, off1=None, off2=None, q1=None, q2=No
         want = M.reads_pair_merge_np(b1, b2, n, len1, len2, insert, q1, q2, off1, off2, phred, cap)
     w_bases, w_quals, w_off, w_rows = want
     nb = len(w_bases)
-    d1, d2 = _dev_bytes(ctx, b1, in_shifts[0]), _dev_bytes(ctx, b2, in_shifts[1])
-    dq1 = _dev_bytes(ctx, q1, in_shifts[2]) if q1 is not None else None
-    dq2 = _dev_bytes(ctx, q2, in_shifts[3]) if q2 is not None else None
-    d_o1, d_o2, d_ins = _dev_words(ctx, off1), _dev_words(ctx, off2), _dev_words(ctx, np.asarray(insert).astype(np.uint64))
+    d1, d2 = dev_bytes(ctx, b1, in_shifts[0]), dev_bytes(ctx, b2, in_shifts[1])
+    dq1 = dev_bytes(ctx, q1, in_shifts[2]) if q1 is not None else None
+    dq2 = dev_bytes(ctx, q2, in_shifts[3]) if q2 is not None else None
+    d_o1, d_o2, d_ins = dev_words(ctx, off1), dev_words(ctx, off2), dev_words(ctx, np.asarray(insert).astype(np.uint64))
     r1 = Reads(d1.data_ptr() if n else None, n, len1, d_o1.data_ptr() if off1 is not None else None)
     r2 = Reads(d2.data_ptr() if n else None, n, len2, d_o2.data_ptr() if off2 is not None else None)
     g_b, g_o = Guarded(ctx, nb, False, out_shifts[0]), Guarded(ctx, n + 1, True)
     g_q = Guarded(ctx, nb, False, out_shifts[1]) if q1 is not None and out_quals else None
     g_r = Guarded(ctx, M.RM_WORDS * n, True) if rows else None
     nm, nbases = C.c_uint64(77), C.c_uint64(77)
-    st = ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r1), C.byref(r2), _p(dq1), _p(dq2), _p(d_ins), 1, phred, cap, g_b.ptr(),
+    st = ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r1), C.byref(r2), ptr(dq1), ptr(dq2), ptr(d_ins), 1, phred, cap, g_b.ptr(),
                                       g_q.ptr() if g_q else None, g_o.ptr(), g_r.ptr() if g_r else None, nb, C.byref(nm), C.byref(nbases))
     assert st == OK, ctx.lib.kmx_last_error(ctx._h)
     assert nbases.value == nb and nm.value == int(np.count_nonzero(w_rows[:, M.RM_LEN]))
@@ -185,7 +159,7 @@ def test_insert_words_by_stride_from_the_overlap_rows_and_garbage_words(ctx):
     g_b, g_q, g_o, g_r = Guarded(ctx, len(want[0]), False), Guarded(ctx, len(want[0]), False), Guarded(ctx, n + 1, True), Guarded(ctx, 4 * n, True)
     r1, r2 = Reads(d1.data_ptr(), n, 0, d_o1.data_ptr()), Reads(d2.data_ptr(), n, 0, d_o2.data_ptr())
     nm, nb = C.c_uint64(0), C.c_uint64(0)
-    st = ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r1), C.byref(r2), _p(dq1), _p(dq2), C.c_void_p(ov.data_ptr() + 8 * A.RP_INSERT), A.RP_WORDS, 33, 41,
+    st = ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r1), C.byref(r2), ptr(dq1), ptr(dq2), C.c_void_p(ov.data_ptr() + 8 * A.RP_INSERT), A.RP_WORDS, 33, 41,
                                       g_b.ptr(), g_q.ptr(), g_o.ptr(), g_r.ptr(), len(want[0]), C.byref(nm), C.byref(nb))
     assert st == OK, ctx.lib.kmx_last_error(ctx._h)
     assert g_b.payload().tobytes() == want[0].tobytes() and g_q.payload().tobytes() == want[1].tobytes()
@@ -259,13 +233,13 @@ def test_count_only_and_max_bases(ctx):
     q1, q2 = quals_like(rng, b1), quals_like(rng, b2)
     w_bases, w_quals, w_off, w_rows = M.reads_pair_merge_np(b1, b2, n, 0, 0, insert, q1, q2, o1, o2)
     nb_want, nm_want = len(w_bases), int(np.count_nonzero(w_rows[:, M.RM_LEN]))
-    d1, d2, dq1, dq2 = (_dev_bytes(ctx, x, s) for x, s in ((b1, 1), (b2, 2), (q1, 3), (q2, 0)))
-    d_o1, d_o2, d_ins = _dev_words(ctx, o1), _dev_words(ctx, o2), _dev_words(ctx, insert)
+    d1, d2, dq1, dq2 = (dev_bytes(ctx, x, s) for x, s in ((b1, 1), (b2, 2), (q1, 3), (q2, 0)))
+    d_o1, d_o2, d_ins = dev_words(ctx, o1), dev_words(ctx, o2), dev_words(ctx, insert)
     r1, r2 = Reads(d1.data_ptr(), n, 0, d_o1.data_ptr()), Reads(d2.data_ptr(), n, 0, d_o2.data_ptr())
 
     def call(g_b, g_q, g_o, g_r, max_bases):
         nm, nb = C.c_uint64(77), C.c_uint64(77)
-        st = ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r1), C.byref(r2), _p(dq1), _p(dq2), _p(d_ins), 1, 33, 41, g_b.ptr() if g_b else None,
+        st = ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r1), C.byref(r2), ptr(dq1), ptr(dq2), ptr(d_ins), 1, 33, 41, g_b.ptr() if g_b else None,
                                           g_q.ptr() if g_q else None, g_o.ptr() if g_o else None, g_r.ptr() if g_r else None, max_bases, C.byref(nm),
                                           C.byref(nb))
         return st, nm.value, nb.value
@@ -294,7 +268,7 @@ def test_working_set_at_the_work_buffer_cap_and_one_below(ctx):
     r = Reads(bases.data_ptr(), n, L, None)
     g_r = Guarded(ctx, 4 * n, True)
     nm, nb = C.c_uint64(77), C.c_uint64(77)
-    call = lambda: ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r), C.byref(r), None, None, _p(insert), 1, 33, 41, None, None, None, g_r.ptr(), 0,  # noqa: E731
+    call = lambda: ctx.lib.kmx_reads_pair_merge(ctx._h, C.byref(r), C.byref(r), None, None, ptr(insert), 1, 33, 41, None, None, None, g_r.ptr(), 0,  # noqa: E731
                                                 C.byref(nm), C.byref(nb))
     try:
         ctx.set_work_buffer_limit(511)
@@ -347,8 +321,8 @@ def test_argument_errors(ctx):
 
     def call(a=r4, b=r4, q1=quals, q2=quals, ins=insert, stride=1, phred=33, cap=41, ob=out_b, oq=out_q, oo=out_o, rw=rows, max_bases=128, h=U,
              hm=U, hb=U):
-        return f(ctx._h if h is U else h, C.byref(a) if a is not None else None, C.byref(b) if b is not None else None, _p(q1), _p(q2), _p(ins), stride,
-                 phred, cap, _p(ob), _p(oq), _p(oo), _p(rw), max_bases, C.byref(nm) if hm is U else hm, C.byref(nb) if hb is U else hb)
+        return f(ctx._h if h is U else h, C.byref(a) if a is not None else None, C.byref(b) if b is not None else None, ptr(q1), ptr(q2), ptr(ins), stride,
+                 phred, cap, ptr(ob), ptr(oq), ptr(oo), ptr(rw), max_bases, C.byref(nm) if hm is U else hm, C.byref(nb) if hb is U else hb)
 
     assert call() == OK and (nm.value, nb.value) == (4, 80)
     assert call(b=r3) == E_ARG and call(a=r3) == E_ARG and call(a=r3, b=r3) == OK           # the two batches differ in n_reads

@@ -14,30 +14,14 @@ from tests import quality_np as Q
 from tests import reads_np
 from tests.count_np import ctx  # noqa: F401  (the fixture, found by name in this module)
 from tests.count_np import u64
+from tests.reads_dev import SENT, SENT_WORD, dev_bytes, dev_words, ptr
 
 pytestmark = pytest.mark.gpu
 
 OK, E_ARG = 0, 1
 GUARD = 64
-SENT = 0xA5
-SENT_WORD = -0x5A5A5A5A5A5A5A5B   # 0xA5A5... as int64
 GW = 8                            # sentinel words on either side of d_rows
 BASE_ALPHA = np.frombuffer(b"ACGTACGTACGTACGTacgtN", np.uint8)
-
-
-def _dev_bytes(ctx, host, shift=0):
-    import torch
-
-    buf = torch.empty(len(host) + shift + 16, dtype=torch.uint8, device=ctx.device)
-    assert buf.data_ptr() % 256 == 0
-    view = buf[shift:shift + len(host)]
-    if len(host):
-        view.copy_(torch.from_numpy(np.ascontiguousarray(host)))
-    return view
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def make_batch(rng, lens, first=0, qlo=33, qhi=33 + 41):
@@ -59,18 +43,18 @@ def run(ctx, bases, quals, n, read_len=0, off=None, bshift=0, qshift=0, mshift=0
 
     if want is None:
         want = Q.reads_quality_np(bases, quals, n, read_len, off, phred, min_q, trim_q, k, weights)
-    d_b = _dev_bytes(ctx, bases, bshift)
-    d_q = _dev_bytes(ctx, quals, qshift)
-    d_off = torch.from_numpy(np.ascontiguousarray(off).view(np.int64)).to(ctx.device) if off is not None else None
-    d_w = torch.from_numpy(np.ascontiguousarray(weights).view(np.int64)).to(ctx.device) if weights is not None else None
+    d_b = dev_bytes(ctx, bases, bshift)
+    d_q = dev_bytes(ctx, quals, qshift)
+    d_off = dev_words(ctx, off)
+    d_w = dev_words(ctx, weights)
     total = len(bases)
     mbuf = torch.full((GUARD + mshift + total + GUARD,), SENT, dtype=torch.uint8, device=ctx.device)
     d_m = d_b if inplace else mbuf[GUARD + mshift:GUARD + mshift + total]
     rbuf = torch.full((2 * GW + Q.RQ_WORDS * n,), SENT_WORD, dtype=torch.int64, device=ctx.device)
     d_r = rbuf[GW:GW + Q.RQ_WORDS * n]
     reads = Reads(d_b.data_ptr() if n else None, n, read_len, d_off.data_ptr() if off is not None else None)
-    st = ctx.lib.kmx_reads_quality(ctx._h, C.byref(reads), _p(d_q), phred, min_q, trim_q, k, _p(d_w), _p(d_m) if mask else None,
-                                   _p(d_r) if rows else None)
+    st = ctx.lib.kmx_reads_quality(ctx._h, C.byref(reads), ptr(d_q), phred, min_q, trim_q, k, ptr(d_w), ptr(d_m) if mask else None,
+                                   ptr(d_r) if rows else None)
     assert st == OK, ctx.lib.kmx_last_error(ctx._h)
     ctx.synchronize()
     got_rows = u64(rbuf)
@@ -211,14 +195,14 @@ def test_argument_errors(ctx):
     f = ctx.lib.kmx_reads_quality
 
     def call(r=reads, q=quals, phred=33, min_q=0, trim_q=0, m=out, rw=rows):
-        return f(ctx._h, C.byref(r) if r is not None else None, _p(q), phred, min_q, trim_q, 0, None, _p(m), _p(rw))
+        return f(ctx._h, C.byref(r) if r is not None else None, ptr(q), phred, min_q, trim_q, 0, None, ptr(m), ptr(rw))
 
     assert call() == OK
     assert call(phred=256) == E_ARG and call(min_q=256) == E_ARG and call(trim_q=256) == E_ARG
     assert call(q=None) == E_ARG                     # d_quals NULL with reads present
     assert call(m=None, rw=None) == E_ARG            # both outputs NULL
     assert call(m=None) == OK and call(rw=None) == OK
-    assert call(r=None) == E_ARG and f(None, C.byref(reads), _p(quals), 33, 0, 0, 0, None, _p(out), _p(rows)) == E_ARG
+    assert call(r=None) == E_ARG and f(None, C.byref(reads), ptr(quals), 33, 0, 0, 0, None, ptr(out), ptr(rows)) == E_ARG
     assert call(m=bases) == OK                       # in place
     assert call(m=bases[1:]) == E_ARG                # any other overlap with the bases ...
     assert call(m=quals[60:]) == E_ARG               # ... and any with the quality bytes
