@@ -918,15 +918,16 @@ int kmx_gen_reads(kmx_ctx *ctx, uint64_t seed, uint64_t first_byte, uint8_t *d_o
 int kmx_kmers_from_bytes(kmx_ctx *ctx, const uint8_t *d_seqs, uint64_t n, uint32_t k, uint64_t *d_words,
                          uint64_t *h_first_bad);
 
-/* Kmer::to_reverse_complement / get_reverse_complement_word (kmer.rs:124-147), k in [1,32] */
+/* Kmer::to_reverse_complement / get_reverse_complement_word (kmer.rs:124-147), k in [1,32].  d_out may equal d_in (in place). */
 int kmx_revcomp_words(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint32_t k, uint64_t *d_out);
 
 /* Kmer::to_canonical + is_canonical (kmer.rs:55-74): d_canon[i] = min(w, rc(w)); d_is_canonical[i] = (w <= rc(w)).
- * Either output may be NULL. */
+ * Either output may be NULL.  d_canon may equal d_in (in place). */
 int kmx_canonical_words(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint32_t k, uint64_t *d_canon,
                         uint8_t *d_is_canonical);
 
-/* hash_one(&state, Kmer) with state = LexHasherState::new(hasher_k) (hash.rs:10-20,60-71) or identity */
+/* hash_one(&state, Kmer) with state = LexHasherState::new(hasher_k) (hash.rs:10-20,60-71) or identity.  d_out may equal d_in
+ * (in place). */
 int kmx_hash_words(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint32_t hasher, uint32_t hasher_k, uint64_t *d_out);
 
 /* hash_one(&state, Kmer) with one of std's BuildHashers (hash.rs:10-20; the reference uses DefaultHasher at kmer.rs:546-557 and
@@ -936,7 +937,7 @@ int kmx_hash_words(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint32_t hash
  * The algorithm lives in Rust's standard library, not in the crate: restated from the SipHash paper (Aumasson, Bernstein 2012);
  * the restatement reproduces the paper's SipHash-2-4 test vectors through the same round function (tests/test_oracle_golden.py),
  * its 1-3 instance the first row of Rust's own SipHasher13 test table (library/core/tests/hash/sip.rs); no reference value for
- * 1-3 exists in the crate itself (its two tests check properties): parity is pinned to that extent. */
+ * 1-3 exists in the crate itself (its two tests check properties): parity is pinned to that extent.  d_out may equal d_in (in place). */
 int kmx_hash_words_sip13(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint64_t key0, uint64_t key1, uint64_t *d_out);
 
 /* CanonicalKmer::get_word_equivalency (canonical_kmer.rs:152-161): out[i] in KMX_{NO,IDENTITY,TWIN}_MATCH */
@@ -963,7 +964,8 @@ int kmx_encode_kmers(kmx_ctx *ctx, const uint8_t *d_seqs, uint64_t n, uint32_t s
 int kmx_encode_windows(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint8_t enc_byte, uint32_t words_per_kmer,
                        uint64_t *d_words);
 /* Encoding::rev_comp::<K> (naive.rs:138-154; xor10.rs:86-103 B>1 loop): result base i =
- * complement(base K-1-i) for i<K, bits >= 2K unchanged.  K in [2, 32*words_per_kmer]. */
+ * complement(base K-1-i) for i<K, bits >= 2K unchanged.  K in [2, 32*words_per_kmer].  d_out may equal d_in (in place: a lane
+ * holds all the words of its k-mer before it writes any). */
 int kmx_encoding_rev_comp(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint32_t K, uint8_t enc_byte,
                           uint32_t words_per_kmer, uint64_t *d_out);
 /* Encoding::decode (naive.rs:126-136): emits ALL 32*words_per_kmer letters per k-mer */
@@ -973,7 +975,7 @@ int kmx_encoding_decode(kmx_ctx *ctx, const uint64_t *d_in, uint64_t n, uint8_t 
 /* ---------------------------------------------------------------- decode / display direction ---- */
 /* Kmer::sub_kmer_word(word, k, pos, width) (src/naive_impl/kmer.rs:156-162) for n words: (word >> 2*pos) & MASK_TABLE[width].
  * The reference asserts pos < k and pos + width <= k: KMX_E_ARG otherwise.  1 <= k <= 32 (width 32 would meet
- * MASK_TABLE[32] == 0, kmer.rs:617, and give 0 like the reference). */
+ * MASK_TABLE[32] == 0, kmer.rs:617, and give 0 like the reference).  d_out may equal d_words (in place). */
 int kmx_sub_kmer_words(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n, uint32_t k, uint32_t pos, uint32_t width,
                        uint64_t *d_out);
 /* String::from(Kmer) (src/naive_impl/kmer.rs:196-207, BASE_TABLE :24): n words -> n*k LOWER-case letters, base 0 first. */
@@ -987,7 +989,8 @@ int kmx_bitmers_to_bytes(kmx_ctx *ctx, const uint64_t *d_mers, uint64_t n, uint3
  * into word i / BITS, bit i % BITS, so the little-endian byte image of a [P; B] is the same flat bit string for every P:
  * the arrays are passed as bytes, word_bits * words_per_kmer / 8 per k-mer, and P only decides the capacity
  * (KMX_E_TOO_LONG where bit_field would panic) and the number of letters decode() emits (word_bits * words_per_kmer / 2).
- * word_bits in {8, 16, 32, 64, 128}; at most 64 bytes per k-mer. */
+ * word_bits in {8, 16, 32, 64, 128}; at most 64 bytes per k-mer.  kmx_encoding_rev_comp_p works a byte per lane, so unlike
+ * kmx_encoding_rev_comp it cannot run in place: d_out == d_in is KMX_E_ARG. */
 int kmx_encode_kmers_p(kmx_ctx *ctx, const uint8_t *d_seqs, uint64_t n, uint32_t seq_len, uint8_t enc_byte,
                        uint32_t word_bits, uint32_t words_per_kmer, void *d_arrays);
 int kmx_encoding_rev_comp_p(kmx_ctx *ctx, const void *d_in, uint64_t n, uint32_t K, uint8_t enc_byte, uint32_t word_bits,
