@@ -1203,6 +1203,28 @@ pub fn reads_pair_merge(ctx: &HipContext, mates1: &Mates<'_>, mates2: &Mates<'_>
     Ok((n_merged, n_bases))
 }
 
+/// Duplicate reads, or with `mates` duplicate mate pairs (`kmx_reads_dedup`; include/kmx.h has the fingerprint, the rank, the decision
+/// and the words of a row).  `strand`: a read's reverse complement, or a pair with its mates exchanged, is the same item.  `scores`:
+/// one score per item as strided words -- `ReadSpans { words: &d_rows_of_reads_quality, first_word: KMX_RQ_QSUM as u64, stride:
+/// KMX_RQ_WORDS as u64, k: 0 }` keeps the best copy of a class; `None` keeps the first.  `hash_bits`: 64 unless collisions are wanted.
+/// `d_rows` gets `KMX_DD_WORDS` u64 per item, `d_keep` (optional) one byte per item for `reads_select`.  Returns the summary
+/// (`KMX_DD_S_*`: kept, dropped, the largest class, collisions).  Synchronous.
+pub fn reads_dedup(ctx: &HipContext, reads: &Mates<'_>, mates: Option<&Mates<'_>>, n_reads: u64, strand: bool, hash_bits: u32,
+                   scores: Option<ReadSpans<'_>>, d_rows: &DeviceBuf<'_>, d_keep: Option<&DeviceBuf<'_>>) -> Result<[u64; 4], KmxError> {
+    let r1 = reads_of(reads.bases, n_reads, reads.read_len, reads.offsets);
+    let r2 = mates.map(|m| reads_of(m.bases, n_reads, m.read_len, m.offsets));
+    assert!(n_reads as u128 * KMX_DD_WORDS as u128 * 8 <= d_rows.len() as u128, "rows shorter than the batch's items");
+    if let Some(kp) = d_keep {
+        assert!(n_reads as u128 <= kp.len() as u128, "keep bytes shorter than the batch's items");
+    }
+    let (d_score, stride, _) = span_args(scores, n_reads);
+    let mut summary = [0u64; KMX_DD_SUMMARY_WORDS as usize];
+    ctx.ck(unsafe { kmx_reads_dedup(ctx.0, &r1, r2.as_ref().map_or(ptr::null(), |r| r as *const _), if strand { KMX_DD_STRAND } else { 0 },
+                                    hash_bits, d_score, stride.max(1), d_rows.as_mut_ptr::<u64>(),
+                                    d_keep.map_or(ptr::null_mut(), |x| x.as_mut_ptr::<u8>()), summary.as_mut_ptr()) })?;
+    Ok(summary)
+}
+
 /// The entries of a table with `min_count <= count <= max_count`, order kept (`kmx_count_filter`): a table again.  The outputs hold
 /// at least `max_out` entries; returns how many were kept, Err(KMX_E_NOMEM) if there are more than `max_out`.
 pub fn count_filter(ctx: &HipContext, table: CountTable<'_>, min_count: u64, max_count: u64, d_kmers_out: &DeviceBuf<'_>,

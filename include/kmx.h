@@ -1300,6 +1300,71 @@ int kmx_reads_pair_merge(kmx_ctx *ctx, const kmx_reads *reads1, const kmx_reads 
                          uint32_t q_cap, uint8_t *d_out_bases, uint8_t *d_out_quals, uint64_t *d_out_offsets, uint64_t *d_rows,
                          uint64_t max_bases, uint64_t *h_n_merged, uint64_t *h_n_bases);
 
+/* ---------------------------------------------------------------- duplicate reads and read pairs ----
+ * BUILD-DEFINED (the reference has nothing like it): what fastp --dedup, clumpify dedupe and samtools markdup do -- reads, or mate
+ * pairs, whose whole content was sequenced before are found and all but one of each class dropped.  EXACT: items are grouped by a
+ * 64-bit fingerprint and every candidate is then compared with the one it would be dropped for, letter by letter.  An ITEM is read
+ * r of `reads` (mates == NULL) or the pair of read r of `reads` and read r of `mates` (mates->n_reads != reads->n_reads:
+ * KMX_E_ARG).  Every layout kmx_reads_pair_overlap takes is taken: uniform or ragged, d_offsets[0] > 0, empty reads, any alignment
+ * of d_bases, the two batches with layouts of their own; a read of 2^31 bases or more, or an offsets pair that descends, has
+ * length 0 (so has, in this call, a read of 2^31 - 4 bases or more: its last dword position does not fit the fetch's 32 bits).
+ *
+ * CODES.  c(b) = 0, 1, 2, 3 for A/a, C/c, G/g, T/t and 4 for any other byte; comp(c) = 3 - c for c < 4, comp(4) = 4.  A read IS its
+ * code sequence S (case is ignored, all other bytes are one letter), L codes long; rc(S)[i] = comp(S[L - 1 - i]).
+ *
+ * FINGERPRINT.  Arithmetic mod 2^64, G = 0x9E3779B97F4A7C15, fmix = the murmur3 64-bit finaliser (x ^= x >> 33;
+ * x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33):
+ *     v_p  = sum_{j < 4} code(4 p + j) << 4 j        for p < ceil(L / 4), with code = 0xF at positions >= L
+ *     H(S) = fmix( (sum_p fmix(((p << 16) | v_p) + G))  ^  (L * G) )                         (H of the empty read is 0)
+ *     P(x, y) = fmix(fmix(x + G) + y)                                                        (a pair)
+ * THE KEY of item r, with t(x) = x >> (64 - hash_bits), 1 <= hash_bits <= 64 (normally 64; fewer bits only make more items share a
+ * key, which costs compares and can only keep more):
+ *     singles:  F_a = t(H(S)),                 F_b = t(H(rc S))
+ *     pairs:    F_a = t(P(H(m1), H(m2))),      F_b = t(P(H(m2), H(m1)))     (the other strand of a fragment is its mates exchanged)
+ * Without KMX_DD_STRAND: Hc = F_a, OTHER = 0.  With it: Hc = min(F_a, F_b), OTHER = (F_b < F_a).
+ *
+ * RANK within a key: s = min(d_score[r * score_stride], 2^32 - 1), 0 for every item where d_score == NULL; higher s first, then the
+ * smaller index.  The HEAD of a key is its first item in that order: (d_rows of kmx_reads_quality + KMX_RQ_QSUM, KMX_RQ_WORDS) as
+ * the score keeps the best copy, no score keeps the first.
+ *
+ * DECISION.  Item r is DROPPED iff it is not the head of its key and EQUALS the head: singles -- the same length and the same code at
+ * every position, or, under KMX_DD_STRAND, rc of it is; pairs -- both mates equal the head's mates, or, under the flag, the head's
+ * mates exchanged.  Both orientations count wherever both can hold ("either").  A non-head that does not equal its head is KEPT
+ * and flagged COLLISION: an item that has no equal is never dropped, and a duplicate is missed only where its key collides with a
+ * different, better ranked item -- which the summary counts.
+ *
+ * OUTPUTS.  d_rows: KMX_DD_WORDS u64 per item in source order (required).  d_keep (optional): one byte per item, 1 iff kept -- what
+ * kmx_reads_select takes, for both mates.  h_summary (host, required): KMX_DD_SUMMARY_WORDS u64.  Nothing else is written; no
+ * load touches an aligned dword that holds no byte of its batch.
+ * mates->n_reads != reads->n_reads, hash_bits out of range, unknown flag bits, score_stride == 0 with d_score, NULL ctx / reads /
+ * d_rows / h_summary, n_reads >= 2^32 (the index shares a word with the score): KMX_E_ARG.  n_reads == 0 checks its arguments,
+ * zeroes the summary and launches nothing.
+ * Working set, laid out in the work buffer before any kernel runs: 42 bytes per item (the sort's records and flags 17, the sorted
+ * records 16, the group of every sorted position and the head of every group 4 + 4 -- they lie where the sort left its counts --
+ * and a byte for OTHER), the two-word counter's area, 18.4 bytes per item, and 32 bytes per wave of the verify kernel's grid (at
+ * most 4 KiB per compute unit): 42 n + count area(n) + 32 waves <= 61 n + 64 KiB + 4 KiB per compute unit bytes.  Above
+ * the cap (kmx_ctx_set_work_buffer_limit): KMX_E_NOMEM with nothing written.  Synchronous (the sort reads a record back per digit
+ * it descends: a class of many equal items goes through all 16).  COUNT is summed with integer atomics: repeated calls give
+ * identical bytes. */
+#define KMX_DD_STRAND 1u /* flags: the other strand is the same item */
+#define KMX_DD_WORDS 4u
+#define KMX_DD_REP 0u   /* the head's index for a dropped item, the item's own index otherwise */
+#define KMX_DD_COUNT 1u /* a head: 1 + the items dropped onto it; any other kept item: 1; a dropped item: 0 */
+#define KMX_DD_FLAGS 2u /* KMX_DD_F_* */
+#define KMX_DD_HASH 3u  /* Hc */
+#define KMX_DD_F_KEPT 1u
+#define KMX_DD_F_FLIPPED 2u   /* dropped, and equal to the head only in the other orientation / exchanged */
+#define KMX_DD_F_COLLISION 4u /* kept although not the head of its key: it differs from the head */
+#define KMX_DD_F_OTHER 8u     /* F_b < F_a */
+#define KMX_DD_SUMMARY_WORDS 4u
+#define KMX_DD_S_KEPT 0u
+#define KMX_DD_S_DROPPED 1u
+#define KMX_DD_S_LARGEST 2u /* the largest COUNT */
+#define KMX_DD_S_COLLISIONS 3u
+int kmx_reads_dedup(kmx_ctx *ctx, const kmx_reads *reads, const kmx_reads *mates /* NULL: single reads */, uint32_t flags,
+                    uint32_t hash_bits, const uint64_t *d_score, uint64_t score_stride, uint64_t *d_rows, uint8_t *d_keep,
+                    uint64_t *h_summary /* KMX_DD_SUMMARY_WORDS, host */);
+
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,
  * canonical_kmer_iterator.rs:72-83), so the scans need no collective.  What is exchanged is the optional bucket

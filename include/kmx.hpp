@@ -542,6 +542,27 @@ inline MergedReads reads_pair_merge(Context& ctx, const kmx_reads& reads1, const
     return m;
 }
 
+// Duplicate reads, or with `mates` duplicate mate pairs (kmx.h, "duplicate reads and read pairs"): the KMX_DD_* words of every item
+// and its keep byte on the host, and the summary.  flags: 0 or KMX_DD_STRAND.  d_score / score_stride: one score per item on the
+// device, strided -- (rows of kmx_reads_quality + KMX_RQ_QSUM, KMX_RQ_WORDS) keeps the best copy -- or nullptr: the first one stays.
+struct ReadDuplicates {
+    std::vector<uint64_t> rows;
+    std::vector<uint8_t> keep;
+    uint64_t summary[KMX_DD_SUMMARY_WORDS] = {0, 0, 0, 0};   // KMX_DD_S_*
+};
+inline ReadDuplicates reads_dedup(Context& ctx, const kmx_reads& reads, const kmx_reads* mates = nullptr, uint32_t flags = 0,
+                                  const uint64_t* d_score = nullptr, uint64_t score_stride = 1, uint32_t hash_bits = 64) {
+    ReadDuplicates d;
+    DeviceBuffer<uint64_t> rows(ctx, reads.n_reads * KMX_DD_WORDS + 1);
+    DeviceBuffer<uint8_t> keep(ctx, reads.n_reads + 1);
+    ctx.check(kmx_reads_dedup(ctx.get(), &reads, mates, flags, hash_bits, d_score, score_stride, rows.data(), keep.data(), d.summary), "reads_dedup");
+    d.rows = rows.download();
+    d.rows.resize(reads.n_reads * KMX_DD_WORDS);
+    d.keep = keep.download();
+    d.keep.resize(reads.n_reads);
+    return d;
+}
+
 // src/naive_impl/seq_vector.rs: the 2-bit packed sequence container, resident on the device.
 class SeqVector {
   public:

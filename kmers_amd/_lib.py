@@ -65,6 +65,13 @@ RP_MAX_LEN = 1024
 # kmx_reads_pair_merge: the words of a pair's row (KMX_RM_*)
 RM_LEN, RM_OVERLAP, RM_TAKEN, RM_INVALID = range(4)
 RM_WORDS = 4
+# kmx_reads_dedup: the flag, the words of an item's row, the bits of its flags word and the words of the summary (KMX_DD_*)
+DD_STRAND = 1
+DD_REP, DD_COUNT, DD_FLAGS, DD_HASH = range(4)
+DD_WORDS = 4
+DD_F_KEPT, DD_F_FLIPPED, DD_F_COLLISION, DD_F_OTHER = 1, 2, 4, 8
+DD_S_KEPT, DD_S_DROPPED, DD_S_LARGEST, DD_S_COLLISIONS = range(4)
+DD_SUMMARY_WORDS = 4
 
 
 class KmxError(RuntimeError):
@@ -192,6 +199,7 @@ SIGNATURES = {
     "kmx_reads_adapter": (_int, [_vp, _RP, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "kmx_reads_pair_overlap": (_int, [_vp, _RP, _RP, _u32, _u32, _u32, _u32, _vp]),
     "kmx_reads_pair_merge": (_int, [_vp, _RP, _RP, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_reads_dedup": (_int, [_vp, _RP, _RP, _u32, _u32, _vp, _u64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "kmx_sub_kmer_words": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp]),
     "kmx_kmers_to_strings": (_int, [_vp, _vp, _u64, _u32, _vp]),
     "kmx_bitmers_to_bytes": (_int, [_vp, _vp, _u64, _u32, _vp]),

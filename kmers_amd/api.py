@@ -537,6 +537,34 @@ class MergedPairs:
     merge_rows: "torch.Tensor"
 
 
+@dataclasses.dataclass
+class ReadDuplicates:
+    """What reads_dedup returns.  rows int64[n, DD_WORDS] (viewable as u64; include/kmx.h has the words) in source order, keep
+    uint8[n] (1 iff kept: what reads_select takes, for both mates of a pair), and the four words of the summary."""
+    rows: "torch.Tensor"
+    keep: "torch.Tensor"
+    kept: int
+    dropped: int
+    largest: int
+    collisions: int
+
+    def histogram(self) -> "torch.Tensor":
+        """int64[largest + 1]: entry c is the number of classes of c items (kept items whose COUNT is c); entry 0 is 0"""
+        counts = self.rows[:, _lib.DD_COUNT]
+        return torch.bincount(counts[counts > 0], minlength=self.largest + 1)
+
+
+@dataclasses.dataclass
+class DeduplicatedReads:
+    """What reads_drop_duplicates returns: the kept reads and, where given, their quality bytes (identical offsets), for pairs the
+    kept mates in step; every batch of bases carries the index of its source item.  `duplicates` belongs to the SOURCE items."""
+    reads: ReadBatch
+    quals: "ReadBatch | None"
+    mates: "ReadBatch | None"
+    mate_quals: "ReadBatch | None"
+    duplicates: ReadDuplicates
+
+
 def _on_ctx_stream(fn):
     """Run a Context method with Context.stream as torch's current stream (see "Stream discipline" above)."""
     @functools.wraps(fn)
@@ -1935,6 +1963,57 @@ class Context:
         un1_q = self.reads_select(quals1, n_reads, read_len1, keep=drop, offsets=offsets1) if quals1 is not None else None
         un2_q = self.reads_select(quals2, n_reads, read_len2, keep=drop, offsets=offsets2) if quals2 is not None else None
         return MergedPairs(merged, merged_q, un1, un2, un1_q, un2_q, overlap_rows, merge_rows)
+
+    # ------------------------------------------------------------ duplicate reads and read pairs
+    @staticmethod
+    def _mates_arg(mates):
+        """mates -> (bases, read_len, offsets): a ReadBatch, or a tuple (bases, read_len) / (bases, read_len, offsets)"""
+        if isinstance(mates, ReadBatch):
+            return mates.bases, mates.max_len(), mates.offsets
+        if len(mates) == 2:
+            return mates[0], mates[1], None
+        return tuple(mates)
+
+    @_on_ctx_stream
+    def reads_dedup(self, bases, n_reads, read_len, offsets=None, mates=None, strand=False, score=None, hash_bits=64) -> ReadDuplicates:
+        """kmx_reads_dedup -> ReadDuplicates: exact duplicate reads, or mate pairs with `mates` (a ReadBatch, or (bases, read_len) /
+        (bases, read_len, offsets) of as many reads), found by a 64-bit fingerprint and verified letter by letter against the
+        read they would be dropped for.  Case is ignored and every byte that is not ACGT is one letter.  strand=True: a read's
+        reverse complement, or a pair with its mates exchanged, is the same item.  `score`: a 1-D int64 tensor, one word per item
+        with any positive element stride (reads_quality(...)[1][:, RQ_QSUM] as it is): the best-scored copy of a class survives,
+        ties and no score keep the first.  include/kmx.h has the contract."""
+        n_reads = int(n_reads)
+        sc_t, sc_p, stride = self._span_arg(score)
+        if sc_t is not None and sc_t.numel() < n_reads:
+            raise ValueError("score: one word per item")
+        r1 = self._reads(bases, n_reads, read_len, offsets)
+        r2 = None
+        if mates is not None:
+            mb, ml, mo = self._mates_arg(mates)
+            r2 = self._reads(mb, n_reads, ml, mo)
+        rows = self.empty(max(_lib.DD_WORDS * n_reads, 1), torch.int64)   # (a pointer also for no reads)
+        keep = self.empty(max(n_reads, 1), torch.uint8)
+        summ = (C.c_uint64 * _lib.DD_SUMMARY_WORDS)()
+        self._ck(self.lib.kmx_reads_dedup(self._h, C.byref(r1), C.byref(r2) if r2 is not None else None, _lib.DD_STRAND if strand else 0,
+                                          int(hash_bits), sc_p, max(stride, 1), _ptr(rows), _ptr(keep), summ))
+        return ReadDuplicates(rows[:_lib.DD_WORDS * n_reads].view(-1, _lib.DD_WORDS), keep[:n_reads], int(summ[_lib.DD_S_KEPT]), int(summ[_lib.DD_S_DROPPED]),
+                              int(summ[_lib.DD_S_LARGEST]), int(summ[_lib.DD_S_COLLISIONS]))
+
+    @_on_ctx_stream
+    def reads_drop_duplicates(self, bases, n_reads, read_len, offsets=None, quals=None, mates=None, mate_quals=None, strand=False, score=None,
+                              hash_bits=64) -> DeduplicatedReads:
+        """reads_dedup, then reads_select on its keep bytes -> DeduplicatedReads.  ONE keep tensor goes into every select -- the
+        bases, the quality bytes (laid out as their bases), and for pairs both mates -- so all the batches stay in step."""
+        n_reads = int(n_reads)
+        d = self.reads_dedup(bases, n_reads, read_len, offsets, mates, strand, score, hash_bits)
+        b = self.reads_select(bases, n_reads, read_len, keep=d.keep, offsets=offsets, index=True)
+        q = self.reads_select(quals, n_reads, read_len, keep=d.keep, offsets=offsets) if quals is not None else None
+        m = mq = None
+        if mates is not None:
+            mb, ml, mo = self._mates_arg(mates)
+            m = self.reads_select(mb, n_reads, ml, keep=d.keep, offsets=mo, index=True)
+            mq = self.reads_select(mate_quals, n_reads, ml, keep=d.keep, offsets=mo) if mate_quals is not None else None
+        return DeduplicatedReads(b, q, m, mq, d)
 
     # ------------------------------------------------------------ a new batch of reads from an old one
     @staticmethod

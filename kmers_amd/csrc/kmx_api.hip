@@ -2551,6 +2551,29 @@ int kmx_reads_pair_merge(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_reads*
     return KMX_OK;
 }
 
+// ---- duplicate reads and read pairs (kmx_reads_dedup.hip) ----
+int kmx_reads_dedup(kmx_ctx* ctx, const kmx_reads* reads, const kmx_reads* mates, uint32_t flags, uint32_t hash_bits, const uint64_t* d_score,
+                    uint64_t score_stride, uint64_t* d_rows, uint8_t* d_keep, uint64_t* h_summary) {
+    const char* who = "kmx_reads_dedup";
+    if (!ctx || !reads_ok(reads) || (mates && !reads_ok(mates)) || !d_rows || !h_summary) return KMX_E_ARG;
+    for (uint32_t w = 0; w < KMX_DD_SUMMARY_WORDS; ++w) h_summary[w] = 0;
+    const uint64_t n = reads->n_reads;
+    if ((mates && mates->n_reads != n) || !reads_batch_ok(reads) || (mates && !reads_batch_ok(mates))) return KMX_E_ARG;
+    if ((flags & ~KMX_DD_STRAND) != 0u || hash_bits < 1u || hash_bits > 64u) return KMX_E_ARG;
+    if (n >= (1ull << 32)) return KMX_E_ARG;   // (the index shares a word with the score)
+    if (d_score && (score_stride == 0 || (n && (n - 1u) > ((1ull << 60) - 1u) / score_stride))) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::reads_dedup_bytes(n, ctx->n_cu), &area)) return st;
+    const kmx::ReadsDedup a{reads->d_bases, mates ? mates->d_bases : nullptr, reads->d_offsets, mates ? mates->d_offsets : nullptr, n, reads->read_len,
+                            mates ? mates->read_len : 0u, mates ? 1u : 0u, flags & KMX_DD_STRAND, hash_bits, d_score, score_stride, d_rows, d_keep};
+    bool bad = false;
+    KMX_HIP(ctx, kmx::launch_reads_dedup(a, area, ctx->h_pinned, h_summary, &bad, ctx->n_cu, ctx->stream));
+    if (bad) return fail_hip(ctx, hipErrorUnknown, "kmx_reads_dedup: the sort did not return every record once");
+    return KMX_OK;
+}
+
 int kmx_reads_length_range(kmx_ctx* ctx, const uint64_t* d_offsets, uint64_t n_reads, uint32_t* h_min_len, uint32_t* h_max_len) {
     if (!ctx || (n_reads && !d_offsets)) return KMX_E_ARG;
     if (h_min_len) *h_min_len = 0;

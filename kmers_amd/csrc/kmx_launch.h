@@ -308,6 +308,25 @@ struct ReadsPairMerge {
 size_t reads_merge_bytes(u64 n_reads);
 hipError_t launch_reads_merge_count(const ReadsPairMerge& a, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
 hipError_t launch_reads_merge_emit(const ReadsPairMerge& a, void* area, int n_cu, hipStream_t st);
+// kmx_reads_dedup.hip: duplicate reads and pairs (kmx_reads_dedup).  Keys, the two-word counter's sort (launch_count_sort /
+// launch_count_emit), groups and the verification, all in `area` of reads_dedup_bytes(n_reads, n_cu); h_summary[0 .. KMX_DD_SUMMARY_WORDS)
+// comes back.  Synchronous: the sort's round trips and one for the summary.  *bad: the sort did not give n_reads distinct records
+// or overflowed its level arrays (a bug, never expected); nothing of the rows is to be trusted then.
+struct ReadsDedup {
+    const uint8_t *bases1, *bases2;
+    const u64 *offsets1, *offsets2;   // nullptr: uniform reads of read_len1 / read_len2 bases
+    u64 n_reads;
+    u32 read_len1, read_len2;
+    u32 pairs;                        // an item is a pair (0: a read of batch 1; batch 2 is not looked at)
+    u32 strand;                       // KMX_DD_STRAND
+    u32 hash_bits;                    // 1 .. 64
+    const u64* score;                 // score[r * score_stride], or nullptr
+    u64 score_stride;
+    u64* rows;
+    uint8_t* keep;                    // or nullptr
+};
+size_t reads_dedup_bytes(u64 n_reads, int n_cu);
+hipError_t launch_reads_dedup(const ReadsDedup& a, void* area, unsigned long long* h_pinned, u64* h_summary, bool* bad, int n_cu, hipStream_t st);
 // kmx_count_setop.hip: set algebra and comparison of two count tables (`words` u64 per key: 1 or 2; n = n_a + n_b)
 size_t count_setop_bytes(u64 n);
 hipError_t launch_count_setop(u32 words, u32 op, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,

@@ -27,8 +27,6 @@ namespace kmx {
 
 namespace {
 
-constexpr u32 ONES = 0x01010101u, HIGH = 0x80808080u;
-
 // The WORDS of pair r, six u64: where mate 1 begins and ends in d_bases, where mate 2 does, the insert word, the pair's output offset
 // (the write and the merge only).  For uniform reads the first four are r and r + 1 times the read length.
 constexpr u32 W_B1 = 0, W_E1 = 1, W_B2 = 2, W_E2 = 3, W_INSERT = 4, W_OUT = 5, W_WORDS = 6;
@@ -96,30 +94,6 @@ __global__ void __launch_bounds__(CT) reads_merge_plan_write_kernel(const ReadsP
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) a.out_offsets[a.n_reads] = tail[1];
 }
-
-// The four bytes base[at .. at + 3] (byte k in bits 8 k ..; `at` may be negative) out of the two aligned dwords that hold them, for
-// base[0 .. n), n >= 1.  Positions count on the dword grid of `base`, g = at + (the address of base mod 4), and the two dword
-// positions are clamped to the first and the last dword that hold a byte of base[0 .. n): no other dword is loaded, and no branch
-// is taken.  A byte that lies outside base[0 .. n) comes back as some byte of those dwords: the caller does not use it.
-__device__ __forceinline__ u32 load4(const uint8_t* base, int at, u32 n) {
-    const int ph = (int)(reinterpret_cast<uintptr_t>(base) & 3u);
-    const int g = at + ph, g0 = g & ~3, last = (ph + (int)n - 1) & ~3;
-    auto clamp = [last](int v) { return v < 0 ? 0 : v > last ? last : v; };
-    const uint8_t* const origin = base - ph;
-    const u32 w0 = *reinterpret_cast<const u32*>(origin + clamp(g0)), w1 = *reinterpret_cast<const u32*>(origin + clamp(g0 + 4));
-    return __builtin_amdgcn_alignbyte(w1, w0, (u32)(g & 3));   // bytes (g & 3) .. + 3 of w1:w0
-}
-
-// bit 7 of every byte of z that is zero (exact: no carry crosses a byte)
-__device__ __forceinline__ u32 zero_bytes(u32 z) { return ~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z) & HIGH; }
-// bit 7 of every byte of w that is A / T (at) or C / G (cg), either case
-__device__ __forceinline__ void letters(u32 w, u32& at, u32& cg) {
-    const u32 u = w & 0xDFDFDFDFu;
-    at = zero_bytes(u ^ ('A' * ONES)) | zero_bytes(u ^ ('T' * ONES));
-    cg = zero_bytes(u ^ ('C' * ONES)) | zero_bytes(u ^ ('G' * ONES));
-}
-// a byte of ones for every bit 7 set in m
-__device__ __forceinline__ u32 spread(u32 m) { return (m >> 7) * 0xFFu; }
 
 // a byte of ones for every byte k of a dword whose position i0 + k lies in [lo, hi)
 __device__ __forceinline__ u32 cover(int i0, int lo, int hi) {
