@@ -1100,6 +1100,66 @@ pub fn fastx_parse_quals(ctx: &HipContext, d_text: &DeviceBuf<'_>, n_bytes: u64,
     Ok((n_reads, n_out, bad))
 }
 
+/// The record names of a FASTQ image (`kmx_fastx_parse_names`): `kmx_fastx_parse_quals` with line 0 of every record in place of
+/// line 3, the name as it stands (`@` included; `fastx_format` skips it with `name_skip = 1`).  `out = None` counts only; otherwise
+/// `out.0` gets the names back to back (room for `n_bytes` always suffices) and `out.1` `max_reads + 1` offsets: a ragged batch that
+/// `reads_gather` reorders.  A text that ends inside a record has one name more than quality lines.  Returns (names, bytes);
+/// Err(KMX_E_NOMEM) above `max_reads`, Err(KMX_E_ARG) for a text that is not FASTQ.  Synchronous.
+pub fn fastx_parse_names(ctx: &HipContext, d_text: &DeviceBuf<'_>, n_bytes: u64, format: u32, out: Option<(&DeviceBuf<'_>, &DeviceBuf<'_>)>,
+                         max_reads: u64) -> Result<(u64, u64), KmxError> {
+    assert!(n_bytes as u128 <= d_text.len() as u128, "text shorter than n_bytes");
+    let (dn, dno) = match out {
+        None => (ptr::null_mut(), ptr::null_mut()),
+        Some((q, o)) => {
+            assert!((max_reads as u128 + 1) * 8 <= o.len() as u128, "offsets shorter than max_reads + 1");
+            (q.as_mut_ptr::<u8>(), o.as_mut_ptr::<u64>())
+        }
+    };
+    let (mut n_names, mut n_out) = (0u64, 0u64);
+    ctx.ck(unsafe { kmx_fastx_parse_names(ctx.0, d_text.as_ptr::<u8>(), n_bytes, format, dn, dno, max_reads, &mut n_names, &mut n_out) })?;
+    Ok((n_names, n_out))
+}
+
+/// What `fastx_format` lays out beside the bases: the names (a ragged batch of `n_reads` names and its `n_reads + 1` offsets, taken
+/// from byte `name_skip` on; `None`: record r is named `name_base + r` in decimal), the quality bytes (laid out as the bases are;
+/// `None`: every quality byte is `qual_fill`), and the bases per FASTA line (0: one line; must be 0 for FASTQ).
+pub struct FastxRecord<'a> {
+    pub names: Option<(&'a DeviceBuf<'a>, &'a DeviceBuf<'a>)>,
+    pub name_skip: u32,
+    pub name_base: u64,
+    pub quals: Option<&'a DeviceBuf<'a>>,
+    pub qual_fill: u32,
+    pub line_width: u32,
+}
+
+/// A batch as a FASTQ (`KMX_FASTX_FASTQ`) or FASTA (`KMX_FASTX_FASTA`) image on the device (`kmx_fastx_format`; include/kmx.h defines
+/// a record byte for byte).  `d_text = None` counts only; otherwise up to `max_bytes` bytes are written (`d_text` may have any
+/// alignment), and with `d_rec_offsets` the `n_reads + 1` words where the records start.  Returns the bytes of the image;
+/// Err(KMX_E_NOMEM) above `max_bytes`, with nothing written.  Synchronous: one device-to-host copy of the result is the file.
+pub fn fastx_format(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>,
+                    rec: &FastxRecord<'_>, format: u32, d_text: Option<&DeviceBuf<'_>>, d_rec_offsets: Option<&DeviceBuf<'_>>, max_bytes: u64)
+                    -> Result<u64, KmxError> {
+    let r = reads_of(d_reads, n_reads, read_len, d_read_offsets);
+    let names = rec.names.map(|(b, o)| {
+        assert!((n_reads as u128 + 1) * 8 <= o.len() as u128, "name offsets shorter than n_reads + 1");
+        reads_of(b, n_reads, 0, Some(o))
+    });
+    let dt = d_text.map_or(ptr::null_mut(), |t| {
+        assert!(max_bytes as u128 <= t.len() as u128, "text shorter than max_bytes");
+        t.as_mut_ptr::<u8>()
+    });
+    let dro = d_rec_offsets.map_or(ptr::null_mut(), |o| {
+        assert!((n_reads as u128 + 1) * 8 <= o.len() as u128, "record offsets shorter than n_reads + 1");
+        o.as_mut_ptr::<u64>()
+    });
+    let mut n_bytes = 0u64;
+    ctx.ck(unsafe {
+        kmx_fastx_format(ctx.0, &r, rec.quals.map_or(ptr::null(), |q| q.as_ptr::<u8>()), names.as_ref().map_or(ptr::null(), |n| n as *const kmx_reads),
+                         rec.name_skip, rec.name_base, format, rec.line_width, rec.qual_fill, dt, dro, max_bytes, &mut n_bytes)
+    })?;
+    Ok(n_bytes)
+}
+
 /// One pass over the bases and quality bytes of a batch (`kmx_reads_quality`; include/kmx.h has the words of a row and the trim
 /// span): `d_quals` is laid out as the reads are.  `d_masked` (may be `d_reads` itself: in place) gets the bases with every base of
 /// q < `min_q` turned into 'N'; `d_rows` gets `KMX_RQ_WORDS` u64 per read.  At least one of the two.  `d_weights`: 256 u64 indexed by

@@ -1161,8 +1161,8 @@ int kmx_reads_gather(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_ind
  * With d_read_offsets (what kmx_fastx_parse wrote for the same image: at least n_reads + 1 words) and h_first_mismatch both given, the
  * lengths of the two offsets arrays are compared on the device: *h_first_mismatch = the smallest r whose quality line and sequence
  * line differ in length, ~0 if there is none.  The status stays KMX_OK: what a mismatch means is the caller's business.
- * KMX_FASTX_SAME_TEXT may be OR-ed into `format` under the contract stated at kmx_fastx_parse, where "the previous call" is either of
- * the two parse calls: the chunk summaries of pass 1 serve both, so reads and qualities of one image cost one summarising pass less,
+ * KMX_FASTX_SAME_TEXT may be OR-ed into `format` under the contract stated at kmx_fastx_parse, where "the previous call" is any of
+ * the parse calls (kmx_fastx_parse_names below included): the chunk summaries of pass 1 serve them all, so reads and qualities of one image cost one summarising pass less,
  * and a count-then-emit pair of this call reuses the count whole.  Synchronous. */
 int kmx_fastx_parse_quals(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t format, uint8_t *d_quals,
                           uint64_t *d_qoffsets, uint64_t max_reads, const uint64_t *d_read_offsets, uint64_t *h_n_reads,
@@ -1364,6 +1364,55 @@ int kmx_reads_pair_merge(kmx_ctx *ctx, const kmx_reads *reads1, const kmx_reads 
 int kmx_reads_dedup(kmx_ctx *ctx, const kmx_reads *reads, const kmx_reads *mates /* NULL: single reads */, uint32_t flags,
                     uint32_t hash_bits, const uint64_t *d_score, uint64_t score_stride, uint64_t *d_rows, uint8_t *d_keep,
                     uint64_t *h_summary /* KMX_DD_SUMMARY_WORDS, host */);
+
+/* ---------------------------------------------------------------- back to a file: record names, and a batch as FASTQ / FASTA text ----
+ * BUILD-DEFINED.  Every read-preparation call ends in a batch -- bytes and offsets in device memory.  The two calls here close the
+ * loop: the names of a FASTQ image are kept, and names, bases and quality bytes are laid out as a FASTQ or FASTA image on the
+ * device, so that one device-to-host copy is the output file.
+ *
+ * kmx_fastx_parse_names.  The contract of kmx_fastx_parse_quals with line i % 4 == 0 in place of line i % 4 == 3.  On the text alone:
+ * split it at '\n'; a final empty piece (the text is empty or ends in '\n') is not a line; name r is line 4r with every '\r'
+ * removed, for every 4r below the number of lines.  The name is the header line as it stands, its first byte ('@') included: no
+ * byte is interpreted (kmx_fastx_format has name_skip for the marker).  A text that ends inside a record has one name more than
+ * quality lines.  d_names = the names back to back, d_noffsets[r] = first byte of name r, d_noffsets[n_names] = the byte total:
+ * a ragged kmx_reads batch, so kmx_reads_gather reorders names by the d_out_index of kmx_reads_select.  format: KMX_FASTX_AUTO or
+ * KMX_FASTX_FASTQ; KMX_FASTX_FASTA, or a text that does not begin with '@', gives KMX_E_ARG (the names of FASTA records are not
+ * parsed by this library).  d_text 16-byte aligned; d_names: room for the bytes (n_bytes always suffices); d_noffsets: max_reads + 1
+ * words.  d_names == d_noffsets == NULL: only the counts; n_names > max_reads: KMX_E_NOMEM with nothing written and the counts
+ * set.  *h_n_names / *h_n_bytes (host, optional) = names / bytes kept.  KMX_FASTX_SAME_TEXT as at kmx_fastx_parse_quals, where "the
+ * previous call" is any of the three parse calls.  Synchronous.
+ *
+ * kmx_fastx_format.  Record r of the image, r < reads->n_reads, is defined on the arrays alone, in 64-bit arithmetic; any bytes
+ * give one answer.
+ *     L, B   the length and the bases of read r under THE SPAN OF A READ above (an offsets pair that descends: 0; 2^31 bases or
+ *            more: 0); the bases are copied verbatim.  Every layout kmx_reads_select takes is taken.
+ *     N      names != NULL (names->n_reads must equal reads->n_reads: KMX_E_ARG otherwise): with len the length of name r under
+ *            the same two rules, the bytes of name r from byte min(name_skip, len) on.  names == NULL: name_base + r (wrapping
+ *            mod 2^64) in decimal without leading zeros.
+ *     KMX_FASTX_FASTQ   '@' N '\n' B '\n' '+' '\n' Q '\n': |N| + 2 L + 6 bytes.  Q = the L bytes of d_quals, laid out as the bases
+ *            are and at any alignment of its own (kmx_reads_quality); d_quals == NULL: L copies of the byte qual_fill
+ *            (qual_fill > 255: KMX_E_ARG).  line_width must be 0: KMX_E_ARG otherwise.
+ *     KMX_FASTX_FASTA   '>' N '\n', then B in lines of line_width bases, each line ended by '\n'; line_width == 0: one line.  Every
+ *            record has at least one sequence line (an empty read: one empty line).  With lines = line_width ? max(1, ceil(L /
+ *            line_width)) : 1 the record is |N| + 2 + L + lines bytes.  d_quals and qual_fill are ignored.
+ *     any other `format` (KMX_FASTX_AUTO included): KMX_E_ARG.
+ * The records lie back to back in d_text; *h_n_bytes (host) = their total, always.  d_rec_offsets (optional): n_reads + 1 words,
+ * where each record starts, the total last.  d_text == NULL = count only (d_rec_offsets is still written if given).  n_bytes >
+ * max_bytes: KMX_E_NOMEM with not one byte of d_text and not one word of d_rec_offsets written, and the count set.  n_reads == 0
+ * is a no-op with a count of 0 (nothing is written).  n_reads up to 2^40, an image below 2^44 bytes.
+ * Memory, as at kmx_reads_select: d_text may have any alignment; not one byte outside [0, n_bytes) is written; no aligned dword
+ * that holds no byte of its batch is loaded from the bases, the quality bytes or the names; d_text overlapping one of the three
+ * sources or d_rec_offsets is KMX_E_ARG where the host can tell.  Deterministic, no atomics.  Synchronous (the count comes back to
+ * the host).  Working set in the work buffer: a256(8 * (n_reads + 1)) for the record offsets when the caller gives none, plus
+ * a256(8 * (2 * ceil(n_reads / 2048) + 6)); above the cap KMX_E_NOMEM before any kernel runs.  NULL ctx / reads / h_n_bytes:
+ * KMX_E_ARG.
+ * Not done: the names of FASTA records, two mates interleaved in one image, multi-line FASTQ, gzip / BGZF, writing to disk from
+ * the device. */
+int kmx_fastx_parse_names(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t format, uint8_t *d_names,
+                          uint64_t *d_noffsets, uint64_t max_reads, uint64_t *h_n_names, uint64_t *h_n_bytes);
+int kmx_fastx_format(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *d_quals, const kmx_reads *names, uint32_t name_skip,
+                     uint64_t name_base, uint32_t format, uint32_t line_width, uint32_t qual_fill, uint8_t *d_text,
+                     uint64_t *d_rec_offsets, uint64_t max_bytes, uint64_t *h_n_bytes);
 
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,

@@ -452,8 +452,20 @@ class FastqReads {
                                         reads_.reads().d_offsets, &nr, &nb, &bad),
                   "fastx_parse_quals");
         if (bad != ~0ull) throw std::runtime_error("FastqReads: read " + std::to_string(bad) + ": quality and sequence lines differ in length");
+        // line 0 of every record as it stands, '@' included (kmx_fastx_parse_names: the summaries of the text are still in the context)
+        uint64_t nn = 0, nnb = 0;
+        ctx.check(kmx_fastx_parse_names(ctx.get(), d.data(), text.size(), KMX_FASTX_FASTQ | KMX_FASTX_SAME_TEXT, nullptr, nullptr, 0, &nn, &nnb),
+                  "fastx_parse_names (count)");
+        if (nn != reads_.len()) throw std::runtime_error("FastqReads: the text ends inside a record");
+        names_.reset(new DeviceBuffer<uint8_t>(ctx, nnb ? nnb : 1));
+        noff_.reset(new DeviceBuffer<uint64_t>(ctx, nn + 1));
+        ctx.check(kmx_fastx_parse_names(ctx.get(), d.data(), text.size(), KMX_FASTX_FASTQ | KMX_FASTX_SAME_TEXT, names_->data(), noff_->data(), nn, &nn,
+                                        &nnb),
+                  "fastx_parse_names");
     }
     const FastxReads& reads() const { return reads_; }
+    // the record names as a ragged batch of their own (what kmx_reads_gather reorders and kmx_fastx_format takes)
+    kmx_reads names() const { return kmx_reads{names_->data(), reads_.len(), 0u, noff_->data()}; }
     const uint8_t* d_quals() const { return quals_->data(); }
     std::vector<uint8_t> quals() const { return quals_->download(); }
     // KMX_RQ_WORDS u64 per read; d_weights: 256 device words by the raw quality byte, or nullptr
@@ -472,8 +484,26 @@ class FastqReads {
   private:
     Context* ctx_;
     FastxReads reads_;
-    std::unique_ptr<DeviceBuffer<uint8_t>> quals_;
+    std::unique_ptr<DeviceBuffer<uint8_t>> quals_, names_;
+    std::unique_ptr<DeviceBuffer<uint64_t>> noff_;
 };
+
+// A batch as a FASTQ (KMX_FASTX_FASTQ) or FASTA (KMX_FASTX_FASTA) image, formatted on the device and brought to the host with one
+// copy (kmx.h, "back to a file").  d_quals: laid out as the bases are, or nullptr (every quality byte is qual_fill); names: a batch
+// of reads.n_reads names taken from byte name_skip on (FastqReads::names() keeps the '@': name_skip = 1), or nullptr (record r is
+// named name_base + r); line_width: bases per FASTA line, 0 = one line.
+inline std::string fastx_format(Context& ctx, const kmx_reads& reads, const uint8_t* d_quals = nullptr, const kmx_reads* names = nullptr,
+                                uint32_t format = KMX_FASTX_FASTQ, uint32_t line_width = 0, uint32_t name_skip = 1, uint64_t name_base = 0,
+                                uint32_t qual_fill = 'I') {
+    uint64_t nb = 0;
+    ctx.check(kmx_fastx_format(ctx.get(), &reads, d_quals, names, name_skip, name_base, format, line_width, qual_fill, nullptr, nullptr, 0, &nb),
+              "fastx_format (count)");
+    DeviceBuffer<uint8_t> image(ctx, nb ? nb : 1);
+    ctx.check(kmx_fastx_format(ctx.get(), &reads, d_quals, names, name_skip, name_base, format, line_width, qual_fill, image.data(), nullptr, nb, &nb),
+              "fastx_format");
+    const std::vector<uint8_t> h = image.download();
+    return std::string(h.begin(), h.begin() + static_cast<std::ptrdiff_t>(nb));
+}
 
 // Adapter read-through (kmx.h, "adapter read-through").  reads_adapter: the KMX_RA_* words of every read on the host -- the leftmost
 // 3' hit of any of `adapters` (up to 8 of up to 64 of ACGTacgt, N a wildcard).  reads_pair_overlap: the KMX_RP_* words of every mate

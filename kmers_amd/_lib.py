@@ -195,6 +195,8 @@ SIGNATURES = {
     "kmx_minimizers_sip13": (_int, [_vp, _RP, _vp, _u32, _u32, _u64, _u64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "kmx_fastx_parse": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_fastx_parse_quals": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_fastx_parse_names": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_fastx_format": (_int, [_vp, C.POINTER(Reads), _vp, C.POINTER(Reads), _u32, _u64, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_reads_quality": (_int, [_vp, _RP, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "kmx_reads_adapter": (_int, [_vp, _RP, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "kmx_reads_pair_overlap": (_int, [_vp, _RP, _RP, _u32, _u32, _u32, _u32, _vp]),

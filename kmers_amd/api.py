@@ -253,6 +253,13 @@ class Unitigs:
         loose = (open_sides == 1) | (open_sides == 2) if islands else open_sides == 1
         return (self.circular == 0) & (self.lengths <= int(max_nodes)) & loose
 
+    def write_fasta(self, file, width: int = 60):
+        """The unitigs as FASTA, formatted on the device (kmx_fastx_format over sequences()): record u is named u, its bases in
+        lines of `width` (0: one line).  `file`: a path or a binary file object -> the bytes written."""
+        step = torch.arange(self.n_unitigs + 1, dtype=torch.int64, device=self.offsets.device) * (self.k - 1)
+        return self._ctx.write_fastx(file, self.sequences(), self.n_unitigs, 0, offsets=self.offsets + step, fmt=_lib.FASTX_FASTA,
+                                     line_width=int(width))
+
     def write_gfa(self, file, links: "UnitigLinks | None" = None, support: "LinkSupport | None" = None):
         """The compacted graph as GFA 1, written on the host -- for graphs one would look at, not for 1e9 nodes.  `file` is a path
         or a text file object.  H VN:Z:1.0; one S line per unitig u, named u, with LN:i (bases) and KC:i (the sum of its entries'
@@ -1788,6 +1795,66 @@ class Context:
         if n > 0 and mn == mx:
             return bases, quals, n, mx, None
         return bases, quals, n, mx, offsets
+
+    @_on_ctx_stream
+    def fastx_names(self, text: torch.Tensor, same_text: bool = False):
+        """kmx_fastx_parse_names: FASTQ file image -> (names uint8[n_bytes], noffsets int64[n + 1]), line 0 of every record as it
+        stands ('@' included; fastx_format skips it with name_skip=1), laid out as fastx_parse gives the reads: a ragged batch that
+        reads_gather reorders.  Two calls: the counts, then the emit into exactly sized buffers.  same_text as in fastx_quals."""
+        n = int(text.numel())
+        nr, nb = C.c_uint64(0), C.c_uint64(0)
+        tp = _ptr(text) if n else None
+        fmt = _lib.FASTX_FASTQ | _lib.FASTX_SAME_TEXT
+        self._ck(self.lib.kmx_fastx_parse_names(self._h, tp, n, fmt if same_text else _lib.FASTX_FASTQ, None, None, 0, C.byref(nr), C.byref(nb)))
+        names = self.empty(max(nb.value, 1), torch.uint8)
+        noffsets = self.empty(nr.value + 1, torch.int64)
+        self._ck(self.lib.kmx_fastx_parse_names(self._h, tp, n, fmt, _ptr(names), _ptr(noffsets), nr.value, C.byref(nr), C.byref(nb)))
+        return names[:nb.value], noffsets
+
+    def fastq_records(self, text: torch.Tensor):
+        """FASTQ file image -> (bases, quals, n_reads, read_len, offsets, names, name_offsets): fastq_reads plus the record names
+        (fastx_names).  ValueError where the image has another number of names than of reads (it ends inside a header line)."""
+        bases, quals, n, read_len, offsets = self.fastq_reads(text)
+        names, noffsets = self.fastx_names(text, same_text=True)
+        if int(noffsets.numel()) - 1 != n:
+            raise ValueError(f"fastq_records: {int(noffsets.numel()) - 1} names for {n} reads (the image ends inside a record)")
+        return bases, quals, n, read_len, offsets, names, noffsets
+
+    @_on_ctx_stream
+    def fastx_format(self, bases, n_reads, read_len, offsets=None, quals=None, names=None, name_offsets=None, name_skip=1, name_base=0,
+                     fmt=_lib.FASTX_FASTQ, line_width=0, qual_fill=ord("I"), rec_offsets=False):
+        """kmx_fastx_format -> the batch as a FASTQ (fmt=FASTX_FASTQ) or FASTA (FASTX_FASTA) image, a uint8 device tensor sized
+        exactly by a count-only call first; with rec_offsets=True -> (image, int64[n_reads + 1]: where every record starts).
+        quals: laid out as the bases are (None: every quality byte is qual_fill).  names / name_offsets: a ragged batch of n_reads
+        names, taken from byte name_skip on (1: without the '@' that fastx_names keeps); names None: record r is named
+        name_base + r.  line_width: bases per FASTA line (0: one line)."""
+        n_reads = int(n_reads)
+        if (names is None) != (name_offsets is None):
+            raise ValueError("names and name_offsets: both or neither")
+        if names is not None and int(name_offsets.numel()) != n_reads + 1:
+            raise ValueError("name_offsets: n_reads + 1 words")
+        r = self._reads(bases, n_reads, read_len, offsets)
+        nm = self._reads(names, n_reads, 0, name_offsets) if names is not None else None
+        nb = C.c_uint64(0)
+        args = (self._h, C.byref(r), _ptr(quals) if quals is not None and quals.numel() else None, C.byref(nm) if nm is not None else None,
+                int(name_skip), int(name_base) & (2**64 - 1), int(fmt), int(line_width), int(qual_fill))
+        self._ck(self.lib.kmx_fastx_format(*args, None, None, 0, C.byref(nb)))
+        out = self.empty(max(nb.value, 1), torch.uint8)
+        off = torch.zeros(n_reads + 1, dtype=torch.int64, device=self.device) if rec_offsets else None
+        if n_reads:
+            self._ck(self.lib.kmx_fastx_format(*args, _ptr(out), _ptr(off), nb.value, C.byref(nb)))
+        return (out[:nb.value], off) if rec_offsets else out[:nb.value]
+
+    def write_fastx(self, file, bases, n_reads, read_len, **kw):
+        """fastx_format(bases, n_reads, read_len, **kw), one device-to-host copy, one write -> the bytes written.  `file`: a path
+        or a binary file object."""
+        image = self.fastx_format(bases, n_reads, read_len, **{**kw, "rec_offsets": False}).cpu().numpy()
+        if isinstance(file, (str, bytes)) or hasattr(file, "__fspath__"):
+            with open(file, "wb") as f:
+                f.write(memoryview(image))
+        else:
+            file.write(memoryview(image))
+        return int(image.size)
 
     # ------------------------------------------------------------ quality bytes acted on
     def _weights_arg(self, weights, phred):

@@ -2347,22 +2347,26 @@ int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint3
     return KMX_OK;
 }
 
-// kmx_fastx_parse with the FASTQ machine entered on line 2: passes 2 and 3 select line 3 of every record (kmx_fastx.hip).  What the
-// context remembers of a count (fx_*) is shared with kmx_fastx_parse: the chunk summaries of pass 1 do not depend on the entry line,
-// the chunk prefixes and totals of pass 2 do (fx_entry).
-int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_quals, uint64_t* d_qoffsets,
-                          uint64_t max_reads, const uint64_t* d_read_offsets, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_first_mismatch) {
+// kmx_fastx_parse with the FASTQ machine entered on another line: passes 2 and 3 select line 3 of every record (entry 2: the quality
+// lines) or line 0 (entry 1: the names) (kmx_fastx.hip).  What the context remembers of a count (fx_*) is shared by the three parse
+// calls: the chunk summaries of pass 1 do not depend on the entry line, the chunk prefixes and totals of pass 2 do (fx_entry).
+// The argument checks (behind them *h_reset = ~0, if given), the count and -- with room -- the launch of pass 3, which is left
+// running: *emitted says so (`what`: the lines, for the messages).
+static int fastq_lines(kmx_ctx* ctx, const char* who, const char* what, uint32_t entry, const uint8_t* d_text, uint64_t n_bytes, uint32_t format,
+                       uint8_t* d_out, uint64_t* d_ooffsets, uint64_t max_reads, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_reset,
+                       uint64_t* n_lines, bool* emitted) {
+    *emitted = false;
     const bool same_text = (format & KMX_FASTX_SAME_TEXT) != 0u;
     format &= ~KMX_FASTX_SAME_TEXT;
-    if (!ctx || format > KMX_FASTX_FASTQ || (n_bytes && !d_text) || (!d_quals != !d_qoffsets)) return KMX_E_ARG;
+    if (!ctx || format > KMX_FASTX_FASTQ || (n_bytes && !d_text) || (!d_out != !d_ooffsets)) return KMX_E_ARG;
     if (!aligned16(d_text)) return KMX_E_ARG;
     if (h_n_reads) *h_n_reads = 0;
     if (h_n_bytes) *h_n_bytes = 0;
-    if (h_first_mismatch) *h_first_mismatch = ~0ull;
+    if (h_reset) *h_reset = ~0ull;
     DeviceGuard g(ctx->device);
     if (n_bytes == 0) {
-        if (d_qoffsets) {
-            KMX_HIP(ctx, hipMemsetAsync(d_qoffsets, 0, 8, ctx->stream));
+        if (d_ooffsets) {
+            KMX_HIP(ctx, hipMemsetAsync(d_ooffsets, 0, 8, ctx->stream));
             KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         return KMX_OK;
@@ -2373,7 +2377,7 @@ int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes,
         KMX_HIP(ctx, hipMemcpyAsync(&first, d_text, 1, hipMemcpyDeviceToHost, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (first != '@') {
-            std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_fastx_parse_quals: the text starts with byte 0x%02x, not with '@' (FASTQ)", first);
+            std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: the text starts with byte 0x%02x, not with '@' (FASTQ)", who, first);
             return KMX_E_ARG;
         }
     }
@@ -2382,38 +2386,104 @@ int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes,
     unsigned long long* d_totals = ctx->d_scratch + KMX_S_FASTX_TOTALS;
     unsigned long long totals[2] = {0, 0};
     const bool summaries = known && scratch == ctx->d_big;   // pass 1 of an earlier count of this text is still in the work buffer
-    if (summaries && ctx->fx_entry == 2u) {
+    if (summaries && ctx->fx_entry == entry) {
         totals[0] = ctx->fx_totals[0];
         totals[1] = ctx->fx_totals[1];
     } else {
         ctx->fx_valid = false;
-        KMX_HIP(ctx, kmx::launch_fastx_count(d_text, n_bytes, false, scratch, d_totals, ctx->stream, 2u, !summaries));
+        KMX_HIP(ctx, kmx::launch_fastx_count(d_text, n_bytes, false, scratch, d_totals, ctx->stream, entry, !summaries));
         KMX_HIP(ctx, hipMemcpyAsync(totals, d_totals, 16, hipMemcpyDeviceToHost, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->fx_text = d_text;
         ctx->fx_bytes = n_bytes;
         ctx->fx_fasta = 0u;
-        ctx->fx_entry = 2u;
+        ctx->fx_entry = entry;
         ctx->fx_totals[0] = totals[0];
         ctx->fx_totals[1] = totals[1];
         ctx->fx_valid = true;
     }
     if (h_n_reads) *h_n_reads = totals[0];
     if (h_n_bytes) *h_n_bytes = totals[1];
-    if (!d_quals) return KMX_OK;
+    *n_lines = totals[0];
+    if (!d_out) return KMX_OK;
     if (totals[0] > max_reads) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_fastx_parse_quals: %llu quality lines, room for %llu", totals[0],
-                      (unsigned long long)max_reads);
+        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu %s, room for %llu", who, totals[0], what, (unsigned long long)max_reads);
         return KMX_E_NOMEM;
     }
-    KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, false, scratch, d_totals, d_quals, d_qoffsets, ctx->stream));
-    if (d_read_offsets && h_first_mismatch && totals[0]) {
+    KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, false, scratch, d_totals, d_out, d_ooffsets, ctx->stream, entry));
+    *emitted = true;
+    return KMX_OK;
+}
+
+int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_quals, uint64_t* d_qoffsets,
+                          uint64_t max_reads, const uint64_t* d_read_offsets, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_first_mismatch) {
+    uint64_t n_lines = 0;
+    bool emitted = false;
+    const int st = fastq_lines(ctx, "kmx_fastx_parse_quals", "quality lines", 2u, d_text, n_bytes, format, d_quals, d_qoffsets, max_reads, h_n_reads,
+                               h_n_bytes, h_first_mismatch, &n_lines, &emitted);
+    if (st != KMX_OK || !emitted) return st;
+    DeviceGuard g(ctx->device);
+    if (d_read_offsets && h_first_mismatch && n_lines) {
         KMX_HIP(ctx, first_bad_reset(ctx));
-        KMX_HIP(ctx, kmx::launch_fastx_length_mismatch(d_qoffsets, d_read_offsets, totals[0], first_bad_of(ctx), ctx->n_cu, ctx->stream));
-        if (int st = first_bad_read(ctx, ctx->h_pinned + KMX_PIN_READ)) return st;
+        KMX_HIP(ctx, kmx::launch_fastx_length_mismatch(d_qoffsets, d_read_offsets, n_lines, first_bad_of(ctx), ctx->n_cu, ctx->stream));
+        if (int st2 = first_bad_read(ctx, ctx->h_pinned + KMX_PIN_READ)) return st2;
         *h_first_mismatch = ctx->h_pinned[KMX_PIN_READ];
         return KMX_OK;
     }
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_fastx_parse_names(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_names, uint64_t* d_noffsets,
+                          uint64_t max_reads, uint64_t* h_n_names, uint64_t* h_n_bytes) {
+    uint64_t n_lines = 0;
+    bool emitted = false;
+    const int st = fastq_lines(ctx, "kmx_fastx_parse_names", "names", 1u, d_text, n_bytes, format, d_names, d_noffsets, max_reads, h_n_names, h_n_bytes,
+                               nullptr, &n_lines, &emitted);
+    if (st != KMX_OK || !emitted) return st;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+// ---- a batch laid out as a FASTQ / FASTA image (kmx_fastx_format.hip) ----
+int kmx_fastx_format(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_quals, const kmx_reads* names, uint32_t name_skip, uint64_t name_base,
+                     uint32_t format, uint32_t line_width, uint32_t qual_fill, uint8_t* d_text, uint64_t* d_rec_offsets, uint64_t max_bytes,
+                     uint64_t* h_n_bytes) {
+    const char* who = "kmx_fastx_format";
+    if (!ctx || !reads_ok(reads) || !h_n_bytes || !reads_batch_ok(reads)) return KMX_E_ARG;
+    if (format != KMX_FASTX_FASTQ && format != KMX_FASTX_FASTA) return KMX_E_ARG;
+    const bool fastq = format == KMX_FASTX_FASTQ;
+    if (fastq && (line_width != 0u || (!d_quals && qual_fill > 255u))) return KMX_E_ARG;
+    if (names && (!reads_ok(names) || !reads_batch_ok(names) || names->n_reads != reads->n_reads)) return KMX_E_ARG;
+    *h_n_bytes = 0;
+    const uint64_t n = reads->n_reads;
+    if (n == 0) return KMX_OK;
+    const kmx::FastxFormat f{reads->d_bases, reads->d_offsets, n, reads->read_len, fastq ? d_quals : nullptr, names ? names->d_bases : nullptr,
+                             names ? names->d_offsets : nullptr, names ? names->read_len : 0u, name_skip, name_base, line_width, qual_fill & 255u,
+                             names != nullptr, fastq};
+    DeviceGuard g(ctx->device);
+    const bool own_offsets = !d_rec_offsets;
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, kmx::fastx_format_bytes(n, own_offsets), &area)) return st;
+    uint64_t h[6] = {0, 0, 0, 0, 0, 0};   // records, bytes of the image, the first and last offset of the reads and of the names
+    KMX_HIP(ctx, kmx::launch_fastx_format_count(f, area, own_offsets, ctx->h_pinned, h, ctx->stream));
+    *h_n_bytes = h[1];
+    if (!d_text && !d_rec_offsets) return KMX_OK;
+    if (d_text) {
+        if (int st = room_for(ctx, who, h[1], "bytes", max_bytes)) return st;
+        if (h[1] >= (1ull << 44)) {   // (the copy is one grid of a block per 64 KiB)
+            std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu bytes in one image", who, (unsigned long long)h[1]);
+            return KMX_E_NOMEM;
+        }
+        // the bytes the three sources span, and the record offsets, against the bytes that are written
+        const Range out = Range::of_bytes(d_text, h[1]);
+        if (Range::of_batch(f.bases, f.offsets, n, f.read_len, h[2], h[3]).overlaps(out)) return KMX_E_ARG;
+        if (Range::of_batch(f.quals, f.offsets, n, f.read_len, h[2], h[3]).overlaps(out)) return KMX_E_ARG;
+        if (names && Range::of_batch(f.names, f.name_offsets, n, f.name_len, h[4], h[5]).overlaps(out)) return KMX_E_ARG;
+        if (Range::of_words(d_rec_offsets, n + 1u).overlaps(out)) return KMX_E_ARG;
+    }
+    KMX_HIP(ctx, kmx::launch_fastx_format_emit(f, area, own_offsets, d_rec_offsets, h[1], d_text, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
 }

@@ -485,8 +485,9 @@ fastx_scan_chunks_kernel(const u32* __restrict__ summ, u64 n_chunks, const u32* 
     __shared__ u64 sh_entry[3];
     // ---- where the block begins: the aggregates of the blocks before it, composed in order (the text starts with a header line
     // ('>' checked by the host) / on line `entry`: 0 for the reads; 2 makes line 3 of every record "the read" and the newline that
-    // ends the '+' line "a record opens" -- the quality lines; FASTA: record 0 opens at byte 0, no newline announces it)
-    u64 state = FASTA ? T_HDR : entry, out_pos = 0, rec = FASTA ? 1 : 0;
+    // ends the '+' line "a record opens" -- the quality lines; 1 makes line 0 "the read" and the newline that ends a quality line
+    // "a record opens" -- the names; FASTA, and the names: record 0 opens at byte 0, no newline announces it)
+    u64 state = FASTA ? T_HDR : entry, out_pos = 0, rec = FASTA || entry == 1u ? 1 : 0;
     for (u64 base = 0; base < blockIdx.x; base += FX_SCAN_THREADS) {
         const u64 bb = base + threadIdx.x;
         __syncthreads();
@@ -654,7 +655,9 @@ fastx_emit_kernel(const uint8_t* __restrict__ text, u64 n, const u64* __restrict
         fastx_emit_rows<FASTA, false>(text, n, c0, (u32)pf[0], pf[1], pf[2], bases, offsets, tmp32, wave_last, stage);
 }
 
-__global__ void fastx_last_offset_kernel(const unsigned long long* __restrict__ totals, u64* __restrict__ offsets) {
+// first_at_zero: record 0 opens at byte 0 and no newline announces it (the names; the FASTA emit kernel writes its own)
+__global__ void fastx_last_offset_kernel(const unsigned long long* __restrict__ totals, u64* __restrict__ offsets, bool first_at_zero) {
+    if (first_at_zero) offsets[0] = 0;
     offsets[totals[0]] = totals[1];
 }
 
@@ -679,7 +682,7 @@ size_t fastx_scratch_bytes(u64 n_bytes) {
 }
 
 // counts: passes 1 and 2; totals (device) receives {n_reads, n_bases}.  entry (FASTQ): the line number the text is taken to begin on,
-// 0 = the reads, 2 = the quality lines; summarise == false: the chunk summaries of an earlier count of the same text are still in
+// 0 = the reads, 2 = the quality lines, 1 = the names (line 0 of every record: the state counts up, so line 0 is "line 1" then); summarise == false: the chunk summaries of an earlier count of the same text are still in
 // `scratch`, only pass 2 runs
 hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scratch, unsigned long long* totals, hipStream_t st, u32 entry,
                               bool summarise) {
@@ -700,9 +703,9 @@ hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scra
     return hipGetLastError();
 }
 
-// pass 3 (after launch_fastx_count on the same scratch)
+// pass 3 (after launch_fastx_count on the same scratch, with the same entry)
 hipError_t launch_fastx_emit(const uint8_t* text, u64 n, bool fasta, const void* scratch, const unsigned long long* totals,
-                             uint8_t* bases, u64* offsets, hipStream_t st) {
+                             uint8_t* bases, u64* offsets, hipStream_t st, u32 entry) {
     const u64 n_chunks = (n + FX_CHUNK - 1u) / FX_CHUNK;
     const u64* prefix = static_cast<const u64*>(scratch);
     const u32* summ = reinterpret_cast<const u32*>(prefix + n_chunks * FX_PFX_WORDS);
@@ -710,7 +713,7 @@ hipError_t launch_fastx_emit(const uint8_t* text, u64 n, bool fasta, const void*
         hipLaunchKernelGGL(fastx_emit_kernel<true>, dim3((unsigned)n_chunks), dim3(FX_THREADS), 0, st, text, n, prefix, summ, bases, offsets);
     else
         hipLaunchKernelGGL(fastx_emit_kernel<false>, dim3((unsigned)n_chunks), dim3(FX_THREADS), 0, st, text, n, prefix, summ, bases, offsets);
-    hipLaunchKernelGGL(fastx_last_offset_kernel, dim3(1), dim3(1), 0, st, totals, offsets);
+    hipLaunchKernelGGL(fastx_last_offset_kernel, dim3(1), dim3(1), 0, st, totals, offsets, !fasta && entry == 1u);
     return hipGetLastError();
 }
 

@@ -63,7 +63,7 @@ hipError_t launch_fastx_count(const uint8_t* text, u64 n, bool fasta, void* scra
                               bool summarise = true);
 hipError_t launch_fastx_length_mismatch(const u64* a, const u64* b, u64 n_reads, unsigned long long* first_bad, int n_cu, hipStream_t st);
 hipError_t launch_fastx_emit(const uint8_t* text, u64 n, bool fasta, const void* scratch, const unsigned long long* totals,
-                             uint8_t* bases, u64* offsets, hipStream_t st);
+                             uint8_t* bases, u64* offsets, hipStream_t st, u32 entry = 0u);
 // kmx_seqvec.hip
 hipError_t launch_seqvec_push(u64* words, u64 first, const uint8_t* bytes, u64 n, unsigned long long* first_bad, int n_cu, hipStream_t st);
 hipError_t launch_seqvec_to_bytes(const u64* words, u64 n, uint8_t* out, int n_cu, hipStream_t st);
@@ -226,8 +226,8 @@ hipError_t launch_count_adjacency_cut(const uint8_t* edges, const uint8_t* flips
                                       u64 n_unitigs, const u64* place, const u64* link_offsets, u64 n_links, const uint8_t* cut, uint8_t* edges_out,
                                       hipStream_t st);
 // The four kmx_reads_*.hip units share kmx_reads_common.h (the span of a read, "is one of ACGTacgt", the wave-per-read launch shape);
-// the two that produce a batch, edit and merge, share kmx_reads_plan.h on top of it (the plan's place in the work area, the body
-// of its count kernel, the scans and the read-back).
+// the two that produce a batch, edit and merge, and kmx_fastx_format.hip share kmx_reads_plan.h on top of it (the plan's place in the
+// work area, the body of its count kernel, the scans and the read-back; the block search and dword assembly of the two copies).
 // kmx_reads_edit.hip: a new ragged batch from an old one (kmx_reads_select / kmx_reads_gather).  A ROW is a source read (select:
 // index == nullptr, n_rows == n_reads) or an entry of the index (gather).  The count plans every row in an area of
 // reads_edit_bytes(n_rows) and brings back h_out[0 .. 4) = output reads, output bases, the batch's first and last offset (0, 0 for
@@ -250,6 +250,28 @@ size_t reads_edit_bytes(u64 n_rows);
 hipError_t launch_reads_edit_count(const ReadsEdit& e, void* area, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
 hipError_t launch_reads_edit_emit(const ReadsEdit& e, void* area, u64 n_out, u64 n_bases, uint8_t* out_bases, u64* out_offsets, u64* out_index,
                                   hipStream_t st);
+// kmx_fastx_format.hip: the batch as a FASTQ / FASTA image (kmx_fastx_format).  The count plans every record in an area of
+// fastx_format_bytes(n_reads, own_offsets) and brings back h_out[0 .. 6) = records, bytes of the image, the first and last offset of
+// the reads and of the names (0, 0 for a uniform batch): synchronous, one round trip.  The emit writes the record offsets (into the
+// area with own_offsets, else into rec_offsets) and, with text != nullptr, the image; asynchronous.
+struct FastxFormat {
+    const uint8_t* bases;
+    const u64* offsets;        // nullptr: uniform reads of read_len bases
+    u64 n_reads;
+    u32 read_len;
+    const uint8_t* quals;      // laid out as the bases are; nullptr: `fill`
+    const uint8_t* names;      // has_names: a batch of n_reads names
+    const u64* name_offsets;   // nullptr: uniform names of name_len bytes
+    u32 name_len;
+    u32 name_skip;
+    u64 name_base;             // !has_names: record r is named name_base + r in decimal
+    u32 width;                 // FASTA: bases per line, 0 = one line
+    u32 fill;
+    bool has_names, fastq;
+};
+size_t fastx_format_bytes(u64 n_reads, bool own_offsets);
+hipError_t launch_fastx_format_count(const FastxFormat& f, void* area, bool own_offsets, unsigned long long* h_pinned, u64* h_out, hipStream_t st);
+hipError_t launch_fastx_format_emit(const FastxFormat& f, void* area, bool own_offsets, u64* rec_offsets, u64 n_bytes, uint8_t* text, hipStream_t st);
 // kmx_reads_quality.hip: the masked copy and / or KMX_RQ_WORDS u64 per read out of the bases and the quality bytes (kmx_reads_quality;
 // a wave per read, asynchronous)
 struct ReadsQuality {
