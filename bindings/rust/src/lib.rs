@@ -1208,6 +1208,24 @@ pub fn reads_pair_overlap(ctx: &HipContext, d_reads1: &DeviceBuf<'_>, read_len1:
     ctx.ck(unsafe { kmx_reads_pair_overlap(ctx.0, &r1, &r2, min_overlap, max_mism, err_num, err_den, d_rows.as_mut_ptr::<u64>()) })
 }
 
+/// Poly-X tails and heads, base composition, neighbour pairs and the DUST numerators of 64-base windows in one pass over the bases
+/// (`kmx_reads_complexity`; include/kmx.h has the poly-X rule, the windows and the words of a row).  `tail_bases` / `head_bases`: bit 0
+/// A, 1 C, 2 G, 3 T (4: poly-G tails, 15: any letter).  `d_masked` (may be `d_reads` itself: in place) gets the bases with every base
+/// of a window whose numerator exceeds `dust_max` turned into 'N'; `d_rows` gets `KMX_RX_WORDS` u64 per read.  At least one of the two.
+/// `ReadSpans { words: &d_rows, first_word: KMX_RX_KEEP as u64, stride: KMX_RX_WORDS as u64, k: 0 }` cuts the ends off with
+/// `reads_select`.  Asynchronous on the context's stream.
+pub fn reads_complexity(ctx: &HipContext, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, d_read_offsets: Option<&DeviceBuf<'_>>,
+                        tail_bases: u32, head_bases: u32, min_len: u32, err_num: u32, err_den: u32, penalty: u32, dust_max: u32,
+                        d_masked: Option<&DeviceBuf<'_>>, d_rows: Option<&DeviceBuf<'_>>) -> Result<(), KmxError> {
+    let r = reads_of(d_reads, n_reads, read_len, d_read_offsets);
+    if let Some(rows) = d_rows {
+        assert!(n_reads as u128 * KMX_RX_WORDS as u128 * 8 <= rows.len() as u128, "rows shorter than the batch's reads");
+    }
+    ctx.ck(unsafe { kmx_reads_complexity(ctx.0, &r, tail_bases, head_bases, min_len, err_num, err_den, penalty, dust_max,
+                                         d_masked.map_or(ptr::null_mut(), |m| m.as_mut_ptr::<u8>()),
+                                         d_rows.map_or(ptr::null_mut(), |x| x.as_mut_ptr::<u64>())) })
+}
+
 /// One batch of mates for `reads_pair_merge`: the bases, their layout and, optionally, the quality bytes laid out as the bases are.
 pub struct Mates<'a> {
     pub bases: &'a DeviceBuf<'a>,

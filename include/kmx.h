@@ -1300,6 +1300,58 @@ int kmx_reads_pair_merge(kmx_ctx *ctx, const kmx_reads *reads1, const kmx_reads 
                          uint32_t q_cap, uint8_t *d_out_bases, uint8_t *d_out_quals, uint64_t *d_out_offsets, uint64_t *d_rows,
                          uint64_t max_bases, uint64_t *h_n_merged, uint64_t *h_n_bases);
 
+/* ---------------------------------------------------------------- poly-X ends, base composition, low complexity ----
+ * BUILD-DEFINED (the reference has nothing like it): what fastp --trim_poly_g / --trim_poly_x / --low_complexity_filter, cutadapt
+ * --poly-a and the DUST score of prinseq / sdust do between the parse and the count.  kmx_reads_complexity is one pass over the
+ * bases of a batch, without quality bytes and without a table.  Every layout kmx_reads_quality takes is taken: uniform and ragged
+ * reads, d_offsets[0] > 0, empty reads, any alignment of d_bases and of d_masked independently.  A read of 2^31 bases or more, or an
+ * offsets pair that descends, counts as empty (L = 0).  Letters are compared with the case ignored; a byte that is not one of
+ * ACGTacgt is INVALID: it matches no letter.
+ *
+ * THE POLY-X RULE.  The bits of tail_bases and head_bases select letters: bit 0 A, bit 1 C, bit 2 G, bit 3 T (tail_bases = 4 is
+ * fastp's --trim_poly_g, 15 its --trim_poly_x).  For a letter X and the suffix of the read that starts at p:
+ *     n = L - p        m = the number of its bases that are not X        s = n - (penalty + 1) * m            (signed, 64-bit)
+ *     the suffix QUALIFIES  iff  base p is X  and  n >= min_len  and  m * err_den <= err_num * n        (64-bit arithmetic)
+ * With penalty = 2 a match is worth +1 and a mismatch -2: cutadapt's poly-A scoring.  The tail for X is the qualifying suffix with
+ * the largest s, of equal s the longest; the read's tail is the best over the selected letters by the same order, then the lowest
+ * bit.  The head is the mirror image on the prefixes that END at p, base p being X, with head_bases.  With t and h the two lengths
+ * (0 where there is none) the KEEP span is empty (the word 0) if h + t >= L, otherwise start h, length L - h - t; with both masks 0
+ * it is the whole read.  (d_rows + KMX_RX_KEEP, KMX_RX_WORDS, 0) is what kmx_reads_select takes.
+ *
+ * COMPOSITION AND NEIGHBOURS.  The counts of A, C, G and T; P = the positions i with bases i and i + 1 both valid, D = those of
+ * them whose two letters differ.  D / P is fastp's complexity with invalid bytes left out (its filter drops reads below 0.30).
+ *
+ * THE DUST NUMERATORS.  Window j covers the bases [32 j, min(32 j + 64, L)); there are W = 0 windows for L = 0, 1 for L <= 64,
+ * ceil((L - 64) / 32) + 1 otherwise.  A triplet of a window COUNTS when it lies wholly inside the window and its three bases are
+ * valid; c_t = the counted triplets that spell t; S_j = the sum over t of c_t * (c_t - 1) / 2.  A full window of one letter has
+ * S = 1891, (AC)n 930, (ACG)n 610, random bases about 30; S / 61 is the sdust / prinseq score of a full window (sdust's threshold of
+ * 2 is a dust_max of about 122).  Window j is DUSTY iff S_j > dust_max; dust_max >= 1891 means never.  The windows are taken over
+ * the WHOLE read, not over the keep span: a caller who wants the trimmed read scored selects first and calls again.
+ * d_masked (optional): same layout, same offsets; a base becomes 'N' iff it lies in at least one DUSTY window, every other byte of
+ * every read is copied as it is -- so every k-mer call skips the windows over a masked base.  d_masked == d_bases (in place) is
+ * allowed; any other overlap with the bases is KMX_E_ARG where the host can tell, exactly as kmx_reads_quality decides it.  Not one
+ * byte outside the bytes of the reads is written, and no load touches an aligned dword that holds no byte of the batch.
+ * d_rows (optional): KMX_RX_WORDS u64 per read, the words below.  At least one of d_masked and d_rows must be given; without d_rows
+ * the poly-X arguments are checked and not used.
+ * Not done here: entropy over k-mers (BBDuk), soft (lower-case) masking, the merging of DUST intervals as sdust does it.
+ * A base mask above 15, err_den == 0, err_num > err_den, min_len == 0 with a nonzero base mask, penalty > 255, both outputs NULL,
+ * NULL ctx / reads: KMX_E_ARG.  n_reads up to 2^40; n_reads == 0 is a no-op whose arguments are still checked.  No work buffer, no
+ * atomics: a row and the bytes of a read are written by the one wave that owns the read, so repeated calls give identical bytes.
+ * Asynchronous on the context's stream (ragged reads with d_masked: after the one round trip for the batch's first and last
+ * offset). */
+#define KMX_RX_WORDS 8u
+#define KMX_RX_KEEP 0u  /* span word in bases: start | len << 32 (what kmx_reads_select takes with span_k = 0) */
+#define KMX_RX_BASES 1u /* L */
+#define KMX_RX_TAIL 2u  /* 0 without a tail, otherwise t | (bit index of X + 1) << 32 */
+#define KMX_RX_HEAD 3u  /* the same for the head */
+#define KMX_RX_AC 4u    /* count of A | count of C << 32 */
+#define KMX_RX_GT 5u    /* count of G | count of T << 32 */
+#define KMX_RX_DIFF 6u  /* D | P << 32 */
+#define KMX_RX_DUST 7u  /* max over j of S_j | (number of DUSTY windows) << 32; 0 for an empty read */
+int kmx_reads_complexity(kmx_ctx *ctx, const kmx_reads *reads, uint32_t tail_bases, uint32_t head_bases, uint32_t min_len,
+                         uint32_t err_num, uint32_t err_den, uint32_t penalty, uint32_t dust_max, uint8_t *d_masked,
+                         uint64_t *d_rows);
+
 /* ---------------------------------------------------------------- duplicate reads and read pairs ----
  * BUILD-DEFINED (the reference has nothing like it): what fastp --dedup, clumpify dedupe and samtools markdup do -- reads, or mate
  * pairs, whose whole content was sequenced before are found and all but one of each class dropped.  EXACT: items are grouped by a

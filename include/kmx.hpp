@@ -534,6 +534,21 @@ inline std::vector<uint64_t> reads_pair_overlap(Context& ctx, const kmx_reads& r
     return out;
 }
 
+// Poly-X ends, base composition and low complexity (kmx.h, "poly-X ends, base composition, low complexity"): the KMX_RX_* words of
+// every read on the host.  tail_bases / head_bases: bit 0 A, 1 C, 2 G, 3 T (4: poly-G tails, 15: any letter).  mask = true also turns
+// every base of a DUSTY window into 'N', in place.  KMX_RX_KEEP is what kmx_reads_select clips by.
+inline std::vector<uint64_t> reads_complexity(Context& ctx, const kmx_reads& reads, uint32_t tail_bases = 4, uint32_t head_bases = 0,
+                                              uint32_t min_len = 10, uint32_t err_num = 1, uint32_t err_den = 10, uint32_t penalty = 2,
+                                              uint32_t dust_max = 122, bool mask = false) {
+    DeviceBuffer<uint64_t> rows(ctx, reads.n_reads * KMX_RX_WORDS + 1);
+    ctx.check(kmx_reads_complexity(ctx.get(), &reads, tail_bases, head_bases, min_len, err_num, err_den, penalty, dust_max,
+                                   mask ? const_cast<uint8_t*>(reads.d_bases) : nullptr, rows.data()),
+              "reads_complexity");
+    auto out = rows.download();   // (synchronises)
+    out.resize(reads.n_reads * KMX_RX_WORDS);
+    return out;
+}
+
 // Overlapping mate pairs merged into consensus reads (kmx.h, "overlapping mate pairs merged"): a ragged batch on the host with one read
 // per PAIR, empty where the pair does not merge -- bases, quality bytes (empty without d_quals1 / d_quals2), n_reads + 1 offsets and
 // the KMX_RM_* words of every pair.  d_insert / insert_stride: the insert size of every pair on the device, strided;

@@ -62,6 +62,10 @@ RA_MAX_ADAPTERS, RA_MAX_ADAPTER_LEN = 8, 64
 RP_INSERT, RP_OVERLAP, RP_KEEP1, RP_KEEP2 = range(4)
 RP_WORDS = 4
 RP_MAX_LEN = 1024
+# kmx_reads_complexity: the words of a read's row (KMX_RX_*)
+RX_KEEP, RX_BASES, RX_TAIL, RX_HEAD, RX_AC, RX_GT, RX_DIFF, RX_DUST = range(8)
+RX_WORDS = 8
+RX_DUST_NEVER = 1891   # a dust_max no window exceeds: the numerator of a full window of one letter
 # kmx_reads_pair_merge: the words of a pair's row (KMX_RM_*)
 RM_LEN, RM_OVERLAP, RM_TAKEN, RM_INVALID = range(4)
 RM_WORDS = 4
@@ -200,6 +204,7 @@ SIGNATURES = {
     "kmx_reads_quality": (_int, [_vp, _RP, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "kmx_reads_adapter": (_int, [_vp, _RP, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "kmx_reads_pair_overlap": (_int, [_vp, _RP, _RP, _u32, _u32, _u32, _u32, _vp]),
+    "kmx_reads_complexity": (_int, [_vp, _RP, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "kmx_reads_pair_merge": (_int, [_vp, _RP, _RP, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_reads_dedup": (_int, [_vp, _RP, _RP, _u32, _u32, _vp, _u64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "kmx_sub_kmer_words": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp]),

@@ -483,6 +483,33 @@ def expected_errors(rows):
     return (w & 0x7FFFFFFFFFFFFFFF).to(torch.float64) / 2.0**32 + (w < 0).to(torch.float64) * 2.0**31
 
 
+def gc_content(rows):
+    """float64[n_reads]: (C + G) / (A + C + G + T) out of reads_complexity's rows; 0 for a read without a valid base"""
+    ac, gt = rows[:, _lib.RX_AC], rows[:, _lib.RX_GT]
+    cg = (ac >> 32) + (gt & 0xFFFFFFFF)
+    total = (ac & 0xFFFFFFFF) + (gt >> 32) + cg
+    return cg.to(torch.float64) / total.clamp(min=1).to(torch.float64)
+
+
+def dust_score(rows):
+    """float64[n_reads]: the largest DUST numerator of a read's windows out of reads_complexity's rows, over 61 -- the sdust /
+    prinseq score of a full 64-base window (a homopolymer: 31, random bases: about 0.5, sdust's threshold: 2)"""
+    return (rows[:, _lib.RX_DUST] & 0xFFFFFFFF).to(torch.float64) / 61.0
+
+
+def _letters_arg(letters) -> int:
+    """"G" -> 4, "ACGT" -> 15, "" -> 0: the base mask of kmx_reads_complexity (an int passes through)"""
+    if isinstance(letters, int):
+        return letters
+    mask = 0
+    for ch in letters:
+        at = "ACGT".find(ch.upper())
+        if at < 0:
+            raise ValueError("letters: a string over ACGT")
+        mask |= 1 << at
+    return mask
+
+
 # The public Illumina adapter sequences, as the 3' read-through shows them: what reads_adapter / reads_trim_adapters take.
 ADAPTERS = {
     "truseq": "AGATCGGAAGAGC",
@@ -1949,6 +1976,67 @@ class Context:
         q = None
         if quals is not None:
             q = self.reads_select(quals, n_reads, read_len, span=span, span_k=0, min_len=min_len, offsets=offsets)
+        return b, q, rows
+
+    # ------------------------------------------------------------ poly-X ends, composition, low complexity
+    @_on_ctx_stream
+    def reads_complexity(self, bases, n_reads, read_len, tail="G", head="", min_len=10, max_error=(1, 10), penalty=2, dust_max=122, offsets=None,
+                         mask=True, out=None):
+        """kmx_reads_complexity -> (masked, rows): masked = the bases with every 64-base window whose DUST numerator exceeds dust_max
+        turned into 'N' (same layout, same offsets; None with mask=False; out=bases masks in place), rows int64[n_reads, RX_WORDS]
+        (viewable as u64; include/kmx.h has the words).  tail / head: the letters looked for at the 3' / 5' end, a string over ACGT
+        ("G": fastp --trim_poly_g, "ACGT": --trim_poly_x, "": none); an end of at least min_len bases with at most max_error =
+        (num, den) other bases per base, scored +1 a match and -(penalty) a mismatch.  rows[:, RX_KEEP] is the span reads_select
+        takes; gc_content and dust_score read the other words."""
+        n_reads = int(n_reads)
+        masked = None
+        if mask:
+            masked = out if out is not None else torch.empty_like(bases)
+            if masked.dtype != torch.uint8 or masked.numel() < bases.numel():
+                raise ValueError("out: a uint8 tensor as large as bases")
+        rows = self.empty(_lib.RX_WORDS * n_reads, torch.int64)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(self.lib.kmx_reads_complexity(self._h, C.byref(r), _letters_arg(tail), _letters_arg(head), int(min_len), int(max_error[0]),
+                                               int(max_error[1]), int(penalty), int(dust_max),
+                                               _ptr(masked) if masked is not None and masked.numel() else None, _ptr(rows) if n_reads else None))
+        return masked, rows.view(-1, _lib.RX_WORDS)
+
+    def _select_pair(self, bases, quals, n_reads, read_len, keep, span, min_len, offsets):
+        """one keep tensor and one span column into two reads_select calls: the bases (with index) and the quality bytes or None, with
+        identical offsets"""
+        b = self.reads_select(bases, n_reads, read_len, keep=keep, span=span, span_k=0, min_len=min_len, offsets=offsets, index=True)
+        q = None
+        if quals is not None:
+            q = self.reads_select(quals, n_reads, read_len, keep=keep, span=span, span_k=0, min_len=min_len, offsets=offsets)
+        return b, q
+
+    @_on_ctx_stream
+    def reads_trim_poly(self, bases, n_reads, read_len, tail="G", head="", min_len=10, max_error=(1, 10), penalty=2, offsets=None, quals=None,
+                        min_len_out=0):
+        """reads_complexity, then reads_select on RX_KEEP -> (ReadBatch of the bases with index, ReadBatch of the quality bytes or None,
+        rows of the SOURCE reads): every read without its poly-X tail and head, clips shorter than min_len_out dropped.  With `quals`
+        (the layout of bases) the same span column goes into a second reads_select, so the two batches have identical offsets."""
+        _, rows = self.reads_complexity(bases, n_reads, read_len, tail, head, min_len, max_error, penalty, _lib.RX_DUST_NEVER, offsets, mask=False)
+        b, q = self._select_pair(bases, quals, n_reads, read_len, None, rows[:, _lib.RX_KEEP], min_len_out, offsets)
+        return b, q, rows
+
+    @_on_ctx_stream
+    def reads_complexity_filter(self, bases, n_reads, read_len, tail="G", head="", min_len=10, max_error=(1, 10), penalty=2, dust_max=122,
+                                offsets=None, min_diff=(3, 10), max_dust=None, trim=True, quals=None, min_len_out=0):
+        """reads_complexity, then reads_select on its rows -> (ReadBatch of the bases with index, ReadBatch of the quality bytes or
+        None, rows of the SOURCE reads).  A read is kept iff D * den >= num * P with min_diff = (num, den) -- fastp's complexity of at
+        least 30 % by default, None: no such test -- and the largest DUST numerator of its windows is at most max_dust (None: no
+        such test); both are exact integer comparisons on the device.  trim=True clips the kept reads to RX_KEEP; clips shorter
+        than min_len_out are dropped.  The bases that are kept are the SOURCE bases, not the masked ones."""
+        _, rows = self.reads_complexity(bases, n_reads, read_len, tail, head, min_len, max_error, penalty, dust_max, offsets, mask=False)
+        keep = None
+        if min_diff is not None:
+            diff = rows[:, _lib.RX_DIFF]
+            keep = (diff & 0xFFFFFFFF) * int(min_diff[1]) >= (diff >> 32) * int(min_diff[0])   # (D, P < 2^31: the words are positive)
+        if max_dust is not None:
+            low = (rows[:, _lib.RX_DUST] & 0xFFFFFFFF) <= int(max_dust)
+            keep = low if keep is None else keep & low
+        b, q = self._select_pair(bases, quals, n_reads, read_len, keep, rows[:, _lib.RX_KEEP] if trim else None, min_len_out, offsets)
         return b, q, rows
 
     @_on_ctx_stream

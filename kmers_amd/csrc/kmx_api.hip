@@ -2488,6 +2488,27 @@ int kmx_fastx_format(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_qual
     return KMX_OK;
 }
 
+// ---- the masked copies of a batch (kmx_reads_quality, kmx_reads_complexity) ----
+// The bytes the batch spans (ragged: its first and last offset, one round trip) against the bytes of d_masked that are written:
+// KMX_E_ARG unless d_masked is d_bases itself (in place) or clear of the bases, and clear of `d_also` -- bytes laid out as the
+// bases are, which the call reads on a dword grid of their own (the quality bytes; nullptr: there are none).
+static int masked_copy_ok(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_masked, const uint8_t* d_also) {
+    uint64_t first = 0, last = 0;
+    if (reads->d_offsets) {
+        unsigned long long* h = ctx->h_pinned;
+        KMX_HIP(ctx, hipMemcpyAsync(h, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipMemcpyAsync(h + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        first = h[0];
+        last = h[1];
+    }
+    auto spanned = [&](const void* base) { return Range::of_batch(base, reads->d_offsets, reads->n_reads, reads->read_len, first, last); };
+    const Range m = spanned(d_masked);
+    if (d_masked != reads->d_bases && m.overlaps(spanned(reads->d_bases))) return KMX_E_ARG;
+    if (m.overlaps(spanned(d_also))) return KMX_E_ARG;
+    return KMX_OK;
+}
+
 // ---- the quality bytes of a batch acted on (kmx_reads_quality.hip) ----
 int kmx_reads_quality(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_quals, uint32_t phred_base, uint32_t min_q, uint32_t trim_q, uint32_t k,
                       const uint64_t* d_weights, uint8_t* d_masked, uint64_t* d_rows) {
@@ -2497,23 +2518,8 @@ int kmx_reads_quality(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_qua
     const bool bytes = reads->d_offsets || reads->read_len;   // (uniform reads of no bases: rows of zeros, nothing is read)
     if (bytes && !d_quals) return KMX_E_ARG;
     DeviceGuard g(ctx->device);
-    if (bytes && d_masked) {
-        // the bytes the batch spans (ragged: its first and last offset, one round trip) against the bytes that are written; the
-        // quality bytes are read on another dword grid than the bases, so they must not be written over either
-        uint64_t first = 0, last = 0;
-        if (reads->d_offsets) {
-            unsigned long long* h = ctx->h_pinned;
-            KMX_HIP(ctx, hipMemcpyAsync(h, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMX_HIP(ctx, hipMemcpyAsync(h + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            first = h[0];
-            last = h[1];
-        }
-        auto spanned = [&](const void* base) { return Range::of_batch(base, reads->d_offsets, reads->n_reads, reads->read_len, first, last); };
-        const Range m = spanned(d_masked);
-        if (d_masked != reads->d_bases && m.overlaps(spanned(reads->d_bases))) return KMX_E_ARG;
-        if (m.overlaps(spanned(d_quals))) return KMX_E_ARG;
-    }
+    if (bytes && d_masked)
+        if (int st = masked_copy_ok(ctx, reads, d_masked, d_quals)) return st;
     const kmx::ReadsQuality a{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, d_quals, phred_base, min_q, trim_q, k, d_weights,
                               d_masked, d_rows};
     KMX_HIP(ctx, kmx::launch_reads_quality(a, ctx->n_cu, ctx->stream));
@@ -2575,6 +2581,23 @@ int kmx_reads_pair_overlap(kmx_ctx* ctx, const kmx_reads* reads1, const kmx_read
     const kmx::ReadsPairOverlap a{reads1->d_bases, reads2->d_bases, reads1->d_offsets, reads2->d_offsets, reads1->n_reads, reads1->read_len,
                                   reads2->read_len, min_overlap, max_mism, err_num, err_den, d_rows};
     KMX_HIP(ctx, kmx::launch_reads_pair_overlap(a, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+// ---- poly-X ends, composition and DUST windows (kmx_reads_complexity.hip) ----
+int kmx_reads_complexity(kmx_ctx* ctx, const kmx_reads* reads, uint32_t tail_bases, uint32_t head_bases, uint32_t min_len, uint32_t err_num,
+                         uint32_t err_den, uint32_t penalty, uint32_t dust_max, uint8_t* d_masked, uint64_t* d_rows) {
+    if (!ctx || !reads_ok(reads) || (!d_masked && !d_rows) || tail_bases > 15u || head_bases > 15u) return KMX_E_ARG;
+    if (err_den == 0u || err_num > err_den || penalty > 255u || (min_len == 0u && (tail_bases | head_bases))) return KMX_E_ARG;
+    if (!reads_batch_ok(reads)) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    const bool bytes = reads->d_offsets || reads->read_len;   // (uniform reads of no bases: rows of zeros, nothing is read)
+    DeviceGuard g(ctx->device);
+    if (bytes && d_masked)
+        if (int st = masked_copy_ok(ctx, reads, d_masked, nullptr)) return st;
+    const kmx::ReadsComplexity a{reads->d_bases, reads->d_offsets, reads->n_reads, reads->read_len, tail_bases, head_bases, min_len, err_num, err_den,
+                                 penalty, dust_max, d_masked, d_rows};
+    KMX_HIP(ctx, kmx::launch_reads_complexity(a, ctx->n_cu, ctx->stream));
     return KMX_OK;
 }
 

@@ -310,6 +310,20 @@ struct ReadsPairOverlap {
 };
 hipError_t launch_reads_adapter(const ReadsAdapter& a, int n_cu, hipStream_t st);
 hipError_t launch_reads_pair_overlap(const ReadsPairOverlap& a, int n_cu, hipStream_t st);
+// kmx_reads_complexity.hip: the masked copy and / or KMX_RX_WORDS u64 per read out of the bases alone (kmx_reads_complexity; a wave
+// per read, asynchronous, no work buffer)
+struct ReadsComplexity {
+    const uint8_t* bases;
+    const u64* offsets;   // nullptr: uniform reads of read_len bases
+    u64 n_reads;
+    u32 read_len;
+    u32 tail_bases, head_bases;   // letters looked for at either end: bit 0 A, 1 C, 2 G, 3 T
+    u32 min_len, err_num, err_den, penalty;
+    u32 dust_max;
+    uint8_t* masked;      // or nullptr
+    u64* rows;            // KMX_RX_WORDS per read, or nullptr
+};
+hipError_t launch_reads_complexity(const ReadsComplexity& a, int n_cu, hipStream_t st);
 // kmx_reads_merge.hip: the consensus read of every mate pair (kmx_reads_pair_merge).  The count lays the plan's partial sums (merged
 // pairs, merged bases, per block of pairs) into `area` of reads_merge_bytes(n_reads) and brings back h_out[0 .. 6) = merged pairs,
 // merged bases, then the first and last offset of batch 1 and of batch 2 (0, 0 for uniform reads): synchronous, one round trip.
