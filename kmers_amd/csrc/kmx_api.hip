@@ -21,8 +21,6 @@ using namespace kmx;   // (the launchers, kmx_launch.h, are called qualified; th
 
 namespace {
 
-void* big_scratch(void* user, size_t bytes);
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
 
 // the words of d_scratch the calls address (kmx_layout.h)
@@ -100,43 +98,71 @@ int queue_clear_marks(kmx_ctx* ctx, uint64_t n_reads, uint32_t k, bool any_k) {
     return prepare_dirty_flags(ctx, n_reads, k, any_k);
 }
 
-// work buffer of the partitioned histogram: grown on demand (hipFree/hipMalloc synchronise, so only when it must grow),
-// kept until the context is destroyed; nullptr => the caller falls back to the global-atomic kernel
-void* big_scratch(void* user, size_t bytes) {
-    kmx_ctx* ctx = static_cast<kmx_ctx*>(user);
-    if (bytes <= ctx->big_bytes) return ctx->d_big;
-    ctx->fx_valid = false;   // (the buffer moves: the fastx chunk prefixes in it are gone)
-    if (ctx->d_big) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->d_big);
-        ctx->d_big = nullptr;
-        ctx->big_bytes = 0;
+// ---- the context's work buffer (kmx_internal.h).  Only this group, the context's creation and destruction and
+// kmx_ctx_work_buffer_info touch d_big / big_bytes / big_allocs. ----
+// A hold on the buffer: where it was, how large as a whole and which allocation it was when it was handed out.  A hold is not
+// exclusive: count_impl and the reads forms of the queries lay their arrays out in the buffer and then call kmx_canonical_windows,
+// which takes the start of the same buffer for its segment plan (count_plan_bytes) -- so whoever called out checks work_kept.
+struct WorkHold {
+    char* base = nullptr;
+    size_t size = 0;
+    unsigned long long allocs = 0;
+    size_t reserved = 0;   // query_scratch: the bytes at the start that are the holder's arrays; the lookup's directory goes behind them
+    bool kept(const kmx_ctx* ctx) const { return ctx->d_big == base && ctx->big_allocs == allocs; }
+};
+
+// The one place the buffer is handed out: grown on demand (hipFree / hipMalloc synchronise, so only when it must grow), kept until
+// the context is destroyed; no base: no memory.  Whoever takes the buffer here has invalidated the FASTX count cache (fx_*, whose
+// chunk prefixes live in the buffer); nothing else needs to.  `keep_fastx`: the FASTX parse itself, whose cache goes only when the
+// buffer moves.
+WorkHold work_acquire(kmx_ctx* ctx, size_t bytes, bool keep_fastx = false) {
+    const bool grow = bytes > ctx->big_bytes;
+    if (grow || !keep_fastx) ctx->fx_valid = false;
+    if (grow) {
+        if (ctx->d_big) {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(ctx->d_big);
+            ctx->d_big = nullptr;
+            ctx->big_bytes = 0;
+        }
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return WorkHold{};
+        }
+        ctx->big_allocs += 1;
+        ctx->d_big = q;
+        ctx->big_bytes = bytes;
     }
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    ctx->big_allocs += 1;
-    ctx->d_big = q;
-    ctx->big_bytes = bytes;
-    return q;
+    return WorkHold{static_cast<char*>(ctx->d_big), ctx->big_bytes, ctx->big_allocs};
 }
+
+// (a callee took a route that grew the work buffer under the arrays laid out in it: a bug, never expected)
+int work_kept(kmx_ctx* ctx, const char* who, const WorkHold& hold) {
+    if (hold.kept(ctx)) return KMX_OK;
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "%s: work buffer moved", who);
+    return fail_hip(ctx, hipErrorUnknown, msg);
+}
+
+// What the histogram launchers ask their scratch of (user = the context); nullptr => they fall back to the global-atomic kernel.
+void* work_callback(void* user, size_t bytes) { return work_acquire(static_cast<kmx_ctx*>(user), bytes).base; }
 
 // The segment arrays of the long-read paths (16-24 bytes per segment): inside the cap of kmx_ctx_set_work_buffer_limit, or not at
 // all -- the call then takes the per-read kernels, as it does when the allocation fails.
-static void* capped_scratch(kmx_ctx* ctx, size_t bytes) {
+void* capped_scratch(kmx_ctx* ctx, size_t bytes) {
     if (ctx->big_limit != 0 && bytes > ctx->big_limit) return nullptr;
-    return big_scratch(ctx, bytes);
+    return work_acquire(ctx, bytes).base;
 }
 
-// an eighth of the device memory, at least 8 GiB (kmx_ctx_set_work_buffer_limit overrides), and at most half of what is free: fewer,
-// larger chunks of reads per call (configs[4], 1.25e8 reads: 6 chunks at 8 GiB 19.3 ms, 2 at 36 GiB 18.6 ms)
+// The cap on the work buffer: an eighth of the device memory, at least 8 GiB (kmx_ctx_set_work_buffer_limit overrides), and at most
+// half of what is free: fewer, larger chunks of reads per call (configs[4], 1.25e8 reads: 6 chunks at 8 GiB 19.3 ms, 2 at 36 GiB 18.6 ms)
 // (`held`: the work buffer the context already owns -- it is not part of "free" any more, but it IS available: without adding
 // it back a second call under memory pressure got a smaller budget than the buffer it holds, cut the reads into more chunks
 // than the first call had, and timing depended on call order)
-size_t hist_scratch_budget(size_t held, size_t limit) {
-    if (limit) return limit;
+size_t work_budget(const kmx_ctx* ctx) {
+    if (ctx->big_limit) return ctx->big_limit;
+    const size_t held = ctx->big_bytes;
     size_t free_b = 0, total_b = 0;
     const bool have = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
     size_t budget = (size_t)8 << 30;
@@ -379,7 +405,6 @@ static int long_ragged_segments(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k
     const uint64_t cap = kmx::segments_capacity(reads->n_reads, o_last - o_first, t_max);
     void* scratch = capped_scratch(ctx, kmx::segments_scratch_bytes(reads->n_reads, cap, win_offsets != nullptr));
     if (!scratch) return -1;
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
     const uint64_t* d_total = nullptr;
     KMX_HIP(ctx, kmx::launch_segments_build(reads->d_offsets, reads->n_reads, k, t_max, cap, scratch, starts, ends, &d_total, too_long_of(ctx), ctx->stream,
                                             win_offsets, wins));
@@ -409,7 +434,6 @@ static int uniform_long_segments(kmx_ctx* ctx, const kmx_reads* reads, uint32_t 
     const uint32_t J = uniform_segments_per_read(reads->read_len, k, &T);
     void* scratch = capped_scratch(ctx, kmx::uniform_segments_scratch_bytes(reads->n_reads * J));
     if (!scratch) return -1;
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
     KMX_HIP(ctx, kmx::launch_uniform_segments_plan(reads->n_reads, reads->read_len, k, T, scratch, starts, ends, wins, n_seg, ctx->stream));
     return 0;
 }
@@ -660,20 +684,41 @@ static size_t count_plan_bytes(const kmx_reads* reads, uint32_t k, uint64_t n_ba
     return kmx::segments_scratch_bytes(reads->n_reads, kmx::segments_capacity(reads->n_reads, n_bases, 257u - k), true);
 }
 
+// The windows kmx_count_canonical(2) and the reads forms of the queries size their arrays for: exact for uniform reads (*n_bound = 0: no
+// window), the number of bases -- a bound, also in *n_bases -- for ragged ones.
+static int query_window_bound(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t* n_bound, uint64_t* n_bases, uint64_t* first = nullptr) {
+    *n_bound = *n_bases = 0;
+    if (reads->d_offsets) {
+        uint64_t o_first = 0, o_last = 0;
+        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
+        if (first) *first = o_first;   // (ragged reads: where the batch's bases start)
+        if (o_last < o_first) return KMX_E_ARG;
+        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
+        *n_bases = *n_bound = o_last - o_first;
+        return KMX_OK;
+    }
+    if (reads->read_len < k) return KMX_OK;
+    const uint64_t w = reads->read_len - k + 1u;
+    if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
+    *n_bound = reads->n_reads * w;
+    return KMX_OK;
+}
+
 // The work buffer of a count-family call, `bytes` of working set: refused above the cap (kmx_ctx_set_work_buffer_limit, or what
-// the device has to spare), grown if need be, and the call's to overwrite.
-static int work_area(kmx_ctx* ctx, const char* who, size_t bytes, void** area) {
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+// the device has to spare), grown if need be, and the call's to overwrite.  `hold`, where asked for: for work_kept behind a nested use.
+static int work_area(kmx_ctx* ctx, const char* who, size_t bytes, void** area, WorkHold* hold = nullptr) {
+    const size_t budget = work_budget(ctx);
     if (bytes > budget) {
         std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, bytes,
                       budget);
         return KMX_E_NOMEM;
     }
-    if (!(*area = big_scratch(ctx, bytes))) {
+    const WorkHold h = work_acquire(ctx, bytes);
+    if (!(*area = h.base)) {
         std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: no memory for %zu bytes of working set", who, bytes);
         return KMX_E_NOMEM;
     }
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
+    if (hold) *hold = h;
     return KMX_OK;
 }
 
@@ -699,29 +744,17 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
     *h_n_distinct = 0;
     if (reads->n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    // the windows the arrays are sized for: exact for uniform reads, the number of bases (a bound) for ragged ones
     uint64_t n_bound = 0, n_bases = 0;
-    if (reads->d_offsets) {
-        uint64_t o_first = 0, o_last = 0;
-        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
-        if (o_last < o_first) return KMX_E_ARG;
-        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
-        n_bases = n_bound = o_last - o_first;
-    } else {
-        if (reads->read_len < k) return KMX_OK;   // no window
-        const uint64_t w = reads->read_len - k + 1u;
-        if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
-        n_bound = reads->n_reads * w;
-    }
-    if (n_bound == 0) return KMX_OK;
+    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
+    if (n_bound == 0) return KMX_OK;   // no window
     const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
     const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
     const size_t canon_at = plan + wo_bytes, flags_at = canon_at + align256(8u * kind.words * n_bound), area_at = flags_at + align256(n_bound);
     const size_t bytes = area_at + kmx::count_area_bytes(kind.words, n_bound);
     void* buf = nullptr;
-    if (int st = work_area(ctx, kind.who, bytes, &buf)) return st;
-    char* base = static_cast<char*>(buf);
-    const unsigned long long allocs = ctx->big_allocs;
+    WorkHold hold;
+    if (int st = work_area(ctx, kind.who, bytes, &buf, &hold)) return st;
+    char* const base = hold.base;
     char msg[96];
     uint64_t n_win = n_bound;
     uint64_t* wo = nullptr;
@@ -736,10 +769,7 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
     uint64_t* canon = reinterpret_cast<uint64_t*>(base + canon_at);
     uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
     if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
-    if (ctx->d_big != base || ctx->big_allocs != allocs) {
-        std::snprintf(msg, sizeof msg, "%s: work buffer moved", kind.who);
-        return fail_hip(ctx, hipErrorUnknown, msg);
-    }
+    if (int st = work_kept(ctx, kind.who, hold)) return st;
     uint64_t n_valid = 0, n_distinct = 0;
     bool bad = false;
     // (the count area is laid out for the n_win windows there are, inside the bytes reserved for n_bound >= n_win)
@@ -817,12 +847,22 @@ struct QueryKind {
 static const QueryKind kQuery1{"kmx_count_lookup", 1u, 1u, 31u, kmx_canonical_windows};
 static const QueryKind kQuery2{"kmx_count_lookup2", 2u, 33u, 64u, kmx_canonical_windows2};
 
-// The lookup behind its argument checks.  `reserved` bytes at the start of the work buffer belong to the caller (the reads form keeps
-// its flags / canonical words there); the directory goes behind them when the byte counts say it pays (count_lookup_wants_dir) and it
-// fits under the cap -- otherwise the plain search, which needs no work buffer: never KMX_E_NOMEM from here.  *dir_out / *p_out,
+// Where the directory of a search for n_query keys among n goes (*p: its prefix bits): into the work buffer when the byte counts say
+// it pays (count_lookup_wants_dir) and it fits under the cap, nullptr otherwise -- the plain search, which needs no work buffer.
+// `hold`: the caller's, whose first `reserved` bytes stay its own (the reads forms keep their flags / canonical words there) -- the
+// directory goes behind them if the buffer as a whole has the room (query_scratch asked for it with the rest, or could not); none: the
+// buffer is taken here.
+static void* lookup_dir(kmx_ctx* ctx, const WorkHold* hold, uint32_t words, uint64_t n, uint32_t k, uint64_t n_query, uint32_t* p) {
+    const size_t dir_bytes = kmx::count_lookup_dir_bytes(n, k, p), reserved = hold ? hold->reserved : 0;
+    if (dir_bytes == 0 || !kmx::count_lookup_wants_dir(n, n_query, words) || reserved + dir_bytes > work_budget(ctx)) return nullptr;
+    if (!hold) return work_acquire(ctx, dir_bytes).base;
+    return reserved + dir_bytes <= hold->size ? hold->base + reserved : nullptr;
+}
+
+// The lookup behind its argument checks, with its directory (lookup_dir) or without: never KMX_E_NOMEM from here.  *dir_out / *p_out,
 // where asked for: the directory that was built and its prefix bits, nullptr = the plain search ran.
 static int lookup_run(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k,
-                      const uint64_t* d_query, const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out, size_t reserved,
+                      const uint64_t* d_query, const uint8_t* d_query_flags, uint64_t n_query, uint64_t* d_out, const WorkHold* hold,
                       const void** dir_out = nullptr, uint32_t* p_out = nullptr) {
     if (dir_out) *dir_out = nullptr;
     if (p_out) *p_out = 0;
@@ -831,20 +871,8 @@ static int lookup_run(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_kme
         KMX_HIP(ctx, hipMemsetAsync(d_out, 0, 8u * n_query, ctx->stream));
         return KMX_OK;
     }
-    void* dir = nullptr;
     uint32_t p = 0;
-    const size_t dir_bytes = kmx::count_lookup_dir_bytes(n, k, &p);
-    if (dir_bytes != 0 && kmx::count_lookup_wants_dir(n, n_query, kind.words) &&
-        reserved + dir_bytes <= hist_scratch_budget(ctx->big_bytes, ctx->big_limit)) {
-        if (reserved == 0) {
-            if (char* base = static_cast<char*>(big_scratch(ctx, dir_bytes))) {
-                ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
-                dir = base;
-            }
-        } else if (reserved + dir_bytes <= ctx->big_bytes) {   // (the reads form reserved its buffer with room for the directory, or without)
-            dir = static_cast<char*>(ctx->d_big) + reserved;
-        }
-    }
+    void* const dir = lookup_dir(ctx, hold, kind.words, n, k, n_query, &p);
     KMX_HIP(ctx, kmx::launch_count_lookup(kind.words, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out, dir, p, ctx->stream));
     if (dir_out) *dir_out = dir;   // (it stays what it is until the work buffer is used again)
     if (p_out) *p_out = p;
@@ -857,7 +885,7 @@ static int lookup_impl(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d_km
     if (kind.words == 2u && (!aligned16(d_kmers) || !aligned16(d_query))) return KMX_E_ARG;
     if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
     DeviceGuard g(ctx->device);
-    return lookup_run(ctx, kind, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out, 0);
+    return lookup_run(ctx, kind, d_kmers, d_counts, n, k, d_query, d_query_flags, n_query, d_out, nullptr);
 }
 
 int kmx_count_lookup(kmx_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_counts, uint64_t n, uint32_t k, const uint64_t* d_query,
@@ -871,31 +899,11 @@ int kmx_count_lookup2(kmx_ctx* ctx, const uint64_t* d_kmers2, const uint64_t* d_
 }
 
 // ---- the reads forms of the queries: kmx_count_lookup_reads(2) and kmx_count_read_stats(2) ----
-// The windows their arrays are sized for, as kmx_count_canonical counts them: exact for uniform reads (*n_bound = 0: no window), the
-// number of bases -- a bound, also in *n_bases -- for ragged ones.
-static int query_window_bound(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64_t* n_bound, uint64_t* n_bases, uint64_t* first = nullptr) {
-    *n_bound = *n_bases = 0;
-    if (reads->d_offsets) {
-        uint64_t o_first = 0, o_last = 0;
-        if (int st = offsets_span(ctx, reads, &o_first, &o_last)) return st;
-        if (first) *first = o_first;   // (ragged reads: where the batch's bases start)
-        if (o_last < o_first) return KMX_E_ARG;
-        if (o_last - o_first >= (1ull << 40)) return KMX_E_NOMEM;
-        *n_bases = *n_bound = o_last - o_first;
-        return KMX_OK;
-    }
-    if (reads->read_len < k) return KMX_OK;
-    const uint64_t w = reads->read_len - k + 1u;
-    if (reads->n_reads > (1ull << 40) / w) return KMX_E_NOMEM;
-    *n_bound = reads->n_reads * w;
-    return KMX_OK;
-}
-
 // Their work buffer: `reserved` bytes for the caller's arrays, refused above the cap, and room for the lookup's directory behind them
 // when it pays for n_query windows and fits (asked for with the rest, so the buffer does not move between the windows call and the
 // lookup; left out, never refused).
-static int query_scratch(kmx_ctx* ctx, const char* who, uint32_t words, size_t reserved, uint64_t n, uint32_t k, uint64_t n_query, char** base_out) {
-    const size_t budget = hist_scratch_budget(ctx->big_bytes, ctx->big_limit);
+static int query_scratch(kmx_ctx* ctx, const char* who, uint32_t words, size_t reserved, uint64_t n, uint32_t k, uint64_t n_query, WorkHold* hold) {
+    const size_t budget = work_budget(ctx);
     if (reserved > budget) {
         std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %zu bytes of working set above the work buffer's cap of %zu", who, reserved, budget);
         return KMX_E_NOMEM;
@@ -903,23 +911,14 @@ static int query_scratch(kmx_ctx* ctx, const char* who, uint32_t words, size_t r
     uint32_t p = 0;
     const size_t dir_bytes = n ? kmx::count_lookup_dir_bytes(n, k, &p) : 0;
     const bool with_dir = dir_bytes != 0 && kmx::count_lookup_wants_dir(n, n_query, words) && reserved + dir_bytes <= budget;
-    char* base = static_cast<char*>(big_scratch(ctx, reserved + (with_dir ? dir_bytes : 0)));
-    if (!base && with_dir) base = static_cast<char*>(big_scratch(ctx, reserved));
-    if (!base) {
+    *hold = work_acquire(ctx, reserved + (with_dir ? dir_bytes : 0));
+    if (!hold->base && with_dir) *hold = work_acquire(ctx, reserved);
+    if (!hold->base) {
         std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: no memory for %zu bytes of working set", who, reserved);
         return KMX_E_NOMEM;
     }
-    ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
-    *base_out = base;
+    hold->reserved = reserved;
     return KMX_OK;
-}
-
-// (the windows call took a route that grew the work buffer under the arrays laid out in it: a bug, never expected)
-static int query_scratch_kept(kmx_ctx* ctx, const char* who, const char* base, unsigned long long allocs) {
-    if (ctx->d_big == base && ctx->big_allocs == allocs) return KMX_OK;
-    char msg[96];
-    std::snprintf(msg, sizeof msg, "%s: work buffer moved", who);
-    return fail_hip(ctx, hipErrorUnknown, msg);
 }
 
 // kmx_count_lookup_reads(2) = kmx_canonical_windows(2) followed by the lookup kernel.  The work buffer is laid out up front, as
@@ -956,14 +955,14 @@ static int lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_read
     const size_t canon_at = plan, flags_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u), reserved = flags_at + align256(n_bound);
     char who[48];
     std::snprintf(who, sizeof who, "%s_reads", kind.who);
-    char* base = nullptr;
-    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_win, &base)) return st;
-    const unsigned long long allocs = ctx->big_allocs;
+    WorkHold hold;
+    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_win, &hold)) return st;
+    char* const base = hold.base;
     uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : d_out;
     uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
     if (int st = kind.windows(ctx, reads, d_win_offsets, k, nullptr, nullptr, canon, flags)) return st;
-    if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
-    return lookup_run(ctx, kind, d_kmers, d_counts, n, k, canon, flags, n_win, d_out, reserved);
+    if (int st = work_kept(ctx, who, hold)) return st;
+    return lookup_run(ctx, kind, d_kmers, d_counts, n, k, canon, flags, n_win, d_out, &hold);
 }
 
 int kmx_count_lookup_reads(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint64_t* d_kmers,
@@ -999,9 +998,9 @@ static int reads_front(kmx_ctx* ctx, const QueryKind& kind, const char* who, con
     const size_t canon_at = plan + wo_bytes, answers_at = canon_at + (kind.words == 2u ? align256(16u * n_bound) : 0u);
     const size_t flags_at = answers_at + align256(8u * n_bound), area_at = flags_at + align256(n_bound);
     const size_t reserved = area_at + extra;
-    char* base = nullptr;
-    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &base)) return st;
-    const unsigned long long allocs = ctx->big_allocs;
+    WorkHold hold;
+    if (int st = query_scratch(ctx, who, kind.words, reserved, n, k, n_bound, &hold)) return st;
+    char* const base = hold.base;
     uint64_t n_win = n_bound;
     uint64_t* wo = nullptr;
     if (reads->d_offsets) {
@@ -1017,8 +1016,8 @@ static int reads_front(kmx_ctx* ctx, const QueryKind& kind, const char* who, con
     uint64_t* canon = kind.words == 2u ? reinterpret_cast<uint64_t*>(base + canon_at) : answers;
     uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
     if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
-    if (int st = query_scratch_kept(ctx, who, base, allocs)) return st;
-    if (int st = lookup_run(ctx, kind, d_kmers, d_values, n, k, canon, flags, n_win, answers, reserved, &f->dir, &f->p)) return st;
+    if (int st = work_kept(ctx, who, hold)) return st;
+    if (int st = lookup_run(ctx, kind, d_kmers, d_values, n, k, canon, flags, n_win, answers, &hold, &f->dir, &f->p)) return st;
     f->base = base;
     f->wo = wo;
     f->answers = answers;
@@ -1207,12 +1206,8 @@ static int adjacency_impl(kmx_ctx* ctx, const QueryKind& kind, const uint64_t* d
     if (k < (kind.words == 1u ? 2u : kind.k_min) || k > kind.k_max) return KMX_E_K_RANGE;   // (a word of one base has no overlap to share)
     if (n == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    void* dir = nullptr;
     uint32_t p = 0;
-    const size_t dir_bytes = kmx::count_lookup_dir_bytes(n, k, &p);
-    if (dir_bytes != 0 && kmx::count_lookup_wants_dir(n, 8u * n, kind.words) && dir_bytes <= hist_scratch_budget(ctx->big_bytes, ctx->big_limit)) {
-        if ((dir = big_scratch(ctx, dir_bytes))) ctx->fx_valid = false;   // (the work buffer is overwritten: the fastx chunk prefixes in it are gone)
-    }
+    void* const dir = lookup_dir(ctx, nullptr, kind.words, n, k, 8u * n, &p);
     KMX_HIP(ctx, kmx::launch_count_adjacency(kind.words, d_kmers, d_counts, n, k, min_count, d_edges, d_flips, d_nbr, dir, p, ctx->stream));
     return KMX_OK;
 }
@@ -1789,7 +1784,6 @@ int kmx_histogram(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t has
     if (hasher == KMX_HASH_LEX && (hasher_k < 1 || hasher_k > 32)) return KMX_E_K_RANGE;
     if (reads->n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    ctx->fx_valid = false;   // (the partitioned histogram writes its id streams over the work buffer)
     {
         bool handled = false;
         KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
@@ -1799,7 +1793,7 @@ int kmx_histogram(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint32_t has
         }
         KMX_HIP(ctx, kmx::launch_hist_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, hasher, hasher_k,
                                               log2_buckets, d_counts, queue_of(ctx), ctx->n_cu, ctx->stream, &handled,
-                                              &big_scratch, ctx, hist_scratch_budget(ctx->big_bytes, ctx->big_limit), reads->d_offsets));
+                                              &work_callback, ctx, work_budget(ctx), reads->d_offsets));
         if (handled) return KMX_OK;
     }
     KMX_HIP(ctx, kmx::launch_histogram_generic(reads, k, hasher, hasher_k, log2_buckets, d_counts, ctx->n_cu, ctx->stream, too_long_of(ctx)));
@@ -2225,13 +2219,12 @@ int kmx_histogram_sip13(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint64
     if (log2_buckets > 30) return KMX_E_ARG;
     if (reads->n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    ctx->fx_valid = false;   // (the partitioned passes write their id streams over the work buffer)
     KMX_HIP(ctx, queue_clear(ctx, KMX_Q_CLEAR_THROUGH_GATE));
     bool handled = false;
     // the routes of kmx_histogram (LDS tables, one- and two-level partitions, device atomics) with the SipHash sinks
     KMX_HIP(ctx, kmx::launch_hist_uniform(reads->d_bases, reads->n_reads, reads->read_len, k, kmx::KMX_HASH_SIP13_INTERNAL, 0u, log2_buckets,
-                                          d_counts, queue_of(ctx), ctx->n_cu, ctx->stream, &handled, &big_scratch, ctx,
-                                          hist_scratch_budget(ctx->big_bytes, ctx->big_limit), reads->d_offsets, key0, key1));
+                                          d_counts, queue_of(ctx), ctx->n_cu, ctx->stream, &handled, &work_callback, ctx,
+                                          work_budget(ctx), reads->d_offsets, key0, key1));
     if (handled) return KMX_OK;
     KMX_HIP(ctx, kmx::launch_histogram_generic_sip(reads, k, key0, key1, log2_buckets, d_counts, ctx->n_cu, ctx->stream, too_long_of(ctx)));
     return KMX_OK;
@@ -2281,84 +2274,31 @@ int kmx_minimizers_sip13(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d
     return KMX_OK;
 }
 
-int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_bases,
-                    uint64_t* d_offsets, uint64_t max_reads, uint64_t* h_n_reads, uint64_t* h_n_bases) {
-    const bool same_text = (format & KMX_FASTX_SAME_TEXT) != 0u;
-    format &= ~KMX_FASTX_SAME_TEXT;
-    if (!ctx || format > KMX_FASTX_FASTA || (n_bytes && !d_text) || (!d_bases != !d_offsets)) return KMX_E_ARG;
-    if (!aligned16(d_text)) return KMX_E_ARG;
-    if (h_n_reads) *h_n_reads = 0;
-    if (h_n_bases) *h_n_bases = 0;
-    DeviceGuard g(ctx->device);
-    if (n_bytes == 0) {
-        if (d_offsets) {
-            KMX_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, ctx->stream));
-            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        return KMX_OK;
-    }
-    // (the emit call of a counts-then-emit pair: the counting call looked at the first byte and settled the format)
-    const bool reuse = same_text && ctx->fx_valid && ctx->fx_entry == 0u && ctx->fx_text == d_text && ctx->fx_bytes == n_bytes &&
-                       (format == KMX_FASTX_AUTO || ctx->fx_fasta == (format == KMX_FASTX_FASTA ? 1u : 0u));
-    if (reuse) {
-        format = ctx->fx_fasta ? KMX_FASTX_FASTA : KMX_FASTX_FASTQ;
-    } else {
-        uint8_t first = 0;
-        KMX_HIP(ctx, hipMemcpyAsync(&first, d_text, 1, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (format == KMX_FASTX_AUTO) format = first == '@' ? KMX_FASTX_FASTQ : first == '>' ? KMX_FASTX_FASTA : 3u;
-        if (format == 3u || first != (format == KMX_FASTX_FASTQ ? '@' : '>')) {
-            std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_fastx_parse: the text starts with byte 0x%02x, not with '@' (FASTQ) or '>' (FASTA)", first);
-            return KMX_E_ARG;
-        }
-    }
-    const bool fasta = format == KMX_FASTX_FASTA;
-    void* scratch = big_scratch(ctx, kmx::fastx_scratch_bytes(n_bytes));
-    if (!scratch) return KMX_E_NOMEM;
-    unsigned long long* d_totals = ctx->d_scratch + KMX_S_FASTX_TOTALS;
-    unsigned long long totals[2] = {0, 0};
-    if (reuse && scratch == ctx->d_big) {
-        // the chunk prefixes of the counting call are still in the work buffer, its totals in d_scratch[KMX_S_FASTX_TOTALS]
-        totals[0] = ctx->fx_totals[0];
-        totals[1] = ctx->fx_totals[1];
-    } else {
-        ctx->fx_valid = false;
-        KMX_HIP(ctx, kmx::launch_fastx_count(d_text, n_bytes, fasta, scratch, d_totals, ctx->stream));
-        KMX_HIP(ctx, hipMemcpyAsync(totals, d_totals, 16, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->fx_text = d_text;
-        ctx->fx_bytes = n_bytes;
-        ctx->fx_fasta = fasta ? 1u : 0u;
-        ctx->fx_entry = 0u;
-        ctx->fx_totals[0] = totals[0];
-        ctx->fx_totals[1] = totals[1];
-        ctx->fx_valid = true;
-    }
-    if (h_n_reads) *h_n_reads = totals[0];
-    if (h_n_bases) *h_n_bases = totals[1];
-    if (!d_bases) return KMX_OK;
-    if (totals[0] > max_reads) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "kmx_fastx_parse: %llu reads, room for %llu", totals[0],
-                      (unsigned long long)max_reads);
-        return KMX_E_NOMEM;
-    }
-    KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, fasta, scratch, d_totals, d_bases, d_offsets, ctx->stream));
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KMX_OK;
-}
+// ---- FASTQ / FASTA text parsed on the device (kmx_fastx.hip) ----
+// What the three parse calls differ in.  The lines of a FASTQ record are selected by the line the machine is entered on: passes 2 and 3
+// take line 1 (entry 0: the reads), line 3 (entry 2: the quality lines) or line 0 (entry 1: the names).
+struct FastxCall {
+    const char* who;
+    const char* what;    // the lines, for the messages
+    uint32_t entry;
+    bool fasta_too;      // FASTA is taken as well, and KMX_FASTX_AUTO tells the two apart by the first byte; otherwise FASTQ only
+    bool any_entry;      // KMX_FASTX_SAME_TEXT may keep pass 1 of a count made for another entry and rerun pass 2 alone
+};
+static const FastxCall kFastxReads{"kmx_fastx_parse", "reads", 0u, true, false};
+static const FastxCall kFastxQuals{"kmx_fastx_parse_quals", "quality lines", 2u, false, true};
+static const FastxCall kFastxNames{"kmx_fastx_parse_names", "names", 1u, false, true};
 
-// kmx_fastx_parse with the FASTQ machine entered on another line: passes 2 and 3 select line 3 of every record (entry 2: the quality
-// lines) or line 0 (entry 1: the names) (kmx_fastx.hip).  What the context remembers of a count (fx_*) is shared by the three parse
-// calls: the chunk summaries of pass 1 do not depend on the entry line, the chunk prefixes and totals of pass 2 do (fx_entry).
-// The argument checks (behind them *h_reset = ~0, if given), the count and -- with room -- the launch of pass 3, which is left
-// running: *emitted says so (`what`: the lines, for the messages).
-static int fastq_lines(kmx_ctx* ctx, const char* who, const char* what, uint32_t entry, const uint8_t* d_text, uint64_t n_bytes, uint32_t format,
-                       uint8_t* d_out, uint64_t* d_ooffsets, uint64_t max_reads, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_reset,
-                       uint64_t* n_lines, bool* emitted) {
+// The one body of the parse calls: the argument checks (behind them *h_reset = ~0, if given), the count and -- with room -- the launch
+// of pass 3, which is left running: *emitted says so.  What the context remembers of a count (fx_*, written here and nowhere else) is
+// shared by the three calls: the chunk summaries of pass 1 do not depend on the entry line, the chunk prefixes and totals of pass 2 do
+// (fx_entry).  They live in the work buffer, so they are as good as fx_valid, which work_acquire clears for every other taker.
+static int fastx_lines(kmx_ctx* ctx, const FastxCall& call, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_out,
+                       uint64_t* d_ooffsets, uint64_t max_reads, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_reset, uint64_t* n_lines,
+                       bool* emitted) {
     *emitted = false;
     const bool same_text = (format & KMX_FASTX_SAME_TEXT) != 0u;
     format &= ~KMX_FASTX_SAME_TEXT;
-    if (!ctx || format > KMX_FASTX_FASTQ || (n_bytes && !d_text) || (!d_out != !d_ooffsets)) return KMX_E_ARG;
+    if (!ctx || format > (call.fasta_too ? KMX_FASTX_FASTA : KMX_FASTX_FASTQ) || (n_bytes && !d_text) || (!d_out != !d_ooffsets)) return KMX_E_ARG;
     if (!aligned16(d_text)) return KMX_E_ARG;
     if (h_n_reads) *h_n_reads = 0;
     if (h_n_bytes) *h_n_bytes = 0;
@@ -2371,33 +2311,43 @@ static int fastq_lines(kmx_ctx* ctx, const char* who, const char* what, uint32_t
         }
         return KMX_OK;
     }
-    const bool known = same_text && ctx->fx_valid && ctx->fx_text == d_text && ctx->fx_bytes == n_bytes && ctx->fx_fasta == 0u;
-    if (!known) {
+    if (!call.fasta_too) format = KMX_FASTX_FASTQ;
+    // (the emit call of a counts-then-emit pair: the counting call looked at the first byte and settled the format)
+    const bool known = same_text && ctx->fx_valid && ctx->fx_text == d_text && ctx->fx_bytes == n_bytes &&
+                       (format == KMX_FASTX_AUTO || ctx->fx_fasta == (format == KMX_FASTX_FASTA ? 1u : 0u)) &&
+                       (call.any_entry || ctx->fx_entry == call.entry);
+    if (known) {
+        format = ctx->fx_fasta ? KMX_FASTX_FASTA : KMX_FASTX_FASTQ;
+    } else {
         uint8_t first = 0;
         KMX_HIP(ctx, hipMemcpyAsync(&first, d_text, 1, hipMemcpyDeviceToHost, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (first != '@') {
-            std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: the text starts with byte 0x%02x, not with '@' (FASTQ)", who, first);
+        if (format == KMX_FASTX_AUTO) format = first == '@' ? KMX_FASTX_FASTQ : first == '>' ? KMX_FASTX_FASTA : 3u;
+        if (format == 3u || first != (format == KMX_FASTX_FASTQ ? '@' : '>')) {
+            std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: the text starts with byte 0x%02x, not with '@' (FASTQ)%s", call.who, first,
+                          call.fasta_too ? " or '>' (FASTA)" : "");
             return KMX_E_ARG;
         }
     }
-    void* scratch = big_scratch(ctx, kmx::fastx_scratch_bytes(n_bytes));
+    const bool fasta = format == KMX_FASTX_FASTA;
+    void* scratch = work_acquire(ctx, kmx::fastx_scratch_bytes(n_bytes), true).base;
     if (!scratch) return KMX_E_NOMEM;
     unsigned long long* d_totals = ctx->d_scratch + KMX_S_FASTX_TOTALS;
     unsigned long long totals[2] = {0, 0};
-    const bool summaries = known && scratch == ctx->d_big;   // pass 1 of an earlier count of this text is still in the work buffer
-    if (summaries && ctx->fx_entry == entry) {
+    const bool summaries = known && ctx->fx_valid;   // the work buffer did not move: pass 1 of the earlier count of this text is still in it
+    if (summaries && ctx->fx_entry == call.entry) {
+        // ... and so are the chunk prefixes of its pass 2, its totals in d_scratch[KMX_S_FASTX_TOTALS]
         totals[0] = ctx->fx_totals[0];
         totals[1] = ctx->fx_totals[1];
     } else {
         ctx->fx_valid = false;
-        KMX_HIP(ctx, kmx::launch_fastx_count(d_text, n_bytes, false, scratch, d_totals, ctx->stream, entry, !summaries));
+        KMX_HIP(ctx, kmx::launch_fastx_count(d_text, n_bytes, fasta, scratch, d_totals, ctx->stream, call.entry, !summaries));
         KMX_HIP(ctx, hipMemcpyAsync(totals, d_totals, 16, hipMemcpyDeviceToHost, ctx->stream));
         KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->fx_text = d_text;
         ctx->fx_bytes = n_bytes;
-        ctx->fx_fasta = 0u;
-        ctx->fx_entry = entry;
+        ctx->fx_fasta = fasta ? 1u : 0u;
+        ctx->fx_entry = call.entry;
         ctx->fx_totals[0] = totals[0];
         ctx->fx_totals[1] = totals[1];
         ctx->fx_valid = true;
@@ -2406,21 +2356,35 @@ static int fastq_lines(kmx_ctx* ctx, const char* who, const char* what, uint32_t
     if (h_n_bytes) *h_n_bytes = totals[1];
     *n_lines = totals[0];
     if (!d_out) return KMX_OK;
-    if (totals[0] > max_reads) {
-        std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu %s, room for %llu", who, totals[0], what, (unsigned long long)max_reads);
-        return KMX_E_NOMEM;
-    }
-    KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, false, scratch, d_totals, d_out, d_ooffsets, ctx->stream, entry));
+    if (int st = room_for(ctx, call.who, totals[0], call.what, max_reads)) return st;
+    KMX_HIP(ctx, kmx::launch_fastx_emit(d_text, n_bytes, fasta, scratch, d_totals, d_out, d_ooffsets, ctx->stream, call.entry));
     *emitted = true;
     return KMX_OK;
+}
+
+// ... and the wait for pass 3, where nothing else follows it.
+static int fastx_lines_wait(kmx_ctx* ctx, const FastxCall& call, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_out,
+                            uint64_t* d_ooffsets, uint64_t max_reads, uint64_t* h_n_reads, uint64_t* h_n_bytes) {
+    uint64_t n_lines = 0;
+    bool emitted = false;
+    const int st = fastx_lines(ctx, call, d_text, n_bytes, format, d_out, d_ooffsets, max_reads, h_n_reads, h_n_bytes, nullptr, &n_lines, &emitted);
+    if (st != KMX_OK || !emitted) return st;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_fastx_parse(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_bases,
+                    uint64_t* d_offsets, uint64_t max_reads, uint64_t* h_n_reads, uint64_t* h_n_bases) {
+    return fastx_lines_wait(ctx, kFastxReads, d_text, n_bytes, format, d_bases, d_offsets, max_reads, h_n_reads, h_n_bases);
 }
 
 int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_quals, uint64_t* d_qoffsets,
                           uint64_t max_reads, const uint64_t* d_read_offsets, uint64_t* h_n_reads, uint64_t* h_n_bytes, uint64_t* h_first_mismatch) {
     uint64_t n_lines = 0;
     bool emitted = false;
-    const int st = fastq_lines(ctx, "kmx_fastx_parse_quals", "quality lines", 2u, d_text, n_bytes, format, d_quals, d_qoffsets, max_reads, h_n_reads,
-                               h_n_bytes, h_first_mismatch, &n_lines, &emitted);
+    const int st = fastx_lines(ctx, kFastxQuals, d_text, n_bytes, format, d_quals, d_qoffsets, max_reads, h_n_reads, h_n_bytes, h_first_mismatch,
+                               &n_lines, &emitted);
     if (st != KMX_OK || !emitted) return st;
     DeviceGuard g(ctx->device);
     if (d_read_offsets && h_first_mismatch && n_lines) {
@@ -2436,14 +2400,7 @@ int kmx_fastx_parse_quals(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes,
 
 int kmx_fastx_parse_names(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t format, uint8_t* d_names, uint64_t* d_noffsets,
                           uint64_t max_reads, uint64_t* h_n_names, uint64_t* h_n_bytes) {
-    uint64_t n_lines = 0;
-    bool emitted = false;
-    const int st = fastq_lines(ctx, "kmx_fastx_parse_names", "names", 1u, d_text, n_bytes, format, d_names, d_noffsets, max_reads, h_n_names, h_n_bytes,
-                               nullptr, &n_lines, &emitted);
-    if (st != KMX_OK || !emitted) return st;
-    DeviceGuard g(ctx->device);
-    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KMX_OK;
+    return fastx_lines_wait(ctx, kFastxNames, d_text, n_bytes, format, d_names, d_noffsets, max_reads, h_n_names, h_n_bytes);
 }
 
 // ---- a batch laid out as a FASTQ / FASTA image (kmx_fastx_format.hip) ----
@@ -2494,14 +2451,8 @@ int kmx_fastx_format(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_qual
 // bases are, which the call reads on a dword grid of their own (the quality bytes; nullptr: there are none).
 static int masked_copy_ok(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_masked, const uint8_t* d_also) {
     uint64_t first = 0, last = 0;
-    if (reads->d_offsets) {
-        unsigned long long* h = ctx->h_pinned;
-        KMX_HIP(ctx, hipMemcpyAsync(h, reads->d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipMemcpyAsync(h + 1, reads->d_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        first = h[0];
-        last = h[1];
-    }
+    if (reads->d_offsets)
+        if (int st = offsets_span(ctx, reads, &first, &last)) return st;
     auto spanned = [&](const void* base) { return Range::of_batch(base, reads->d_offsets, reads->n_reads, reads->read_len, first, last); };
     const Range m = spanned(d_masked);
     if (d_masked != reads->d_bases && m.overlaps(spanned(reads->d_bases))) return KMX_E_ARG;

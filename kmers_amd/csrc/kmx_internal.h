@@ -19,15 +19,20 @@ struct kmx_ctx {
     unsigned long long* h_pub;      // eight pinned host words the bit-sliced scan's last block can leave {token, marked reads, summary} in (kmx_canonical_reduce_host)
     uint32_t pub_token;             // the token of the last such launch (24 bits)
     bool queue_clean;               // the heads and KMX_Q_MARKED of the queue block are zero: only self-closing launches (kmx_layout.h) ran since the last clear
-    void* d_big;                    // grow-only work buffer of the partitioned histogram (bucket-id streams)
-    size_t big_bytes;
-    size_t big_limit;               // kmx_ctx_set_work_buffer_limit: 0 = automatic (an eighth of the device memory, at most half of what is free)
-    unsigned long long big_allocs;  // how often the work buffer was (re)allocated (kmx_ctx_work_buffer_info)
     unsigned long long dirty_desc;  // address of the dirty-tile flags as last written behind the queue heads
     uint8_t* d_flags;               // one byte per tile, all zero between calls
     size_t flags_bytes;
-    // kmx_fastx_parse: what the last counting pass was run on -- a second call on the same image with KMX_FASTX_SAME_TEXT
-    // reuses its chunk prefixes (they live in d_big) instead of summarising the text again
+    // The work buffer: grow-only device memory that every call family lays its working set out in (the id streams of the partitioned
+    // histogram, the segment plans of long reads, the arrays of the count, query and reads families, the chunk summaries of the FASTX
+    // parses); a call's contents are dead when the call returns.  d_big, big_bytes and big_allocs are read and written only by the
+    // acquire group at the top of kmx_api.hip (work_acquire), context creation / destruction and kmx_ctx_work_buffer_info.
+    void* d_big;
+    size_t big_bytes;
+    unsigned long long big_allocs;  // how often the work buffer was (re)allocated (kmx_ctx_work_buffer_info)
+    size_t big_limit;               // kmx_ctx_set_work_buffer_limit: 0 = automatic (an eighth of the device memory, at most half of what is free)
+    // The FASTX count cache, the one thing in the work buffer that outlives a call: what the last counting pass of a parse was run on --
+    // a second call on the same image with KMX_FASTX_SAME_TEXT reuses its chunk prefixes (they live in d_big) instead of summarising
+    // the text again.  Written by the parse body (fastx_lines) alone; work_acquire clears fx_valid for every other taker of the buffer.
     const uint8_t* fx_text;
     uint64_t fx_bytes;
     uint32_t fx_fasta;

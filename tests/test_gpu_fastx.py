@@ -160,6 +160,84 @@ def test_same_text_flag_only_reuses_what_it_may(ctx, orc):
     assert np.array_equal(got[0], ea[0]) and np.array_equal(got[1], ea[1])
 
 
+def _sorted_table(ctx, n=1000, k=21):
+    """a count table of n entries for k: sorted distinct words, counts of 1..99 (device tensors)"""
+    rng = np.random.default_rng(1000 + k)
+    keys = np.unique(rng.integers(0, 4**k, 2 * n, dtype=np.uint64))[:n]
+    assert len(keys) == n
+    return ctx.to_device(keys), ctx.to_device(rng.integers(1, 100, n, dtype=np.uint64))
+
+
+def _ragged_long_windows(ctx):
+    lens = np.array([100, 300, 80, 120])
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    ctx.canonical_windows(ctx.gen_reads(int(offsets[-1])), 4, 300, 31, offsets=ctx.to_device(offsets), host_offsets=offsets)
+
+
+# One call per route to the context's work buffer, each at the smallest shape that still takes it (a call is (ctx, table) -> None).
+WORK_BUFFER_TAKERS = {
+    "count_filter": lambda ctx, t: ctx.count_filter(t[0], t[1], 10, 50),                                           # a count-family working set
+    "reads_dedup": lambda ctx, t: ctx.reads_dedup(ctx.gen_reads(50 * 256), 256, 50),                               # a reads-family working set
+    "windows_uniform_long": lambda ctx, t: ctx.canonical_windows(ctx.gen_reads(4 * 600), 4, 600, 31),              # the planned segments of long uniform reads
+    "windows_ragged_long": lambda ctx, t: _ragged_long_windows(ctx),                                               # the cut segments of long ragged reads
+    "count_lookup_reads": lambda ctx, t: ctx.count_lookup_reads(ctx.gen_reads(150 * 64), 64, 150, 21, t[0], t[1]),  # the reads forms of the queries
+    "count_lookup": lambda ctx, t: ctx.count_lookup(t[0], t[1], 21, ctx.to_device(np.arange(4096, dtype=np.uint64))),   # the lookup's directory
+    "count_adjacency": lambda ctx, t: ctx.count_adjacency(t[0], t[1], 21),                                         # the adjacency's directory
+    "histogram_sip13": lambda ctx, t: ctx.histogram_sip13(ctx.gen_reads(150 * 8192), 8192, 150, 31, 20, 1, 2),     # the histogram launchers' callback
+}
+
+
+@pytest.mark.parametrize("taker,line", [(t, "reads") for t in sorted(WORK_BUFFER_TAKERS)] + [("count_filter", "quals"), ("count_filter", "names")])
+def test_same_text_behind_every_taker_of_the_work_buffer(orc, taker, line):
+    """The chunk prefixes a counting parse leaves behind live in the context's work buffer, so whoever takes the buffer in between
+    -- by whichever route -- must make the emit parse with KMX_FASTX_SAME_TEXT summarise the text again.  The buffer is grown to
+    its final size first, so the case rests on the invalidation alone, not on the buffer having moved (n_allocations is unchanged);
+    on a fresh context the taker alone makes the buffer exist, which says that its route is the one meant.  `line`: the emit is the
+    read parse's, or Context.fastx_quals / fastx_names with same_text behind the count-only read parse."""
+    import ctypes as C
+
+    from kmers_amd import _lib
+    from kmers_amd.api import Context, _ptr, u64_numpy
+    from tests import fastx_out_np as F
+    from tests import quality_np as Q
+
+    text = fastq_text(np.random.default_rng(77), 3000, 20, 200)
+    ctx = Context()
+    try:
+        table = _sorted_table(ctx)
+        take = WORK_BUFFER_TAKERS[taker]
+        d = ctx.to_device(text)
+
+        def count():
+            nr, nb = C.c_uint64(0), C.c_uint64(0)
+            ctx._ck(ctx.lib.kmx_fastx_parse(ctx._h, _ptr(d), d.numel(), 0, None, None, 0, C.byref(nr), C.byref(nb)))
+            return nr.value, nb.value
+
+        assert ctx.work_buffer_info() == (0, 0)
+        take(ctx, table)
+        assert ctx.work_buffer_info()[0] > 0, "this shape does not take the work buffer"
+        count()
+        allocs = ctx.work_buffer_info()[1]
+        nr, nb = count()
+        take(ctx, table)
+        if line == "reads":
+            eb, eo = orc.fastx_parse(text, 0)
+            import torch
+
+            bases, offsets = ctx.empty(max(nb, 1), torch.uint8), ctx.empty(nr + 1, torch.int64)
+            r, b = C.c_uint64(0), C.c_uint64(0)
+            ctx._ck(ctx.lib.kmx_fastx_parse(ctx._h, _ptr(d), d.numel(), _lib.FASTX_SAME_TEXT, _ptr(bases), _ptr(offsets), nr, C.byref(r), C.byref(b)))
+            assert (r.value, b.value) == (len(eo) - 1, len(eb))
+            assert np.array_equal(u64_numpy(offsets), eo) and np.array_equal(bases.cpu().numpy(), eb)
+        else:
+            want = Q.fastq_quals(text) if line == "quals" else F.fastq_names(text)
+            got, off = ctx.fastx_quals(d, same_text=True) if line == "quals" else ctx.fastx_names(d, same_text=True)
+            assert np.array_equal(u64_numpy(off), want[1]) and got.cpu().numpy().tobytes() == want[0].tobytes()
+        assert ctx.work_buffer_info()[1] == allocs
+    finally:
+        ctx.close()
+
+
 def test_fastx_reads_picks_the_layout(ctx, orc):
     """Context.fastx_reads: uniform layout when every read has the same length, else ragged with the tight bound; the
     summaries equal the oracle's over the parsed reads either way"""
