@@ -412,6 +412,138 @@ pub fn count_merge2(ctx: &HipContext, a: (&DeviceBuf<'_>, &DeviceBuf<'_>, u64), 
     Ok(n_out)
 }
 
+// ------------------------------------------------------------------------------------------------ the counting sketch
+
+/// A counting sketch on the device (`kmx_sketch_*`, include/kmx.h "the counting sketch"): `64 << log2_blocks` saturating byte
+/// cells, zero when new and accumulated into; a key's four cells lie in one 64-byte block chosen by its hash under `seed`.
+pub struct Sketch<'c> {
+    pub cells: DeviceBuf<'c>,
+    pub log2_blocks: u32,
+    pub seed: u64,
+}
+
+/// A zeroed sketch of `2^log2_blocks` blocks (`log2_blocks <= 32`).
+pub fn sketch_new(ctx: &HipContext, log2_blocks: u32, seed: u64) -> Result<Sketch<'_>, KmxError> {
+    assert!(log2_blocks <= 32, "log2_blocks above 32");
+    let cells = ctx.alloc(64usize << log2_blocks)?;
+    ctx.ck(unsafe { kmx_memset(ctx.0, cells.as_mut_ptr(), 0, cells.len()) })?;
+    Ok(Sketch { cells, log2_blocks, seed })
+}
+
+fn sketch_reads(d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32) -> kmx_reads {
+    assert!(n_reads as u128 * read_len as u128 <= d_reads.len() as u128, "reads past the end of the device buffer");
+    kmx_reads { d_bases: d_reads.as_ptr(), n_reads, read_len, d_offsets: ptr::null() }
+}
+
+/// Weight 1 for every valid window of a uniform batch already on the device (`kmx_sketch_add`, k in 1..=31).
+pub fn sketch_add(ctx: &HipContext, sketch: &Sketch<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8) -> Result<(), KmxError> {
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    ctx.ck(unsafe { kmx_sketch_add(ctx.0, &r, k as u32, sketch.cells.as_mut_ptr::<u8>(), sketch.log2_blocks, sketch.seed) })
+}
+
+/// The same for two-word k-mers, k in 33..=64 (`kmx_sketch_add2`).
+pub fn sketch_add2(ctx: &HipContext, sketch: &Sketch<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8) -> Result<(), KmxError> {
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    ctx.ck(unsafe { kmx_sketch_add2(ctx.0, &r, k as u32, sketch.cells.as_mut_ptr::<u8>(), sketch.log2_blocks, sketch.seed) })
+}
+
+/// `n` one-word keys as they are, each with its u64 weight (clipped to 255) or 1 (`kmx_sketch_add_words`): a table with its counts,
+/// or the canonical words of a windows call.
+pub fn sketch_add_words(ctx: &HipContext, sketch: &Sketch<'_>, d_words: &DeviceBuf<'_>, d_weights: Option<&DeviceBuf<'_>>, n: u64)
+                        -> Result<(), KmxError> {
+    assert!(n as u128 * 8 <= d_words.len() as u128 && d_weights.map_or(true, |w| n as u128 * 8 <= w.len() as u128), "keys or weights shorter than n");
+    let w = d_weights.map_or(ptr::null(), |w| w.as_ptr::<u64>());
+    ctx.ck(unsafe { kmx_sketch_add_words(ctx.0, d_words.as_ptr::<u64>(), w, n, sketch.cells.as_mut_ptr::<u8>(), sketch.log2_blocks, sketch.seed) })
+}
+
+/// The same for two-word keys, (low, high) pairs (`kmx_sketch_add_words2`).
+pub fn sketch_add_words2(ctx: &HipContext, sketch: &Sketch<'_>, d_words2: &DeviceBuf<'_>, d_weights: Option<&DeviceBuf<'_>>, n: u64)
+                         -> Result<(), KmxError> {
+    assert!(n as u128 * 16 <= d_words2.len() as u128 && d_weights.map_or(true, |w| n as u128 * 8 <= w.len() as u128), "keys or weights shorter than n");
+    let w = d_weights.map_or(ptr::null(), |w| w.as_ptr::<u64>());
+    ctx.ck(unsafe { kmx_sketch_add_words2(ctx.0, d_words2.as_ptr::<u64>(), w, n, sketch.cells.as_mut_ptr::<u8>(), sketch.log2_blocks, sketch.seed) })
+}
+
+/// The estimate of `n` one-word keys (`kmx_sketch_lookup`): never below min(255, the key's true total).
+pub fn sketch_lookup(ctx: &HipContext, sketch: &Sketch<'_>, d_words: &DeviceBuf<'_>, n: u64) -> Result<Vec<u8>, KmxError> {
+    assert!(n as u128 * 8 <= d_words.len() as u128, "keys shorter than n");
+    let d_est = ctx.alloc(n as usize + 1)?;
+    ctx.ck(unsafe { kmx_sketch_lookup(ctx.0, d_words.as_ptr::<u64>(), n, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, sketch.seed,
+                                      d_est.as_mut_ptr::<u8>()) })?;
+    d_est.download::<u8>(n as usize)
+}
+
+/// The same for two-word keys (`kmx_sketch_lookup2`).
+pub fn sketch_lookup2(ctx: &HipContext, sketch: &Sketch<'_>, d_words2: &DeviceBuf<'_>, n: u64) -> Result<Vec<u8>, KmxError> {
+    assert!(n as u128 * 16 <= d_words2.len() as u128, "keys shorter than n");
+    let d_est = ctx.alloc(n as usize + 1)?;
+    ctx.ck(unsafe { kmx_sketch_lookup2(ctx.0, d_words2.as_ptr::<u64>(), n, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, sketch.seed,
+                                       d_est.as_mut_ptr::<u8>()) })?;
+    d_est.download::<u8>(n as usize)
+}
+
+/// One estimate per window of a uniform batch, read r at `r * (read_len - k + 1)`; 0 for a window with an invalid byte
+/// (`kmx_sketch_lookup_reads`, k in 1..=31).
+pub fn sketch_lookup_reads(ctx: &HipContext, sketch: &Sketch<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8)
+                           -> Result<Vec<u8>, KmxError> {
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    let n = n_reads as usize * (read_len as usize + 1).saturating_sub(k as usize);
+    let d_est = ctx.alloc(n + 1)?;
+    ctx.ck(unsafe { kmx_sketch_lookup_reads(ctx.0, &r, ptr::null(), k as u32, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, sketch.seed,
+                                            d_est.as_mut_ptr::<u8>()) })?;
+    d_est.download::<u8>(n)
+}
+
+/// The same for k in 33..=64 (`kmx_sketch_lookup_reads2`).
+pub fn sketch_lookup_reads2(ctx: &HipContext, sketch: &Sketch<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8)
+                            -> Result<Vec<u8>, KmxError> {
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    let n = n_reads as usize * (read_len as usize + 1).saturating_sub(k as usize);
+    let d_est = ctx.alloc(n + 1)?;
+    ctx.ck(unsafe { kmx_sketch_lookup_reads2(ctx.0, &r, ptr::null(), k as u32, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, sketch.seed,
+                                             d_est.as_mut_ptr::<u8>()) })?;
+    d_est.download::<u8>(n)
+}
+
+/// `acc` += `other`, cellwise and saturating (`kmx_sketch_merge` with the output on its first input): sketches of disjoint batches
+/// with one size and seed merge into the sketch of their union, bit for bit.
+pub fn sketch_merge(ctx: &HipContext, acc: &Sketch<'_>, other: &Sketch<'_>) -> Result<(), KmxError> {
+    assert!(acc.log2_blocks == other.log2_blocks && acc.seed == other.seed, "sketches of different size or seed do not merge");
+    ctx.ck(unsafe { kmx_sketch_merge(ctx.0, acc.cells.as_ptr::<u8>(), other.cells.as_ptr::<u8>(), acc.log2_blocks, acc.cells.as_mut_ptr::<u8>()) })
+}
+
+/// How many cells hold each value, 256 bins (`kmx_sketch_stats`); `1 - bins[0] / cells` is the fill a sketch is sized by.
+pub fn sketch_stats(ctx: &HipContext, sketch: &Sketch<'_>) -> Result<Vec<u64>, KmxError> {
+    let d_hist = ctx.alloc(8 * 256)?;
+    ctx.ck(unsafe { kmx_memset(ctx.0, d_hist.as_mut_ptr(), 0, d_hist.len()) })?;
+    ctx.ck(unsafe { kmx_sketch_stats(ctx.0, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, d_hist.as_mut_ptr::<u64>()) })?;
+    d_hist.download::<u64>(256)
+}
+
+/// `count_canonical` of the windows whose estimate in `sketch` is at least `min_est` (`kmx_count_canonical_min`): with a sketch that
+/// has seen every batch, the k-mers that can occur `min_est` times in all of them.
+pub fn count_canonical_min(ctx: &HipContext, sketch: &Sketch<'_>, min_est: u32, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8,
+                           d_kmers: &DeviceBuf<'_>, d_counts: &DeviceBuf<'_>, max_distinct: u64) -> Result<u64, KmxError> {
+    assert!(max_distinct as u128 * 8 <= d_kmers.len().min(d_counts.len()) as u128, "outputs shorter than max_distinct");
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    let mut n_distinct = 0u64;
+    ctx.ck(unsafe { kmx_count_canonical_min(ctx.0, &r, k as u32, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, sketch.seed, min_est,
+                                            d_kmers.as_mut_ptr::<u64>(), d_counts.as_mut_ptr::<u64>(), max_distinct, &mut n_distinct) })?;
+    Ok(n_distinct)
+}
+
+/// The same for two-word k-mers, k in 33..=64 (`kmx_count_canonical_min2`; `d_kmers2` holds at least `2 * max_distinct` u64).
+pub fn count_canonical_min2(ctx: &HipContext, sketch: &Sketch<'_>, min_est: u32, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8,
+                            d_kmers2: &DeviceBuf<'_>, d_counts: &DeviceBuf<'_>, max_distinct: u64) -> Result<u64, KmxError> {
+    assert!(max_distinct as u128 * 16 <= d_kmers2.len() as u128 && max_distinct as u128 * 8 <= d_counts.len() as u128,
+            "outputs shorter than max_distinct");
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    let mut n_distinct = 0u64;
+    ctx.ck(unsafe { kmx_count_canonical_min2(ctx.0, &r, k as u32, sketch.cells.as_ptr::<u8>(), sketch.log2_blocks, sketch.seed, min_est,
+                                             d_kmers2.as_mut_ptr::<u64>(), d_counts.as_mut_ptr::<u64>(), max_distinct, &mut n_distinct) })?;
+    Ok(n_distinct)
+}
+
 /// A count table on the device: `keys` (`words` u64 per entry: 1 for k <= 31, 2 for k in 33..=64; ascending, distinct), one u64
 /// count per entry in `counts` (`None`: membership only, where a call allows it), `n` entries.
 #[derive(Clone, Copy)]

@@ -256,6 +256,81 @@ int kmx_count_merge2(kmx_ctx *ctx, const uint64_t *d_kmers2_a, const uint64_t *d
                      const uint64_t *d_counts_b, uint64_t n_b, uint64_t *d_kmers2_out, uint64_t *d_counts_out, uint64_t max_out,
                      uint64_t *h_n_out);
 
+/* ---------------------------------------------------------------- the counting sketch ----
+ * BUILD-DEFINED (the reference crate has no approximate structure).  A small approximate counter that every batch of a large input
+ * is added to, so that the exact counter then only has to hold the k-mers that can be solid: kmx_count_canonical_min(2) counts the
+ * windows whose estimate reaches a threshold, and over any number of batches
+ *     merge of kmx_count_canonical_min(batch, min_est = m), filtered with kmx_count_filter(min_count = m)
+ *  == kmx_count_filter(count of all batches together, min_count = m)        (1 <= m <= 255), key for key and count for count,
+ * because an estimate is never below the true total (clipped to 255) -- the sketch only lets too MANY windows through, and the final
+ * filter removes those.
+ *
+ * LAYOUT.  A blocked count-min sketch of saturating 8-bit cells in caller-owned device memory: d_sketch holds 64 << log2_blocks
+ * bytes, 64-byte aligned, 0 <= log2_blocks <= 32 (KMX_E_ARG otherwise), zeroed by the caller and ACCUMULATED into, as kmx_histogram
+ * accumulates into d_counts.  A block is 64 bytes -- 4 rows of 16 cells, one cache line.  A key touches exactly one block and exactly
+ * one cell in each of its rows: the four cells of a key are always four distinct bytes.
+ * KEY HASH.  One definition for both widths: a one-word key is (lo = the canonical word, hi = 0), a two-word key the (lo, hi) pair
+ * of the slot layout of kmx_canonical_windows2.  Arithmetic mod 2^64, fmix64 = the murmur3 64-bit finaliser (x ^= x >> 33;
+ * x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33):
+ *     h     = fmix64(lo ^ fmix64(hi + seed + 0x9e3779b97f4a7c15))
+ *     block = log2_blocks ? h >> (64 - log2_blocks) : 0
+ *     the cell of row j (0..3) is byte  64 * block + 16 * j + ((h >> (4 * j)) & 15)  of d_sketch.
+ * ADD.  Adding weight w to a key sets each of its four cells to min(255, cell + min(w, 255)).  Saturating adds commute: after any
+ * set of adds in any order a cell holds min(255, the sum of the weights that hit it).  That is the whole determinism contract --
+ * repeated calls, other streams and other launch shapes give identical bytes, and a host model reproduces the sketch exactly.
+ * ESTIMATE.  The estimate of a key is the minimum of its four cells: >= min(255, the key's true total weight), never less.  Hence
+ * every k-mer that occurs at least m <= 255 times in all that was added has an estimate >= m.
+ * Argument checks, KMX_E_K_RANGE (k in [1,31]; the calls named ...2: k in [33,64], two-word keys 16-byte aligned) and the behaviour
+ * on empty input (n == 0, n_reads == 0, no window: nothing is touched; d_sketch may then be NULL) follow the count family.  A NULL
+ * d_sketch with work to do, one that is not 64-byte aligned, or log2_blocks > 32: KMX_E_ARG. */
+
+/* Adds n keys as they are (a table's keys with its counts as weights, or the canon array of kmx_canonical_windows): key i with weight
+ * d_weights[i] (u64; clipped to 255; 0 adds nothing), or 1 each with d_weights == NULL.  n up to 2^40.  No working set; asynchronous:
+ * it only enqueues work on the context's stream. */
+int kmx_sketch_add_words(kmx_ctx *ctx, const uint64_t *d_words, const uint64_t *d_weights, uint64_t n, uint8_t *d_sketch,
+                         uint32_t log2_blocks, uint64_t seed);
+int kmx_sketch_add_words2(kmx_ctx *ctx, const uint64_t *d_words2, const uint64_t *d_weights, uint64_t n, uint8_t *d_sketch,
+                          uint32_t log2_blocks, uint64_t seed);
+/* Adds weight 1 for every window of the batch that kmx_canonical_windows(2) marks KMX_WIN_VALID: kmx_sketch_add_words(2) over the
+ * canon / flags of that call.  Every input those calls take is taken (uniform reads of any length, ragged reads with any bound --
+ * the window offsets are made on the device --, any d_bases alignment, invalid bytes, lower case, reads above 256 bases).
+ * Working set in the context's work buffer: 9 bytes per window (add2: 17; windows counted as for kmx_count_canonical: uniform reads
+ * n_reads * (read_len - k + 1), ragged reads the batch's number of BASES plus 9 bytes per read), each array rounded up to 256, and
+ * the segment plan of reads above 256 bases.  Above the cap: KMX_E_NOMEM BEFORE any kernel runs, the sketch untouched.  Ragged
+ * reads bring two words back to the host (the span of the offsets, the number of windows); otherwise asynchronous. */
+int kmx_sketch_add(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint8_t *d_sketch, uint32_t log2_blocks, uint64_t seed);
+int kmx_sketch_add2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint8_t *d_sketch, uint32_t log2_blocks, uint64_t seed);
+/* d_est[i] (one byte) = the estimate of key i.  No working set; asynchronous. */
+int kmx_sketch_lookup(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n, const uint8_t *d_sketch, uint32_t log2_blocks, uint64_t seed,
+                      uint8_t *d_est);
+int kmx_sketch_lookup2(kmx_ctx *ctx, const uint64_t *d_words2, uint64_t n, const uint8_t *d_sketch, uint32_t log2_blocks, uint64_t seed,
+                       uint8_t *d_est);
+/* One byte per window slot, in the slot layout of kmx_canonical_windows(2) (r * (read_len - k + 1) + p, or d_win_offsets[r] + p;
+ * ragged reads need their d_win_offsets): the estimate of the window's canonical k-mer, 0 for a window without KMX_WIN_VALID.  It IS
+ * the windows call followed by the lookup, as kmx_count_lookup_reads(2) is, with that call's inputs, routes and synchronisation.
+ * Working set: 9 (17) bytes per window, counted and refused as for kmx_sketch_add. */
+int kmx_sketch_lookup_reads(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_win_offsets, uint32_t k, const uint8_t *d_sketch,
+                            uint32_t log2_blocks, uint64_t seed, uint8_t *d_est);
+int kmx_sketch_lookup_reads2(kmx_ctx *ctx, const kmx_reads *reads, const uint64_t *d_win_offsets, uint32_t k, const uint8_t *d_sketch,
+                             uint32_t log2_blocks, uint64_t seed, uint8_t *d_est);
+/* d_out = cellwise min(255, a + b) of two sketches of the same log2_blocks; d_out may be d_a or d_b.  Sketches of disjoint batches
+ * built with the same seed and size merge into the sketch of their union, bit for bit -- the law that lets batches, streams and ranks
+ * each fill a sketch of their own.  No working set; asynchronous. */
+int kmx_sketch_merge(kmx_ctx *ctx, const uint8_t *d_a, const uint8_t *d_b, uint32_t log2_blocks, uint8_t *d_out);
+/* d_hist[v] += the number of cells that hold v: 256 u64, ACCUMULATED into (the caller zeroes).  1 - d_hist[0] / cells, the share of
+ * non-zero cells, is what a caller sizes the sketch by.  Integer atomics: deterministic.  No working set; asynchronous. */
+int kmx_sketch_stats(kmx_ctx *ctx, const uint8_t *d_sketch, uint32_t log2_blocks, uint64_t *d_hist);
+/* kmx_count_canonical(2) restricted to the windows whose estimate in the sketch is >= min_est: between the windows call and the sort
+ * one kernel clears KMX_WIN_VALID of every other window.  Everything else is kmx_count_canonical(2)'s: order, max_distinct /
+ * KMX_E_NOMEM with nothing written, both outputs NULL = count only, working set, synchrony.  min_est <= 1 on a sketch that has seen
+ * the batch gives the unfiltered table (min_est == 0 does not read the sketch); min_est > 255 gives the empty table. */
+int kmx_count_canonical_min(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint8_t *d_sketch, uint32_t log2_blocks,
+                            uint64_t seed, uint32_t min_est, uint64_t *d_kmers, uint64_t *d_counts, uint64_t max_distinct,
+                            uint64_t *h_n_distinct);
+int kmx_count_canonical_min2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, const uint8_t *d_sketch, uint32_t log2_blocks,
+                             uint64_t seed, uint32_t min_est, uint64_t *d_kmers2, uint64_t *d_counts, uint64_t max_distinct,
+                             uint64_t *h_n_distinct);
+
 /* ---------------------------------------------------------------- queries on a count table ----
  * BUILD-DEFINED, like the counters.  A TABLE is what kmx_count_canonical(2) / kmx_count_merge(2) / kmx_count_filter(2) write: n keys
  * ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs, 16-byte aligned (KMX_E_ARG otherwise), ordered

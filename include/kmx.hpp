@@ -608,6 +608,77 @@ inline ReadDuplicates reads_dedup(Context& ctx, const kmx_reads& reads, const km
     return d;
 }
 
+// The counting sketch (kmx.h, "the counting sketch"): 64 << log2_blocks zeroed cells on the device, every batch of a large input
+// added to it, then the exact count of the windows whose estimate reaches min_est -- the k-mers that can be solid.  k picks the
+// width of the calls: 1..31 one-word, 33..64 two-word (a table's keys then come as (low, high) pairs).
+struct CountTable {
+    std::vector<uint64_t> kmers, counts;
+};
+class Sketch {
+  public:
+    Sketch(Context& ctx, uint32_t log2_blocks, uint64_t seed = 0) : ctx_(ctx), cells_(ctx, size_t(64) << log2_blocks), log2_blocks_(log2_blocks), seed_(seed) {
+        ctx_.check(kmx_memset(ctx_.get(), cells_.data(), 0, cells_.size()), "kmx_memset");
+    }
+    uint8_t* data() const { return cells_.data(); }
+    size_t size() const { return cells_.size(); }
+    uint32_t log2_blocks() const { return log2_blocks_; }
+    uint64_t seed() const { return seed_; }
+    void add(const kmx_reads& reads, uint32_t k) {
+        ctx_.check(k <= 32 ? kmx_sketch_add(ctx_.get(), &reads, k, data(), log2_blocks_, seed_) : kmx_sketch_add2(ctx_.get(), &reads, k, data(), log2_blocks_, seed_),
+                   "sketch_add");
+    }
+    // n keys on the device, with their weights or 1 each; words = 1 or 2 u64 per key
+    void add_words(const uint64_t* d_words, const uint64_t* d_weights, uint64_t n, uint32_t words = 1) {
+        ctx_.check(words == 1 ? kmx_sketch_add_words(ctx_.get(), d_words, d_weights, n, data(), log2_blocks_, seed_)
+                              : kmx_sketch_add_words2(ctx_.get(), d_words, d_weights, n, data(), log2_blocks_, seed_),
+                   "sketch_add_words");
+    }
+    std::vector<uint8_t> lookup(const uint64_t* d_words, uint64_t n, uint32_t words = 1) const {
+        DeviceBuffer<uint8_t> est(ctx_, n + 1);
+        ctx_.check(words == 1 ? kmx_sketch_lookup(ctx_.get(), d_words, n, data(), log2_blocks_, seed_, est.data())
+                              : kmx_sketch_lookup2(ctx_.get(), d_words, n, data(), log2_blocks_, seed_, est.data()),
+                   "sketch_lookup");
+        auto out = est.download();   // (synchronises)
+        out.resize(n);
+        return out;
+    }
+    // this += other (cellwise, saturating): sketches of one size and seed
+    void merge(const Sketch& other) {
+        if (other.log2_blocks_ != log2_blocks_ || other.seed_ != seed_) throw Panic(KMX_E_ARG, "sketch_merge");
+        ctx_.check(kmx_sketch_merge(ctx_.get(), data(), other.data(), log2_blocks_, data()), "sketch_merge");
+    }
+    std::vector<uint64_t> stats() const {
+        DeviceBuffer<uint64_t> hist(ctx_, 256);
+        ctx_.check(kmx_memset(ctx_.get(), hist.data(), 0, 256 * sizeof(uint64_t)), "kmx_memset");
+        ctx_.check(kmx_sketch_stats(ctx_.get(), data(), log2_blocks_, hist.data()), "sketch_stats");
+        return hist.download();
+    }
+    double fill() const { return 1.0 - double(stats()[0]) / double(size()); }   // the share of non-zero cells
+    // kmx_count_canonical_min(2) on the host: a count-only call sizes the buffers
+    CountTable count_min(const kmx_reads& reads, uint32_t k, uint32_t min_est) const {
+        const uint32_t words = k <= 32 ? 1 : 2;
+        auto call = [&](uint64_t* d_kmers, uint64_t* d_counts, uint64_t max_distinct, uint64_t* n) {
+            return words == 1 ? kmx_count_canonical_min(ctx_.get(), &reads, k, data(), log2_blocks_, seed_, min_est, d_kmers, d_counts, max_distinct, n)
+                              : kmx_count_canonical_min2(ctx_.get(), &reads, k, data(), log2_blocks_, seed_, min_est, d_kmers, d_counts, max_distinct, n);
+        };
+        uint64_t n = 0;
+        ctx_.check(call(nullptr, nullptr, 0, &n), "count_canonical_min");
+        CountTable t;
+        if (n == 0) return t;
+        DeviceBuffer<uint64_t> kmers(ctx_, words * n), counts(ctx_, n);
+        ctx_.check(call(kmers.data(), counts.data(), n, &n), "count_canonical_min");
+        t.kmers = kmers.download();
+        t.counts = counts.download();
+        return t;
+    }
+
+  private:
+    Context& ctx_;
+    DeviceBuffer<uint8_t> cells_;
+    uint32_t log2_blocks_;
+    uint64_t seed_;
+};
+
 // src/naive_impl/seq_vector.rs: the 2-bit packed sequence container, resident on the device.
 class SeqVector {
   public:

@@ -76,6 +76,11 @@ DD_WORDS = 4
 DD_F_KEPT, DD_F_FLIPPED, DD_F_COLLISION, DD_F_OTHER = 1, 2, 4, 8
 DD_S_KEPT, DD_S_DROPPED, DD_S_LARGEST, DD_S_COLLISIONS = range(4)
 DD_SUMMARY_WORDS = 4
+# kmx_sketch_*: a block's bytes, the largest log2_blocks, and the lanes per compute unit of one grid sweep of the add, lookup and
+# filter kernels (kmx_sketch.hip: SKETCH_BLOCKS_PER_CU blocks of 256 -- where the tests put their "more than one sweep")
+SKETCH_BLOCK_BYTES = 64
+SKETCH_MAX_LOG2_BLOCKS = 32
+SKETCH_SWEEP_LANES_PER_CU = 1024
 
 
 class KmxError(RuntimeError):
@@ -156,6 +161,18 @@ SIGNATURES = {
     "kmx_count_merge": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_canonical2": (_int, [_vp, _RP, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_merge2": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_sketch_add_words": (_int, [_vp, _vp, _vp, _u64, _vp, _u32, _u64]),
+    "kmx_sketch_add_words2": (_int, [_vp, _vp, _vp, _u64, _vp, _u32, _u64]),
+    "kmx_sketch_add": (_int, [_vp, _RP, _u32, _vp, _u32, _u64]),
+    "kmx_sketch_add2": (_int, [_vp, _RP, _u32, _vp, _u32, _u64]),
+    "kmx_sketch_lookup": (_int, [_vp, _vp, _u64, _vp, _u32, _u64, _vp]),
+    "kmx_sketch_lookup2": (_int, [_vp, _vp, _u64, _vp, _u32, _u64, _vp]),
+    "kmx_sketch_lookup_reads": (_int, [_vp, _RP, _vp, _u32, _vp, _u32, _u64, _vp]),
+    "kmx_sketch_lookup_reads2": (_int, [_vp, _RP, _vp, _u32, _vp, _u32, _u64, _vp]),
+    "kmx_sketch_merge": (_int, [_vp, _vp, _vp, _u32, _vp]),
+    "kmx_sketch_stats": (_int, [_vp, _vp, _u32, _vp]),
+    "kmx_count_canonical_min": (_int, [_vp, _RP, _u32, _vp, _u32, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_count_canonical_min2": (_int, [_vp, _RP, _u32, _vp, _u32, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_lookup": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_lookup2": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     "kmx_count_lookup_reads": (_int, [_vp, _RP, _vp, _u32, _vp, _vp, _u64, _vp]),

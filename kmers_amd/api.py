@@ -599,6 +599,22 @@ class DeduplicatedReads:
     duplicates: ReadDuplicates
 
 
+@dataclasses.dataclass
+class Sketch:
+    """A counting sketch on the device (kmx_sketch_*): `cells`, uint8[64 << log2_blocks], zero when new; a key's four cells lie in
+    block h >> (64 - log2_blocks) of 64 bytes, h its hash under `seed` (kmx.h has the definition).  `ctx` is the context that made
+    it (for fill)."""
+    cells: "torch.Tensor"
+    log2_blocks: int
+    seed: int = 0
+    ctx: "Context | None" = dataclasses.field(default=None, repr=False, compare=False)
+
+    def fill(self) -> float:
+        """the share of non-zero cells (kmx_sketch_stats: one host round trip), what a sketch is sized by"""
+        hist = self.ctx.sketch_stats(self)
+        return 1.0 - int(hist[0].item()) / int(self.cells.numel())
+
+
 def _on_ctx_stream(fn):
     """Run a Context method with Context.stream as torch's current stream (see "Stream discipline" above)."""
     @functools.wraps(fn)
@@ -1093,6 +1109,178 @@ class Context:
     def count_filter2(self, kmers, counts, min_count=1, max_count=2**64 - 1, max_out=None):
         """kmx_count_filter2 -> (kmers int64[n, 2], counts) for the tables of count_canonical2."""
         return self._filter(self.lib.kmx_count_filter2, 2, kmers, counts, min_count, max_count, max_out)
+
+    # ------------------------------------------------------------ the counting sketch
+    @_on_ctx_stream
+    def sketch_new(self, log2_blocks, seed=0) -> Sketch:
+        """a zeroed sketch of 2^log2_blocks blocks of 64 bytes"""
+        if not 0 <= int(log2_blocks) <= _lib.SKETCH_MAX_LOG2_BLOCKS:
+            raise ValueError("log2_blocks outside 0..32")
+        cells = torch.zeros(_lib.SKETCH_BLOCK_BYTES << int(log2_blocks), dtype=torch.uint8, device=self.device)
+        return Sketch(cells, int(log2_blocks), int(seed) & (2**64 - 1), self)
+
+    def _sketch_args(self, sketch):
+        return _ptr(sketch.cells), int(sketch.log2_blocks), int(sketch.seed)
+
+    def _sketch_add(self, fn, sketch, bases, n_reads, read_len, k, offsets):
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), k, *self._sketch_args(sketch)))
+        return sketch
+
+    @_on_ctx_stream
+    def sketch_add(self, sketch, bases, n_reads, read_len, k, offsets=None) -> Sketch:
+        """kmx_sketch_add: weight 1 for every valid window of the batch, accumulated into `sketch` (returned)."""
+        return self._sketch_add(self.lib.kmx_sketch_add, sketch, bases, n_reads, read_len, k, offsets)
+
+    @_on_ctx_stream
+    def sketch_add2(self, sketch, bases, n_reads, read_len, k, offsets=None) -> Sketch:
+        """kmx_sketch_add2 (k 33..64)."""
+        return self._sketch_add(self.lib.kmx_sketch_add2, sketch, bases, n_reads, read_len, k, offsets)
+
+    def _sketch_add_words(self, fn, words, sketch, keys, weights):
+        n = int(keys.numel()) // words
+        keys = keys.contiguous()
+        self._ck(fn(self._h, _ptr(keys) if n else None, _ptr(weights) if weights is not None and n else None, n, *self._sketch_args(sketch)))
+        return sketch
+
+    @_on_ctx_stream
+    def sketch_add_words(self, sketch, words, weights=None) -> Sketch:
+        """kmx_sketch_add_words: the keys as they are (int64 holding u64 words), each with its weight (int64 holding u64, clipped to
+        255) or 1: a table with its counts, or the canon array of canonical_windows."""
+        return self._sketch_add_words(self.lib.kmx_sketch_add_words, 1, sketch, words, weights)
+
+    @_on_ctx_stream
+    def sketch_add_words2(self, sketch, words, weights=None) -> Sketch:
+        """kmx_sketch_add_words2: words int64[n, 2] = (low, high)."""
+        return self._sketch_add_words(self.lib.kmx_sketch_add_words2, 2, sketch, words, weights)
+
+    def _sketch_lookup(self, fn, words, sketch, keys, out):
+        n = int(keys.numel()) // words
+        keys = keys.contiguous()
+        if out is None:
+            out = self.empty(n, torch.uint8)
+        self._ck(fn(self._h, _ptr(keys) if n else None, n, *self._sketch_args(sketch), _ptr(out) if n else None))
+        return out
+
+    @_on_ctx_stream
+    def sketch_lookup(self, sketch, words, out=None):
+        """kmx_sketch_lookup -> uint8[n]: the estimate of every key, never below min(255, its true total)."""
+        return self._sketch_lookup(self.lib.kmx_sketch_lookup, 1, sketch, words, out)
+
+    @_on_ctx_stream
+    def sketch_lookup2(self, sketch, words, out=None):
+        """kmx_sketch_lookup2: words int64[n, 2] -> uint8[n]."""
+        return self._sketch_lookup(self.lib.kmx_sketch_lookup2, 2, sketch, words, out)
+
+    def _sketch_lookup_reads(self, fn, sketch, bases, n_reads, read_len, k, offsets, win_offsets, out):
+        if offsets is not None and win_offsets is None:
+            lens = offsets[1:] - offsets[:-1]
+            w = (lens - int(k) + 1).clamp_(min=0)
+            w[lens > 0x7FFFFFFF] = 0
+            win_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(w, 0)])
+        if out is None:
+            total = int(win_offsets[-1].item()) if win_offsets is not None else int(n_reads) * max(int(read_len) - int(k) + 1, 0)
+            out = self.empty(total, torch.uint8)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), _ptr(win_offsets), k, *self._sketch_args(sketch), _ptr(out) if out.numel() else None))
+        return out
+
+    @_on_ctx_stream
+    def sketch_lookup_reads(self, sketch, bases, n_reads, read_len, k, offsets=None, win_offsets=None, out=None):
+        """kmx_sketch_lookup_reads -> uint8[windows]: the estimate of the canonical k-mer of every window of the batch, in the slot
+        layout of canonical_windows; 0 for a window with an invalid byte.  Ragged reads: `win_offsets` is made from `offsets` when
+        not given."""
+        return self._sketch_lookup_reads(self.lib.kmx_sketch_lookup_reads, sketch, bases, n_reads, read_len, k, offsets, win_offsets, out)
+
+    @_on_ctx_stream
+    def sketch_lookup_reads2(self, sketch, bases, n_reads, read_len, k, offsets=None, win_offsets=None, out=None):
+        """kmx_sketch_lookup_reads2 (k 33..64)."""
+        return self._sketch_lookup_reads(self.lib.kmx_sketch_lookup_reads2, sketch, bases, n_reads, read_len, k, offsets, win_offsets, out)
+
+    @_on_ctx_stream
+    def sketch_merge(self, a: Sketch, b: Sketch, out: "Sketch | None" = None) -> Sketch:
+        """kmx_sketch_merge -> the cellwise saturating sum of two sketches of one size and seed; `out` may be `a` or `b`."""
+        if a.log2_blocks != b.log2_blocks or a.seed != b.seed:
+            raise ValueError("sketches of different size or seed do not merge")
+        if out is None:
+            out = Sketch(self.empty(a.cells.numel(), torch.uint8), a.log2_blocks, a.seed, self)
+        elif out.log2_blocks != a.log2_blocks or out.seed != a.seed:
+            raise ValueError("sketches of different size or seed do not merge")
+        self._ck(self.lib.kmx_sketch_merge(self._h, _ptr(a.cells), _ptr(b.cells), a.log2_blocks, _ptr(out.cells)))
+        return out
+
+    @_on_ctx_stream
+    def sketch_stats(self, sketch: Sketch, out=None):
+        """kmx_sketch_stats -> int64[256]: how many cells hold each value; zeroed bins unless handed some (they are accumulated into)."""
+        if out is None:
+            out = torch.zeros(256, dtype=torch.int64, device=self.device)
+        self._ck(self.lib.kmx_sketch_stats(self._h, _ptr(sketch.cells), int(sketch.log2_blocks), _ptr(out)))
+        return out
+
+    def _count_min(self, fn, words, sketch, min_est, bases, n_reads, read_len, k, offsets, max_distinct, count_only):
+        nd = C.c_uint64(0)
+        r = self._reads(bases, n_reads, read_len, offsets)
+        if count_only:
+            self._ck(fn(self._h, C.byref(r), k, *self._sketch_args(sketch), int(min_est), None, None, 0, C.byref(nd)))
+            return int(nd.value)
+        if max_distinct is None:
+            max_distinct = self._max_windows(n_reads, read_len, k, offsets)
+        kmers = self.empty(words * max(max_distinct, 1), torch.int64)
+        counts = self.empty(max(max_distinct, 1), torch.int64)
+        self._ck(fn(self._h, C.byref(r), k, *self._sketch_args(sketch), int(min_est), _ptr(kmers), _ptr(counts), int(max_distinct), C.byref(nd)))
+        kmers = kmers[:words * nd.value]
+        return (kmers.view(-1, 2) if words == 2 else kmers), counts[:nd.value]
+
+    @_on_ctx_stream
+    def count_canonical_min(self, sketch, min_est, bases, n_reads, read_len, k, offsets=None, max_distinct=None, count_only=False):
+        """kmx_count_canonical_min -> (kmers, counts) as count_canonical, of the windows whose estimate in `sketch` is >= min_est
+        (0..2^32 - 1; above 255: the empty table).  count_only: the number of distinct k-mers, nothing written."""
+        return self._count_min(self.lib.kmx_count_canonical_min, 1, sketch, min_est, bases, n_reads, read_len, k, offsets, max_distinct, count_only)
+
+    @_on_ctx_stream
+    def count_canonical_min2(self, sketch, min_est, bases, n_reads, read_len, k, offsets=None, max_distinct=None, count_only=False):
+        """kmx_count_canonical_min2 (k 33..64) -> (kmers int64[n, 2], counts)."""
+        return self._count_min(self.lib.kmx_count_canonical_min2, 2, sketch, min_est, bases, n_reads, read_len, k, offsets, max_distinct, count_only)
+
+    @staticmethod
+    def _batch_args(b):
+        if isinstance(b, ReadBatch):
+            return b.bases, b.n_reads, b.max_len(), b.offsets
+        bases, n_reads, read_len, offsets = b
+        return bases, n_reads, read_len, offsets
+
+    def _count_solid(self, words, batches, k, min_count, log2_blocks, seed, tables):
+        if not 1 <= int(min_count) <= 255:
+            raise ValueError("min_count outside 1..255: a cell of the sketch counts to 255")
+        add, count, merge, flt = ((self.sketch_add, self.count_canonical_min, self.count_merge, self.count_filter) if words == 1 else
+                                  (self.sketch_add2, self.count_canonical_min2, self.count_merge2, self.count_filter2))
+        sketch = self.sketch_new(log2_blocks, seed)
+        for b in batches:
+            bases, n_reads, read_len, offsets = self._batch_args(b)
+            add(sketch, bases, n_reads, read_len, k, offsets=offsets)
+        kmers = self.empty(0, torch.int64).view(-1, 2) if words == 2 else self.empty(0, torch.int64)
+        counts = self.empty(0, torch.int64)
+        for b in batches:
+            bases, n_reads, read_len, offsets = self._batch_args(b)
+            bk, bc = count(sketch, int(min_count), bases, n_reads, read_len, k, offsets=offsets)
+            if tables is not None:
+                tables.append(int(bc.numel()))
+            kmers, counts = merge(kmers, counts, bk, bc)
+        kmers, counts = flt(kmers, counts, int(min_count), 2**64 - 1)
+        return kmers, counts, sketch
+
+    def count_solid(self, batches, k, min_count, log2_blocks, seed=0, tables=None):
+        """The k-mers that occur at least `min_count` (1..255) times in all of `batches` together, counted without ever holding the
+        rest: (kmers, counts, sketch).  `batches`: a sequence, iterable twice, of (bases, n_reads, read_len, offsets) or ReadBatch.
+        Pass 1 adds every batch to one sketch of 2^log2_blocks blocks; pass 2 counts, per batch, the windows whose estimate reaches
+        min_count (count_canonical_min), folds the tables with count_merge and keeps the entries of at least min_count
+        (count_filter).  Equal, key for key and count for count, to count_filter of the count of all reads at once -- for any
+        sketch size: a small sketch only lets more through.  `tables`, a list: the size of every batch's table is appended."""
+        return self._count_solid(1, batches, k, min_count, log2_blocks, seed, tables)
+
+    def count_solid2(self, batches, k, min_count, log2_blocks, seed=0, tables=None):
+        """count_solid for k 33..64 (kmers int64[n, 2])."""
+        return self._count_solid(2, batches, k, min_count, log2_blocks, seed, tables)
 
     # ------------------------------------------------------------ a count table as a de Bruijn graph
     def _adjacency(self, fn, words, kmers, counts, k, min_count, flips, neighbors):

@@ -737,30 +737,50 @@ struct CountKind {
     int (*windows)(kmx_ctx*, const kmx_reads*, const uint64_t*, uint32_t, uint64_t*, uint64_t*, uint64_t*, uint8_t*);
 };
 
-// The body of kmx_count_canonical / kmx_count_canonical2 behind their argument checks: sizing, cap, work buffer, window offsets,
-// windows, sort, emit.
-static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const CountKind& kind, uint64_t* d_kmers, uint64_t* d_counts,
-                      uint64_t max_distinct, uint64_t* h_n_distinct) {
-    *h_n_distinct = 0;
-    if (reads->n_reads == 0) return KMX_OK;
-    DeviceGuard g(ctx->device);
+// A counting sketch as the calls take it (kmx.h): 64 << log2_blocks bytes, 64-byte aligned.
+struct Sketch {
+    const uint8_t* cells;
+    uint32_t log2_blocks;
+    uint64_t seed;
+};
+static bool sketch_ok(const void* d_sketch, uint32_t log2_blocks, bool needed) {
+    return log2_blocks <= 32u && (reinterpret_cast<uintptr_t>(d_sketch) & 63u) == 0 && (d_sketch != nullptr || !needed);
+}
+// The filter step of kmx_count_canonical_min(2): the windows whose estimate in `sketch` is below min_est lose KMX_WIN_VALID.
+struct CountFilter {
+    Sketch sketch;
+    uint32_t min_est;
+};
+
+// The front half kmx_count_canonical(2) and kmx_sketch_add(2) share: sizing, cap, work buffer, window offsets, windows.  The work
+// buffer, laid out up front: [segment plan of long reads][ragged: window offsets][canon 8 (16) B/window][flags 1 B/window][the caller's
+// area: area_bytes(words, windows), none without it].
+struct WindowsFront {
+    char* base = nullptr;        // the work buffer
+    uint64_t n_win = 0;          // the windows there are; 0 = none, and no kernel wrote canon / flags
+    uint64_t* canon = nullptr;   // one key per window
+    uint8_t* flags = nullptr;    // one byte per window
+    size_t area_at = 0;          // where the caller's area starts
+};
+static int windows_front(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const CountKind& kind, size_t (*area_bytes)(uint32_t, uint64_t),
+                         WindowsFront* f) {
     uint64_t n_bound = 0, n_bases = 0;
     if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
     if (n_bound == 0) return KMX_OK;   // no window
     const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
     const size_t wo_bytes = reads->d_offsets ? align256(kmx::win_offsets_bytes(reads->n_reads)) : 0;
     const size_t canon_at = plan + wo_bytes, flags_at = canon_at + align256(8u * kind.words * n_bound), area_at = flags_at + align256(n_bound);
-    const size_t bytes = area_at + kmx::count_area_bytes(kind.words, n_bound);
+    const size_t bytes = area_at + (area_bytes ? area_bytes(kind.words, n_bound) : 0u);
     void* buf = nullptr;
     WorkHold hold;
     if (int st = work_area(ctx, kind.who, bytes, &buf, &hold)) return st;
     char* const base = hold.base;
-    char msg[96];
     uint64_t n_win = n_bound;
     uint64_t* wo = nullptr;
     if (reads->d_offsets) {
         KMX_HIP(ctx, kmx::launch_count_win_offsets(reads->d_offsets, reads->n_reads, k, base + plan, &wo, ctx->h_pinned, &n_win, ctx->stream));
         if (n_win > n_bound) {
+            char msg[96];
             std::snprintf(msg, sizeof msg, "%s: window count above its bound", kind.who);
             return fail_hip(ctx, hipErrorUnknown, msg);
         }
@@ -770,19 +790,38 @@ static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const Co
     uint8_t* flags = reinterpret_cast<uint8_t*>(base + flags_at);
     if (int st = kind.windows(ctx, reads, wo, k, nullptr, nullptr, canon, flags)) return st;
     if (int st = work_kept(ctx, kind.who, hold)) return st;
+    *f = WindowsFront{base, n_win, canon, flags, area_at};
+    return KMX_OK;
+}
+
+// The body of kmx_count_canonical(2) and kmx_count_canonical_min(2) behind their argument checks: the windows (windows_front), the
+// filter step where there is one, sort, emit.
+static int count_impl(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const CountKind& kind, uint64_t* d_kmers, uint64_t* d_counts,
+                      uint64_t max_distinct, uint64_t* h_n_distinct, const CountFilter* filter = nullptr) {
+    *h_n_distinct = 0;
+    if (reads->n_reads == 0) return KMX_OK;
+    if (filter && filter->min_est > 255u) return KMX_OK;   // (no estimate is above 255: the empty table)
+    DeviceGuard g(ctx->device);
+    WindowsFront f;
+    if (int st = windows_front(ctx, reads, k, kind, kmx::count_area_bytes, &f)) return st;
+    if (f.n_win == 0) return KMX_OK;
+    if (filter && filter->min_est > 0u)
+        KMX_HIP(ctx, kmx::launch_sketch_filter(kind.words, f.canon, f.flags, f.n_win, filter->sketch.cells, filter->sketch.log2_blocks,
+                                               filter->sketch.seed, filter->min_est, ctx->n_cu, ctx->stream));
     uint64_t n_valid = 0, n_distinct = 0;
     bool bad = false;
-    // (the count area is laid out for the n_win windows there are, inside the bytes reserved for n_bound >= n_win)
-    void* area = base + area_at;
-    KMX_HIP(ctx, kmx::launch_count_sort(kind.words, canon, flags, n_win, k, area, ctx->h_pinned, &n_valid, &n_distinct, &bad, ctx->stream));
+    // (the count area is laid out for the n_win windows there are, inside the bytes reserved for the bound on them)
+    void* area = f.base + f.area_at;
+    KMX_HIP(ctx, kmx::launch_count_sort(kind.words, f.canon, f.flags, f.n_win, k, area, ctx->h_pinned, &n_valid, &n_distinct, &bad, ctx->stream));
     if (bad) {
+        char msg[96];
         std::snprintf(msg, sizeof msg, "%s: partition arrays above their bounds", kind.who);
         return fail_hip(ctx, hipErrorUnknown, msg);
     }
     *h_n_distinct = n_distinct;
     if (!d_kmers || n_distinct == 0) return KMX_OK;
     if (int st = room_for(ctx, kind.who, n_distinct, "distinct k-mers", max_distinct)) return st;
-    KMX_HIP(ctx, kmx::launch_count_emit(kind.words, canon, n_win, n_valid, area, d_kmers, d_counts, ctx->stream));
+    KMX_HIP(ctx, kmx::launch_count_emit(kind.words, f.canon, f.n_win, n_valid, area, d_kmers, d_counts, ctx->stream));
     KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMX_OK;
 }
@@ -802,6 +841,26 @@ int kmx_count_canonical2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint6
     if (k < 33 || k > 64) return KMX_E_K_RANGE;
     static const CountKind kind{"kmx_count_canonical2", 2u, kmx_canonical_windows2};
     return count_impl(ctx, reads, k, kind, d_kmers2, d_counts, max_distinct, h_n_distinct);
+}
+
+int kmx_count_canonical_min(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed,
+                            uint32_t min_est, uint64_t* d_kmers, uint64_t* d_counts, uint64_t max_distinct, uint64_t* h_n_distinct) {
+    if (!ctx || !reads_ok(reads) || !h_n_distinct || ((d_kmers == nullptr) != (d_counts == nullptr))) return KMX_E_ARG;
+    if (!sketch_ok(d_sketch, log2_blocks, reads->n_reads != 0)) return KMX_E_ARG;
+    if (k < 1 || k > 31) return KMX_E_K_RANGE;
+    static const CountKind kind{"kmx_count_canonical_min", 1u, kmx_canonical_windows};
+    const CountFilter filter{{d_sketch, log2_blocks, seed}, min_est};
+    return count_impl(ctx, reads, k, kind, d_kmers, d_counts, max_distinct, h_n_distinct, &filter);
+}
+
+int kmx_count_canonical_min2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, const uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed,
+                             uint32_t min_est, uint64_t* d_kmers2, uint64_t* d_counts, uint64_t max_distinct, uint64_t* h_n_distinct) {
+    if (!ctx || !reads_ok(reads) || !h_n_distinct || ((d_kmers2 == nullptr) != (d_counts == nullptr)) || !aligned16(d_kmers2)) return KMX_E_ARG;
+    if (!sketch_ok(d_sketch, log2_blocks, reads->n_reads != 0)) return KMX_E_ARG;
+    if (k < 33 || k > 64) return KMX_E_K_RANGE;
+    static const CountKind kind{"kmx_count_canonical_min2", 2u, kmx_canonical_windows2};
+    const CountFilter filter{{d_sketch, log2_blocks, seed}, min_est};
+    return count_impl(ctx, reads, k, kind, d_kmers2, d_counts, max_distinct, h_n_distinct, &filter);
 }
 
 static int merge_impl(kmx_ctx* ctx, const char* who, uint32_t words, const uint64_t* d_kmers_a, const uint64_t* d_counts_a, uint64_t n_a,
@@ -921,6 +980,29 @@ static int query_scratch(kmx_ctx* ctx, const char* who, uint32_t words, size_t r
     return KMX_OK;
 }
 
+// The windows the arrays of a reads form are sized for (query_window_bound) and the windows there are in the caller's slot layout
+// (*n_win; 0 = none): ragged reads by the last of their d_win_offsets, which comes back to the host.
+static int caller_windows(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, uint64_t* n_bound, uint64_t* n_bases,
+                          uint64_t* n_win) {
+    *n_win = 0;
+    if (int st = query_window_bound(ctx, reads, k, n_bound, n_bases)) return st;
+    if (reads->d_offsets) {
+        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *n_win = ctx->h_pinned[KMX_PIN_READ];
+        if (*n_win > *n_bound) return KMX_E_ARG;   // (more windows than bases: not this batch's window offsets)
+        return KMX_OK;
+    }
+    if (*n_bound == 0) return KMX_OK;   // no window
+    if (d_win_offsets) {   // (uniform reads in slots of the caller's: kmx_canonical_windows serves them, so they are served)
+        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->h_pinned[KMX_PIN_READ] != *n_bound) return KMX_E_ARG;
+    }
+    *n_win = *n_bound;
+    return KMX_OK;
+}
+
 // kmx_count_lookup_reads(2) = kmx_canonical_windows(2) followed by the lookup kernel.  The work buffer is laid out up front, as
 // count_impl lays its arrays out: [segment plan of long reads][two-word keys: canon 16 B/window][flags 1 B/window][directory, when
 // it pays and fits].  One-word keys: the windows call writes its canonical words into d_out and they are looked up in place.
@@ -932,23 +1014,8 @@ static int lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const kmx_read
     if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
     if (reads->n_reads == 0) return KMX_OK;
     DeviceGuard g(ctx->device);
-    // the windows the arrays are sized for and the windows there are
     uint64_t n_bound = 0, n_bases = 0, n_win = 0;
-    if (int st = query_window_bound(ctx, reads, k, &n_bound, &n_bases)) return st;
-    if (reads->d_offsets) {
-        KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        n_win = ctx->h_pinned[KMX_PIN_READ];
-        if (n_win > n_bound) return KMX_E_ARG;   // (more windows than bases: not this batch's window offsets)
-    } else {
-        if (n_bound == 0) return KMX_OK;   // no window
-        n_win = n_bound;
-        if (d_win_offsets) {   // (uniform reads in slots of the caller's: kmx_canonical_windows serves them, so they are served)
-            KMX_HIP(ctx, hipMemcpyAsync(ctx->h_pinned + KMX_PIN_READ, d_win_offsets + reads->n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->h_pinned[KMX_PIN_READ] != n_win) return KMX_E_ARG;
-        }
-    }
+    if (int st = caller_windows(ctx, reads, d_win_offsets, k, &n_bound, &n_bases, &n_win)) return st;
     if (n_win == 0) return KMX_OK;
     if (!d_out) return KMX_E_ARG;
     const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
@@ -973,6 +1040,121 @@ int kmx_count_lookup_reads(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t*
 int kmx_count_lookup_reads2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint64_t* d_kmers2,
                             const uint64_t* d_counts, uint64_t n, uint64_t* d_out) {
     return lookup_reads_impl(ctx, kQuery2, reads, d_win_offsets, k, d_kmers2, d_counts, n, d_out);
+}
+
+// ---- the counting sketch (kmx_sketch.hip) ----
+static const CountKind kSketchAdd1{"kmx_sketch_add", 1u, kmx_canonical_windows};
+static const CountKind kSketchAdd2{"kmx_sketch_add2", 2u, kmx_canonical_windows2};
+
+static int sketch_add_words_impl(kmx_ctx* ctx, uint32_t words, const uint64_t* d_words, const uint64_t* d_weights, uint64_t n, uint8_t* d_sketch,
+                                 uint32_t log2_blocks, uint64_t seed) {
+    if (!ctx || (n && !d_words) || n > (1ull << 40) || !sketch_ok(d_sketch, log2_blocks, n != 0)) return KMX_E_ARG;
+    if (words == 2u && !aligned16(d_words)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_sketch_add(words, d_words, d_weights, nullptr, n, d_sketch, log2_blocks, seed, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_sketch_add_words(kmx_ctx* ctx, const uint64_t* d_words, const uint64_t* d_weights, uint64_t n, uint8_t* d_sketch, uint32_t log2_blocks,
+                         uint64_t seed) {
+    return sketch_add_words_impl(ctx, 1u, d_words, d_weights, n, d_sketch, log2_blocks, seed);
+}
+
+int kmx_sketch_add_words2(kmx_ctx* ctx, const uint64_t* d_words2, const uint64_t* d_weights, uint64_t n, uint8_t* d_sketch, uint32_t log2_blocks,
+                          uint64_t seed) {
+    return sketch_add_words_impl(ctx, 2u, d_words2, d_weights, n, d_sketch, log2_blocks, seed);
+}
+
+// kmx_sketch_add(2) = the windows of the batch as the counter makes them (windows_front), then the add kernel over (canon, flags).
+static int sketch_add_impl(kmx_ctx* ctx, const CountKind& kind, uint32_t k_min, uint32_t k_max, const kmx_reads* reads, uint32_t k,
+                           uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed) {
+    if (!ctx || !reads_ok(reads) || !sketch_ok(d_sketch, log2_blocks, reads->n_reads != 0)) return KMX_E_ARG;
+    if (k < k_min || k > k_max) return KMX_E_K_RANGE;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    WindowsFront f;
+    if (int st = windows_front(ctx, reads, k, kind, nullptr, &f)) return st;
+    KMX_HIP(ctx, kmx::launch_sketch_add(kind.words, f.canon, nullptr, f.flags, f.n_win, d_sketch, log2_blocks, seed, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_sketch_add(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed) {
+    return sketch_add_impl(ctx, kSketchAdd1, 1u, 31u, reads, k, d_sketch, log2_blocks, seed);
+}
+
+int kmx_sketch_add2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed) {
+    return sketch_add_impl(ctx, kSketchAdd2, 33u, 64u, reads, k, d_sketch, log2_blocks, seed);
+}
+
+static int sketch_lookup_impl(kmx_ctx* ctx, uint32_t words, const uint64_t* d_words, uint64_t n, const uint8_t* d_sketch, uint32_t log2_blocks,
+                              uint64_t seed, uint8_t* d_est) {
+    if (!ctx || (n && (!d_words || !d_est)) || n > (1ull << 40) || !sketch_ok(d_sketch, log2_blocks, n != 0)) return KMX_E_ARG;
+    if (words == 2u && !aligned16(d_words)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_sketch_lookup(words, d_words, nullptr, n, d_sketch, log2_blocks, seed, d_est, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_sketch_lookup(kmx_ctx* ctx, const uint64_t* d_words, uint64_t n, const uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed,
+                      uint8_t* d_est) {
+    return sketch_lookup_impl(ctx, 1u, d_words, n, d_sketch, log2_blocks, seed, d_est);
+}
+
+int kmx_sketch_lookup2(kmx_ctx* ctx, const uint64_t* d_words2, uint64_t n, const uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed,
+                       uint8_t* d_est) {
+    return sketch_lookup_impl(ctx, 2u, d_words2, n, d_sketch, log2_blocks, seed, d_est);
+}
+
+// kmx_sketch_lookup_reads(2) = kmx_canonical_windows(2) into the work buffer -- [segment plan of long reads][canon 8 (16) B/window]
+// [flags 1 B/window] -- followed by the lookup kernel, in the caller's slot layout as kmx_count_lookup_reads(2).
+static int sketch_lookup_reads_impl(kmx_ctx* ctx, const QueryKind& kind, const char* who, const kmx_reads* reads, const uint64_t* d_win_offsets,
+                                    uint32_t k, const uint8_t* d_sketch, uint32_t log2_blocks, uint64_t seed, uint8_t* d_est) {
+    if (!ctx || !reads_ok(reads) || !sketch_ok(d_sketch, log2_blocks, reads->n_reads != 0)) return KMX_E_ARG;
+    if (k < kind.k_min || k > kind.k_max) return KMX_E_K_RANGE;
+    if (reads->d_offsets && !d_win_offsets) return KMX_E_ARG;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    uint64_t n_bound = 0, n_bases = 0, n_win = 0;
+    if (int st = caller_windows(ctx, reads, d_win_offsets, k, &n_bound, &n_bases, &n_win)) return st;
+    if (n_win == 0) return KMX_OK;
+    if (!d_est) return KMX_E_ARG;
+    const size_t plan = align256(count_plan_bytes(reads, k, n_bases));
+    const size_t canon_at = plan, flags_at = canon_at + align256(8u * kind.words * n_bound), bytes = flags_at + align256(n_bound);
+    void* buf = nullptr;
+    WorkHold hold;
+    if (int st = work_area(ctx, who, bytes, &buf, &hold)) return st;
+    uint64_t* canon = reinterpret_cast<uint64_t*>(hold.base + canon_at);
+    uint8_t* flags = reinterpret_cast<uint8_t*>(hold.base + flags_at);
+    if (int st = kind.windows(ctx, reads, d_win_offsets, k, nullptr, nullptr, canon, flags)) return st;
+    if (int st = work_kept(ctx, who, hold)) return st;
+    KMX_HIP(ctx, kmx::launch_sketch_lookup(kind.words, canon, flags, n_win, d_sketch, log2_blocks, seed, d_est, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_sketch_lookup_reads(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint8_t* d_sketch,
+                            uint32_t log2_blocks, uint64_t seed, uint8_t* d_est) {
+    return sketch_lookup_reads_impl(ctx, kQuery1, "kmx_sketch_lookup_reads", reads, d_win_offsets, k, d_sketch, log2_blocks, seed, d_est);
+}
+
+int kmx_sketch_lookup_reads2(kmx_ctx* ctx, const kmx_reads* reads, const uint64_t* d_win_offsets, uint32_t k, const uint8_t* d_sketch,
+                             uint32_t log2_blocks, uint64_t seed, uint8_t* d_est) {
+    return sketch_lookup_reads_impl(ctx, kQuery2, "kmx_sketch_lookup_reads2", reads, d_win_offsets, k, d_sketch, log2_blocks, seed, d_est);
+}
+
+int kmx_sketch_merge(kmx_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, uint32_t log2_blocks, uint8_t* d_out) {
+    if (!ctx || !sketch_ok(d_a, log2_blocks, true) || !sketch_ok(d_b, log2_blocks, true) || !sketch_ok(d_out, log2_blocks, true)) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_sketch_merge(d_a, d_b, log2_blocks, d_out, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_sketch_stats(kmx_ctx* ctx, const uint8_t* d_sketch, uint32_t log2_blocks, uint64_t* d_hist) {
+    if (!ctx || !sketch_ok(d_sketch, log2_blocks, true) || !d_hist) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_sketch_stats(d_sketch, log2_blocks, d_hist, ctx->n_cu, ctx->stream));
+    return KMX_OK;
 }
 
 // The front half the per-read calls share (kmx_count_read_stats(2), kmx_count_read_paths(2), kmx_count_correct_reads(2), kmx_count_read_colors(2)):

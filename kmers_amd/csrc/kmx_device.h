@@ -148,6 +148,16 @@ __device__ __forceinline__ u64 splitmix64(u64 x) {
     return x ^ (x >> 31);
 }
 
+// the murmur3 64-bit finaliser: the fingerprints of kmx_reads_dedup and the key hash of the sketch (kmx.h)
+__host__ __device__ __forceinline__ u64 fmix64(u64 x) {
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
 // BUILD-DEFINED bucket of a hash value (include/kmx.h, oracle kmo_bucket_of): the top log2_buckets bits of the 32-bit sum of the
 // two halves, each times its own odd constant.  One v_mul_lo_u32 and one multiply-add: the partition pass of the histogram
 // is bound by VALU issue, and the 64-bit Fibonacci product of round 1 (top bits of h * 0x9E3779B97F4A7C15) cost it 6

@@ -371,4 +371,15 @@ hipError_t launch_count_setop_emit(u32 words, u32 op, u32 rule, const u64* ka, c
                                    const void* area, u64* out_k, u64* out_c, hipStream_t st);
 hipError_t launch_count_compare(u32 words, const u64* ka, const u64* ca, u64 na, const u64* kb, const u64* cb, u64 nb, void* area,
                                 unsigned long long* h_pinned, u64* h_rec, hipStream_t st);
+// kmx_sketch.hip: the counting sketch (`words` u64 per key: 1 or 2; sketch: 64 << log2_blocks bytes, 64-byte aligned).  add: weights
+// may be nullptr (1 each); flags may be nullptr, otherwise a key counts where its flag has KMX_WIN_VALID.  lookup: est[i] = 0 where the
+// flag lacks it.  filter: clears KMX_WIN_VALID where the estimate is below min_est (1..255).  All asynchronous, no working set.
+hipError_t launch_sketch_add(u32 words, const u64* keys, const u64* weights, const uint8_t* flags, u64 n, uint8_t* sketch, u32 log2_blocks, u64 seed,
+                             int n_cu, hipStream_t st);
+hipError_t launch_sketch_lookup(u32 words, const u64* keys, const uint8_t* flags, u64 n, const uint8_t* sketch, u32 log2_blocks, u64 seed,
+                                uint8_t* est, int n_cu, hipStream_t st);
+hipError_t launch_sketch_filter(u32 words, const u64* keys, uint8_t* flags, u64 n, const uint8_t* sketch, u32 log2_blocks, u64 seed, u32 min_est,
+                                int n_cu, hipStream_t st);
+hipError_t launch_sketch_merge(const uint8_t* a, const uint8_t* b, u32 log2_blocks, uint8_t* out, int n_cu, hipStream_t st);
+hipError_t launch_sketch_stats(const uint8_t* sketch, u32 log2_blocks, u64* hist, int n_cu, hipStream_t st);
 }  // namespace kmx

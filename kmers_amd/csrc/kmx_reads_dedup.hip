@@ -30,16 +30,7 @@ namespace {
 constexpr u64 DD_G = 0x9E3779B97F4A7C15ull;
 constexpr u32 DD_OTHER = 1u, DD_AMBIGUOUS = 2u;   // the bits of an item's byte: F_b < F_a, F_a == F_b (both only under KMX_DD_STRAND)
 
-// the murmur3 64-bit finaliser
-__device__ __forceinline__ u64 fmix(u64 x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-__device__ __forceinline__ u64 pair_hash(u64 x, u64 y) { return fmix(fmix(x + DD_G) + y); }
+__device__ __forceinline__ u64 pair_hash(u64 x, u64 y) { return fmix64(fmix64(x + DD_G) + y); }
 
 // the codes of four bytes, one per byte: 0, 1, 2, 3 for A, C, G, T in either case, 4 for any other byte; comp: of the complement
 __device__ __forceinline__ u32 codes4(u32 w, bool comp) {
@@ -69,9 +60,9 @@ __device__ __forceinline__ u64 read_hash(const uint8_t* base, u32 L, bool rc, u3
         const u32 m = inside(q0, L);
         const u32 c = (codes_at(base, L, q0, rc) & m) | ((0xFu * ONES) & ~m);
         const u32 v = (c & 0xFu) | ((c >> 4) & 0xF0u) | ((c >> 8) & 0xF00u) | ((c >> 12) & 0xF000u);
-        sum += fmix((((u64)(q0 >> 2) << 16) | v) + DD_G);
+        sum += fmix64((((u64)(q0 >> 2) << 16) | v) + DD_G);
     }
-    return fmix(wave_sum(sum) ^ ((u64)L * DD_G));
+    return fmix64(wave_sum(sum) ^ ((u64)L * DD_G));
 }
 
 // x[0 .. Lx) and y[0 .. Ly), or with rc the reverse complement of y, are the same code sequence; every lane of the wave enters
