@@ -1252,6 +1252,61 @@ pub fn fastx_parse_names(ctx: &HipContext, d_text: &DeviceBuf<'_>, n_bytes: u64,
     Ok((n_names, n_out))
 }
 
+/// What `bgzf_index` found: blocks, bytes of text, bytes behind the last complete block (0 for a sound file), and whether the last
+/// block is the 28-byte EOF marker.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct BgzfInfo {
+    pub n_blocks: u64,
+    pub n_text_bytes: u64,
+    pub trailing: u64,
+    pub has_eof: bool,
+}
+
+/// The block index of a BGZF image on the device (`kmx_bgzf_index`; include/kmx.h has the header a block begins with): `out = None`
+/// counts only; otherwise `out.0` gets the `n_blocks + 1` block offsets and `out.1` the exclusive prefix sum of the blocks' ISIZE
+/// words, both with room for `max_blocks + 1` words.  The chain is followed exactly from byte 0.  Err(KMX_E_NOMEM) above
+/// `max_blocks`, with nothing written; Err(KMX_E_ARG) for an image that does not begin with a BGZF header (plain gzip, plain text).
+/// Synchronous.
+pub fn bgzf_index(ctx: &HipContext, d_file: &DeviceBuf<'_>, n_bytes: u64, out: Option<(&DeviceBuf<'_>, &DeviceBuf<'_>)>, max_blocks: u64)
+                  -> Result<BgzfInfo, KmxError> {
+    assert!(n_bytes as u128 <= d_file.len() as u128, "image shorter than n_bytes");
+    let (dbo, dto) = match out {
+        None => (ptr::null_mut(), ptr::null_mut()),
+        Some((b, t)) => {
+            assert!((max_blocks as u128 + 1) * 8 <= b.len() as u128 && (max_blocks as u128 + 1) * 8 <= t.len() as u128, "offsets shorter than max_blocks + 1");
+            (b.as_mut_ptr::<u64>(), t.as_mut_ptr::<u64>())
+        }
+    };
+    let mut info = [0u64; 4];
+    ctx.ck(unsafe { kmx_bgzf_index(ctx.0, d_file.as_ptr::<u8>(), n_bytes, dbo, dto, max_blocks, info.as_mut_ptr()) })?;
+    Ok(BgzfInfo { n_blocks: info[0], n_text_bytes: info[1], trailing: info[2], has_eof: info[3] != 0 })
+}
+
+/// The blocks of a BGZF image inflated on the device (`kmx_bgzf_inflate`): block b goes to `d_text` + (text_offsets[b] -
+/// text_offsets[0]); `first_block` advances both offset arrays, so blocks `first_block..first_block + n_blocks` go into a buffer of
+/// their own size.  `d_text`: 16-byte aligned (as `alloc` gives it), `text_capacity` bytes.  `flags`: `KMX_BGZF_NO_CRC` skips the CRC-32
+/// comparison.  `d_status`: `n_blocks` u32, 0 or the `KMX_BGZF_ST_*` reason.  Returns the lowest block that is not sound (`u64::MAX`:
+/// none) beside the status of the call: Err(KMX_E_ARG) with a bad block, its sound neighbours written in full all the same.
+/// Synchronous.
+pub fn bgzf_inflate(ctx: &HipContext, d_file: &DeviceBuf<'_>, n_bytes: u64, d_block_offsets: &DeviceBuf<'_>, d_text_offsets: &DeviceBuf<'_>,
+                    first_block: u64, n_blocks: u64, flags: u32, d_text: &DeviceBuf<'_>, text_capacity: u64, d_status: Option<&DeviceBuf<'_>>)
+                    -> (Result<(), KmxError>, u64) {
+    assert!(n_bytes as u128 <= d_file.len() as u128, "image shorter than n_bytes");
+    assert!(text_capacity as u128 <= d_text.len() as u128, "text shorter than text_capacity");
+    let words = (first_block as u128 + n_blocks as u128 + 1) * 8;
+    assert!(words <= d_block_offsets.len() as u128 && words <= d_text_offsets.len() as u128, "offsets shorter than first_block + n_blocks + 1");
+    let ds = d_status.map_or(ptr::null_mut(), |s| {
+        assert!(n_blocks as u128 * 4 <= s.len() as u128, "status shorter than n_blocks");
+        s.as_mut_ptr::<u32>()
+    });
+    let mut bad = u64::MAX;
+    let st = ctx.ck(unsafe {
+        kmx_bgzf_inflate(ctx.0, d_file.as_ptr::<u8>(), n_bytes, d_block_offsets.as_ptr::<u64>().add(first_block as usize),
+                         d_text_offsets.as_ptr::<u64>().add(first_block as usize), n_blocks, flags, d_text.as_mut_ptr::<u8>(), text_capacity, ds, &mut bad)
+    });
+    (st, bad)
+}
+
 /// What `fastx_format` lays out beside the bases: the names (a ragged batch of `n_reads` names and its `n_reads + 1` offsets, taken
 /// from byte `name_skip` on; `None`: record r is named `name_base + r` in decimal), the quality bytes (laid out as the bases are;
 /// `None`: every quality byte is `qual_fill`), and the bases per FASTA line (0: one line; must be 0 for FASTQ).

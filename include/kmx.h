@@ -1541,6 +1541,56 @@ int kmx_fastx_format(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *d_qual
                      uint64_t name_base, uint32_t format, uint32_t line_width, uint32_t qual_fill, uint8_t *d_text,
                      uint64_t *d_rec_offsets, uint64_t max_bytes, uint64_t *h_n_bytes);
 
+/* ---------------------------------------------------------------- BGZF-compressed images (kmx_bgzf.hip) ----
+ * BUILD-DEFINED.  A .fastq.gz written by bgzip / htslib / samtools is BGZF: a chain of independent gzip members ("blocks") of at most
+ * 64 KiB, each one DEFLATE stream with its own CRC-32 and length.  The two calls here turn such an image in device memory into the
+ * text kmx_fastx_parse takes.  A block header is the 18 bytes htslib writes: 1f 8b 08 04, six ignored bytes, XLEN = 6, 'B' 'C' 02 00,
+ * BSIZE; the block's size is BSIZE + 1, at least 28, inside the file; its last eight bytes are CRC-32 and ISIZE.  Plain single-member
+ * gzip, and headers with further extra subfields, are NOT taken: there is nothing to split them at.
+ *
+ * kmx_bgzf_index.  d_file: the image, any alignment.  The chain of blocks is followed exactly from byte 0 (a header pattern inside
+ * compressed or stored data is not a block): d_block_offsets[b] = first byte of block b, d_block_offsets[n_blocks] = the end of the
+ * last complete block; d_text_offsets = the exclusive prefix sum of the blocks' ISIZE words (n_blocks + 1 words); both arrays hold
+ * max_blocks + 1 words.  h_info (host, four words): n_blocks, n_text_bytes, the bytes behind the last complete block (0 for a sound
+ * file), 1 if the last block is the 28-byte EOF marker.  Empty blocks (ISIZE 0) are blocks wherever they stand.  A chain that comes
+ * to a byte which is no header, or to a block that would pass the end of the file, ends there.  With both arrays NULL only h_info is
+ * written; with n_blocks > max_blocks: KMX_E_NOMEM, nothing written to the device, h_info set (the convention of kmx_fastx_parse).  A
+ * file that does not begin with the 18-byte header pattern (plain gzip, plain text, fewer than 18 bytes): KMX_E_ARG; n_bytes == 0: no
+ * blocks.  Working set in the work buffer: 4 bytes per KiB of file and 24 bytes per header pattern found; above the cap KMX_E_NOMEM.
+ * Synchronous.
+ *
+ * kmx_bgzf_inflate.  Block b of d_block_offsets / d_text_offsets (n_blocks + 1 device words each, as the index wrote them, or
+ * both advanced by i to inflate blocks i.. alone) is written at d_text + (d_text_offsets[b] - d_text_offsets[0]).  d_text: 16-byte
+ * aligned, text_capacity bytes; the span d_text_offsets[n_blocks] - d_text_offsets[0] is read back first and a larger one is
+ * KMX_E_NOMEM with nothing written.  d_status (device, n_blocks u32, optional): 0 or the KMX_BGZF_ST_* reason of block b;
+ * *h_first_bad (host, optional) = the lowest block with a non-zero status, or ~0; a bad block makes the call return KMX_E_ARG, with
+ * the sound blocks written in full and nothing written outside a bad block's own output range.  A block is sound iff its header
+ * is the one above with BSIZE + 1 == d_block_offsets[b+1] - d_block_offsets[b]; its DEFLATE stream decodes under zlib's rules and
+ * reaches the end-of-block of a final block inside the payload (whole unused bytes behind it are tolerated, as zlib tolerates them);
+ * it produced exactly ISIZE == d_text_offsets[b+1] - d_text_offsets[b] bytes; and -- unless flags holds KMX_BGZF_NO_CRC -- their
+ * CRC-32 is the footer's.  No byte outside [d_block_offsets[b], d_block_offsets[b+1]) and [0, n_bytes) is read for block b.
+ * Deterministic.  Synchronous.  Uses the work buffer when d_status is NULL. */
+#define KMX_BGZF_NO_CRC 1
+#define KMX_BGZF_ST_HEADER 1   /* not the 18-byte header, or BSIZE + 1 is not the distance to the next offset, or the offsets are unsound */
+#define KMX_BGZF_ST_BTYPE 2    /* block type 3 */
+#define KMX_BGZF_ST_STORED 3   /* stored block: LEN != ~NLEN, or longer than the input or the room */
+#define KMX_BGZF_ST_COUNTS 4   /* HLIT above 286 or HDIST above 30 */
+#define KMX_BGZF_ST_REPEAT 5   /* repeat code with no previous length, or running past HLIT + HDIST */
+#define KMX_BGZF_ST_NO_EOB 6   /* no code for symbol 256 */
+#define KMX_BGZF_ST_CODESET 7  /* a code-length set over-subscribed or incomplete (zlib's inflate_table rule) */
+#define KMX_BGZF_ST_BADCODE 8  /* a bit pattern that is no code */
+#define KMX_BGZF_ST_SYMBOL 9   /* length symbol 286 / 287 or distance symbol 30 / 31 */
+#define KMX_BGZF_ST_DISTANCE 10 /* a distance larger than the bytes the block has produced */
+#define KMX_BGZF_ST_OUTPUT 11  /* output passing ISIZE */
+#define KMX_BGZF_ST_INPUT 12   /* input running out */
+#define KMX_BGZF_ST_LENGTH 13  /* produced bytes != ISIZE, or ISIZE != d_text_offsets[b+1] - d_text_offsets[b] */
+#define KMX_BGZF_ST_CRC 14     /* CRC-32 differs from the footer's */
+int kmx_bgzf_index(kmx_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, uint64_t *d_block_offsets, uint64_t *d_text_offsets,
+                   uint64_t max_blocks, uint64_t *h_info);
+int kmx_bgzf_inflate(kmx_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const uint64_t *d_block_offsets,
+                     const uint64_t *d_text_offsets, uint64_t n_blocks, uint32_t flags, uint8_t *d_text, uint64_t text_capacity,
+                     uint32_t *d_status, uint64_t *h_first_bad);
+
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,
  * canonical_kmer_iterator.rs:72-83), so the scans need no collective.  What is exchanged is the optional bucket

@@ -376,6 +376,30 @@ inline kmx_summary canonical_reduce(Context& ctx, const kmx_reads& reads, uint32
     return out.download()[0];
 }
 
+// A BGZF file image (.fastq.gz as bgzip / htslib write it; kmx.h, "BGZF-compressed images") -> its text: the compressed bytes go to
+// the device, the blocks are indexed and inflated there (CRC-32 checked unless verify is false), one copy brings the text back.
+// Throws for an image that is not BGZF (plain gzip has no blocks to inflate in parallel: bgzip writes the form that has), for bytes
+// behind the last complete block, and for a block that is not sound (the message names it).
+inline std::string bgzf_inflate(Context& ctx, const std::string& image, bool verify = true) {
+    DeviceBuffer<uint8_t> d(ctx, image.size() ? image.size() : 1);
+    if (!image.empty()) d.upload(reinterpret_cast<const uint8_t*>(image.data()), image.size());
+    uint64_t info[4] = {0, 0, 0, 0};
+    ctx.check(kmx_bgzf_index(ctx.get(), d.data(), image.size(), nullptr, nullptr, 0, info), "bgzf_index (count)");
+    if (info[2] != 0) throw std::runtime_error("bgzf_inflate: " + std::to_string(info[2]) + " bytes behind the last complete block: a truncated file");
+    const uint64_t nb = info[0], nt = info[1];
+    DeviceBuffer<uint64_t> bo(ctx, nb + 1), to(ctx, nb + 1);
+    ctx.check(kmx_bgzf_index(ctx.get(), d.data(), image.size(), bo.data(), to.data(), nb, info), "bgzf_index");
+    DeviceBuffer<uint8_t> text(ctx, nt ? nt : 1);
+    uint64_t bad = ~0ull;
+    const int st = kmx_bgzf_inflate(ctx.get(), d.data(), image.size(), bo.data(), to.data(), nb, verify ? 0u : (uint32_t)KMX_BGZF_NO_CRC, text.data(), nt,
+                                    nullptr, &bad);
+    if (st == KMX_E_ARG && bad != ~0ull) throw std::runtime_error("bgzf_inflate: block " + std::to_string(bad) + " is not sound");
+    ctx.check(st, "bgzf_inflate");
+    auto bytes = text.download();
+    return std::string(bytes.begin(), bytes.begin() + nt);
+}
+struct Bgzf {};   // FastqReads(Bgzf{}, image): the image is BGZF-compressed
+
 // FASTA / FASTQ ingestion (build-defined, the reference has no parser): a file image -> the reads
 // back to back on the device + their offsets, i.e. the ragged `kmx_reads` the calls above take.
 class FastxReads {
@@ -463,6 +487,8 @@ class FastqReads {
                                         &nnb),
                   "fastx_parse_names");
     }
+    // ... from a BGZF image (a .fastq.gz): inflated on the device first
+    FastqReads(Bgzf, const std::string& image, Context& ctx = Context::instance()) : FastqReads(bgzf_inflate(ctx, image), ctx) {}
     const FastxReads& reads() const { return reads_; }
     // the record names as a ragged batch of their own (what kmx_reads_gather reorders and kmx_fastx_format takes)
     kmx_reads names() const { return kmx_reads{names_->data(), reads_.len(), 0u, noff_->data()}; }

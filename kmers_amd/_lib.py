@@ -217,6 +217,8 @@ SIGNATURES = {
     "kmx_fastx_parse": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_fastx_parse_quals": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_fastx_parse_names": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kmx_bgzf_index": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "kmx_bgzf_inflate": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u64, _vp, C.POINTER(C.c_uint64)]),
     "kmx_fastx_format": (_int, [_vp, C.POINTER(Reads), _vp, C.POINTER(Reads), _u32, _u64, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_reads_quality": (_int, [_vp, _RP, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "kmx_reads_adapter": (_int, [_vp, _RP, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
@@ -243,6 +245,17 @@ SIGNATURES = {
 
 FASTX_AUTO, FASTX_FASTQ, FASTX_FASTA = 0, 1, 2
 FASTX_SAME_TEXT = 0x100   # or-ed into the format of the emit call that follows the counting call on the same image
+
+BGZF_NO_CRC = 1   # kmx_bgzf_inflate flags: the CRC-32 of the blocks is not compared
+# KMX_BGZF_ST_*: why a block is not sound (d_status of kmx_bgzf_inflate)
+BGZF_ST_HEADER, BGZF_ST_BTYPE, BGZF_ST_STORED, BGZF_ST_COUNTS, BGZF_ST_REPEAT, BGZF_ST_NO_EOB, BGZF_ST_CODESET, BGZF_ST_BADCODE, BGZF_ST_SYMBOL, \
+    BGZF_ST_DISTANCE, BGZF_ST_OUTPUT, BGZF_ST_INPUT, BGZF_ST_LENGTH, BGZF_ST_CRC = range(1, 15)
+BGZF_ST_NAMES = {0: "sound", BGZF_ST_HEADER: "block header", BGZF_ST_BTYPE: "DEFLATE block type 3", BGZF_ST_STORED: "stored block length",
+                 BGZF_ST_COUNTS: "HLIT / HDIST out of range", BGZF_ST_REPEAT: "code-length repeat", BGZF_ST_NO_EOB: "no end-of-block code",
+                 BGZF_ST_CODESET: "code-length set over-subscribed or incomplete", BGZF_ST_BADCODE: "bit pattern that is no code",
+                 BGZF_ST_SYMBOL: "invalid length or distance symbol", BGZF_ST_DISTANCE: "distance too far back",
+                 BGZF_ST_OUTPUT: "output passes ISIZE", BGZF_ST_INPUT: "input runs out", BGZF_ST_LENGTH: "length differs from ISIZE",
+                 BGZF_ST_CRC: "CRC-32 mismatch"}
 
 _LIB = None
 

@@ -615,6 +615,45 @@ class Sketch:
         return 1.0 - int(hist[0].item()) / int(self.cells.numel())
 
 
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # the empty block every BGZF file ends with
+
+
+def bgzf_compress(data, level: int = 6, block_bytes: int = 65280) -> bytes:
+    """bytes -> a BGZF file image (host zlib): one raw-DEFLATE gzip member per `block_bytes` of data (65280, what htslib takes, keeps
+    every block within 64 KiB at any level), each with the 18-byte 'BC' header, CRC-32 and ISIZE, and the 28-byte EOF marker behind
+    them.  What bgzip writes; Context.load_fastx / bgzf_inflate take it back."""
+    import zlib
+
+    data = memoryview(bytes(data) if not isinstance(data, (bytes, bytearray, memoryview)) else data).cast("B")
+    if not 1 <= block_bytes <= 65280:
+        raise ValueError("bgzf_compress: block_bytes in 1..65280")
+    out = []
+    for i in range(0, len(data), block_bytes):
+        piece = data[i:i + block_bytes]
+        co = zlib.compressobj(level, zlib.DEFLATED, -15, 9)
+        payload = co.compress(piece) + co.flush()
+        size = len(payload) + 26
+        if size > 65536:
+            raise ValueError("bgzf_compress: a block does not fit 64 KiB")
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + (size - 1).to_bytes(2, "little") + payload +
+                   zlib.crc32(piece).to_bytes(4, "little") + len(piece).to_bytes(4, "little"))
+    out.append(BGZF_EOF)
+    return b"".join(out)
+
+
+@dataclasses.dataclass
+class BgzfIndex:
+    """kmx_bgzf_index: block b of the image is bytes [block_offsets[b], block_offsets[b+1]) and inflates to bytes
+    [text_offsets[b], text_offsets[b+1]) of the text (int64 device tensors of n_blocks + 1 words); trailing: bytes behind the last
+    complete block (0 for a sound file); has_eof: the last block is the 28-byte EOF marker."""
+    block_offsets: torch.Tensor
+    text_offsets: torch.Tensor
+    n_blocks: int
+    n_text_bytes: int
+    trailing: int
+    has_eof: bool
+
+
 def _on_ctx_stream(fn):
     """Run a Context method with Context.stream as torch's current stream (see "Stream discipline" above)."""
     @functools.wraps(fn)
@@ -2035,6 +2074,67 @@ class Context:
             raise ValueError(f"fastq_records: {int(noffsets.numel()) - 1} names for {n} reads (the image ends inside a record)")
         return bases, quals, n, read_len, offsets, names, noffsets
 
+    # ------------------------------------------------------------ BGZF-compressed images
+    @_on_ctx_stream
+    def bgzf_index(self, image: torch.Tensor) -> BgzfIndex:
+        """kmx_bgzf_index: a BGZF file image (uint8, on the device) -> BgzfIndex.  Two calls: the counts, then the arrays.  KmxError
+        (KMX_E_ARG) for an image that does not begin with a BGZF block header (plain gzip, plain text)."""
+        n = int(image.numel())
+        info = (C.c_uint64 * 4)()
+        ip = _ptr(image) if n else None
+        self._ck(self.lib.kmx_bgzf_index(self._h, ip, n, None, None, 0, info))
+        nb = int(info[0])
+        bo = self.empty(nb + 1, torch.int64)
+        to = self.empty(nb + 1, torch.int64)
+        self._ck(self.lib.kmx_bgzf_index(self._h, ip, n, _ptr(bo), _ptr(to), nb, info))
+        return BgzfIndex(bo, to, nb, int(info[1]), int(info[2]), bool(info[3]))
+
+    @_on_ctx_stream
+    def bgzf_inflate(self, image: torch.Tensor, index: "BgzfIndex | None" = None, verify: bool = True, blocks=None) -> torch.Tensor:
+        """kmx_bgzf_inflate: a BGZF file image (uint8, on the device) -> its text, a uint8 device tensor (16-byte aligned: fastx_parse
+        takes it as it is).  index: what bgzf_index returned for the image (None: made here).  verify=False skips the CRC-32
+        comparison.  blocks=(i, j): blocks i..j-1 alone.  ValueError naming the first block that is not sound, and why.  Bytes
+        behind the last complete block (index.trailing) are the caller's to judge: load_fastx refuses such a file."""
+        if index is None:
+            index = self.bgzf_index(image)
+        i, j = (0, index.n_blocks) if blocks is None else (int(blocks[0]), int(blocks[1]))
+        if not 0 <= i <= j <= index.n_blocks:
+            raise ValueError("bgzf_inflate: blocks (i, j) with 0 <= i <= j <= n_blocks")
+        if i == j:
+            return self.empty(0, torch.uint8)
+        span = int(index.text_offsets[j].item()) - int(index.text_offsets[i].item()) if blocks is not None else index.n_text_bytes
+        text = self.empty(max(span, 1), torch.uint8)
+        status = torch.zeros(j - i, dtype=torch.int32, device=self.device)
+        bad = C.c_uint64(2**64 - 1)
+        st = self.lib.kmx_bgzf_inflate(self._h, _ptr(image), int(image.numel()), _ptr(index.block_offsets[i:]), _ptr(index.text_offsets[i:]), j - i,
+                                       0 if verify else _lib.BGZF_NO_CRC, _ptr(text), span, _ptr(status), C.byref(bad))
+        if st == _lib.E_ARG and bad.value != 2**64 - 1:
+            why = int(status[bad.value].item())
+            raise ValueError(f"bgzf_inflate: block {i + bad.value} is not sound: {_lib.BGZF_ST_NAMES.get(why, why)} (KMX_BGZF_ST {why})")
+        self._ck(st)
+        return text[:span]
+
+    def load_fastx(self, source) -> torch.Tensor:
+        """A FASTA / FASTQ file -- a path, or its bytes -- -> its text on the device.  A BGZF image (.fastq.gz as bgzip, htslib and
+        samtools write it) is copied compressed and inflated on the device; plain text is copied.  Plain single-member gzip raises
+        ValueError: it has no blocks to inflate in parallel.  ctx.fastq_records(ctx.load_fastx(path)) is the whole ingest."""
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            data = bytes(source)
+        else:
+            with open(source, "rb") as f:
+                data = f.read()
+        if data[:2] != b"\x1f\x8b":
+            return self.to_device(data) if data else self.empty(0, torch.uint8)
+        if not (len(data) >= 18 and data[2:4] == b"\x08\x04" and data[10:16] == b"\x06\0BC\x02\0"):
+            raise ValueError("load_fastx: a gzip file that is not BGZF: one DEFLATE stream cannot be inflated in parallel; "
+                             "recompress it with bgzip (`gunzip -c f.gz | bgzip > f.bgz.gz`), which writes the blocked form that can")
+        image = self.to_device(data)
+        index = self.bgzf_index(image)
+        if index.trailing:
+            raise ValueError(f"load_fastx: {index.trailing} bytes behind the last complete BGZF block (block {index.n_blocks}): a truncated or "
+                             "damaged file")
+        return self.bgzf_inflate(image, index)
+
     @_on_ctx_stream
     def fastx_format(self, bases, n_reads, read_len, offsets=None, quals=None, names=None, name_offsets=None, name_skip=1, name_base=0,
                      fmt=_lib.FASTX_FASTQ, line_width=0, qual_fill=ord("I"), rec_offsets=False):
@@ -2060,10 +2160,12 @@ class Context:
             self._ck(self.lib.kmx_fastx_format(*args, _ptr(out), _ptr(off), nb.value, C.byref(nb)))
         return (out[:nb.value], off) if rec_offsets else out[:nb.value]
 
-    def write_fastx(self, file, bases, n_reads, read_len, **kw):
+    def write_fastx(self, file, bases, n_reads, read_len, bgzf_level=None, **kw):
         """fastx_format(bases, n_reads, read_len, **kw), one device-to-host copy, one write -> the bytes written.  `file`: a path
-        or a binary file object."""
+        or a binary file object.  bgzf_level (0..9; None: plain text): the image goes through bgzf_compress (host zlib) first."""
         image = self.fastx_format(bases, n_reads, read_len, **{**kw, "rec_offsets": False}).cpu().numpy()
+        if bgzf_level is not None:
+            image = np.frombuffer(bgzf_compress(memoryview(image), int(bgzf_level)), dtype=np.uint8)
         if isinstance(file, (str, bytes)) or hasattr(file, "__fspath__"):
             with open(file, "wb") as f:
                 f.write(memoryview(image))

@@ -2585,6 +2585,120 @@ int kmx_fastx_parse_names(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes,
     return fastx_lines_wait(ctx, kFastxNames, d_text, n_bytes, format, d_names, d_noffsets, max_reads, h_n_names, h_n_bytes);
 }
 
+// ---- BGZF-compressed images (kmx_bgzf.hip) ----
+int kmx_bgzf_index(kmx_ctx* ctx, const uint8_t* d_file, uint64_t n_bytes, uint64_t* d_block_offsets, uint64_t* d_text_offsets, uint64_t max_blocks,
+                   uint64_t* h_info) {
+    const char* who = "kmx_bgzf_index";
+    if (!ctx || !h_info || (n_bytes && !d_file) || (!d_block_offsets != !d_text_offsets)) return KMX_E_ARG;
+    h_info[0] = h_info[1] = h_info[3] = 0;
+    h_info[2] = n_bytes;
+    DeviceGuard g(ctx->device);
+    uint64_t n_blocks = 0, n_text = 0, end = 0, last_start = 0;
+    uint32_t n_cand = 0;
+    void* area = nullptr;
+    if (n_bytes) {
+        uint8_t head[18] = {0};
+        if (n_bytes >= sizeof head) {
+            KMX_HIP(ctx, hipMemcpyAsync(head, d_file, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        static const uint8_t kAt[10] = {0, 1, 2, 3, 10, 11, 12, 13, 14, 15}, kIs[10] = {0x1f, 0x8b, 8, 4, 6, 0, 'B', 'C', 2, 0};
+        bool is = n_bytes >= sizeof head;
+        for (int i = 0; i < 10; ++i) is = is && head[kAt[i]] == kIs[i];
+        if (!is) {
+            std::snprintf(ctx->last_error, sizeof ctx->last_error,
+                          "%s: the image does not begin with a BGZF block header (plain gzip and plain text are not BGZF; bgzip writes it)", who);
+            return KMX_E_ARG;
+        }
+        // the counting pass in the small front of the layout, then -- the candidates known -- the whole; a buffer that moved in between
+        // has lost the counts
+        WorkHold first;
+        if (int st = work_area(ctx, who, kmx::bgzf_index_units_bytes(n_bytes), &area, &first)) return st;
+        unsigned long long cand = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            KMX_HIP(ctx, kmx::launch_bgzf_count_candidates(d_file, n_bytes, area, ctx->n_cu, ctx->stream));
+            KMX_HIP(ctx, hipMemcpyAsync(&cand, static_cast<unsigned long long*>(area) + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (pass == 1) break;
+            if (cand >= 0xFFFFFFF0ull) {
+                std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: %llu header patterns in the image", who, cand);
+                return KMX_E_NOMEM;
+            }
+            WorkHold whole;
+            if (int st = work_area(ctx, who, kmx::bgzf_index_scratch_bytes(n_bytes, cand), &area, &whole)) return st;
+            if (whole.base == first.base && whole.allocs == first.allocs) break;
+        }
+        n_cand = (uint32_t)cand;
+        if (n_cand) {
+            unsigned long long stats[6] = {0, 0, 0, 0, 0, 0};
+            KMX_HIP(ctx, kmx::launch_bgzf_chain(d_file, n_bytes, area, n_cand, ctx->n_cu, ctx->stream));
+            KMX_HIP(ctx, hipMemcpyAsync(stats, area, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            n_text = stats[0];
+            end = stats[1];
+            n_blocks = stats[3];
+            last_start = stats[5];
+        }
+        if (n_blocks && end >= 28u) {
+            static const uint8_t kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            uint8_t tail[28];
+            KMX_HIP(ctx, hipMemcpyAsync(tail, d_file + end - 28u, sizeof tail, hipMemcpyDeviceToHost, ctx->stream));
+            KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            h_info[3] = end - last_start == 28u && std::memcmp(tail, kEof, sizeof tail) == 0 ? 1u : 0u;
+        }
+    }
+    h_info[0] = n_blocks;
+    h_info[1] = n_text;
+    h_info[2] = n_bytes - end;
+    if (!d_block_offsets) return KMX_OK;
+    if (int st = room_for(ctx, who, n_blocks, "blocks", max_blocks)) return st;
+    if (n_blocks == 0) {
+        KMX_HIP(ctx, hipMemsetAsync(d_block_offsets, 0, 8, ctx->stream));
+        KMX_HIP(ctx, hipMemsetAsync(d_text_offsets, 0, 8, ctx->stream));
+    } else {
+        KMX_HIP(ctx, kmx::launch_bgzf_write_index(d_file, n_bytes, area, n_cand, n_blocks, end, d_block_offsets, d_text_offsets, ctx->n_cu, ctx->stream));
+    }
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_bgzf_inflate(kmx_ctx* ctx, const uint8_t* d_file, uint64_t n_bytes, const uint64_t* d_block_offsets, const uint64_t* d_text_offsets,
+                     uint64_t n_blocks, uint32_t flags, uint8_t* d_text, uint64_t text_capacity, uint32_t* d_status, uint64_t* h_first_bad) {
+    const char* who = "kmx_bgzf_inflate";
+    if (!ctx || (flags & ~(uint32_t)KMX_BGZF_NO_CRC) || (n_blocks && (!d_file || !d_block_offsets || !d_text_offsets)) || !aligned16(d_text) ||
+        n_blocks > (1ull << 32))
+        return KMX_E_ARG;
+    if (h_first_bad) *h_first_bad = ~0ull;
+    if (n_blocks == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    uint64_t t0 = 0, t1 = 0;
+    KMX_HIP(ctx, hipMemcpyAsync(&t0, d_text_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipMemcpyAsync(&t1, d_text_offsets + n_blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (t1 < t0) return KMX_E_ARG;
+    const uint64_t span = t1 - t0;
+    if (int st = room_for(ctx, who, span, "bytes of text", text_capacity)) return st;
+    if (span && !d_text) return KMX_E_ARG;
+    uint32_t* status = d_status;
+    if (!status) {
+        void* area = nullptr;
+        if (int st = work_area(ctx, who, (size_t)n_blocks * 4u, &area)) return st;
+        status = static_cast<uint32_t*>(area);
+    }
+    KMX_HIP(ctx, first_bad_reset(ctx));
+    KMX_HIP(ctx, kmx::launch_bgzf_inflate(d_file, n_bytes, d_block_offsets, d_text_offsets, n_blocks, span, d_text, status, first_bad_of(ctx),
+                                          (flags & KMX_BGZF_NO_CRC) == 0u, ctx->stream));
+    if (int st = first_bad_read(ctx, ctx->h_pinned + KMX_PIN_READ)) return st;
+    const unsigned long long bad = ctx->h_pinned[KMX_PIN_READ];
+    if (h_first_bad) *h_first_bad = bad;
+    if (bad == ~0ull) return KMX_OK;
+    uint32_t why = 0;
+    KMX_HIP(ctx, hipMemcpyAsync(&why, status + bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::snprintf(ctx->last_error, sizeof ctx->last_error, "%s: block %llu is not sound (KMX_BGZF_ST_* reason %u)", who, bad, why);
+    return KMX_E_ARG;
+}
+
 // ---- a batch laid out as a FASTQ / FASTA image (kmx_fastx_format.hip) ----
 int kmx_fastx_format(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_quals, const kmx_reads* names, uint32_t name_skip, uint64_t name_base,
                      uint32_t format, uint32_t line_width, uint32_t qual_fill, uint8_t* d_text, uint64_t* d_rec_offsets, uint64_t max_bytes,

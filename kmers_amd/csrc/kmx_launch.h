@@ -382,4 +382,15 @@ hipError_t launch_sketch_filter(u32 words, const u64* keys, uint8_t* flags, u64 
                                 int n_cu, hipStream_t st);
 hipError_t launch_sketch_merge(const uint8_t* a, const uint8_t* b, u32 log2_blocks, uint8_t* out, int n_cu, hipStream_t st);
 hipError_t launch_sketch_stats(const uint8_t* sketch, u32 log2_blocks, u64* hist, int n_cu, hipStream_t st);
+// kmx_bgzf.hip: the block index of a BGZF image and its inflation.  The index's working set: `units` bytes for the counting pass, the
+// whole once the number of candidates (header patterns) is known.  Its first words (`stats`) after count_candidates: [2] = candidates;
+// after chain: [0] = text bytes, [1] = end of the last block, [3] = blocks, [5] = start of the last block.  All asynchronous.
+size_t bgzf_index_units_bytes(u64 n_bytes);
+size_t bgzf_index_scratch_bytes(u64 n_bytes, u64 n_candidates);
+hipError_t launch_bgzf_count_candidates(const uint8_t* file, u64 n_bytes, void* scratch, int n_cu, hipStream_t st);
+hipError_t launch_bgzf_chain(const uint8_t* file, u64 n_bytes, void* scratch, u32 n_candidates, int n_cu, hipStream_t st);
+hipError_t launch_bgzf_write_index(const uint8_t* file, u64 n_bytes, void* scratch, u32 n_candidates, u64 n_blocks, u64 end, u64* block_offsets,
+                                   u64* text_offsets, int n_cu, hipStream_t st);
+hipError_t launch_bgzf_inflate(const uint8_t* file, u64 n_bytes, const u64* block_offsets, const u64* text_offsets, u64 n_blocks, u64 span, uint8_t* text,
+                               u32* status, unsigned long long* first_bad, bool check_crc, hipStream_t st);
 }  // namespace kmx
