@@ -1939,8 +1939,13 @@ class Context:
         mw, mp = self.empty(tot, torch.int64), self.empty(tot, torch.int32)
         r = self._reads(bases, n_reads, read_len, offsets)
         bad = C.c_uint64(0)
-        self._ck(self.lib.kmx_minimizers(self._h, C.byref(r), _ptr(win_offsets) if win_offsets is not None else None, k, w, hasher, hasher_k,
-                                         _ptr(mw) if tot else None, _ptr(mp) if tot else None, C.byref(bad) if check else None))
+        st = self.lib.kmx_minimizers(self._h, C.byref(r), _ptr(win_offsets) if win_offsets is not None else None, k, w, hasher, hasher_k,
+                                     _ptr(mw) if tot else None, _ptr(mp) if tot else None, C.byref(bad) if check else None)
+        if st == _lib.E_INVALID_BASE:
+            e = KmxError(st, f"invalid base in read {bad.value}")
+            e.first_bad = bad.value
+            raise e
+        self._ck(st)
         return mw, mp
 
     # ---- minimizers under std's DefaultHasher (keys 0, 0) / RandomState (its keys): SipHash-1-3 of each l-mer

@@ -112,7 +112,7 @@ hipError_t launch_calib_stream_read(const uint8_t* buf, u64 nbytes, unsigned lon
 hipError_t launch_length_range(const u64* offsets, u64 n_reads, u32* out, int n_cu, hipStream_t st);
 hipError_t launch_offsets_uniform_gate(const u64* offsets, u64 n_reads, u32 bound, u32 k, u32* gate, int n_cu, hipStream_t st);
 hipError_t launch_fix_hash_fold(kmx_summary* out, u32 k, u32 hasher, u32 hk, hipStream_t st);
-// kmx_minimizers.hip
+// kmx_minimizers.hip (first_bad: the context's scratch word -- the 24 bytes from it are readable: the tiled kernel's idle prefetch)
 hipError_t launch_minimizers_reads(const uint8_t* bases, u64 total_bytes, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L,
                                    u32 bound, u32 k, u32 w, u32 hasher, u32 hk, u64* out_word, u32* out_pos,
                                    unsigned long long* first_bad, int n_cu, hipStream_t st, bool* tiled);

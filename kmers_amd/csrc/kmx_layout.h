@@ -45,6 +45,8 @@ constexpr size_t KMX_Q_CLEAR_HEADS = 8u * KMX_Q_HEADS * KMX_Q_HEAD_STRIDE, KMX_Q
 constexpr size_t KMX_PIN_BYTES = 64;
 constexpr uint32_t KMX_PIN_READ = 0, KMX_PIN_SUMMARY = 2, KMX_PIN_HOST_VIEW = 7;
 
+// (minimizers_reads_kernel's idle threads load the 20 bytes from [KMX_S_FIRST_BAD] as a stand-in and ignore them: kmx_minimizers.hip)
+static_assert(8u * (KMX_S_FIRST_BAD + 3u) <= KMX_SCRATCH_BYTES, "three readable words from KMX_S_FIRST_BAD");
 static_assert(KMX_S_FASTX_TOTALS > KMX_S_FIRST_BAD && KMX_S_LEN_RANGE >= KMX_S_FASTX_TOTALS + 2 && KMX_S_TOO_LONG > KMX_S_LEN_RANGE &&
               KMX_S_QUEUE > KMX_S_TOO_LONG, "d_scratch words overlap");
 static_assert(KMX_Q_MARKED >= KMX_Q_HEADS * KMX_Q_HEAD_STRIDE && KMX_Q_GATE > KMX_Q_MARKED && KMX_Q_MASKS > KMX_Q_GATE &&

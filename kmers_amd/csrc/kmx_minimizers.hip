@@ -88,6 +88,9 @@ minimizers_reads_kernel(const uint8_t* __restrict__ bases, u64 total_bytes, cons
     // A thread packs the dwords j16 and j16 + 16 of its piece (a piece is at most 18 dwords).  Their bytes are REQUESTED one block
     // iteration ahead -- dword-aligned loads: a 16-byte load from an odd address is taken apart by the memory pipeline -- so that a
     // block never starts by waiting for memory (the 16 reads of an iteration are 2.4 KB: nothing else hides the latency).
+    // A thread with nothing to request loads a stand-in, so that no branch goes around the loads: the 20 bytes at first_bad, which are
+    // the context's own (kmx_layout.h: d_scratch) -- NOT bytes of the batch: a batch may be shorter than 20 bytes, and the caller's
+    // buffer ends with its last base (include/kmx.h).  What a stand-in holds is never looked at.
     u32 xa[2][5];
     auto request = [&](const Piece& q) {
 #pragma unroll
@@ -96,7 +99,7 @@ minimizers_reads_kernel(const uint8_t* __restrict__ bases, u64 total_bytes, cons
             const uint8_t* p = q.sp + 16u * d;
             const u32 rsh = (u32)(reinterpret_cast<uintptr_t>(p) & 3u);
             const bool fast = 16u * d < q.len && p + 20 <= buf_end && p - rsh >= bases;
-            const u32* a4 = reinterpret_cast<const u32*>(fast ? p - rsh : bases - (reinterpret_cast<uintptr_t>(bases) & 3u) + 4u);
+            const u32* a4 = fast ? reinterpret_cast<const u32*>(p - rsh) : reinterpret_cast<const u32*>(first_bad);
 #pragma unroll
             for (int i = 0; i < 5; ++i) xa[h][i] = a4[i];
         }
@@ -308,7 +311,8 @@ minimizers_reads_generic_kernel(const uint8_t* __restrict__ bases, const MmrGeom
     }
 }
 
-// bound: the longest read (uniform: L).  *tiled: whether the sliding-minimum kernel ran (the caller's diagnostics / tests)
+// bound: the longest read (uniform: L).  *tiled: whether the sliding-minimum kernel ran (the caller's diagnostics / tests).
+// first_bad: kmx_ctx::d_scratch + KMX_S_FIRST_BAD -- the tiled kernel reads (and ignores) the 20 bytes from it as its stand-in source.
 hipError_t launch_minimizers_reads(const uint8_t* bases, u64 total_bytes, const u64* offsets, const u64* win_offsets, u64 n_reads, u32 L,
                                    u32 bound, u32 k, u32 w, u32 hasher, u32 hk, u64* out_word, u32* out_pos,
                                    unsigned long long* first_bad, int n_cu, hipStream_t st, bool* tiled) {
@@ -317,7 +321,7 @@ hipError_t launch_minimizers_reads(const uint8_t* bases, u64 total_bytes, const 
     *tiled = false;
     const bool keys_fit = hash_bits <= 56u && w <= 28u && k > w;
     u32 Lmax = bound;
-    if (!offsets && L > 256u) {          // pieces of at most 256 bases: T k-mers each, the same for every read
+    if (!offsets && L > 256u && k <= 256u) {   // pieces of at most 256 bases: T k-mers each, the same for every read (k = 257: T would be 0)
         geo.T = 256u - k + 1u;
         geo.J = (L - k + 1u + geo.T - 1u) / geo.T;
         Lmax = 256u;

@@ -224,22 +224,25 @@ seqvec_minimizers_slide_kernel(const u64* __restrict__ words, u64 n_reads, u32 L
     const u32 ND = ((2u * L + 31u) >> 5) + 2u;                  // dwords of a staged read (+2: the field reads look ahead)
     u32* FW = reinterpret_cast<u32*>(hs + 2u * RB * NL);
     u32* RV = FW + RB * ND;
-    const u64 n_words = (n_reads * (u64)L + 31u) >> 5;
+    const u32* const words32 = reinterpret_cast<const u32*>(words);
+    const u64 n_dwords = 2u * ((n_reads * (u64)L + 31u) >> 5);
     const u32 r = threadIdx.x >> 4, j16 = threadIdx.x & 15u;
     const u32 recipW = W > 1u ? (u32)(0x100000000ull / W) + 1u : 0u;   // e / W = umulhi(e, recipW) for e < RB * W <= 2^12 (W = 1: e itself)
     for (u64 r0 = (u64)blockIdx.x * RB; r0 < n_reads; r0 += (u64)gridDim.x * RB) {
         const u32 nr = (u32)(n_reads - r0 < RB ? n_reads - r0 : RB);
         key_t* A = reinterpret_cast<key_t*>(hs);
         key_t* B = reinterpret_cast<key_t*>(hs + RB * NL);
-        // the read, realigned: dword d = its bits [32d, 32d+32) (whatever follows the read in the vector comes along: never looked at)
+        // the read, realigned: dword d = its bits [32d, 32d+32) (whatever follows the read in the vector comes along: never looked at).
+        // The vector as dwords and ONE funnel shift, not a 64-bit shift by a register.  Observed with the 64-bit form: the
+        // MODE 1 / K32 instantiation, whose shift amount lay in the last of its 32 VGPRs, gave rows shifted by the lane's number when
+        // several blocks shared a compute unit.  Why is not established; this form has no such shift to go wrong.
         if (r < nr) {
             const u64 bit0 = 2u * (r0 + r) * (u64)L;
             for (u32 d = j16; d < ND; d += 16u) {
                 const u64 b = bit0 + 32u * d;
-                const u64 q = b >> 6;
-                const u32 sh = (u32)(b & 63u);
-                const u64 lo = q < n_words ? words[q] : 0ull, hi = (sh && q + 1u < n_words) ? words[q + 1u] : 0ull;
-                FW[r * ND + d] = (u32)(sh ? ((lo >> sh) | (hi << (64u - sh))) : lo);
+                const u64 q = b >> 5;
+                const u32 lo = q < n_dwords ? words32[q] : 0u, hi = q + 1u < n_dwords ? words32[q + 1u] : 0u;
+                FW[r * ND + d] = __builtin_amdgcn_alignbit(hi, lo, (u32)(b & 31u));
             }
         }
         __syncthreads();
@@ -248,7 +251,7 @@ seqvec_minimizers_slide_kernel(const u64* __restrict__ words, u64 n_reads, u32 L
             for (u32 d = j16; d < ND; d += 16u) {
                 const int off = (int)L - 16 * (int)d - 16;      // may be negative: the read has fewer bases left
                 u32 x;
-                if (off >= 0) x = (u32)lds_field(FW + r * ND, 2u * (u32)off, 32u);
+                if (off >= 0) x = __builtin_amdgcn_alignbit(FW[r * ND + ((u32)off >> 4) + 1u], FW[r * ND + ((u32)off >> 4)], 2u * ((u32)off & 15u));
                 else x = off > -16 ? FW[r * ND] << (2u * (u32)(-off)) : 0u;
                 x = __builtin_bitreverse32(x);
                 RV[r * ND + d] = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);   // bit-reversed pairs back in order

@@ -176,7 +176,7 @@ uint64_t kmo_mm_hash(uint64_t lmer, size_t hasher_k);
 /* Kmer::minimizer_word (kmer.rs:170-192): leftmost minimum over the k-w+1 sub-words (strict `<` against u64::MAX) */
 int kmo_minimizer_word(uint64_t word, size_t k, size_t width, size_t hasher_k, uint64_t *out_mmer, size_t *out_offset);
 /* SeqVecMinimizerIter (seq_vector/minimizers.rs:39-141) with its monotone deque, over slice [start, end) */
-#define KMO_DQ_CAP 96
+#define KMO_DQ_CAP 256
 typedef struct {
     uint64_t lmer;
     size_t pos;

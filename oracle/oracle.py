@@ -55,13 +55,16 @@ class DQMer(C.Structure):   # seq_vector/minimizers.rs:8-13
     _fields_ = [("lmer", C.c_uint64), ("pos", C.c_size_t), ("hash", C.c_uint64)]
 
 
+DQ_CAP = 256   # KMO_DQ_CAP: the deque holds k - w + 2 entries at the most (k = 250 / w = 11 in tests/minimizers_np.py)
+
+
 class MMIter(C.Structure):  # SeqVecMinimizerIter, seq_vector/minimizers.rs:39-46
-    _fields_ = [("dq", DQMer * 96), ("head", C.c_size_t), ("len", C.c_size_t), ("k", C.c_size_t), ("w", C.c_size_t),
+    _fields_ = [("dq", DQMer * DQ_CAP), ("head", C.c_size_t), ("len", C.c_size_t), ("k", C.c_size_t), ("w", C.c_size_t),
                 ("curr_km_i", C.c_size_t), ("words", C.c_void_p), ("n_bases", C.c_size_t), ("start", C.c_size_t),
                 ("slice_len", C.c_size_t), ("hasher_k", C.c_size_t)]
 
     def dq_hashes(self):
-        return [self.dq[(self.head + i) % 96].hash for i in range(self.len)]
+        return [self.dq[(self.head + i) % DQ_CAP].hash for i in range(self.len)]
 
 
 class Summary(C.Structure):
@@ -78,18 +81,21 @@ class Summary2(C.Structure):
     ]
 
 
+def _newest_source() -> float:
+    # (the header too: MMIter above mirrors a struct it defines)
+    return max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("kmx_oracle.c", "kmx_oracle.h"))
+
+
 def build(force: bool = False) -> str:
     """Compile oracle/libkmx_oracle.so (portable flags) if missing; return its path.
     KMX_ORACLE_SANITIZE=1 (tests/test_sanitizers.py: a python started with libasan preloaded): the ASan + UBSan build."""
     if os.environ.get("KMX_ORACLE_SANITIZE") == "1":
         so = os.path.join(_HERE, "libkmx_oracle_asan.so")
-        src = os.path.join(_HERE, "kmx_oracle.c")
-        if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        if force or not os.path.exists(so) or os.path.getmtime(so) < _newest_source():
             subprocess.check_call(["make", "-C", _HERE, "libkmx_oracle_asan.so"], stdout=subprocess.DEVNULL)
         return so
     so = os.path.join(_HERE, "libkmx_oracle.so")
-    src = os.path.join(_HERE, "kmx_oracle.c")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+    if force or not os.path.exists(so) or os.path.getmtime(so) < _newest_source():
         subprocess.check_call(["make", "-C", _HERE, "libkmx_oracle.so"], stdout=subprocess.DEVNULL)
     return so
 

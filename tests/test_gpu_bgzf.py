@@ -116,7 +116,7 @@ def test_capacity_and_arguments(ctx):
     assert buf[:n_text].cpu().numpy().tobytes() == B.host_text(f)
 
 
-@pytest.mark.parametrize("image", [gzip.compress(b"@r\nACGT\n+\nIIII\n"), b"@r\nACGT\n+\nIIII\n", b"\x1f\x8b\x08\x04", B.HEADER[:10] + b"\x0c\0BC\x02\0"
+@pytest.mark.parametrize("image", [gzip.compress(b"@r\nACGT\n+\nIIII\n", mtime=0), b"@r\nACGT\n+\nIIII\n", b"\x1f\x8b\x08\x04", B.HEADER[:10] + b"\x0c\0BC\x02\0"
                                    + b"\x27\0" + b"XY\x02\0\0\0" + b"\x03\0" + bytes(8)])
 def test_what_is_not_bgzf_is_an_argument_error(ctx, image):
     d_file = dev_bytes(ctx, np.frombuffer(image, np.uint8))

@@ -333,7 +333,7 @@ def test_minimizers_invalid_byte_is_reported(ctx):
     host[80 * L] = ord("N")
     with pytest.raises(KmxError) as ei:
         ctx.minimizers(ctx.to_device(host), n, L, 31, 15, _lib.HASH_LEX, 15)
-    assert ei.value.status == _lib.E_INVALID_BASE
+    assert ei.value.status == _lib.E_INVALID_BASE and ei.value.first_bad == 57
     mw, mp = ctx.minimizers(ctx.to_device(host), n, L, 31, 15, _lib.HASH_LEX, 15, check=False)     # asked not to look: no error
     assert mw.numel() == n * 120
 
