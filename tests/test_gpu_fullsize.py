@@ -132,7 +132,8 @@ def test_full_size_counts_linearity_and_prefix(ctx, orc, big, k):
     o = orc.canonical_reduce(host, n_chk, L, k, hasher_k=k)
     g = ctx.canonical_reduce(big[: n_chk * L], n_chk, L, k, _lib.HASH_LEX, k, _lib.REDUCE_SUM_FW)
     assert (g.n_valid, g.sum_canon, g.xor_hash, g.sum_fw) == (o.n_valid, o.sum_canon, o.xor_hash, o.sum_fw)
-    # the generic (reference-shaped) kernel and the fast kernel agree on a mid-size slice
+    # the ragged bit-sliced scan (the same reads behind offsets, no bound: REDUCE_SUM_FW keeps them off the uniform gate) and the
+    # uniform one agree on a mid-size slice
     n_mid = min(N_FULL, 3_000_000)
     off = ctx.to_device(np.arange(n_mid + 1, dtype=np.uint64) * np.uint64(L))
     gg = ctx.canonical_reduce(big[: n_mid * L], n_mid, 0, k, _lib.HASH_LEX, k, _lib.REDUCE_SUM_FW, offsets=off)
