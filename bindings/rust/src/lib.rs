@@ -1307,6 +1307,43 @@ pub fn bgzf_inflate(ctx: &HipContext, d_file: &DeviceBuf<'_>, n_bytes: u64, d_bl
     (st, bad)
 }
 
+/// What `bgzf_deflate` made: the blocks of the image (the EOF marker counted, as `bgzf_index` counts it), the bytes of the image (the
+/// marker included), the stored blocks among them, the bytes of text.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct BgzfDeflateInfo {
+    pub n_blocks: u64,
+    pub n_image_bytes: u64,
+    pub n_stored: u64,
+    pub n_text_bytes: u64,
+}
+
+/// The capacity that always holds the BGZF image of `n_bytes` of text cut every `block_bytes` (0: 65280): every block stored.
+pub fn bgzf_deflate_bound(n_bytes: u64, block_bytes: u32) -> u64 {
+    unsafe { kmx_bgzf_deflate_bound(n_bytes, block_bytes) }
+}
+
+/// A text on the device compressed to a BGZF image there (`kmx_bgzf_deflate`): one block per `block_bytes` of text (1..=65280, 0:
+/// 65280), the EOF marker last.  `d_file = None` compresses and reports the size only; otherwise up to `file_capacity` bytes are
+/// written (any alignment), and with `d_block_offsets` the `n_blocks + 1` words where the blocks start.  `flags`:
+/// `KMX_BGZF_DEFLATE_STORED` stores every block.  Err(KMX_E_NOMEM) for an image above `file_capacity`, with nothing written.  The bytes
+/// depend on the text, `block_bytes` and `flags` alone.  Synchronous.
+pub fn bgzf_deflate(ctx: &HipContext, d_text: &DeviceBuf<'_>, n_bytes: u64, block_bytes: u32, flags: u32, d_file: Option<&DeviceBuf<'_>>,
+                    file_capacity: u64, d_block_offsets: Option<&DeviceBuf<'_>>) -> Result<BgzfDeflateInfo, KmxError> {
+    assert!(n_bytes as u128 <= d_text.len() as u128, "text shorter than n_bytes");
+    let df = d_file.map_or(ptr::null_mut(), |f| {
+        assert!(file_capacity as u128 <= f.len() as u128, "image buffer shorter than file_capacity");
+        f.as_mut_ptr::<u8>()
+    });
+    let bb = if block_bytes == 0 { 65280 } else { block_bytes as u64 };
+    let dbo = d_block_offsets.map_or(ptr::null_mut(), |o| {
+        assert!((((n_bytes + bb - 1) / bb) as u128 + 2) * 8 <= o.len() as u128, "offsets shorter than n_blocks + 1");
+        o.as_mut_ptr::<u64>()
+    });
+    let mut info = [0u64; 4];
+    ctx.ck(unsafe { kmx_bgzf_deflate(ctx.0, d_text.as_ptr::<u8>(), n_bytes, block_bytes, flags, df, file_capacity, dbo, info.as_mut_ptr()) })?;
+    Ok(BgzfDeflateInfo { n_blocks: info[0], n_image_bytes: info[1], n_stored: info[2], n_text_bytes: info[3] })
+}
+
 /// What `fastx_format` lays out beside the bases: the names (a ragged batch of `n_reads` names and its `n_reads + 1` offsets, taken
 /// from byte `name_skip` on; `None`: record r is named `name_base + r` in decimal), the quality bytes (laid out as the bases are;
 /// `None`: every quality byte is `qual_fill`), and the bases per FASTA line (0: one line; must be 0 for FASTQ).

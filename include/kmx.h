@@ -1533,8 +1533,8 @@ int kmx_reads_dedup(kmx_ctx *ctx, const kmx_reads *reads, const kmx_reads *mates
  * the host).  Working set in the work buffer: a256(8 * (n_reads + 1)) for the record offsets when the caller gives none, plus
  * a256(8 * (2 * ceil(n_reads / 2048) + 6)); above the cap KMX_E_NOMEM before any kernel runs.  NULL ctx / reads / h_n_bytes:
  * KMX_E_ARG.
- * Not done: the names of FASTA records, two mates interleaved in one image, multi-line FASTQ, gzip / BGZF, writing to disk from
- * the device. */
+ * Not done: the names of FASTA records, two mates interleaved in one image, multi-line FASTQ, plain gzip (BGZF: the two sections
+ * below), writing to disk from the device. */
 int kmx_fastx_parse_names(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t format, uint8_t *d_names,
                           uint64_t *d_noffsets, uint64_t max_reads, uint64_t *h_n_names, uint64_t *h_n_bytes);
 int kmx_fastx_format(kmx_ctx *ctx, const kmx_reads *reads, const uint8_t *d_quals, const kmx_reads *names, uint32_t name_skip,
@@ -1590,6 +1590,36 @@ int kmx_bgzf_index(kmx_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, uint64
 int kmx_bgzf_inflate(kmx_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const uint64_t *d_block_offsets,
                      const uint64_t *d_text_offsets, uint64_t n_blocks, uint32_t flags, uint8_t *d_text, uint64_t text_capacity,
                      uint32_t *d_status, uint64_t *h_first_bad);
+
+/* ---------------------------------------------------------------- text compressed to BGZF (kmx_bgzf.hip) ----
+ * BUILD-DEFINED.  The way back: a text in device memory (the image kmx_fastx_format wrote, or any bytes) becomes a BGZF image there,
+ * so that one device-to-host copy is the .gz file.  The text is cut into ceil(n_bytes / block_bytes) pieces; block_bytes in
+ * [1, 65280], 0 = 65280 (what htslib takes), anything else KMX_E_ARG.  Each piece becomes one block: the 18-byte header above with
+ * the six ignored bytes 00 00 00 00 00 ff, one raw DEFLATE stream whose last block is final, CRC-32 and ISIZE.  The 28-byte EOF
+ * marker follows the last block; n_bytes == 0 gives the marker alone.
+ * The DEFLATE stream of a piece of n bytes is either dynamic blocks (greedy LZ77 over a one-entry hash table of 4-byte strings and
+ * the distance-1 candidate, one block per 4096 tokens, code lengths limited to 15 / 7 bits) or the stored form, which is zlib's at
+ * level 0 byte for byte (one final stored block of n + 5 bytes below 32768 bytes of text; from there on a stored block and an empty
+ * final one, n + 10): the dynamic form is taken iff it is shorter in whole bytes.  flags = KMX_BGZF_DEFLATE_STORED stores every
+ * piece (zlib's level 0).
+ * The bytes are a function of the text, block_bytes and flags alone: the same across calls, streams, contexts and devices, and the
+ * ones tests/cpp/bgzf_encode_check.cpp writes on the host.
+ * d_text, d_file: any alignment.  d_block_offsets (optional): n_blocks + 1 device words as kmx_bgzf_index would write them for the
+ * image (the EOF marker is a block: n_blocks = pieces + 1).  h_info (host, four words, always set on KMX_OK / KMX_E_NOMEM):
+ * n_blocks (the marker counted, as kmx_bgzf_index counts it), the bytes of the image (the marker included), the stored blocks, the
+ * bytes of text.  d_file == NULL: compresses and reports only (d_block_offsets is still written if given).  An image larger than
+ * file_capacity: KMX_E_NOMEM with not one byte of d_file and not one word of d_block_offsets written and h_info set.  No byte at or
+ * behind the image's end is written.  kmx_bgzf_deflate_bound(n_bytes, block_bytes): the capacity that always suffices (every piece
+ * stored: 31 bytes around a piece below 32768 bytes, 36 from there on, and the marker); 0 for a block_bytes out of range.
+ * Working set in the work buffer: 16 bytes per block and one slot of a256(block_bytes + 16) bytes per piece coded at a time; when the
+ * cap does not hold a slot for every piece the pieces are coded in chunks, and -- as the size must be known before the first byte
+ * is written -- coded twice; not even one slot: KMX_E_NOMEM before any kernel runs.  Synchronous.  NULL ctx / h_info, flags other
+ * than the one below, n_bytes != 0 with d_text NULL, n_bytes of 2^44 or more: KMX_E_ARG.
+ * Not done: lazy matching, hash chains, compression levels, plain single-member gzip. */
+#define KMX_BGZF_DEFLATE_STORED 1
+uint64_t kmx_bgzf_deflate_bound(uint64_t n_bytes, uint32_t block_bytes);
+int kmx_bgzf_deflate(kmx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t block_bytes, uint32_t flags,
+                     uint8_t *d_file, uint64_t file_capacity, uint64_t *d_block_offsets, uint64_t *h_info);
 
 /* ---------------------------------------------------------------- multi-GPU exchange ----
  * The reference has no distributed code; reads shard embarrassingly (k-mers never span reads,

@@ -398,6 +398,22 @@ inline std::string bgzf_inflate(Context& ctx, const std::string& image, bool ver
     auto bytes = text.download();
     return std::string(bytes.begin(), bytes.begin() + nt);
 }
+// The way back (kmx.h, "text compressed to BGZF"): a text -> its BGZF image, compressed on the device into a buffer of
+// kmx_bgzf_deflate_bound bytes; one copy brings the image back.  block_bytes: text bytes per block (0: 65280); stored: every block a
+// stored block.  The bytes depend on the text, block_bytes and stored alone.
+inline std::string bgzf_deflate(Context& ctx, const std::string& text, uint32_t block_bytes = 0, bool stored = false) {
+    const uint64_t room = kmx_bgzf_deflate_bound(text.size(), block_bytes);
+    if (room == 0) throw std::runtime_error("bgzf_deflate: block_bytes in 1..65280 (0: 65280)");
+    DeviceBuffer<uint8_t> d(ctx, text.size() ? text.size() : 1);
+    if (!text.empty()) d.upload(reinterpret_cast<const uint8_t*>(text.data()), text.size());
+    DeviceBuffer<uint8_t> image(ctx, room);
+    uint64_t info[4] = {0, 0, 0, 0};
+    ctx.check(kmx_bgzf_deflate(ctx.get(), d.data(), text.size(), block_bytes, stored ? (uint32_t)KMX_BGZF_DEFLATE_STORED : 0u, image.data(), room, nullptr,
+                               info),
+              "bgzf_deflate");
+    auto bytes = image.download();
+    return std::string(bytes.begin(), bytes.begin() + info[1]);
+}
 struct Bgzf {};   // FastqReads(Bgzf{}, image): the image is BGZF-compressed
 
 // FASTA / FASTQ ingestion (build-defined, the reference has no parser): a file image -> the reads

@@ -219,6 +219,8 @@ SIGNATURES = {
     "kmx_fastx_parse_names": (_int, [_vp, _vp, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kmx_bgzf_index": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_bgzf_inflate": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u64, _vp, C.POINTER(C.c_uint64)]),
+    "kmx_bgzf_deflate_bound": (_u64, [_u64, _u32]),
+    "kmx_bgzf_deflate": (_int, [_vp, _vp, _u64, _u32, _u32, _vp, _u64, _vp, C.POINTER(C.c_uint64)]),
     "kmx_fastx_format": (_int, [_vp, C.POINTER(Reads), _vp, C.POINTER(Reads), _u32, _u64, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_reads_quality": (_int, [_vp, _RP, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "kmx_reads_adapter": (_int, [_vp, _RP, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
@@ -247,6 +249,7 @@ FASTX_AUTO, FASTX_FASTQ, FASTX_FASTA = 0, 1, 2
 FASTX_SAME_TEXT = 0x100   # or-ed into the format of the emit call that follows the counting call on the same image
 
 BGZF_NO_CRC = 1   # kmx_bgzf_inflate flags: the CRC-32 of the blocks is not compared
+BGZF_DEFLATE_STORED = 1   # kmx_bgzf_deflate flags: every block a stored block (level 0)
 # KMX_BGZF_ST_*: why a block is not sound (d_status of kmx_bgzf_inflate)
 BGZF_ST_HEADER, BGZF_ST_BTYPE, BGZF_ST_STORED, BGZF_ST_COUNTS, BGZF_ST_REPEAT, BGZF_ST_NO_EOB, BGZF_ST_CODESET, BGZF_ST_BADCODE, BGZF_ST_SYMBOL, \
     BGZF_ST_DISTANCE, BGZF_ST_OUTPUT, BGZF_ST_INPUT, BGZF_ST_LENGTH, BGZF_ST_CRC = range(1, 15)

@@ -2119,6 +2119,30 @@ class Context:
         self._ck(st)
         return text[:span]
 
+    @_on_ctx_stream
+    def bgzf_deflate(self, text: torch.Tensor, block_bytes: int = 65280, stored: bool = False, offsets: bool = False):
+        """kmx_bgzf_deflate: a text (uint8, on the device) -> its BGZF image, a uint8 device tensor of its own size (one call
+        compresses and writes into a buffer of kmx_bgzf_deflate_bound bytes; a shorter image is copied out of it, so the buffer
+        goes when the call returns): one block per `block_bytes` of text (1..65280), dynamic DEFLATE blocks or -- where that is
+        not shorter, and throughout with stored=True -- stored ones, the EOF marker last.
+        offsets=True -> (image, int64[n_blocks + 1]: where every block starts, the marker included, the image's end last).  The
+        bytes depend on the text, block_bytes and stored alone."""
+        if not 1 <= int(block_bytes) <= 65280:
+            raise ValueError("bgzf_deflate: block_bytes in 1..65280")
+        if text.dtype != torch.uint8 or not text.is_cuda:
+            raise ValueError("bgzf_deflate: a uint8 CUDA tensor")
+        text = text.contiguous()
+        n = int(text.numel())
+        info = (C.c_uint64 * 4)()
+        room = int(self.lib.kmx_bgzf_deflate_bound(n, int(block_bytes)))
+        image = self.empty(room, torch.uint8)
+        off = self.empty((n + int(block_bytes) - 1) // int(block_bytes) + 2, torch.int64) if offsets else None
+        self._ck(self.lib.kmx_bgzf_deflate(self._h, _ptr(text) if n else None, n, int(block_bytes), _lib.BGZF_DEFLATE_STORED if stored else 0,
+                                           _ptr(image), room, _ptr(off) if offsets else None, info))
+        if int(info[1]) < room:
+            image = image[:int(info[1])].clone()
+        return (image, off) if offsets else image
+
     def load_fastx(self, source) -> torch.Tensor:
         """A FASTA / FASTQ file -- a path, or its bytes -- -> its text on the device.  A BGZF image (.fastq.gz as bgzip, htslib and
         samtools write it) is copied compressed and inflated on the device; plain text is copied.  Plain single-member gzip raises
@@ -2165,10 +2189,18 @@ class Context:
             self._ck(self.lib.kmx_fastx_format(*args, _ptr(out), _ptr(off), nb.value, C.byref(nb)))
         return (out[:nb.value], off) if rec_offsets else out[:nb.value]
 
-    def write_fastx(self, file, bases, n_reads, read_len, bgzf_level=None, **kw):
+    def write_fastx(self, file, bases, n_reads, read_len, bgzf_level=None, bgzf_device=False, **kw):
         """fastx_format(bases, n_reads, read_len, **kw), one device-to-host copy, one write -> the bytes written.  `file`: a path
-        or a binary file object.  bgzf_level (0..9; None: plain text): the image goes through bgzf_compress (host zlib) first."""
-        image = self.fastx_format(bases, n_reads, read_len, **{**kw, "rec_offsets": False}).cpu().numpy()
+        or a binary file object.  bgzf_level (0..9; None: plain text): the image goes through bgzf_compress (host zlib) first.
+        bgzf_device=True: the image is compressed on the device instead (bgzf_deflate) and the one copy is the .gz file; the
+        device codes one form, so bgzf_level is None (that form) or 0 (stored blocks) then, and any other level is a ValueError."""
+        if bgzf_device and bgzf_level is not None and int(bgzf_level) != 0:
+            raise ValueError("write_fastx: bgzf_device=True has no compression levels: bgzf_level None (compressed) or 0 (stored)")
+        image = self.fastx_format(bases, n_reads, read_len, **{**kw, "rec_offsets": False})
+        if bgzf_device:
+            image = self.bgzf_deflate(image, stored=bgzf_level is not None and int(bgzf_level) == 0)
+            bgzf_level = None
+        image = image.cpu().numpy()
         if bgzf_level is not None:
             image = np.frombuffer(bgzf_compress(memoryview(image), int(bgzf_level)), dtype=np.uint8)
         if isinstance(file, (str, bytes)) or hasattr(file, "__fspath__"):

@@ -2699,6 +2699,62 @@ int kmx_bgzf_inflate(kmx_ctx* ctx, const uint8_t* d_file, uint64_t n_bytes, cons
     return KMX_E_ARG;
 }
 
+// ---- a text compressed to BGZF (kmx_bgzf.hip) ----
+uint64_t kmx_bgzf_deflate_bound(uint64_t n_bytes, uint32_t block_bytes) {
+    if (block_bytes > 65280u) return 0;
+    const uint64_t bb = block_bytes ? block_bytes : 65280u;
+    const uint64_t whole = n_bytes / bb, rest = n_bytes % bb;      // per piece: header and footer, and zlib's level-0 stored form
+    return n_bytes + whole * (bb < 32768u ? 31u : 36u) + (rest ? (rest < 32768u ? 31u : 36u) : 0u) + 28u;
+}
+
+int kmx_bgzf_deflate(kmx_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t block_bytes, uint32_t flags, uint8_t* d_file,
+                     uint64_t file_capacity, uint64_t* d_block_offsets, uint64_t* h_info) {
+    const char* who = "kmx_bgzf_deflate";
+    if (!ctx || !h_info || (flags & ~(uint32_t)KMX_BGZF_DEFLATE_STORED) || (n_bytes && !d_text) || n_bytes >= (1ull << 44) || block_bytes > 65280u)
+        return KMX_E_ARG;
+    const uint32_t bb = block_bytes ? block_bytes : 65280u;
+    const uint64_t pieces = (n_bytes + bb - 1u) / bb;
+    h_info[0] = pieces + 1u;
+    h_info[1] = h_info[2] = 0;
+    h_info[3] = n_bytes;
+    DeviceGuard g(ctx->device);
+    // the per-piece words, and as many slots behind them as the cap holds: all pieces, or chunks of them
+    const uint32_t slot = (flags & KMX_BGZF_DEFLATE_STORED) || pieces == 0 ? 0u : kmx::bgzf_deflate_slot_bytes(bb);   // (no text: the marker alone)
+    const size_t meta = kmx::bgzf_deflate_meta_bytes(pieces), budget = work_budget(ctx);
+    uint64_t chunk = pieces;
+    if (slot && pieces && meta < budget && (budget - meta) / slot < pieces) chunk = (budget - meta) / slot;
+    void* area = nullptr;
+    if (int st = work_area(ctx, who, meta + (size_t)(chunk ? chunk : 1u) * slot, &area)) return st;   // (not one slot under the cap: refused here)
+    KMX_HIP(ctx, hipMemsetAsync(area, 0, 256, ctx->stream));
+    for (uint64_t b0 = 0; b0 < pieces; b0 += chunk)
+        KMX_HIP(ctx, kmx::launch_bgzf_deflate_blocks(d_text, n_bytes, bb, pieces, b0, b0 + chunk < pieces ? b0 + chunk : pieces, slot, true, area, ctx->n_cu,
+                                                     ctx->stream));
+    KMX_HIP(ctx, kmx::launch_bgzf_deflate_offsets(pieces, area, ctx->stream));
+    unsigned long long stats[2] = {0, 0};
+    KMX_HIP(ctx, hipMemcpyAsync(stats, area, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h_info[1] = stats[0];
+    h_info[2] = stats[1];
+    if (d_file) {
+        if (int st = room_for(ctx, who, stats[0], "bytes of image", file_capacity)) return st;
+        if (chunk >= pieces) {
+            KMX_HIP(ctx, kmx::launch_bgzf_deflate_copy(d_text, n_bytes, bb, pieces, 0, 0, pieces + 1u, slot, area, stats[0], d_file, ctx->n_cu, ctx->stream));
+        } else {
+            // the slots held a chunk at a time and the size had to be known before the first byte: every chunk coded again, then written
+            for (uint64_t b0 = 0; b0 < pieces; b0 += chunk) {
+                const uint64_t b1 = b0 + chunk < pieces ? b0 + chunk : pieces;
+                KMX_HIP(ctx, kmx::launch_bgzf_deflate_blocks(d_text, n_bytes, bb, pieces, b0, b1, slot, false, area, ctx->n_cu, ctx->stream));
+                KMX_HIP(ctx, kmx::launch_bgzf_deflate_copy(d_text, n_bytes, bb, pieces, b0, b0, b1 == pieces ? pieces + 1u : b1, slot, area,
+                                                           (b1 - b0 + 1u) * (bb + 31ull), d_file, ctx->n_cu, ctx->stream));
+            }
+        }
+    }
+    if (d_block_offsets)
+        KMX_HIP(ctx, hipMemcpyAsync(d_block_offsets, kmx::bgzf_deflate_offsets(area), (size_t)(pieces + 2u) * 8u, hipMemcpyDeviceToDevice, ctx->stream));
+    KMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMX_OK;
+}
+
 // ---- a batch laid out as a FASTQ / FASTA image (kmx_fastx_format.hip) ----
 int kmx_fastx_format(kmx_ctx* ctx, const kmx_reads* reads, const uint8_t* d_quals, const kmx_reads* names, uint32_t name_skip, uint64_t name_base,
                      uint32_t format, uint32_t line_width, uint32_t qual_fill, uint8_t* d_text, uint64_t* d_rec_offsets, uint64_t max_bytes,

@@ -393,4 +393,17 @@ hipError_t launch_bgzf_write_index(const uint8_t* file, u64 n_bytes, void* scrat
                                    u64* text_offsets, int n_cu, hipStream_t st);
 hipError_t launch_bgzf_inflate(const uint8_t* file, u64 n_bytes, const u64* block_offsets, const u64* text_offsets, u64 n_blocks, u64 span, uint8_t* text,
                                u32* status, unsigned long long* first_bad, bool check_crc, hipStream_t st);
+// kmx_bgzf.hip: a text compressed to BGZF.  The working set: bgzf_deflate_meta_bytes for the per-piece words, and behind them one
+// slot of bgzf_deflate_slot_bytes per piece coded at a time (slot_bytes 0: every piece stored, no slots).  Its first words (`stats`,
+// cleared by the caller) after deflate_offsets: [0] = bytes of the image, [1] = stored blocks; bgzf_deflate_offsets: the n_pieces + 2
+// offsets (the marker's, the image's end).  blocks(sizing) over all pieces, offsets, then copy -- or, where the slots do not hold all
+// pieces, per chunk blocks(!sizing) and copy.  All asynchronous.
+size_t bgzf_deflate_meta_bytes(u64 n_pieces);
+u32 bgzf_deflate_slot_bytes(u32 block_bytes);
+const void* bgzf_deflate_offsets(void* scratch);
+hipError_t launch_bgzf_deflate_blocks(const uint8_t* text, u64 n_bytes, u32 block_bytes, u64 n_pieces, u64 b0, u64 b1, u32 slot_bytes, bool sizing,
+                                      void* scratch, int n_cu, hipStream_t st);
+hipError_t launch_bgzf_deflate_offsets(u64 n_pieces, void* scratch, hipStream_t st);
+hipError_t launch_bgzf_deflate_copy(const uint8_t* text, u64 n_bytes, u32 block_bytes, u64 n_pieces, u64 slot_b0, u64 b0, u64 b1, u32 slot_bytes,
+                                    void* scratch, u64 bytes_about, uint8_t* file, int n_cu, hipStream_t st);
 }  // namespace kmx
