@@ -869,17 +869,27 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
             const u32 c_keep2 = tr_keep[2], c_keep3 = tr_keep[3], c_keep4 = tr_keep[4], c_sel8 = tr_sel8;
 #define KMX_HRUN_BEGIN __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(3);
 #define KMX_HRUN_END __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0);
+// between two instructions of a run: keeps them in program order.  Stages xor-16 and xor-8 merge group g as soon as ITS exchange is back
+// (s_waitcnt lgkmcnt(NXT - 1 - g), as stage xor-4 has it); unpinned, hipcc put the merge of the LAST group first, and the whole run waited
+// with lgkmcnt(0) for the last of the NXT exchanges.  No instruction.
+#define KMX_HRUN_ORDER __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g < NXT; ++g) Y[g] = (u32)__builtin_amdgcn_ds_swizzle((int)F[g], (16 << 10) | 0x1f);
             KMX_HRUN_BEGIN
 #pragma unroll
-            for (int g = 0; g < NXT; ++g) F[g] = __builtin_amdgcn_perm(Y[g], F[g], c_sel16);
+            for (int g = 0; g < NXT; ++g) {
+                F[g] = __builtin_amdgcn_perm(Y[g], F[g], c_sel16);
+                KMX_HRUN_ORDER
+            }
             KMX_HRUN_END
 #pragma unroll
             for (int g = 0; g < NXT; ++g) Y[g] = (u32)__builtin_amdgcn_ds_swizzle((int)F[g], (8 << 10) | 0x1f);
             KMX_HRUN_BEGIN
 #pragma unroll
-            for (int g = 0; g < NXT; ++g) F[g] = __builtin_amdgcn_perm(Y[g], F[g], c_sel8);
+            for (int g = 0; g < NXT; ++g) {
+                F[g] = __builtin_amdgcn_perm(Y[g], F[g], c_sel8);
+                KMX_HRUN_ORDER
+            }
             KMX_HRUN_END
 #pragma unroll
             for (int g = 0; g < NXT; ++g) Y[g] = (u32)__builtin_amdgcn_ds_swizzle((int)F[g], (4 << 10) | 0x1f);
@@ -962,6 +972,7 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
             for (int e = 0; e < NE; ++e) atomicAdd(&QT[e * 64 + lane], Y[NW + e]);               // ragged: read-end planes, totals only
 #undef KMX_HRUN_BEGIN
 #undef KMX_HRUN_END
+#undef KMX_HRUN_ORDER
         }
         lds_fence();
 
@@ -1027,12 +1038,22 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
                 for (int j = J0; j >= JEND; --j) {
                     if (j - P1D >= JEND) fetch(j - P1D);
                     __builtin_amdgcn_sched_barrier(0);
+                    // Odd K: at j = J0 a window's middle base meets its own complement (ia == iq), and the two ripples come to
+                    // ripple(ripple(0, a0, a0), a1, a1) = ~a1 -- the middle base is below its complement when its high bit is clear.
+                    // Nothing is computed for that step: the next one starts from lt = ~mid_hi, folded into its first ripple,
+                    //   ripple(~mid_hi, a, q) = (~a & ~q) | ((a ^ q) & ~mid_hi),
+                    // the truth table of 0x71 with S0 complemented (S0 = mid_hi = 0xF0, S1 = a = 0xCC, S2 = q = 0xAA):
+                    // 0x11 | (0x66 & 0x0F) = 0x17.  2 WPL instructions a tile less.
+                    if constexpr ((K & 1) != 0) {
+                        if (j == J0) continue;
+                    }
 #pragma unroll
                     for (int w = 0; w < WPL; ++w) {
                         const int ia = K - 1 - j + w, iq = j + w;
                         const u32 a0 = (u32)Pv[ia], a1 = (u32)(Pv[ia] >> 32);
                         const u32 q0 = (u32)Pv[iq], q1 = (u32)(Pv[iq] >> 32);
-                        lt[w] = ripple(lt[w], a0, q0);
+                        if ((K & 1) != 0 && j == J0 - 1) lt[w] = __builtin_amdgcn_bitop3_b32((u32)(Pv[J0 + w] >> 32), a0, q0, 0x17);
+                        else lt[w] = ripple(lt[w], a0, q0);
                         lt[w] = ripple(lt[w], a1, q1);
                     }
                 }
@@ -1094,19 +1115,41 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
                 }
                 lds_fence();
                 const u32 pp = lane & 31u;
-                u32 ab[WPL];
+                // A window block past the last window (32 i >= W).  Its 32 mask words are all zero -- the lanes past the last group
+                // write zeros, see `nwin` above -- so its products add exact zeros to the accumulators, and the planes they meet lie inside
+                // the frame (q + 2 i < NW): skipping it never changed a result, it saves matrix instructions.  launch_bs only checks
+                // W <= 32 WPL.  The ASCII launchers of the single-word k pick WPL = ceil(W / 32) for every frame, so such a block
+                // exists only for packed reads far shorter than their frame (W <= 64 on the 10-word frame, <= 224 on the 16-word one)
+                // and where the uniform / ragged gate found a length below the launch's bound; the two-word k, the ragged and the
+                // segment launchers run whole ranges of W on ONE instantiation.  The test is wave-uniform but a run-time one, and it cuts
+                // pass 2 into a basic block per plane group: ds_read_b32, s_waitcnt lgkmcnt(0) right behind it, the operand, one or
+                // two products, a branch -- NW LDS round trips sat out one after the other, 20 branches a tile at k = 31.
+                // So: the single-word uniform variants (ASCII and packed) run pass 2 unguarded, as ONE block -- all WPL mask words
+                // and NW plane words are requested before the first product (pass 1's plane window Pv[] is dead: the register peak stays
+                // where it was), the waits are counted down group by group, and group g + 1's operand is built under group g's products --
+                // and pay the odd empty block's products where there is one; the other variants keep the guard.
+                constexpr bool GUARDED = K > 32 || RAGGED || SEG;
+                u32 ab[WPL], pw[NW];
 #pragma unroll
                 for (int i = 0; i < WPL; ++i) ab[i] = MW[set * (32u * WPL) + 32u * i + pp];
                 // the lane's own planes, where phase C put them
                 const u32 b0 = pp >> 1;
                 const u32 slot0 = ROT ? (b0 % (u32)RW) * S2 + (b0 / (u32)RW) : b0;
                 const u32* const prd = PL + (set * SP + 2u * slot0 + (pp & 1u));
+                if constexpr (!GUARDED) {
+#pragma unroll
+                    for (int g = 0; g < NW; ++g) pw[g] = prd[ROT ? (32 / RW) * g : 32 * g];
+                    // (left to itself hipcc sinks every second request down to its use: a full round trip again.  The 13- and the 16-word
+                    // frame, 52 / 64 prefetch registers, are left to it: pinned, the 16-word frame at eight windows per lane spills 52 bytes)
+                    if constexpr (NW <= 11) __builtin_amdgcn_sched_barrier(0);
+                }
                 const int unit = 0x7F7F7F7F;    // E8M0 scale 2^0 in every byte
                 const int rows_lo = pp < 16u ? unit : 0, rows_hi = pp < 16u ? 0 : unit;   // the shared accumulator block: which rows of A count
                 bs_v8i A[WPL];
 #pragma unroll
                 for (int g = 0; g < NW; ++g) {
-                    const bs_v8i B = fp4_operand_b(prd[ROT ? (32 / RW) * g : 32 * g]);
+                    if constexpr (GUARDED) pw[g] = prd[ROT ? (32 / RW) * g : 32 * g];
+                    const bs_v8i B = fp4_operand_b(pw[g]);
                     // (window blocks in ascending order for even g, descending for odd g: two products into the shared block are then
                     // never back to back)
 #pragma unroll
@@ -1114,7 +1157,9 @@ scan_bitsliced_kernel(const uint8_t* __restrict__ bases, u64 n_reads, u32 L, u32
                         const int i = (g & 1) ? WPL - 1 - ii : ii;
                         const int q = g - 2 * i;
                         if (q < 0 || q >= NAB) continue;
-                        if (32u * (u32)i >= W) continue;             // (wave-uniform: a window block past the last window -- the two-word k on the long frames run with more windows per lane than their reads have)
+                        if constexpr (GUARDED) {
+                            if (32u * (u32)i >= W) continue;         // (wave-uniform)
+                        }
                         if (q == 0) A[i] = fp4_operand_a(ab[i]);     // first use of window block i
                         if (q == 0)
                             acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[i], B, acc[0], 4, 4, 0, rows_lo, 0, unit);
