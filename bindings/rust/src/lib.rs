@@ -544,6 +544,121 @@ pub fn count_canonical_min2(ctx: &HipContext, sketch: &Sketch<'_>, min_est: u32,
     Ok(n_distinct)
 }
 
+// ------------------------------------------------------------------------------------------------ the distinct-key estimator
+
+/// HyperLogLog registers on the device (`kmx_hll_*`, include/kmx.h "the distinct-key estimator"): `1 << log2_regs` bytes, zero when
+/// new and accumulated into; a key raises the register named by the top bits of its hash under `seed` to the rank of the rest.
+pub struct Hll<'c> {
+    pub regs: DeviceBuf<'c>,
+    pub log2_regs: u32,
+    pub seed: u64,
+}
+
+/// Zeroed registers, `2^log2_regs` of them (`4 <= log2_regs <= 24`): a relative standard error of about `1.04 / sqrt(2^log2_regs)`.
+pub fn hll_new(ctx: &HipContext, log2_regs: u32, seed: u64) -> Result<Hll<'_>, KmxError> {
+    assert!((4..=24).contains(&log2_regs), "log2_regs outside 4..=24");
+    let regs = ctx.alloc(1usize << log2_regs)?;
+    ctx.ck(unsafe { kmx_memset(ctx.0, regs.as_mut_ptr(), 0, regs.len()) })?;
+    Ok(Hll { regs, log2_regs, seed })
+}
+
+/// Every valid window of a uniform batch already on the device (`kmx_hll_add`, k in 1..=31).
+pub fn hll_add(ctx: &HipContext, hll: &Hll<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8) -> Result<(), KmxError> {
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    ctx.ck(unsafe { kmx_hll_add(ctx.0, &r, k as u32, hll.regs.as_mut_ptr::<u8>(), hll.log2_regs, hll.seed) })
+}
+
+/// The same for two-word k-mers, k in 33..=64 (`kmx_hll_add2`).
+pub fn hll_add2(ctx: &HipContext, hll: &Hll<'_>, d_reads: &DeviceBuf<'_>, n_reads: u64, read_len: u32, k: u8) -> Result<(), KmxError> {
+    let r = sketch_reads(d_reads, n_reads, read_len);
+    ctx.ck(unsafe { kmx_hll_add2(ctx.0, &r, k as u32, hll.regs.as_mut_ptr::<u8>(), hll.log2_regs, hll.seed) })
+}
+
+/// `n` one-word keys as they are (`kmx_hll_add_words`): a table's keys, or the canonical words of a windows call.
+pub fn hll_add_words(ctx: &HipContext, hll: &Hll<'_>, d_words: &DeviceBuf<'_>, n: u64) -> Result<(), KmxError> {
+    assert!(n as u128 * 8 <= d_words.len() as u128, "keys shorter than n");
+    ctx.ck(unsafe { kmx_hll_add_words(ctx.0, d_words.as_ptr::<u64>(), n, hll.regs.as_mut_ptr::<u8>(), hll.log2_regs, hll.seed) })
+}
+
+/// The same for two-word keys, (low, high) pairs (`kmx_hll_add_words2`).
+pub fn hll_add_words2(ctx: &HipContext, hll: &Hll<'_>, d_words2: &DeviceBuf<'_>, n: u64) -> Result<(), KmxError> {
+    assert!(n as u128 * 16 <= d_words2.len() as u128, "keys shorter than n");
+    ctx.ck(unsafe { kmx_hll_add_words2(ctx.0, d_words2.as_ptr::<u64>(), n, hll.regs.as_mut_ptr::<u8>(), hll.log2_regs, hll.seed) })
+}
+
+/// `acc` = max(`acc`, `other`), bytewise (`kmx_hll_merge` with the output on its first input): registers of one size and seed merge
+/// into the registers of the union of what they saw, bit for bit.
+pub fn hll_merge(ctx: &HipContext, acc: &Hll<'_>, other: &Hll<'_>) -> Result<(), KmxError> {
+    assert!(acc.log2_regs == other.log2_regs && acc.seed == other.seed, "registers of different size or seed do not merge");
+    ctx.ck(unsafe { kmx_hll_merge(ctx.0, acc.regs.as_ptr::<u8>(), other.regs.as_ptr::<u8>(), acc.log2_regs, acc.regs.as_mut_ptr::<u8>()) })
+}
+
+/// How many registers hold each value (`kmx_hll_stats`): 64 bins, or with `other` 192 -- those of `hll`, of `other` and of their
+/// bytewise maximum, the registers of the union.
+pub fn hll_stats(ctx: &HipContext, hll: &Hll<'_>, other: Option<&Hll<'_>>) -> Result<Vec<u64>, KmxError> {
+    assert!(other.map_or(true, |o| o.log2_regs == hll.log2_regs && o.seed == hll.seed), "registers of different size or seed do not compare");
+    let n = if other.is_some() { 192 } else { 64 };
+    let d_hist = ctx.alloc(8 * n)?;
+    ctx.ck(unsafe { kmx_memset(ctx.0, d_hist.as_mut_ptr(), 0, d_hist.len()) })?;
+    let b = other.map_or(ptr::null(), |o| o.regs.as_ptr::<u8>());
+    ctx.ck(unsafe { kmx_hll_stats(ctx.0, hll.regs.as_ptr::<u8>(), b, hll.log2_regs, d_hist.as_mut_ptr::<u64>()) })?;
+    d_hist.download::<u64>(n)
+}
+
+fn hll_sigma(mut x: f64) -> f64 {
+    if x == 1.0 {
+        return f64::INFINITY;
+    }
+    let (mut y, mut z) = (1.0f64, x);
+    loop {
+        x *= x;
+        let z0 = z;
+        z += x * y;
+        y += y;
+        if z == z0 {
+            return z;
+        }
+    }
+}
+
+fn hll_tau(mut x: f64) -> f64 {
+    if x == 0.0 || x == 1.0 {
+        return 0.0;
+    }
+    let (mut y, mut z) = (1.0f64, 1.0 - x);
+    loop {
+        x = x.sqrt();
+        let z0 = z;
+        y *= 0.5;
+        z -= (1.0 - x) * (1.0 - x) * y;
+        if z == z0 {
+            return z / 3.0;
+        }
+    }
+}
+
+/// The number of distinct keys behind registers, from their 64 bins (`hll_stats`): Ertl's improved estimator exactly as include/kmx.h
+/// spells it out, in double precision.  All registers zero gives 0.
+pub fn hll_estimate(hist: &[u64], log2_regs: u32) -> f64 {
+    assert!((4..=24).contains(&log2_regs), "log2_regs outside 4..=24");
+    let q = (64 - log2_regs) as usize;
+    assert!(hist.len() >= q + 2, "fewer bins than 66 - log2_regs");
+    let m = (1u64 << log2_regs) as f64;
+    let mut z = m * hll_tau(1.0 - hist[q + 1] as f64 / m);
+    for j in (1..=q).rev() {
+        z = 0.5 * (z + hist[j] as f64);
+    }
+    z += m * hll_sigma(hist[0] as f64 / m);
+    m * m / (2.0 * std::f64::consts::LN_2) / z
+}
+
+/// The smallest `log2_blocks` in 0..=32 at which a counting sketch that `n_distinct` keys were added to is at most `fill` full
+/// (the occupancy of a 16-cell row, `1 - exp(-n / (16 * 2^b))`): what `sketch_new` is sized by from `hll_estimate`.
+pub fn hll_sketch_log2_blocks(n_distinct: f64, fill: f64) -> u32 {
+    assert!(fill > 0.0 && fill < 1.0, "fill outside (0, 1)");
+    (0..32u32).find(|&b| 1.0 - (-n_distinct / (16.0 * (1u64 << b) as f64)).exp() <= fill).unwrap_or(32)
+}
+
 /// A count table on the device: `keys` (`words` u64 per entry: 1 for k <= 31, 2 for k in 33..=64; ascending, distinct), one u64
 /// count per entry in `counts` (`None`: membership only, where a call allows it), `n` entries.
 #[derive(Clone, Copy)]

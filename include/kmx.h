@@ -331,6 +331,58 @@ int kmx_count_canonical_min2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, c
                              uint64_t seed, uint32_t min_est, uint64_t *d_kmers2, uint64_t *d_counts, uint64_t max_distinct,
                              uint64_t *h_n_distinct);
 
+/* ---------------------------------------------------------------- the distinct-key estimator ----
+ * BUILD-DEFINED.  HOW MANY distinct canonical k-mers an input holds, from one streaming pass and before anything is counted: the
+ * number a caller sizes a sketch (log2_blocks), a table (max_distinct) or a merge by, and -- from the registers of two samples -- a
+ * first look at their Jaccard index and containment without either exact table.  A HyperLogLog: 2^p byte registers, each a maximum.
+ *
+ * REGISTERS.  Caller-owned device memory: d_regs holds 1 << log2_regs bytes, 16-byte aligned, 4 <= log2_regs <= 24 (KMX_E_ARG
+ * otherwise), zeroed by the caller and ACCUMULATED into.
+ * HASH.  The key hash of the counting sketch above, the same definition: h = fmix64(lo ^ fmix64(hi + seed + 0x9e3779b97f4a7c15)),
+ * hi = 0 for a one-word key.
+ * UPDATE.  With p = log2_regs, adding a key does
+ *     idx  = h >> (64 - p)
+ *     w    = h << p
+ *     rank = min(clz64(w), 64 - p) + 1          (1 .. 65 - p; w == 0 gives 65 - p)
+ *     regs[idx] = max(regs[idx], rank)
+ * A maximum commutes and is idempotent.  That is the whole determinism contract -- repeated calls, other streams and other launch
+ * shapes give identical bytes, adding the same keys again changes nothing, and a host model reproduces the registers exactly.  The
+ * bytewise maximum of two register arrays of one size and seed IS the register array of the union of what they saw.
+ * ESTIMATE.  A function of the 64 bins of kmx_hll_stats alone, computed on the host in double precision: the device never touches a
+ * float.  Ertl's improved estimator (arXiv:1702.01284) -- no bias table, no empirical switch between ranges.  With m = 2^p,
+ * q = 64 - p and bins C[0 .. q + 1] (C[v] = the number of registers that hold v):
+ *     z = m * tau(1 - C[q + 1] / m)
+ *     for j = q down to 1:  z = (z + C[j]) / 2
+ *     z += m * sigma(C[0] / m)
+ *     E = m * m / (2 ln 2) / z
+ *     sigma(x): x == 1 -> infinity;  y = 1, z = x;  repeat { x *= x; z0 = z; z += x * y; y += y } until z == z0;  return z
+ *     tau(x):   x == 0 or x == 1 -> 0;  y = 1, z = 1 - x;
+ *               repeat { x = sqrt(x); z0 = z; y /= 2; z -= (1 - x)^2 * y } until z == z0;  return z / 3
+ * All registers zero gives E = 0.  The relative standard error is about 1.04 / sqrt(m).  kmx::hll_estimate (kmx.hpp),
+ * kmers_amd.api.hll_estimate and kmers_hip::hll_estimate implement exactly this.
+ * Argument checks, KMX_E_K_RANGE (k in [1,31]; the calls named ...2: k in [33,64], two-word keys 16-byte aligned) and the behaviour
+ * on empty input (n == 0, n_reads == 0, no window: nothing is touched; d_regs may then be NULL) follow kmx_sketch_*.  A NULL d_regs
+ * with work to do, one that is not 16-byte aligned, or log2_regs outside [4, 24]: KMX_E_ARG. */
+
+/* Adds n keys as they are (a table's keys, or the canon array of kmx_canonical_windows).  n up to 2^40.  No working set;
+ * asynchronous: it only enqueues work on the context's stream. */
+int kmx_hll_add_words(kmx_ctx *ctx, const uint64_t *d_words, uint64_t n, uint8_t *d_regs, uint32_t log2_regs, uint64_t seed);
+int kmx_hll_add_words2(kmx_ctx *ctx, const uint64_t *d_words2, uint64_t n, uint8_t *d_regs, uint32_t log2_regs, uint64_t seed);
+/* Adds every window of the batch that kmx_canonical_windows(2) marks KMX_WIN_VALID: kmx_hll_add_words(2) over the canon / flags of
+ * that call.  Inputs, working set (9 bytes per window, add2: 17), KMX_E_NOMEM before any kernel runs with the registers untouched,
+ * and synchrony are exactly those of kmx_sketch_add(2). */
+int kmx_hll_add(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint8_t *d_regs, uint32_t log2_regs, uint64_t seed);
+int kmx_hll_add2(kmx_ctx *ctx, const kmx_reads *reads, uint32_t k, uint8_t *d_regs, uint32_t log2_regs, uint64_t seed);
+/* d_out = bytewise max(a, b) of two register arrays of the same log2_regs; d_out may be d_a or d_b.  Arrays built with the same
+ * seed merge into the registers of the union of their inputs, bit for bit, whether or not the inputs overlap.  No working set;
+ * asynchronous. */
+int kmx_hll_merge(kmx_ctx *ctx, const uint8_t *d_a, const uint8_t *d_b, uint32_t log2_regs, uint8_t *d_out);
+/* d_hist[v] += the number of registers of d_a that hold v: 64 u64, ACCUMULATED into (the caller zeroes); a byte above 63, which no
+ * call writes, is counted in bin 63.  With d_b != NULL d_hist holds 192 words: the 64 bins of a, the 64 of b and the 64 of
+ * max(a, b) -- the registers of the union -- so a comparison of two samples reads each array once and writes no third one.  Integer
+ * atomics: deterministic.  No working set; asynchronous. */
+int kmx_hll_stats(kmx_ctx *ctx, const uint8_t *d_a, const uint8_t *d_b, uint32_t log2_regs, uint64_t *d_hist);
+
 /* ---------------------------------------------------------------- queries on a count table ----
  * BUILD-DEFINED, like the counters.  A TABLE is what kmx_count_canonical(2) / kmx_count_merge(2) / kmx_count_filter(2) write: n keys
  * ascending and distinct, one u64 count per key; two-word keys as (low, high) pairs, 16-byte aligned (KMX_E_ARG otherwise), ordered

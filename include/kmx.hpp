@@ -13,8 +13,10 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <memory>
 #include <string>
@@ -721,6 +723,97 @@ class Sketch {
     uint64_t seed_;
 };
 
+// The distinct-key estimator (kmx.h, "the distinct-key estimator").  hll_estimate: Ertl's improved estimator from the 64 bins of
+// kmx_hll_stats, exactly as kmx.h spells it out (hist[v] = the registers that hold v; log2_regs in 4..24); all registers zero gives 0.
+namespace hll_detail {
+inline double sigma(double x) {
+    if (x == 1.0) return std::numeric_limits<double>::infinity();
+    double y = 1.0, z = x, z0;
+    do {
+        x *= x;
+        z0 = z;
+        z += x * y;
+        y += y;
+    } while (z != z0);
+    return z;
+}
+inline double tau(double x) {
+    if (x == 0.0 || x == 1.0) return 0.0;
+    double y = 1.0, z = 1.0 - x, z0;
+    do {
+        x = std::sqrt(x);
+        z0 = z;
+        y *= 0.5;
+        z -= (1.0 - x) * (1.0 - x) * y;
+    } while (z != z0);
+    return z / 3.0;
+}
+}  // namespace hll_detail
+inline double hll_estimate(const uint64_t* hist, uint32_t log2_regs) {
+    if (log2_regs < 4 || log2_regs > 24) throw Panic(KMX_E_ARG, "hll_estimate");
+    const double m = double(uint64_t(1) << log2_regs);
+    const uint32_t q = 64 - log2_regs;
+    double z = m * hll_detail::tau(1.0 - double(hist[q + 1]) / m);
+    for (uint32_t j = q; j >= 1; --j) z = 0.5 * (z + double(hist[j]));
+    z += m * hll_detail::sigma(double(hist[0]) / m);
+    return m * m / (2.0 * std::log(2.0)) / z;
+}
+// The smallest log2_blocks in 0..32 at which a counting sketch that n_distinct keys were added to is at most `fill` full: the
+// occupancy of a 16-cell row, 1 - exp(-n / (16 * 2^b)).
+inline uint32_t hll_sketch_log2_blocks(double n_distinct, double fill = 0.25) {
+    for (uint32_t b = 0; b < 32; ++b)
+        if (1.0 - std::exp(-n_distinct / (16.0 * double(uint64_t(1) << b))) <= fill) return b;
+    return 32;
+}
+// 1 << log2_regs zeroed registers on the device; k picks the width of the calls as for Sketch.
+class Hll {
+  public:
+    explicit Hll(Context& ctx, uint32_t log2_regs = 14, uint64_t seed = 0) : ctx_(ctx), regs_(ctx, size_t(1) << log2_regs), log2_regs_(log2_regs), seed_(seed) {
+        ctx_.check(kmx_memset(ctx_.get(), regs_.data(), 0, regs_.size()), "kmx_memset");
+    }
+    uint8_t* data() const { return regs_.data(); }
+    size_t size() const { return regs_.size(); }
+    uint32_t log2_regs() const { return log2_regs_; }
+    uint64_t seed() const { return seed_; }
+    void add(const kmx_reads& reads, uint32_t k) {
+        ctx_.check(k <= 32 ? kmx_hll_add(ctx_.get(), &reads, k, data(), log2_regs_, seed_) : kmx_hll_add2(ctx_.get(), &reads, k, data(), log2_regs_, seed_),
+                   "hll_add");
+    }
+    // n keys on the device; words = 1 or 2 u64 per key
+    void add_words(const uint64_t* d_words, uint64_t n, uint32_t words = 1) {
+        ctx_.check(words == 1 ? kmx_hll_add_words(ctx_.get(), d_words, n, data(), log2_regs_, seed_)
+                              : kmx_hll_add_words2(ctx_.get(), d_words, n, data(), log2_regs_, seed_),
+                   "hll_add_words");
+    }
+    // this = max(this, other), bytewise: registers of one size and seed
+    void merge(const Hll& other) {
+        if (other.log2_regs_ != log2_regs_ || other.seed_ != seed_) throw Panic(KMX_E_ARG, "hll_merge");
+        ctx_.check(kmx_hll_merge(ctx_.get(), data(), other.data(), log2_regs_, data()), "hll_merge");
+    }
+    // 64 bins; with `other` 192: this, other, max(this, other)
+    std::vector<uint64_t> histogram(const Hll* other = nullptr) const {
+        if (other && (other->log2_regs_ != log2_regs_ || other->seed_ != seed_)) throw Panic(KMX_E_ARG, "hll_stats");
+        const size_t n = other ? 192 : 64;
+        DeviceBuffer<uint64_t> hist(ctx_, n);
+        ctx_.check(kmx_memset(ctx_.get(), hist.data(), 0, n * sizeof(uint64_t)), "kmx_memset");
+        ctx_.check(kmx_hll_stats(ctx_.get(), data(), other ? other->data() : nullptr, log2_regs_, hist.data()), "hll_stats");
+        return hist.download();
+    }
+    double estimate() const { return hll_estimate(histogram().data(), log2_regs_); }
+    uint32_t sketch_log2_blocks(double fill = 0.25) const { return hll_sketch_log2_blocks(estimate(), fill); }
+    // the estimated sizes of this, other and their union from one kmx_hll_stats: {a, b, union}
+    std::array<double, 3> compare(const Hll& other) const {
+        const auto h = histogram(&other);
+        return {hll_estimate(h.data(), log2_regs_), hll_estimate(h.data() + 64, log2_regs_), hll_estimate(h.data() + 128, log2_regs_)};
+    }
+
+  private:
+    Context& ctx_;
+    DeviceBuffer<uint8_t> regs_;
+    uint32_t log2_regs_;
+    uint64_t seed_;
+};
+
 // src/naive_impl/seq_vector.rs: the 2-bit packed sequence container, resident on the device.
 class SeqVector {
   public:
@@ -826,6 +919,11 @@ class SeqVector {
 };
 
 }  // namespace naive_impl
+
+// the distinct-key estimator has no counterpart in the reference crate's modules: it is kmx::Hll, kmx::hll_estimate
+using naive_impl::Hll;
+using naive_impl::hll_estimate;
+using naive_impl::hll_sketch_log2_blocks;
 
 // ---------------------------------------------------------------------------------------------------
 namespace encoding {

@@ -81,6 +81,14 @@ DD_SUMMARY_WORDS = 4
 SKETCH_BLOCK_BYTES = 64
 SKETCH_MAX_LOG2_BLOCKS = 32
 SKETCH_SWEEP_LANES_PER_CU = 1024
+# kmx_hll_*: the range of log2_regs, the bins of one array of kmx_hll_stats, and the cut-over of the add kernel (kmx_hll.hip:
+# block-private LDS registers up to HLL_LDS_MAX_LOG2_REGS, once every block of the sweep has HLL_LDS_KEYS_PER_DWORD keys for each
+# dword it flushes -- where the tests put their keys to run both routes)
+HLL_MIN_LOG2_REGS = 4
+HLL_MAX_LOG2_REGS = 24
+HLL_BINS = 64
+HLL_LDS_MAX_LOG2_REGS = 14
+HLL_LDS_KEYS_PER_DWORD = 1
 
 
 class KmxError(RuntimeError):
@@ -171,6 +179,12 @@ SIGNATURES = {
     "kmx_sketch_lookup_reads2": (_int, [_vp, _RP, _vp, _u32, _vp, _u32, _u64, _vp]),
     "kmx_sketch_merge": (_int, [_vp, _vp, _vp, _u32, _vp]),
     "kmx_sketch_stats": (_int, [_vp, _vp, _u32, _vp]),
+    "kmx_hll_add_words": (_int, [_vp, _vp, _u64, _vp, _u32, _u64]),
+    "kmx_hll_add_words2": (_int, [_vp, _vp, _u64, _vp, _u32, _u64]),
+    "kmx_hll_add": (_int, [_vp, _RP, _u32, _vp, _u32, _u64]),
+    "kmx_hll_add2": (_int, [_vp, _RP, _u32, _vp, _u32, _u64]),
+    "kmx_hll_merge": (_int, [_vp, _vp, _vp, _u32, _vp]),
+    "kmx_hll_stats": (_int, [_vp, _vp, _vp, _u32, _vp]),
     "kmx_count_canonical_min": (_int, [_vp, _RP, _u32, _vp, _u32, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_canonical_min2": (_int, [_vp, _RP, _u32, _vp, _u32, _u64, _u32, _vp, _vp, _u64, C.POINTER(C.c_uint64)]),
     "kmx_count_lookup": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),

@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import functools
+import math
 
 import numpy as np
 import torch
@@ -613,6 +614,111 @@ class Sketch:
         """the share of non-zero cells (kmx_sketch_stats: one host round trip), what a sketch is sized by"""
         hist = self.ctx.sketch_stats(self)
         return 1.0 - int(hist[0].item()) / int(self.cells.numel())
+
+
+def _hll_sigma(x: float) -> float:
+    if x == 1.0:
+        return math.inf
+    y, z = 1.0, x
+    while True:
+        x *= x
+        z0 = z
+        z += x * y
+        y += y
+        if z == z0:
+            return z
+
+
+def _hll_tau(x: float) -> float:
+    if x == 0.0 or x == 1.0:
+        return 0.0
+    y, z = 1.0, 1.0 - x
+    while True:
+        x = math.sqrt(x)
+        z0 = z
+        y *= 0.5
+        z -= (1.0 - x) ** 2 * y
+        if z == z0:
+            return z / 3.0
+
+
+def hll_estimate(hist, log2_regs: int) -> float:
+    """The number of distinct keys behind HyperLogLog registers, from their 64 bins (kmx_hll_stats; hist[v] = the registers that hold
+    v): Ertl's improved estimator as include/kmx.h spells it out, in double precision.  All registers zero gives 0."""
+    p = int(log2_regs)
+    if not _lib.HLL_MIN_LOG2_REGS <= p <= _lib.HLL_MAX_LOG2_REGS:
+        raise ValueError("log2_regs outside 4..24")
+    c = [int(v) for v in (hist.tolist() if hasattr(hist, "tolist") else hist)]
+    m, q = float(1 << p), 64 - p
+    if len(c) < q + 2 or sum(c[:q + 2]) != 1 << p:
+        raise ValueError("hll_estimate: the bins 0 .. 65 - log2_regs do not hold 2^log2_regs registers")
+    z = m * _hll_tau(1.0 - c[q + 1] / m)
+    for j in range(q, 0, -1):
+        z = 0.5 * (z + c[j])
+    z += m * _hll_sigma(c[0] / m)
+    return m * m / (2.0 * math.log(2.0)) / z if z else math.inf   # (every register at the top rank: no upper end)
+
+
+def hll_sketch_log2_blocks(n_distinct: float, fill: float = 0.25) -> int:
+    """The smallest log2_blocks in 0..32 at which a counting sketch that n_distinct keys were added to is at most `fill` full: a key
+    marks one of the 16 cells of each row of its block, so the occupancy of a row is 1 - exp(-n / (16 * 2^b)) (at fill = 0.25 about
+    14 bytes per distinct key).  32 where even the largest sketch is fuller."""
+    if not 0.0 < fill < 1.0:
+        raise ValueError("fill outside (0, 1)")
+    for b in range(_lib.SKETCH_MAX_LOG2_BLOCKS + 1):
+        if 1.0 - math.exp(-float(n_distinct) / (16.0 * float(1 << b))) <= fill:
+            return b
+    return _lib.SKETCH_MAX_LOG2_BLOCKS
+
+
+@dataclasses.dataclass
+class Hll:
+    """HyperLogLog registers on the device (kmx_hll_*): `regs`, uint8[1 << log2_regs], zero when new; a key raises register
+    h >> (64 - log2_regs) to the rank of the rest of its hash h under `seed` (kmx.h has the definition).  `ctx` is the context that
+    made it."""
+    regs: "torch.Tensor"
+    log2_regs: int
+    seed: int = 0
+    ctx: "Context | None" = dataclasses.field(default=None, repr=False, compare=False)
+
+    def histogram(self):
+        """kmx_hll_stats -> int64[64] on the device: how many registers hold each value"""
+        return self.ctx.hll_stats(self)
+
+    def estimate(self) -> float:
+        """the number of distinct keys added (hll_estimate of the histogram: one host round trip)"""
+        return hll_estimate(self.histogram().cpu(), self.log2_regs)
+
+    def sketch_log2_blocks(self, fill: float = 0.25) -> int:
+        """the log2_blocks of a counting sketch that what was added here fills to at most `fill` (hll_sketch_log2_blocks)"""
+        return hll_sketch_log2_blocks(self.estimate(), fill)
+
+
+@dataclasses.dataclass
+class HllComparison:
+    """Context.hll_compare: the estimated distinct keys of two samples (a, b), of their union (the bytewise maximum of the registers)
+    and, by inclusion-exclusion clipped at 0, of their intersection.  Each carries the estimator's error of about
+    1.04 / sqrt(2^log2_regs) of the UNION's size: a small intersection of large samples is mostly noise."""
+    a: float
+    b: float
+    union: float
+    intersection: float = dataclasses.field(init=False)
+
+    def __post_init__(self):
+        self.intersection = max(self.a + self.b - self.union, 0.0)
+
+    @property
+    def jaccard(self) -> float:
+        return self.intersection / self.union if self.union else 0.0
+
+    @property
+    def containment_a(self) -> float:
+        """the share of a's keys that b holds"""
+        return min(self.intersection / self.a, 1.0) if self.a else 0.0
+
+    @property
+    def containment_b(self) -> float:
+        return min(self.intersection / self.b, 1.0) if self.b else 0.0
 
 
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # the empty block every BGZF file ends with
@@ -1293,6 +1399,12 @@ class Context:
             raise ValueError("min_count outside 1..255: a cell of the sketch counts to 255")
         add, count, merge, flt = ((self.sketch_add, self.count_canonical_min, self.count_merge, self.count_filter) if words == 1 else
                                   (self.sketch_add2, self.count_canonical_min2, self.count_merge2, self.count_filter2))
+        if log2_blocks is None:   # one more pass: the distinct k-mers of all batches, and the sketch they fill to a quarter
+            hll, hll_add = self.hll_new(seed=seed), (self.hll_add if words == 1 else self.hll_add2)
+            for b in batches:
+                bases, n_reads, read_len, offsets = self._batch_args(b)
+                hll_add(hll, bases, n_reads, read_len, k, offsets=offsets)
+            log2_blocks = hll.sketch_log2_blocks()
         sketch = self.sketch_new(log2_blocks, seed)
         for b in batches:
             bases, n_reads, read_len, offsets = self._batch_args(b)
@@ -1308,18 +1420,93 @@ class Context:
         kmers, counts = flt(kmers, counts, int(min_count), 2**64 - 1)
         return kmers, counts, sketch
 
-    def count_solid(self, batches, k, min_count, log2_blocks, seed=0, tables=None):
+    def count_solid(self, batches, k, min_count, log2_blocks=None, seed=0, tables=None):
         """The k-mers that occur at least `min_count` (1..255) times in all of `batches` together, counted without ever holding the
         rest: (kmers, counts, sketch).  `batches`: a sequence, iterable twice, of (bases, n_reads, read_len, offsets) or ReadBatch.
         Pass 1 adds every batch to one sketch of 2^log2_blocks blocks; pass 2 counts, per batch, the windows whose estimate reaches
         min_count (count_canonical_min), folds the tables with count_merge and keeps the entries of at least min_count
         (count_filter).  Equal, key for key and count for count, to count_filter of the count of all reads at once -- for any
-        sketch size: a small sketch only lets more through.  `tables`, a list: the size of every batch's table is appended."""
+        sketch size: a small sketch only lets more through.  `tables`, a list: the size of every batch's table is appended.
+        log2_blocks = None: one more pass over `batches` first (hll_add into 2^14 registers), and the sketch is the smallest that
+        the estimated distinct k-mers fill to at most a quarter (Hll.sketch_log2_blocks)."""
         return self._count_solid(1, batches, k, min_count, log2_blocks, seed, tables)
 
-    def count_solid2(self, batches, k, min_count, log2_blocks, seed=0, tables=None):
+    def count_solid2(self, batches, k, min_count, log2_blocks=None, seed=0, tables=None):
         """count_solid for k 33..64 (kmers int64[n, 2])."""
         return self._count_solid(2, batches, k, min_count, log2_blocks, seed, tables)
+
+    # ------------------------------------------------------------ the distinct-key estimator
+    @_on_ctx_stream
+    def hll_new(self, log2_regs=14, seed=0) -> Hll:
+        """zeroed HyperLogLog registers, 2^log2_regs bytes (4..24): a relative standard error of about 1.04 / sqrt(2^log2_regs)"""
+        if not _lib.HLL_MIN_LOG2_REGS <= int(log2_regs) <= _lib.HLL_MAX_LOG2_REGS:
+            raise ValueError("log2_regs outside 4..24")
+        regs = torch.zeros(1 << int(log2_regs), dtype=torch.uint8, device=self.device)
+        return Hll(regs, int(log2_regs), int(seed) & (2**64 - 1), self)
+
+    def _hll_args(self, hll):
+        return _ptr(hll.regs), int(hll.log2_regs), int(hll.seed)
+
+    def _hll_add(self, fn, hll, bases, n_reads, read_len, k, offsets):
+        r = self._reads(bases, n_reads, read_len, offsets)
+        self._ck(fn(self._h, C.byref(r), k, *self._hll_args(hll)))
+        return hll
+
+    @_on_ctx_stream
+    def hll_add(self, hll, bases, n_reads, read_len, k, offsets=None) -> Hll:
+        """kmx_hll_add: every valid window of the batch, accumulated into `hll` (returned)."""
+        return self._hll_add(self.lib.kmx_hll_add, hll, bases, n_reads, read_len, k, offsets)
+
+    @_on_ctx_stream
+    def hll_add2(self, hll, bases, n_reads, read_len, k, offsets=None) -> Hll:
+        """kmx_hll_add2 (k 33..64)."""
+        return self._hll_add(self.lib.kmx_hll_add2, hll, bases, n_reads, read_len, k, offsets)
+
+    def _hll_add_words(self, fn, words, hll, keys):
+        n = int(keys.numel()) // words
+        keys = keys.contiguous()
+        self._ck(fn(self._h, _ptr(keys) if n else None, n, *self._hll_args(hll)))
+        return hll
+
+    @_on_ctx_stream
+    def hll_add_words(self, hll, words) -> Hll:
+        """kmx_hll_add_words: the keys as they are (int64 holding u64 words): a table's keys, or the canon array of canonical_windows."""
+        return self._hll_add_words(self.lib.kmx_hll_add_words, 1, hll, words)
+
+    @_on_ctx_stream
+    def hll_add_words2(self, hll, words) -> Hll:
+        """kmx_hll_add_words2: words int64[n, 2] = (low, high)."""
+        return self._hll_add_words(self.lib.kmx_hll_add_words2, 2, hll, words)
+
+    @_on_ctx_stream
+    def hll_merge(self, a: Hll, b: Hll, out: "Hll | None" = None) -> Hll:
+        """kmx_hll_merge -> the bytewise maximum of two register arrays of one size and seed, the registers of the union of what they
+        saw; `out` may be `a` or `b`."""
+        if a.log2_regs != b.log2_regs or a.seed != b.seed:
+            raise ValueError("registers of different size or seed do not merge")
+        if out is None:
+            out = Hll(self.empty(a.regs.numel(), torch.uint8), a.log2_regs, a.seed, self)
+        elif out.log2_regs != a.log2_regs or out.seed != a.seed:
+            raise ValueError("registers of different size or seed do not merge")
+        self._ck(self.lib.kmx_hll_merge(self._h, _ptr(a.regs), _ptr(b.regs), a.log2_regs, _ptr(out.regs)))
+        return out
+
+    @_on_ctx_stream
+    def hll_stats(self, a: Hll, b: "Hll | None" = None, out=None):
+        """kmx_hll_stats -> int64[64]: how many registers of `a` hold each value; with `b` int64[192]: the bins of a, of b and of
+        max(a, b).  Zeroed bins unless handed some (they are accumulated into)."""
+        if b is not None and (a.log2_regs != b.log2_regs or a.seed != b.seed):
+            raise ValueError("registers of different size or seed do not compare")
+        if out is None:
+            out = torch.zeros(_lib.HLL_BINS * (3 if b is not None else 1), dtype=torch.int64, device=self.device)
+        self._ck(self.lib.kmx_hll_stats(self._h, _ptr(a.regs), _ptr(b.regs) if b is not None else None, int(a.log2_regs), _ptr(out)))
+        return out
+
+    def hll_compare(self, a: Hll, b: Hll) -> HllComparison:
+        """The estimated sizes of two samples, their union and their intersection, with Jaccard index and containment, from one
+        kmx_hll_stats over both register arrays (one host round trip)."""
+        h = self.hll_stats(a, b).cpu().view(3, _lib.HLL_BINS)
+        return HllComparison(*(hll_estimate(h[j], a.log2_regs) for j in range(3)))
 
     # ------------------------------------------------------------ a count table as a de Bruijn graph
     def _adjacency(self, fn, words, kmers, counts, k, min_count, flips, neighbors):

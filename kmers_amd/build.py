@@ -24,9 +24,9 @@ SOURCES = ["kmx_sweep.hip", "kmx_hist.hip", "kmx_hist32.hip", "kmx_bitslice.hip"
            "kmx_bitslice_k24_27.hip", "kmx_bitslice_k28_30.hip", "kmx_bitslice_k33_39.hip", "kmx_bitslice_k41_47.hip", "kmx_bitslice_k49_55.hip",
            "kmx_bitslice_k57_61.hip", "kmx_bitslice_k34_40.hip", "kmx_bitslice_k42_48.hip", "kmx_bitslice_k50_56.hip", "kmx_bitslice_k58_64.hip",
            "kmx_bitslice_ragged_k9_12.hip", "kmx_bitslice_ragged_k13_16.hip", "kmx_bitslice_ragged_k17_20.hip", "kmx_bitslice_ragged_k21_24.hip", "kmx_bitslice_ragged_k25_28.hip",
-           "kmx_bitslice_ragged_k29_31.hip", "kmx_bitslice_ragged2_k33_36.hip", "kmx_bitslice_ragged2_k37_40.hip", "kmx_bitslice_ragged2_k41_44.hip", "kmx_bitslice_ragged2_k45_48.hip", "kmx_bitslice_ragged2_k49_52.hip", "kmx_bitslice_ragged2_k53_56.hip", "kmx_bitslice_ragged2_k57_60.hip", "kmx_bitslice_ragged2_k61_64.hip", "kmx_generic.hip", "kmx_segments.hip", "kmx_elem.hip", "kmx_seqvec.hip", "kmx_minimizers.hip", "kmx_sip13.hip", "kmx_fastx.hip", "kmx_fastx_format.hip", "kmx_bgzf.hip", "kmx_count.hip", "kmx_count_query.hip", "kmx_count_setop.hip", "kmx_count_read_stats.hip", "kmx_count_correct.hip", "kmx_count_color.hip", "kmx_count_graph.hip", "kmx_count_unitigs.hip", "kmx_count_paths.hip", "kmx_count_links.hip", "kmx_count_clean.hip", "kmx_count_components.hip", "kmx_count_link_support.hip", "kmx_reads_edit.hip", "kmx_reads_quality.hip", "kmx_reads_adapter.hip", "kmx_reads_complexity.hip", "kmx_reads_merge.hip", "kmx_reads_dedup.hip", "kmx_sketch.hip", "kmx_comm.hip", "kmx_api.hip"]
+           "kmx_bitslice_ragged_k29_31.hip", "kmx_bitslice_ragged2_k33_36.hip", "kmx_bitslice_ragged2_k37_40.hip", "kmx_bitslice_ragged2_k41_44.hip", "kmx_bitslice_ragged2_k45_48.hip", "kmx_bitslice_ragged2_k49_52.hip", "kmx_bitslice_ragged2_k53_56.hip", "kmx_bitslice_ragged2_k57_60.hip", "kmx_bitslice_ragged2_k61_64.hip", "kmx_generic.hip", "kmx_segments.hip", "kmx_elem.hip", "kmx_seqvec.hip", "kmx_minimizers.hip", "kmx_sip13.hip", "kmx_fastx.hip", "kmx_fastx_format.hip", "kmx_bgzf.hip", "kmx_count.hip", "kmx_count_query.hip", "kmx_count_setop.hip", "kmx_count_read_stats.hip", "kmx_count_correct.hip", "kmx_count_color.hip", "kmx_count_graph.hip", "kmx_count_unitigs.hip", "kmx_count_paths.hip", "kmx_count_links.hip", "kmx_count_clean.hip", "kmx_count_components.hip", "kmx_count_link_support.hip", "kmx_reads_edit.hip", "kmx_reads_quality.hip", "kmx_reads_adapter.hip", "kmx_reads_complexity.hip", "kmx_reads_merge.hip", "kmx_reads_dedup.hip", "kmx_sketch.hip", "kmx_hll.hip", "kmx_comm.hip", "kmx_api.hip"]
 HEADERS = [os.path.join(CSRC, "kmx_device.h"), os.path.join(CSRC, "kmx_hist_part.h"), os.path.join(CSRC, "kmx_bitslice_kernel.h"), os.path.join(CSRC, "kmx_internal.h"), os.path.join(CSRC, "kmx_scan_kernel.h"),
-           os.path.join(CSRC, "kmx_layout.h"), os.path.join(CSRC, "kmx_launch.h"), os.path.join(CSRC, "kmx_count_common.h"), os.path.join(CSRC, "kmx_reads_common.h"), os.path.join(CSRC, "kmx_reads_plan.h"), os.path.join(CSRC, "kmx_count_dir.h"), os.path.join(CSRC, "kmx_count_links.h"), os.path.join(CSRC, "kmx_bgzf_decode.h"), os.path.join(CSRC, "kmx_bgzf_encode.h"), os.path.join(HERE, "..", "include", "kmx.h")]
+           os.path.join(CSRC, "kmx_layout.h"), os.path.join(CSRC, "kmx_launch.h"), os.path.join(CSRC, "kmx_count_common.h"), os.path.join(CSRC, "kmx_key_hash.h"), os.path.join(CSRC, "kmx_reads_common.h"), os.path.join(CSRC, "kmx_reads_plan.h"), os.path.join(CSRC, "kmx_count_dir.h"), os.path.join(CSRC, "kmx_count_links.h"), os.path.join(CSRC, "kmx_bgzf_decode.h"), os.path.join(CSRC, "kmx_bgzf_encode.h"), os.path.join(HERE, "..", "include", "kmx.h")]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
             "-fno-gpu-rdc", "-munsafe-fp-atomics"]
@@ -60,7 +60,9 @@ def _headers_of(src: str) -> list[str]:
         if base == "kmx_hist_part.h" and src == "kmx_scan.hip":
             continue
         if base == "kmx_count_common.h" and src not in ("kmx_count.hip", "kmx_count_query.hip", "kmx_count_setop.hip", "kmx_count_read_stats.hip",
-                                                        "kmx_count_graph.hip", "kmx_count_unitigs.hip", "kmx_count_paths.hip", "kmx_count_links.hip", "kmx_count_correct.hip", "kmx_count_color.hip", "kmx_count_components.hip", "kmx_reads_edit.hip", "kmx_reads_merge.hip", "kmx_reads_dedup.hip", "kmx_fastx_format.hip", "kmx_sketch.hip"):
+                                                        "kmx_count_graph.hip", "kmx_count_unitigs.hip", "kmx_count_paths.hip", "kmx_count_links.hip", "kmx_count_correct.hip", "kmx_count_color.hip", "kmx_count_components.hip", "kmx_reads_edit.hip", "kmx_reads_merge.hip", "kmx_reads_dedup.hip", "kmx_fastx_format.hip", "kmx_sketch.hip", "kmx_hll.hip"):
+            continue
+        if base == "kmx_key_hash.h" and src not in ("kmx_sketch.hip", "kmx_hll.hip"):
             continue
         if base == "kmx_reads_common.h" and not (src.startswith("kmx_reads_") or src == "kmx_fastx_format.hip"):
             continue

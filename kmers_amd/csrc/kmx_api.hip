@@ -1157,6 +1157,67 @@ int kmx_sketch_stats(kmx_ctx* ctx, const uint8_t* d_sketch, uint32_t log2_blocks
     return KMX_OK;
 }
 
+// ---- the distinct-key estimator (kmx_hll.hip) ----
+// HyperLogLog registers as the calls take them (kmx.h): 1 << log2_regs bytes, 16-byte aligned, 4 <= log2_regs <= 24.
+static bool hll_ok(const void* d_regs, uint32_t log2_regs, bool needed) {
+    return log2_regs >= 4u && log2_regs <= 24u && (reinterpret_cast<uintptr_t>(d_regs) & 15u) == 0 && (d_regs != nullptr || !needed);
+}
+static const CountKind kHllAdd1{"kmx_hll_add", 1u, kmx_canonical_windows};
+static const CountKind kHllAdd2{"kmx_hll_add2", 2u, kmx_canonical_windows2};
+
+static int hll_add_words_impl(kmx_ctx* ctx, uint32_t words, const uint64_t* d_words, uint64_t n, uint8_t* d_regs, uint32_t log2_regs, uint64_t seed) {
+    if (!ctx || (n && !d_words) || n > (1ull << 40) || !hll_ok(d_regs, log2_regs, n != 0)) return KMX_E_ARG;
+    if (words == 2u && !aligned16(d_words)) return KMX_E_ARG;
+    if (n == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_hll_add(words, d_words, nullptr, n, d_regs, log2_regs, seed, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_hll_add_words(kmx_ctx* ctx, const uint64_t* d_words, uint64_t n, uint8_t* d_regs, uint32_t log2_regs, uint64_t seed) {
+    return hll_add_words_impl(ctx, 1u, d_words, n, d_regs, log2_regs, seed);
+}
+
+int kmx_hll_add_words2(kmx_ctx* ctx, const uint64_t* d_words2, uint64_t n, uint8_t* d_regs, uint32_t log2_regs, uint64_t seed) {
+    return hll_add_words_impl(ctx, 2u, d_words2, n, d_regs, log2_regs, seed);
+}
+
+// kmx_hll_add(2) = the windows of the batch as the counter makes them (windows_front), then the add kernel over (canon, flags):
+// kmx_sketch_add(2) with the other kernel behind it.
+static int hll_add_impl(kmx_ctx* ctx, const CountKind& kind, uint32_t k_min, uint32_t k_max, const kmx_reads* reads, uint32_t k, uint8_t* d_regs,
+                        uint32_t log2_regs, uint64_t seed) {
+    if (!ctx || !reads_ok(reads) || !hll_ok(d_regs, log2_regs, reads->n_reads != 0)) return KMX_E_ARG;
+    if (k < k_min || k > k_max) return KMX_E_K_RANGE;
+    if (reads->n_reads == 0) return KMX_OK;
+    DeviceGuard g(ctx->device);
+    WindowsFront f;
+    if (int st = windows_front(ctx, reads, k, kind, nullptr, &f)) return st;
+    KMX_HIP(ctx, kmx::launch_hll_add(kind.words, f.canon, f.flags, f.n_win, d_regs, log2_regs, seed, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_hll_add(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint8_t* d_regs, uint32_t log2_regs, uint64_t seed) {
+    return hll_add_impl(ctx, kHllAdd1, 1u, 31u, reads, k, d_regs, log2_regs, seed);
+}
+
+int kmx_hll_add2(kmx_ctx* ctx, const kmx_reads* reads, uint32_t k, uint8_t* d_regs, uint32_t log2_regs, uint64_t seed) {
+    return hll_add_impl(ctx, kHllAdd2, 33u, 64u, reads, k, d_regs, log2_regs, seed);
+}
+
+int kmx_hll_merge(kmx_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, uint32_t log2_regs, uint8_t* d_out) {
+    if (!ctx || !hll_ok(d_a, log2_regs, true) || !hll_ok(d_b, log2_regs, true) || !hll_ok(d_out, log2_regs, true)) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_hll_merge(d_a, d_b, log2_regs, d_out, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
+int kmx_hll_stats(kmx_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, uint32_t log2_regs, uint64_t* d_hist) {
+    if (!ctx || !hll_ok(d_a, log2_regs, true) || !hll_ok(d_b, log2_regs, false) || !d_hist) return KMX_E_ARG;
+    DeviceGuard g(ctx->device);
+    KMX_HIP(ctx, kmx::launch_hll_stats(d_a, d_b, log2_regs, d_hist, ctx->n_cu, ctx->stream));
+    return KMX_OK;
+}
+
 // The front half the per-read calls share (kmx_count_read_stats(2), kmx_count_read_paths(2), kmx_count_correct_reads(2), kmx_count_read_colors(2)):
 // kmx_canonical_windows(2) and the lookup kernel, which leave one u64 answer (the count, or whatever `d_values` holds per entry) and one
 // flag byte per window.  The work buffer, laid out up front: [segment plan of long reads][ragged reads: window offsets][two-word keys:

@@ -382,6 +382,12 @@ hipError_t launch_sketch_filter(u32 words, const u64* keys, uint8_t* flags, u64 
                                 int n_cu, hipStream_t st);
 hipError_t launch_sketch_merge(const uint8_t* a, const uint8_t* b, u32 log2_blocks, uint8_t* out, int n_cu, hipStream_t st);
 hipError_t launch_sketch_stats(const uint8_t* sketch, u32 log2_blocks, u64* hist, int n_cu, hipStream_t st);
+// kmx_hll.hip: the distinct-key estimator (`words` u64 per key: 1 or 2; regs: 1 << log2_regs bytes, 16-byte aligned, 4 <= log2_regs
+// <= 24).  add: flags may be nullptr, otherwise a key counts where its flag has KMX_WIN_VALID.  stats: b may be nullptr (64
+// bins), otherwise 192: a, b, max(a, b).  All asynchronous, no working set.
+hipError_t launch_hll_add(u32 words, const u64* keys, const uint8_t* flags, u64 n, uint8_t* regs, u32 log2_regs, u64 seed, int n_cu, hipStream_t st);
+hipError_t launch_hll_merge(const uint8_t* a, const uint8_t* b, u32 log2_regs, uint8_t* out, int n_cu, hipStream_t st);
+hipError_t launch_hll_stats(const uint8_t* a, const uint8_t* b, u32 log2_regs, u64* hist, int n_cu, hipStream_t st);
 // kmx_bgzf.hip: the block index of a BGZF image and its inflation.  The index's working set: `units` bytes for the counting pass, the
 // whole once the number of candidates (header patterns) is known.  Its first words (`stats`) after count_candidates: [2] = candidates;
 // after chain: [0] = text bytes, [1] = end of the last block, [3] = blocks, [5] = start of the last block.  All asynchronous.

@@ -17,19 +17,13 @@
 //   stats   The values of the cells, tallied in block-private LDS words (a block sees fewer than 2^32 cells) with the zero cells --
 //           most of a well-sized sketch -- counted in registers and added once per wave; one device atomic per non-empty bin.
 // Vector loads, vector stores and integer device atomics only.
-#include "kmx_count_common.h"
+#include "kmx_key_hash.h"   // (the key hash and the sweep's grid: shared with kmx_hll.hip)
 
 namespace kmx {
 
 namespace {
 
-constexpr u64 SK_G = 0x9E3779B97F4A7C15ull;
 constexpr u32 SK_STATS_IPT = 4;   // uint4 pieces per thread and grid step of the stats
-
-// the key hash of kmx.h: one definition for both widths, a one-word key being (lo, hi = 0)
-template <u32 W> __device__ __forceinline__ u64 key_hash(const Key<W>& q, u64 seed);
-template <> __device__ __forceinline__ u64 key_hash<1>(const Key<1>& q, u64 seed) { return fmix64(q.lo ^ fmix64(seed + SK_G)); }
-template <> __device__ __forceinline__ u64 key_hash<2>(const Key<2>& q, u64 seed) { return fmix64(q.lo ^ fmix64(q.hi + seed + SK_G)); }
 
 // byte offset of the key's block (no shift by 64: log2_blocks = 0 is one block)
 __device__ __forceinline__ u64 block_at(u64 h, u32 log2_blocks) { return log2_blocks ? (h >> (64u - log2_blocks)) << 6 : 0ull; }
@@ -156,13 +150,6 @@ __global__ void __launch_bounds__(CT) sketch_stats_kernel(const uint4* __restric
     if (c) atomicAdd(&hist[threadIdx.x], (unsigned long long)c);
 }
 static_assert(CT == 256, "the stats kernel keeps one bin per thread");
-
-// lanes of a sweep: SKETCH_BLOCKS_PER_CU blocks of CT on every compute unit; more keys than that and a lane takes several
-constexpr u32 SKETCH_BLOCKS_PER_CU = 4;
-unsigned sweep_blocks(u64 n, int n_cu) {
-    const u64 cap = (u64)(n_cu > 0 ? n_cu : 256) * SKETCH_BLOCKS_PER_CU, nb = ceil_div(n, CT);
-    return (unsigned)(nb < cap ? nb : cap);
-}
 
 }  // namespace
 
